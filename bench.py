@@ -7,7 +7,11 @@
 
 One step = zero_grad -> UNet.forward -> SimpleLoss -> backward -> SGD-Nesterov step on one
 synthetic batch of 8 images 512x512 per GPU (inputs resident in HBM), train mode (dropout on).
-Rank 0 prints ONE JSON line; `value` is images/s over all GPUs (weak scaling).
+Rank 0 prints ONE JSON line; `value` is images/s over all GPUs (weak scaling), `ms_per_step`
+the time of one timed step.  `--dump-outputs DIR` also writes what the last step of each timed
+leg computed: DIR/eager_*.npy (eager loop) and DIR/graph_*.npy (HIP-graph replay, when it runs);
+`dumped` in the line maps `value_path` to its files.  Inputs and seeds are fixed, so runs of two
+builds compare output for output.
 """
 import argparse
 import json
@@ -127,6 +131,29 @@ def synthetic_batch(seed, n, h, w):
     return img, torch.from_numpy(mask)
 
 
+DUMP_SAMPLE = 1 << 21    # entries kept of each flattened output: two legs x 2 x 8 MiB of float32
+
+
+def dump_outputs(path, prefix, model, loss):
+    """--dump-outputs: what the last step of a timed leg computed, as its caller receives it - the
+    loss the step returns, and the parameters and gradients it leaves in the model - written as
+    PATH/<prefix><name>.npy (float32).  Parameters and gradients are flattened in named_parameters()
+    order; where that holds more than DUMP_SAMPLE entries, the same seeded sample of positions is
+    kept every run, so two builds can be compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    params = [p for _, p in model.named_parameters()]
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1)
+                        for p in params])
+    n = flat_p.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.random.Generator(np.random.PCG64(0)).choice(n, DUMP_SAMPLE, replace=False)
+        idx = torch.from_numpy(np.sort(idx)).to(flat_p.device)
+        flat_p, flat_g = flat_p[idx], flat_g[idx]
+    for name, t in (("loss", loss.detach().reshape(())), ("params", flat_p), ("grads", flat_g)):
+        np.save(os.path.join(path, prefix + name + ".npy"), t.float().cpu().numpy())
+
+
 def cpu_model():
     try:
         with open("/proc/cpuinfo") as f:
@@ -235,7 +262,15 @@ def main():
                     help="skip the extra leg that replays the step from a HIP graph")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last step of each timed leg computed (loss, and a fixed "
+                         "seeded sample of the updated parameters and their gradients): the eager "
+                         "loop as DIR/eager_{loss,params,grads}.npy, the HIP-graph replay leg (when "
+                         "it runs) as DIR/graph_*.npy; the result line's `dumped` maps `value_path` "
+                         "to the files of that path; rank 0 only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process
@@ -361,6 +396,12 @@ def main():
     final_loss = loss.item()
     if not (final_loss == final_loss):
         raise SystemExit("loss is NaN")
+    # --dump-outputs: value_path -> the files holding what that path's last timed step computed
+    dumped = {}
+    if args.dump_outputs and rank == 0:
+        # before any other leg steps the model on
+        dump_outputs(args.dump_outputs, "eager_", model, loss)
+        dumped["eager"] = "eager_*.npy"
     gsumm, gsteps = groups_pass() if timer is not None else (None, None)
 
     def enqueue_ms(reps=5):
@@ -418,6 +459,8 @@ def main():
                                             "brackets only the roofline group)")
         if cpu_base is not None:
             result["cpu_baseline"] = cpu_base
+        if args.dump_outputs:
+            result["dumped"] = dumped     # the graph leg adds its files below
 
     emitted = []
 
@@ -467,10 +510,11 @@ def main():
     ddp_graph = use_dist and backend == "nccl" and \
         os.environ.get("UNET_BENCH_DDP_GRAPH", "1" if world == 1 else "0") != "0"
 
-    def graph_leg():
+    def graph_leg(dump=False):
         """The same K steps replayed from ONE HIP graph (ua.GraphedTrainStep): what the step
         costs once the host walk is out of the way.  Plain UNet only; with a process group the
-        bucketed all-reduces are captured with the step (backend nccl = RCCL)."""
+        bucketed all-reduces are captured with the step (backend nccl = RCCL).  `dump`: the leg
+        of the headline mode writes its last step for --dump-outputs."""
         if (use_dist and not ddp_graph) or args.clip or args.no_graph:
             return None
         gstep = ua.GraphedTrainStep(model, opt, lossf, img, tgt, grad_sync=sync)
@@ -487,6 +531,9 @@ def main():
             tt = torch.tensor([dt_g], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt_g = tt.item()
+        if dump and args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, "graph_", model, gstep.loss)
+            dumped["hip_graph_replay"] = "graph_*.npy"
         opt.use_device_hyper(False)
         return {"value": args.batch * world * args.steps / dt_g, "unit": "images/s",
                 "ms_per_step": 1e3 * dt_g / args.steps,
@@ -495,10 +542,10 @@ def main():
                 "note": "train step captured once in a HIP graph and replayed (same kernels, "
                         "same order; dropout masks drawn inside the graph)"}
 
-    def guarded_graph_leg(what):
+    def guarded_graph_leg(what, dump=False):
         try:
             with Bailout(240.0, what):
-                return graph_leg()
+                return graph_leg(dump)
         except Exception as e:   # capture refused: keep the eager figures
             if world > 1:        # (a half-captured collective leaves the group unusable: stop here)
                 if result is not None:
@@ -507,7 +554,7 @@ def main():
                 os._exit(0)
             return {"error": f"{type(e).__name__}: {e}"[:300]}
 
-    graph = guarded_graph_leg("graph replay of the data-parallel step")
+    graph = guarded_graph_leg("graph replay of the data-parallel step", dump=True)
     if rank == 0 and graph is not None:
         result["graph_replay"] = graph
         if graph.get("value", 0.0) > result["value"]:
