@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UNET_ABI_VERSION 8
+#define UNET_ABI_VERSION 9
 
 #define UNET_OK 0
 #define UNET_E_INVALID (-1) /* bad argument / unsupported shape */
@@ -726,6 +726,54 @@ int unet_head1x1_in_bwd_bs_b16(const unet_act_src* x, float slope, const float* 
                                const float* w, uint16_t* da, float* dw, float* db,
                                void* workspace, size_t workspace_bytes, int N, int HW, int K,
                                unet_bwd_stats* bs, unet_stream_t stream);
+
+/* ---- autoencoder pretraining step (recon.hip) ------------------------------------------------
+ * The reference's phase 1 of transfer learning (AE_pretrained/README.md) on the same body as the
+ * segmentation net.  x_bf16 selects the storage type of the layer tensors (x->x and da): 0 = fp32,
+ * 1 = bf16 (matmul_precision="bf16"); the arithmetic is fp32 in both cases. */
+
+/* reconstruction_output = Sequential(Conv2d(32, 3, 3, padding=1), Sigmoid())
+ * (AE_pretrained/reconstruction/models/autoencoder.py:377-387, applied at :444): out (NCHW fp32
+ * [N,K,H,W]) = sigmoid(conv3x3(act(x)) + b); x is activated on load as in unet_head1x1_in_fwd
+ * (x->alpha == NULL: a plain activation), the zero padding applied after the activation.
+ * w is OIHW [K][32][3][3]; x->C == 32, K == 3. */
+int unet_recon3x3_fwd(const unet_act_src* x, int x_bf16, float slope, const float* w,
+                      const float* b, float* out_nchw, int N, int H, int W, int K,
+                      unet_stream_t stream);
+size_t unet_recon3x3_bwd_workspace_bytes(int N, int H, int W);
+/* autograd of the same (the Sigmoid and Conv2d backward of loss.backward(), src/train.py:434):
+ * dz = dout * out * (1 - out) formed on load; da = dL/d act(x) (NHWC, the layer tensors' type:
+ * the 3 -> 32 transposed 3x3 conv of dz), dw [K][32][3][3] and db [K] through per-workgroup
+ * partials and a fixed-order double finalize.  bs (nullable): as unet_head1x1_in_bwd_bs, also
+ * leave the InstanceNorm-backward reductions of the layer whose raw output x->x is
+ * (bs->tiles_out summaries per image; 0 = not emitted, run unet_instnorm_lrelu_drop_bwd). */
+int unet_recon3x3_bwd(const unet_act_src* x, int x_bf16, float slope, const float* dout_nchw,
+                      const float* out_nchw, const float* w, void* da, float* dw, float* db,
+                      void* workspace, size_t workspace_bytes, int N, int H, int W, int K,
+                      unet_bwd_stats* bs, unet_stream_t stream);
+
+/* nn.MSELoss() (reduction "mean") of the output against the input image
+ * (AE_pretrained/reconstruction/src/train.py:420-437, called at :531 and :467).  target is the
+ * NCHW fp32 tensor (target_u8 == 0) or the dataset's uint8 NHWC image [N,H,W,3] (target_u8 == 1,
+ * t = v / 255 correctly rounded to fp32: the CPU division of image.float() / 255.0 at :257-266).
+ * loss_out[0] = sum (out - t)^2 / (N*C*H*W); per_image[N] (double) = the per-image sums of
+ * squares (validation's per-image MSE and PSNR, :470-477). */
+size_t unet_mse_loss_workspace_bytes(int N, int C, int H, int W);
+int unet_mse_loss_fwd(const float* out_nchw, const void* target, int target_u8, float* loss_out,
+                      double* per_image, void* workspace, size_t workspace_bytes, int N, int C,
+                      int H, int W, unet_stream_t stream);
+/* dout = upstream[0] * 2 (out - t) / (N*C*H*W); upstream: a device float or NULL (= 1) */
+int unet_mse_loss_grad(const float* out_nchw, const void* target, int target_u8,
+                       const float* upstream, float* dout_nchw, int N, int C, int H, int W,
+                       unet_stream_t stream);
+
+/* optim.Adam(params, lr, weight_decay) (AE_pretrained/reconstruction/src/train.py:377-397;
+ * amsgrad = maximize = False, coupled L2) over n floats: g = grad * grad_scale + wd * p, then
+ * torch's exp_avg / exp_avg_sq / bias-corrected update.  hyper (fp64, device):
+ * {lr, beta1, beta2, eps, weight_decay, grad_scale, step, -}, so a graph-captured step follows the
+ * LR schedule and the bias correction; advance_step != 0 first adds 1 to hyper[6] on the device. */
+int unet_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                   int64_t n, double* hyper, int advance_step, unet_stream_t stream);
 
 #ifdef __cplusplus
 }

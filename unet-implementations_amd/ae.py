@@ -1,0 +1,133 @@
+"""The autoencoder pretraining loop of AE_pretrained/reconstruction/src/train.py on the HIP path
+(`ua.ae`): phase 1 of the reference's transfer-learning recipe, whose checkpoint's encoder
+`UNet.load_pretrained_encoder` loads for phase 2.
+
+Function for function: `create_model` (:340-375), `create_optimizer` (:377-397),
+`create_lr_scheduler` (:399-418), `get_loss_function` (:420-437), `validate` (:440-498),
+`train_one_epoch` (:501-554), `save_checkpoint` (:556-600) and `load_checkpoint`.  The step order
+is the reference's, so `ua.train_step` / `ua.GraphedTrainStep` run it unchanged.
+"""
+import math
+import os
+
+import torch
+
+from .autoencoder import Autoencoder
+from .losses import MSELoss
+from .optim import FusedAdam
+from .train import train_step
+
+
+def create_model(device="cuda"):
+    """The exact configuration built at src/train.py:340-375 (lower dropout than the UNet's)."""
+    model = Autoencoder(in_channels=3, out_channels=3, n_stages=6,
+                        features_per_stage=[32, 64, 128, 256, 512, 512],
+                        kernel_sizes=[[3, 3]] * 6,
+                        strides=[[1, 1], [2, 2], [2, 2], [2, 2], [2, 2], [2, 2]],
+                        n_conv_per_stage=[2] * 6, n_conv_per_stage_decoder=[2] * 5,
+                        conv_bias=True, norm_op=torch.nn.InstanceNorm2d,
+                        norm_op_kwargs={"eps": 1e-5, "affine": True}, dropout_op=None,
+                        nonlin=torch.nn.LeakyReLU, nonlin_kwargs={"inplace": True},
+                        encoder_dropout_rates=[0.0, 0.0, 0.05, 0.1, 0.15, 0.15],
+                        decoder_dropout_rates=[0.15, 0.1, 0.1, 0.05, 0.0])
+    return model.to(device)
+
+
+def create_optimizer(model, lr=1e-3, weight_decay=1e-5):
+    """Adam as at src/train.py:377-397 (defaults from the reference's argument parser)."""
+    return FusedAdam(model.parameters(), lr=lr, weight_decay=weight_decay, model=model)
+
+
+def create_lr_scheduler(optimizer, max_epochs):
+    """Cosine annealing to 1e-6 over the run, stepped per epoch (src/train.py:399-418)."""
+    return torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=max_epochs, eta_min=1e-6)
+
+
+def get_loss_function(device=None, target_layout="nchw"):
+    """nn.MSELoss() (src/train.py:420-437)."""
+    return MSELoss(target_layout=target_layout)
+
+
+def train_one_epoch(model, train_loader, optimizer, loss_function, device, scaler=None):
+    """src/train.py:501-554 without the per-step `loss.item()` sync: the losses are summed on the
+    device and read once at the end."""
+    if scaler is not None:
+        raise NotImplementedError("fp16 GradScaler AMP is not part of the HIP path "
+                                  "(use matmul_precision='bf16')")
+    model.train()
+    total = torch.zeros((), device=device)
+    n = 0
+    for batch in train_loader:
+        images = batch["image"].to(device, non_blocking=True)
+        targets = batch["target"].to(device, non_blocking=True)
+        total += train_step(model, optimizer, loss_function, images, targets)
+        n += 1
+    return (total / max(n, 1)).item()
+
+
+@torch.no_grad()
+def validate(model, val_loader, loss_function, device):
+    """src/train.py:440-498: eval-mode loss averaged over batches; per-image MSE and
+    PSNR = 10 log10(1 / mse) summed over images and divided by the dataset size.  Everything stays
+    on the device (the per-image sums come out of the loss kernel); one sync at the end.
+    Returns (val_loss, {"loss", "mse", "psnr"})."""
+    model.eval()
+    val_loss = torch.zeros((), device=device, dtype=torch.float64)
+    mse_sum = torch.zeros((), device=device, dtype=torch.float64)
+    psnr_sum = torch.zeros((), device=device, dtype=torch.float64)
+    batches = 0
+    for batch in val_loader:
+        images = batch["image"].to(device, non_blocking=True)
+        targets = batch["target"].to(device, non_blocking=True)
+        outputs = model(images)
+        val_loss += loss_function(outputs, targets).double()
+        N, C, H, W = outputs.shape
+        mse = (loss_function.last_per_image / (C * H * W)).float()    # per image, fp32
+        mse_sum += mse.double().sum()
+        psnr_sum += (10 * torch.log10(1.0 / mse)).double().sum()
+        batches += 1
+    ds = getattr(val_loader, "dataset", None)
+    num_samples = len(ds) if ds is not None else None
+    vals = torch.stack([val_loss, mse_sum, psnr_sum]).tolist()
+    if num_samples is None:
+        raise TypeError("validate needs a DataLoader-like object with a .dataset")
+    loss = vals[0] / max(batches, 1)
+    metrics = {"loss": loss, "mse": vals[1] / num_samples, "psnr": vals[2] / num_samples}
+    return loss, metrics
+
+
+def save_checkpoint(model, optimizer, scheduler, epoch, best_loss, output_dir, is_best=False):
+    """Same files and dictionary keys as src/train.py:556-600 (`best_loss`,
+    `config.out_channels`); the config records the model's actual geometry."""
+    ckpt_dir = os.path.join(str(output_dir), "checkpoints")
+    os.makedirs(ckpt_dir, exist_ok=True)
+    n = model.n_stages
+    checkpoint = {
+        "epoch": epoch,
+        "model_state_dict": model.state_dict(),
+        "optimizer_state_dict": optimizer.state_dict(),
+        "scheduler_state_dict": scheduler.state_dict() if scheduler is not None else None,
+        "best_loss": best_loss,
+        "config": {"in_channels": model.in_channels, "out_channels": model.out_channels,
+                   "n_stages": n, "features_per_stage": list(model.features_per_stage),
+                   "kernel_sizes": [[3, 3]] * n, "strides": [[1, 1]] + [[2, 2]] * (n - 1),
+                   "n_conv_per_stage": [2] * n, "n_conv_per_stage_decoder": [2] * (n - 1),
+                   "conv_bias": True, "norm_op_kwargs": {"eps": 1e-5, "affine": True},
+                   "nonlin_kwargs": {"inplace": True}},
+    }
+    path = os.path.join(ckpt_dir, f"checkpoint_epoch_{epoch}.pth")
+    torch.save(checkpoint, path)
+    if is_best:
+        torch.save(checkpoint, os.path.join(str(output_dir), "best_model.pth"))
+    return path
+
+
+def load_checkpoint(path, model, optimizer=None, scheduler=None, device="cuda"):
+    """Resume from a save_checkpoint file; returns (start_epoch, best_loss)."""
+    checkpoint = torch.load(path, map_location=device, weights_only=True)
+    model.load_state_dict(checkpoint["model_state_dict"])
+    if optimizer is not None and checkpoint.get("optimizer_state_dict") is not None:
+        optimizer.load_state_dict(checkpoint["optimizer_state_dict"])
+    if scheduler is not None and checkpoint.get("scheduler_state_dict") is not None:
+        scheduler.load_state_dict(checkpoint["scheduler_state_dict"])
+    return checkpoint["epoch"] + 1, checkpoint.get("best_loss", math.inf)

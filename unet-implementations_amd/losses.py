@@ -96,3 +96,54 @@ class SimpleLoss(nn.Module):
         if dynamic != bool(self.dynamic_weights):
             raise NotImplementedError("empty batch")
         return _LossFunction.apply(input.contiguous().float(), target.contiguous(), mod, cw)
+
+
+class _MSEFunction(torch.autograd.Function):
+    """Forward: the loss and the per-image sums of squares (unet_mse_loss_fwd).  Backward: ONE
+    launch of the gradient kernel with autograd's upstream scalar applied inside it."""
+
+    @staticmethod
+    def forward(ctx, output, target, mod, target_u8):
+        loss, per_image = ops.mse_loss_fwd(output, target, target_u8)
+        mod.last_per_image = per_image      # fp64 [N] on the device (no sync)
+        if ctx.needs_input_grad[0]:
+            ctx.held = (output, target, target_u8)
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        output, target, target_u8 = ctx.held
+        ctx.held = None
+        return ops.mse_loss_grad(output, target, g, target_u8), None, None, None
+
+
+class MSELoss(nn.Module):
+    """`nn.MSELoss()` (reduction "mean") on the HIP path: the autoencoder's loss
+    (AE_pretrained/reconstruction/src/train.py:420-437).  `forward(output[N,C,H,W] fp32, target)`
+    returns a 0-dim fp32 tensor supporting `.backward()`.  The target is the NCHW fp32 tensor, or -
+    with `target_layout="nhwc_u8"` - the dataset's uint8 [N,H,W,3] image itself, read as
+    v / 255 rounded once to fp32 (what the reference's CPU dataset computes for
+    `image.float() / 255.0`: the two forms give the same loss bit for bit).  `last_per_image` keeps the per-image sums of squared differences (fp64,
+    on the device) of the last call."""
+
+    def __init__(self, size_average=None, reduce=None, reduction="mean", target_layout="nchw"):
+        super().__init__()
+        if size_average is not None or reduce is not None or reduction != "mean":
+            raise NotImplementedError("MSELoss on the HIP path implements reduction='mean' "
+                                      "(the reference setting)")
+        if target_layout not in ("nchw", "nhwc_u8"):
+            raise ValueError("target_layout must be 'nchw' or 'nhwc_u8'")
+        self.reduction = reduction
+        self.target_layout = target_layout
+        self.last_per_image = None
+
+    def forward(self, input, target):
+        if not input.is_cuda:
+            raise RuntimeError("unet-implementations_amd.MSELoss runs on MI355X only "
+                               "(no CPU fallback exists)")
+        if input.dim() != 4:
+            raise ValueError("expected an NCHW output")
+        u8 = self.target_layout == "nhwc_u8"
+        if not u8 and target.dtype != torch.float32:
+            target = target.float()
+        return _MSEFunction.apply(input.contiguous().float(), target.contiguous(), self, u8)

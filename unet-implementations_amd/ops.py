@@ -1187,3 +1187,105 @@ def sgd_nesterov_step_dev(params, grads, momentum, hyper, first_step):
 def add_inplace(a, b):
     check(lib().unet_add_inplace(_ptr(a), _ptr(b), a.numel(), _stream()))
     return a
+
+
+# ---- autoencoder pretraining step (recon.hip) ------------------------------------------------
+def recon3x3_fwd(x, slope, w, b):
+    """sigmoid(conv3x3(act(x)) + b) of the autoencoder's reconstruction head: NCHW fp32 [N,3,H,W].
+    x: the last decoder layer's output (ops.Act or a plain NHWC tensor, fp32 or bf16)."""
+    x, rx = _act(x)
+    N, H, W, C = x.shape
+    K = w.shape[0]
+    out = _f32((N, K, H, W), x.x)
+    t0 = _timer.begin() if _timer is not None else None
+    check(lib().unet_recon3x3_fwd(rx, 1 if _is_b16(x.x) else 0, slope, _ptr(w), _ptr(b),
+                                  _ptr(out), N, H, W, K, _stream()))
+    if t0 is not None:
+        _timer.end("recon_fwd", 2.0 * N * H * W * K * C * 9, 1, t0,
+                   nbytes=x.x.element_size() * x.x.numel() + 4.0 * out.numel())
+    return out
+
+
+_recon_ws = {}
+
+
+def recon3x3_bwd(x, slope, dout, out, w, dw, db, nxt=None):
+    """dL/d act(x) (NHWC, x's storage type) of the reconstruction head; dw / db are written.
+    nxt (NextNorm of the layer whose raw output x.x is): also leave the reductions of that layer's
+    InstanceNorm backward (nxt.tiles == 0: not emitted for this call)."""
+    x, rx = _act(x)
+    N, H, W, C = x.shape
+    K = w.shape[0]
+    da = torch.empty_like(x.x)
+    key = (N, H, W, x.x.device)
+    ws = _recon_ws.get(key)
+    if ws is None:
+        ws = _recon_ws[key] = _ws(lib().unet_recon3x3_bwd_workspace_bytes(N, H, W), x.x)
+    bs = nxt.c_struct() if nxt is not None else None
+    t0 = _timer.begin() if _timer is not None else None
+    check(lib().unet_recon3x3_bwd(rx, 1 if _is_b16(x.x) else 0, slope, _ptr(dout), _ptr(out),
+                                  _ptr(w), _ptr(da), _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), N,
+                                  H, W, K, ctypes.byref(bs) if bs is not None else None,
+                                  _stream()))
+    if nxt is not None:
+        nxt.tiles = bs.tiles_out
+    if t0 is not None:   # x in, da out, dout + out in
+        _timer.end("recon_bwd", 4.0 * N * H * W * K * C * 9, 2, t0,
+                   nbytes=da.element_size() * 2.0 * da.numel() + 8.0 * dout.numel())
+    return da
+
+
+def _mse_target(out, target, target_u8):
+    N, C, H, W = out.shape
+    if target_u8:
+        if target.dtype != torch.uint8 or tuple(target.shape) != (N, H, W, C):
+            raise TypeError("a uint8 target is the [N,H,W,3] image of the output's size")
+    elif target.dtype != torch.float32 or target.shape != out.shape:
+        raise TypeError("the target must be an fp32 tensor of the output's shape")
+    return target.contiguous()
+
+
+def mse_loss_fwd(out, target, target_u8=False):
+    """(loss fp32 [1], per-image sums of squares fp64 [N]) of nn.MSELoss() on the device."""
+    N, C, H, W = out.shape
+    target = _mse_target(out, target, target_u8)
+    loss = _f32((1,), out)
+    per_image = torch.empty((N,), dtype=torch.float64, device=out.device)
+    ws = _ws(lib().unet_mse_loss_workspace_bytes(N, C, H, W), out)
+    t0 = _timer.begin() if _timer is not None else None
+    check(lib().unet_mse_loss_fwd(_ptr(out), _ptr(target), 1 if target_u8 else 0, _ptr(loss),
+                                  per_image.data_ptr(), _ptr(ws), ws.numel(), N, C, H, W,
+                                  _stream()))
+    if t0 is not None:
+        _timer.end("mse_loss", 0.0, 2, t0, nbytes=4.0 * out.numel() + target.element_size() *
+                   target.numel())
+    return loss, per_image
+
+
+def mse_loss_grad(out, target, upstream=None, target_u8=False):
+    """dL/dout = upstream * 2 (out - t) / numel; upstream: a device scalar (autograd's) or None."""
+    N, C, H, W = out.shape
+    target = _mse_target(out, target, target_u8)
+    dout = torch.empty_like(out)
+    if upstream is not None:
+        upstream = upstream.reshape(1).float().contiguous()
+    t0 = _timer.begin() if _timer is not None else None
+    check(lib().unet_mse_loss_grad(_ptr(out), _ptr(target), 1 if target_u8 else 0, _ptr(upstream),
+                                   _ptr(dout), N, C, H, W, _stream()))
+    if t0 is not None:
+        _timer.end("mse_grad", 0.0, 1, t0, nbytes=8.0 * out.numel() + target.element_size() *
+                   target.numel())
+    return dout
+
+
+def adam_step(params, grads, exp_avg, exp_avg_sq, hyper, advance_step):
+    """torch.optim.Adam's update over flat fp32 tensors; hyper: the fp64 [8] device tensor
+    {lr, beta1, beta2, eps, weight_decay, grad_scale, step, -} (advance_step: step += 1 first)."""
+    n = params.numel()
+    if hyper.dtype != torch.float64 or not hyper.is_cuda or hyper.numel() < 8:
+        raise TypeError("hyper must be an fp64 [8] device tensor")
+    t0 = _timer.begin() if _timer is not None else None
+    check(lib().unet_adam_step(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n,
+                               hyper.data_ptr(), 1 if advance_step else 0, _stream()))
+    if t0 is not None:   # p, g, m, v in; p, m, v out
+        _timer.end("adam", 0.0, 2 if advance_step else 1, t0, nbytes=4.0 * 7 * n)

@@ -11,7 +11,7 @@ import torch
 
 from . import ops
 from .losses import SimpleLoss
-from .optim import FusedSGD
+from .optim import FusedAdam, FusedSGD
 from .unet import UNet
 
 
@@ -88,8 +88,8 @@ class GraphedTrainStep:
     def __init__(self, model, optimizer, loss_function, images, masks, warmup=2, grad_sync=None):
         if not images.is_cuda:
             raise RuntimeError("GraphedTrainStep needs ROCm tensors (no CPU fallback exists)")
-        if not isinstance(optimizer, FusedSGD):
-            raise TypeError("GraphedTrainStep needs the FusedSGD optimizer")
+        if not isinstance(optimizer, (FusedSGD, FusedAdam)):
+            raise TypeError("GraphedTrainStep needs the FusedSGD or FusedAdam optimizer")
         if grad_sync is None and model.grad_ready_hook is not None:
             raise RuntimeError("the model has a data-parallel gradient hook: pass its "
                                "GradBucketAllReduce as grad_sync so the exchange is captured")
@@ -107,11 +107,9 @@ class GraphedTrainStep:
         self.masks = masks.detach().clone()
         arena, _ = model.flat_parameters()
         keep_arena = arena.detach().clone()
-        # the momentum the optimizer holds NOW (zeros for a fresh one, the loaded buffers after
-        # load_state_dict) is what the first replay must start from
-        optimizer.adopt_flat_momentum()
-        keep_buf = optimizer._flat_buf.detach().clone()
-        keep_steps = optimizer._steps
+        # the momentum (Adam: moments and step count) the optimizer holds NOW (zeros for a fresh
+        # one, the loaded buffers after load_state_dict) is what the first replay must start from
+        keep_opt = optimizer._snapshot()
         optimizer.use_device_hyper(True)
         cur = torch.cuda.current_stream()
         side = torch.cuda.Stream()
@@ -135,8 +133,7 @@ class GraphedTrainStep:
         # undo the throw-away steps (the captured step itself did not execute)
         with torch.no_grad():
             arena.copy_(keep_arena)
-            optimizer._flat_buf.copy_(keep_buf)
-        optimizer._steps = keep_steps
+            optimizer._restore(keep_opt)
 
     def __call__(self, images, masks):
         if images.shape != self.images.shape or masks.shape != self.masks.shape:
@@ -148,7 +145,7 @@ class GraphedTrainStep:
             self.masks.copy_(masks, non_blocking=True)
         self.optimizer.sync_device_hyper()
         self.graph.replay()
-        self.optimizer._steps += 1
+        self.optimizer._advanced()      # (FusedAdam: the replay advanced the device step count)
         return self.loss
 
 

@@ -313,8 +313,7 @@ class UNet(nn.Module):
                         features_per_stage[lvl], kernel_sizes[lvl],
                         n_convs=n_conv_per_stage_decoder[lvl],
                         spatial_dropout_rate=decoder_dropout_rates[s], **common))
-        self.segmentation_output = nn.Conv2d(features_per_stage[0], num_classes, kernel_size=1,
-                                             stride=1, padding=0, bias=True)
+        self._build_head(features_per_stage[0], num_classes)
         self.initialize_weights()
         self._plan = None
         self._arena = None       # flat fp32 parameter arena (parameters are views into it)
@@ -347,6 +346,50 @@ class UNet(nn.Module):
     def _build_bottleneck(self, common):
         """Hook for variants that add modules between encoder and decoder (CLIPUNet)."""
 
+    # -- the head: a model-level hook of the fused walk (the Autoencoder plugs in its own) -------
+    def _build_head(self, in_features, out_channels):
+        self.segmentation_output = nn.Conv2d(in_features, out_channels, kernel_size=1, stride=1,
+                                             padding=0, bias=True)
+
+    def _head_module(self):
+        return self.segmentation_output
+
+    def _check_head(self):
+        head = self.segmentation_output
+        if _as_int(head.kernel_size) != 1 or head.in_channels != 32 or head.out_channels != 3:
+            raise NotImplementedError("the HIP head kernel is the 32 -> 3 1x1 convolution")
+
+    def _head_fwd(self, ctx, cur, fused, slope, need_grad):
+        """NCHW fp32 output of the head over the last decoder layer's output `cur` (ops.Act on the
+        fused pipeline, the activated NHWC tensor otherwise)."""
+        head = self.segmentation_output
+        hw = head.weight.detach().view(head.out_channels, -1)
+        if fused:
+            return ops.head1x1_in_fwd(cur, slope, hw, head.bias.detach())
+        return ops.head1x1_fwd(cur, hw, head.bias.detach())
+
+    def _head_bwd(self, ctx, saved, dout, fused, slope, gv):
+        """dL/da of the last decoder layer's output; writes the head's weight gradients."""
+        head = self.segmentation_output
+        hw = head.weight.detach().view(head.out_channels, -1)
+        if fused:
+            # g is the final gradient of the last decoder layer's output: the head's backward
+            # also leaves the reductions of that layer's InstanceNorm backward (NextNorm)
+            pr_ = saved[-1]
+            pl_ = pr_["layer"]
+            nxt_h = ops.NextNorm(pr_["y"], pr_["st"], pl_.norm.weight.detach(),
+                                 pl_.norm.bias.detach(), pr_["mask"], pl_.slope) \
+                if isinstance(ctx.last, ops.Act) and ctx.last.alpha is not None else None
+            g = ops.head1x1_in_bwd(ctx.last, slope, dout, hw,
+                                   gv(head.weight).view(head.out_channels, -1), gv(head.bias),
+                                   nxt=nxt_h)
+            if nxt_h is not None and nxt_h.tiles > 0:
+                pr_["nxt"] = nxt_h
+        else:
+            g = ops.head1x1_bwd(saved[-1]["a"], dout, hw,
+                                gv(head.weight).view(head.out_channels, -1), gv(head.bias))
+        return g
+
     # -- reference: Our_UNet/models/unet.py:386-397 --------------------------------------
     def initialize_weights(self):
         for m in self.modules():
@@ -369,9 +412,7 @@ class UNet(nn.Module):
                for i, b in enumerate(self.encoder_stages)]
         dec = [self._block_layers(b.conv_block, True, f"decoder_stages.{i}.conv_block")
                for i, b in enumerate(self.decoder_stages)]
-        head = self.segmentation_output
-        if _as_int(head.kernel_size) != 1 or head.in_channels != 32 or head.out_channels != 3:
-            raise NotImplementedError("the HIP head kernel is the 32 -> 3 1x1 convolution")
+        self._check_head()
         if enc[0][0].stride != 1:
             raise NotImplementedError("first encoder conv must be stride 1")
         self._plan = (enc, dec)
@@ -501,7 +542,7 @@ class UNet(nn.Module):
         feature map."""
         inner = self.__dict__.get("_inner_modules")
         if inner is None:
-            ok = {id(self), id(self.segmentation_output), id(self.encoder_stages),
+            ok = {id(self), id(self._head_module()), id(self.encoder_stages),
                   id(self.decoder_stages)}
             ok.update(id(m) for m in self.encoder_stages)
             for d in self.decoder_stages:
@@ -799,13 +840,8 @@ class _UNetFunction(torch.autograd.Function):
                     cur = run_layer(l, up, skip) if li == 0 else run_layer(l, cur, None)
             _fire_forward_hooks([model.decoder_stages[di], model.decoder_stages[di].conv_block],
                                 lambda: stage_output(cur))
-        head = model.segmentation_output
-        hw = head.weight.detach().view(head.out_channels, -1)
-        if fused:
-            logits = ops.head1x1_in_fwd(cur, slope, hw, head.bias.detach())
-        else:
-            logits = ops.head1x1_fwd(cur, hw, head.bias.detach())
-        _fire_forward_hooks([head], lambda: logits)
+        logits = model._head_fwd(ctx, cur, fused, slope, need_grad)
+        _fire_forward_hooks([model._head_module()], lambda: logits)
         if need_grad:
             ctx.model = model
             ctx.saved = saved
@@ -841,29 +877,13 @@ class _UNetFunction(torch.autograd.Function):
                 "added.  Clear model.grad_ready_hook for the accumulation micro-steps, or call "
                 "optimizer.zero_grad() (set_to_none=True) before each backward.")
         touched = set()      # ids of parameters whose gradient this backward produced
-        head = model.segmentation_output
+        head = model._head_module()
         fused, slope = ctx.fused, ctx.slope
         b16_bwd = ctx.bf16 == "bf16"
         x3_bwd = ctx.fused and ctx.bf16 == "bf16x3"
-        hw = head.weight.detach().view(head.out_channels, -1)
-        if fused:
-            # g is the final gradient of the last decoder layer's output: the head's backward
-            # also leaves the reductions of that layer's InstanceNorm backward (NextNorm)
-            pr_ = saved[-1]
-            pl_ = pr_["layer"]
-            nxt_h = ops.NextNorm(pr_["y"], pr_["st"], pl_.norm.weight.detach(),
-                                 pl_.norm.bias.detach(), pr_["mask"], pl_.slope) \
-                if isinstance(ctx.last, ops.Act) and ctx.last.alpha is not None else None
-            g = ops.head1x1_in_bwd(ctx.last, slope, dlogits, hw,
-                                   gv(head.weight).view(head.out_channels, -1), gv(head.bias),
-                                   nxt=nxt_h)
-            if nxt_h is not None and nxt_h.tiles > 0:
-                pr_["nxt"] = nxt_h
-        else:
-            g = ops.head1x1_bwd(saved[-1]["a"], dlogits, hw,
-                                gv(head.weight).view(head.out_channels, -1), gv(head.bias))
+        g = model._head_bwd(ctx, saved, dlogits, fused, slope, gv)
         ctx.last = None
-        touched.update(id(q) for q in (head.weight, head.bias))
+        touched.update(id(q) for q in head.parameters())
 
         idx = len(saved) - 1
         skip_grads = {}
