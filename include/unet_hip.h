@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UNET_ABI_VERSION 9
+#define UNET_ABI_VERSION 10
 
 #define UNET_OK 0
 #define UNET_E_INVALID (-1) /* bad argument / unsupported shape */
@@ -774,6 +774,38 @@ int unet_mse_loss_grad(const float* out_nchw, const void* target, int target_u8,
  * LR schedule and the bias correction; advance_step != 0 first adds 1 to hyper[6] on the device. */
 int unet_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
                    int64_t n, double* hyper, int advance_step, unet_stream_t stream);
+
+/* ---- SSIM (ssim.hip) ---------------------------------------------------------------------------
+ * The 11-tap Gaussian-window SSIM of the reference's reconstruction metrics and SSIM loss over
+ * pred (NCHW fp32 [N,C,H,W]) and target: the NCHW fp32 tensor (target_u8 == 0) or the dataset's
+ * uint8 NHWC image [N,H,W,3] (target_u8 == 1, t = v / 255 rounded once to fp32, as
+ * unet_mse_loss_fwd).  gauss11: 11 host floats, the 1-D window (the 2-D window is its outer
+ * product); c1, c2: the stabilisers ((0.01 max_val)^2, (0.03 max_val)^2).  The window moments are
+ * taken with zero padding outside the image (conv2d(padding=5)).  Any H, W >= 1. */
+
+/* calculate_ssim / calculate_psnr / evaluate_reconstructions
+ * (AE_pretrained/reconstruction/utils/metrics.py:15-147; src/evaluate.py:268-377) and the forward
+ * of SSIMLoss / ReconstructionLoss (models/losses.py:12-79, :178-245).  One read of both images:
+ * ssim_per_image[N] (double) = the mean of the SSIM map over C, H, W; sq_per_image[N] (double) =
+ * the sum of (pred - t)^2 (MSE and PSNR).  loss_out (nullable, fp32 [1]) =
+ * w_ssim * (1 - mean SSIM) + w_mse * sum sq / (N*C*H*W).  Per-workgroup partials and a
+ * fixed-order finalize whose order depends on (C, H, W) only: an image's values are bit-identical
+ * in any batch. */
+size_t unet_ssim_workspace_bytes(int N, int C, int H, int W);
+int unet_ssim_fwd(const float* pred_nchw, const void* target, int target_u8, const float* gauss11,
+                  float c1, float c2, double* ssim_per_image, double* sq_per_image,
+                  float* loss_out, double w_ssim, double w_mse, void* workspace,
+                  size_t workspace_bytes, int N, int C, int H, int W, unet_stream_t stream);
+/* autograd of L = up * [w_ssim * (1 - mean SSIM) + w_mse * mean (pred - t)^2] (SSIMLoss /
+ * ReconstructionLoss backward, models/losses.py:54-79, :226-245) in one launch: dpred (NCHW fp32).
+ * upstream_per_image == 0: the means run over all N*C*H*W elements and up = upstream[0]
+ * (size_average=True); 1: over each image's C*H*W and up = upstream[n] (size_average=False).
+ * upstream: a device float array or NULL (= 1; not with upstream_per_image).  No saved maps: the
+ * moments are recomputed on a 10-pixel halo. */
+int unet_ssim_grad(const float* pred_nchw, const void* target, int target_u8,
+                   const float* gauss11, float c1, float c2, const float* upstream,
+                   int upstream_per_image, double w_ssim, double w_mse, float* dpred_nchw, int N,
+                   int C, int H, int W, unet_stream_t stream);
 
 #ifdef __cplusplus
 }

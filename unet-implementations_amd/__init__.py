@@ -7,8 +7,9 @@ root: `import unet_implementations_amd as ua`.
 """
 from . import _lib, ops  # noqa: F401
 from ._lib import LIB_PATH, UNetHipError, build, lib  # noqa: F401
-from .losses import MSELoss, SimpleLoss  # noqa: F401
-from .metrics import SegmentationMetrics  # noqa: F401
+from .losses import MSELoss, ReconstructionLoss, SimpleLoss, SSIMLoss  # noqa: F401
+from .metrics import (SegmentationMetrics, calculate_psnr, calculate_ssim,  # noqa: F401
+                      evaluate_reconstructions)
 from .optim import FusedAdam, FusedSGD  # noqa: F401
 from .train import (create_lr_scheduler, create_model, create_optimizer,  # noqa: F401
                     get_loss_function, load_checkpoint, save_checkpoint, train_one_epoch,
@@ -18,6 +19,6 @@ from .unet import ConvBlock, SpatialDropout2d, UNet, UpBlock  # noqa: F401
 from .autoencoder import Autoencoder  # noqa: F401
 from . import ae  # noqa: F401
 
-__all__ = ["UNet", "Autoencoder", "CLIPUNet", "ConvBlock", "UpBlock", "SpatialDropout2d", "SimpleLoss", "MSELoss", "SegmentationMetrics", "FusedSGD", "FusedAdam", "ae",
+__all__ = ["UNet", "Autoencoder", "CLIPUNet", "ConvBlock", "UpBlock", "SpatialDropout2d", "SimpleLoss", "MSELoss", "SSIMLoss", "ReconstructionLoss", "calculate_psnr", "calculate_ssim", "evaluate_reconstructions", "SegmentationMetrics", "FusedSGD", "FusedAdam", "ae",
            "create_model", "create_optimizer", "create_lr_scheduler", "get_loss_function",
            "train_step", "GraphedTrainStep", "train_one_epoch", "save_checkpoint", "load_checkpoint", "validate", "predict_masks", "ops", "build", "lib", "UNetHipError", "LIB_PATH"]

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UNET_HIP_LIB") or os.path.join(_HERE, "libunet_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 
-ABI_VERSION = 9      # UNET_ABI_VERSION of include/unet_hip.h this binding was written against
+ABI_VERSION = 10     # UNET_ABI_VERSION of include/unet_hip.h this binding was written against
 
 _c = ctypes
 _p = _c.c_void_p
@@ -184,6 +184,11 @@ SIGNATURES = {
     "unet_mse_loss_fwd": (_i, [_p, _p, _i, _p, _p, _p, _sz, _i, _i, _i, _i, _p]),
     "unet_mse_loss_grad": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _p]),
     "unet_adam_step": (_i, [_p, _p, _p, _p, _i64, _p, _i, _p]),
+    "unet_ssim_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "unet_ssim_fwd": (_i, [_p, _p, _i, _c.POINTER(_f), _f, _f, _p, _p, _p, _c.c_double,
+                           _c.c_double, _p, _sz, _i, _i, _i, _i, _p]),
+    "unet_ssim_grad": (_i, [_p, _p, _i, _c.POINTER(_f), _f, _f, _p, _i, _c.c_double, _c.c_double,
+                            _p, _i, _i, _i, _i, _p]),
 }
 
 _lib = None

@@ -4,7 +4,8 @@
 
 Function for function: `create_model` (:340-375), `create_optimizer` (:377-397),
 `create_lr_scheduler` (:399-418), `get_loss_function` (:420-437), `validate` (:440-498),
-`train_one_epoch` (:501-554), `save_checkpoint` (:556-600) and `load_checkpoint`.  The step order
+`train_one_epoch` (:501-554), `save_checkpoint` (:556-600) and `load_checkpoint`; and
+`evaluate_reconstruction_quality` of src/evaluate.py:268-377.  The step order
 is the reference's, so `ua.train_step` / `ua.GraphedTrainStep` run it unchanged.
 """
 import math
@@ -12,6 +13,7 @@ import os
 
 import torch
 
+from . import ops
 from .autoencoder import Autoencoder
 from .losses import MSELoss
 from .optim import FusedAdam
@@ -94,6 +96,39 @@ def validate(model, val_loader, loss_function, device):
     loss = vals[0] / max(batches, 1)
     metrics = {"loss": loss, "mse": vals[1] / num_samples, "psnr": vals[2] / num_samples}
     return loss, metrics
+
+
+@torch.no_grad()
+def evaluate_reconstruction_quality(model, test_loader, device, output_dir=None,
+                                    visualize_samples=0):
+    """src/evaluate.py:268-377: eval mode, per-image MSE, PSNR and SSIM (calculate_psnr /
+    calculate_ssim) summed over the test set and divided by the number of images.  One fused
+    forward per batch gives all three; the sums stay on the device and are read once at the end.
+    Returns {"mse", "psnr", "ssim", "num_samples"}.  The reference's comparison images need cv2:
+    `visualize_samples > 0` is not supported, and nothing is written to `output_dir`."""
+    if visualize_samples > 0:
+        raise NotImplementedError("reconstruction visualisations are not part of the HIP path "
+                                  "(use visualize_samples=0)")
+    model.eval()
+    sums = torch.zeros(3, device=device, dtype=torch.float64)
+    num_samples = 0
+    for batch in test_loader:
+        images = batch["image"].to(device, non_blocking=True)
+        targets = batch["target"].to(device, non_blocking=True)
+        recon = model(images).contiguous().float()
+        u8 = targets.dtype == torch.uint8
+        if not u8 and targets.dtype != torch.float32:
+            targets = targets.float()
+        _, ssim, sq = ops.ssim_fwd(recon, targets.contiguous(), u8, want_loss=False)
+        N, C, H, W = recon.shape
+        mse = (sq / (C * H * W)).float()
+        psnr = 10 * torch.log10(1.0 / torch.clamp(mse, min=1e-10))
+        sums += torch.stack([mse.double().sum(), psnr.double().sum(), ssim.float().double().sum()])
+        num_samples += N
+    if num_samples == 0:
+        raise ValueError("evaluate_reconstruction_quality: empty test loader")
+    mse, psnr, ssim = (v / num_samples for v in sums.tolist())
+    return {"mse": mse, "psnr": psnr, "ssim": ssim, "num_samples": num_samples}
 
 
 def save_checkpoint(model, optimizer, scheduler, epoch, best_loss, output_dir, is_best=False):

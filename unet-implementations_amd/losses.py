@@ -147,3 +147,106 @@ class MSELoss(nn.Module):
         if not u8 and target.dtype != torch.float32:
             target = target.float()
         return _MSEFunction.apply(input.contiguous().float(), target.contiguous(), self, u8)
+
+
+class _SSIMFunction(torch.autograd.Function):
+    """Forward: one fused pass for w_ssim * (1 - SSIM) + w_mse * MSE and the per-image SSIM and
+    sums of squares (unet_ssim_fwd).  Backward: ONE launch of the gradient kernel with both weights
+    and autograd's upstream (a scalar, or one value per image) applied inside it."""
+
+    @staticmethod
+    def forward(ctx, output, target, mod, target_u8, w_ssim, w_mse, per_image):
+        loss, ssim, sq = ops.ssim_fwd(output, target, target_u8, w_ssim=w_ssim, w_mse=w_mse,
+                                      want_loss=not per_image)
+        mod.last_ssim_per_image = ssim      # fp64 [N] on the device (no sync)
+        mod.last_per_image = sq
+        if ctx.needs_input_grad[0]:
+            ctx.held = (output, target, target_u8, w_ssim, w_mse, per_image)
+        if per_image:
+            return (1.0 - ssim).float()
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        output, target, target_u8, w_ssim, w_mse, per_image = ctx.held
+        ctx.held = None
+        d = ops.ssim_grad(output, target, g, per_image, target_u8, w_ssim=w_ssim, w_mse=w_mse)
+        return d, None, None, None, None, None, None
+
+
+def _check_input(name, input, target_layout):
+    if not input.is_cuda:
+        raise RuntimeError(f"unet-implementations_amd.{name} runs on MI355X only "
+                           "(no CPU fallback exists)")
+    if input.dim() != 4:
+        raise ValueError("expected an NCHW output")
+    return input.contiguous().float()
+
+
+class SSIMLoss(nn.Module):
+    """`SSIMLoss` (AE_pretrained/reconstruction/models/losses.py:178-245) on the HIP path:
+    1 - SSIM with the 11-tap Gaussian window (sigma 1.5), C1 = 0.01^2, C2 = 0.03^2, zero padding.
+    `size_average=True` returns a 0-dim fp32 tensor (1 - the mean SSIM over N*C*H*W);
+    `size_average=False` one value per image [N].  The reference's constructor raises (its window
+    builder calls torch.exp on a Python float); this implements the window it evidently intends,
+    which equals utils/metrics.py's gaussian_kernel(11, 1.5).  `target_layout` as `MSELoss`.
+    `last_ssim_per_image` / `last_per_image` keep the per-image SSIM and sums of squared
+    differences (fp64, on the device) of the last call."""
+
+    def __init__(self, window_size=11, size_average=True, target_layout="nchw"):
+        super().__init__()
+        if window_size != 11:
+            raise NotImplementedError("the HIP SSIM kernels implement window_size=11")
+        if target_layout not in ("nchw", "nhwc_u8"):
+            raise ValueError("target_layout must be 'nchw' or 'nhwc_u8'")
+        self.window_size = window_size
+        self.size_average = size_average
+        self.channel = 3
+        self.target_layout = target_layout
+        self.last_ssim_per_image = None
+        self.last_per_image = None
+
+    def forward(self, output, target):
+        output = _check_input("SSIMLoss", output, self.target_layout)
+        u8 = self.target_layout == "nhwc_u8"
+        if not u8 and target.dtype != torch.float32:
+            target = target.float()
+        return _SSIMFunction.apply(output, target.contiguous(), self, u8, 1.0, 0.0,
+                                   not self.size_average)
+
+
+class ReconstructionLoss(nn.Module):
+    """`ReconstructionLoss` (AE_pretrained/reconstruction/models/losses.py:12-79) on the HIP path:
+    mse_weight * MSE + ssim_weight * (1 - SSIM), a 0-dim fp32 tensor.  With ssim_weight > 0 the
+    loss is one fused forward (two launches) and one gradient launch; with ssim_weight == 0 it runs
+    exactly `MSELoss`'s launches (the same bits).  The perceptual term needs VGG16 weights and is
+    not implemented.  `target_layout` as `MSELoss`; `last_per_image` keeps the per-image sums of
+    squared differences (fp64, on the device) of the last call."""
+
+    def __init__(self, mse_weight=1.0, perceptual_weight=0.0, ssim_weight=0.0,
+                 perceptual_layers=None, target_layout="nchw"):
+        super().__init__()
+        if perceptual_weight > 0:
+            raise NotImplementedError("the perceptual (VGG16) term is not part of the HIP path")
+        self.mse_weight = mse_weight
+        self.perceptual_weight = perceptual_weight
+        self.ssim_weight = ssim_weight
+        self.target_layout = target_layout
+        self.mse_loss = MSELoss(target_layout=target_layout)
+        self.perceptual_loss = None
+        self.ssim_loss = SSIMLoss(target_layout=target_layout) if ssim_weight > 0 else None
+        self.last_per_image = None
+
+    def forward(self, output, target):
+        if self.ssim_loss is None:
+            mse = self.mse_loss(output, target)
+            self.last_per_image = self.mse_loss.last_per_image
+            return mse if self.mse_weight == 1.0 else self.mse_weight * mse
+        output = _check_input("ReconstructionLoss", output, self.target_layout)
+        u8 = self.target_layout == "nhwc_u8"
+        if not u8 and target.dtype != torch.float32:
+            target = target.float()
+        loss = _SSIMFunction.apply(output, target.contiguous(), self.ssim_loss, u8,
+                                   float(self.ssim_weight), float(self.mse_weight), False)
+        self.last_per_image = self.ssim_loss.last_per_image
+        return loss

@@ -8,6 +8,10 @@ and loops over classes in numpy (`_update_single`, :59-91); here one launch of
 {intersection, predicted, labelled} x class (ignore pixels masked out) and they are summed in
 an int64 device tensor - no host sync until a `compute_*` method (or an accumulator) is read.
 
+The reconstruction metrics of AE_pretrained/reconstruction/utils/metrics.py (`calculate_psnr`,
+`calculate_ssim`, `evaluate_reconstructions`) keep the reference's signatures and return shapes;
+each is one fused forward (`unet_ssim_fwd`, or `unet_mse_loss_fwd` for PSNR alone).
+
 `update_from_logits(logits, target)` takes the network output itself (argmax inside the
 kernel); `update(pred, target)` takes class maps like the reference's method (device tensors;
 routed through the same kernel as one-hot scores).  Targets hold {0, 1, 2, ignore_index}
@@ -145,3 +149,66 @@ class SegmentationMetrics:
                 "precision": self.compute_precision(cls), "recall": self.compute_recall(cls),
                 "f1_score": self.compute_f1_score(cls)}
         return results
+
+
+# ---- reconstruction metrics (reference: AE_pretrained/reconstruction/utils/metrics.py) ----------
+def _recon_operands(name, pred, target):
+    if not torch.is_tensor(pred) or not pred.is_cuda:
+        raise RuntimeError(f"unet-implementations_amd.{name} runs on MI355X only "
+                           "(no CPU fallback exists)")
+    if pred.dim() != 4:
+        raise ValueError("expected NCHW predictions")
+    pred = pred.contiguous().float()
+    u8 = target.dtype == torch.uint8        # the dataset's [N,H,W,3] image itself
+    if not u8 and target.dtype != torch.float32:
+        target = target.float()
+    return pred, target.contiguous(), u8
+
+
+def _psnr(mse, max_val):
+    return 10 * torch.log10(max_val ** 2 / torch.clamp(mse, min=1e-10))
+
+
+def calculate_psnr(pred, target, max_val=1.0):
+    """Per-image PSNR [B] (fp32) of (B, C, H, W) images (utils/metrics.py:15-41)."""
+    pred, target, u8 = _recon_operands("calculate_psnr", pred, target)
+    _, sq = ops.mse_loss_fwd(pred, target, u8)
+    C, H, W = pred.shape[1:]
+    return _psnr((sq / (C * H * W)).float(), max_val)
+
+
+def _check_kernel(kernel_size):
+    if kernel_size % 2 == 0:     # the reference's gaussian_kernel bumps an even size
+        kernel_size += 1
+    if kernel_size != 11:
+        raise NotImplementedError("the HIP SSIM kernels implement an 11-tap window")
+
+
+def _reduce(v, reduction):
+    if reduction == "mean":
+        return v.mean()
+    if reduction == "sum":
+        return v.sum()
+    return v
+
+
+def calculate_ssim(pred, target, kernel_size=11, sigma=1.5, max_val=1.0, reduction="none"):
+    """SSIM per image [B] (fp32; or its mean / sum) with the Gaussian window of gaussian_kernel
+    (kernel_size, sigma), zero padding, C1 = (0.01 max_val)^2, C2 = (0.03 max_val)^2
+    (utils/metrics.py:76-147)."""
+    _check_kernel(kernel_size)
+    pred, target, u8 = _recon_operands("calculate_ssim", pred, target)
+    _, ssim, _ = ops.ssim_fwd(pred, target, u8, window=ops.gaussian_window(11, float(sigma)),
+                              c1=(0.01 * max_val) ** 2, c2=(0.03 * max_val) ** 2,
+                              want_loss=False)
+    return _reduce(ssim.float(), reduction)
+
+
+def evaluate_reconstructions(pred, target):
+    """{"psnr", "ssim", "mse"}, each per image [B] fp32, from one fused pass
+    (utils/metrics.py:150-181)."""
+    pred, target, u8 = _recon_operands("evaluate_reconstructions", pred, target)
+    _, ssim, sq = ops.ssim_fwd(pred, target, u8, want_loss=False)
+    C, H, W = pred.shape[1:]
+    mse = (sq / (C * H * W)).float()
+    return {"psnr": _psnr(mse, 1.0), "ssim": ssim.float(), "mse": mse}

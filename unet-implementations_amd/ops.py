@@ -7,6 +7,7 @@ launches asynchronously on `torch.cuda.current_stream()`.
 import torch
 
 import ctypes
+import functools
 
 from ._lib import ActSrc, BwdStats, check, lib
 
@@ -1289,3 +1290,66 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, hyper, advance_step):
                                hyper.data_ptr(), 1 if advance_step else 0, _stream()))
     if t0 is not None:   # p, g, m, v in; p, m, v out
         _timer.end("adam", 0.0, 2 if advance_step else 1, t0, nbytes=4.0 * 7 * n)
+
+
+# ---- SSIM (unet_ssim_*) -------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def gaussian_window(size=11, sigma=1.5):
+    """The 1-D window of the reference's gaussian_kernel (utils/metrics.py:44-73): fp32 exp of the
+    centred coordinates, normalised by its sum (the 2-D window is its outer product)."""
+    coords = torch.arange(size).float() - (size - 1) / 2
+    g = torch.exp(-(coords ** 2) / (2 * sigma ** 2))
+    return tuple((g / g.sum()).tolist())
+
+
+def _gauss11(window):
+    w = [float(v) for v in window]
+    if len(w) != 11:
+        raise ValueError("the SSIM kernels take an 11-tap window")
+    return (ctypes.c_float * 11)(*w)
+
+
+def ssim_fwd(pred, target, target_u8=False, window=None, c1=1e-4, c2=9e-4, w_ssim=1.0,
+             w_mse=0.0, want_loss=True):
+    """(loss fp32 [1] or None, per-image mean SSIM fp64 [N], per-image sums of squares fp64 [N])
+    from one read of both images; loss = w_ssim * (1 - mean SSIM) + w_mse * mean sq."""
+    N, C, H, W = pred.shape
+    target = _mse_target(pred, target, target_u8)
+    g = _gauss11(window if window is not None else gaussian_window())
+    loss = _f32((1,), pred) if want_loss else None
+    ssim = torch.empty((N,), dtype=torch.float64, device=pred.device)
+    sq = torch.empty((N,), dtype=torch.float64, device=pred.device)
+    ws = _ws(lib().unet_ssim_workspace_bytes(N, C, H, W), pred)
+    t0 = _timer.begin() if _timer is not None else None
+    check(lib().unet_ssim_fwd(_ptr(pred), _ptr(target), 1 if target_u8 else 0, g, c1, c2,
+                              ssim.data_ptr(), sq.data_ptr(), _ptr(loss), w_ssim, w_mse, _ptr(ws),
+                              ws.numel(), N, C, H, W, _stream()))
+    if t0 is not None:
+        _timer.end("ssim_fwd", 0.0, 2, t0, nbytes=4.0 * pred.numel() + target.element_size() *
+                   target.numel())
+    return loss, ssim, sq
+
+
+def ssim_grad(pred, target, upstream=None, upstream_per_image=False, target_u8=False, window=None,
+              c1=1e-4, c2=9e-4, w_ssim=1.0, w_mse=0.0):
+    """dL/dpred of L = up * [w_ssim * (1 - mean SSIM) + w_mse * mean (pred - t)^2]; upstream: a
+    device scalar (means over the batch) or, with upstream_per_image, a device [N] (means per
+    image), or None (= 1)."""
+    N, C, H, W = pred.shape
+    target = _mse_target(pred, target, target_u8)
+    g = _gauss11(window if window is not None else gaussian_window())
+    dpred = torch.empty_like(pred)
+    if upstream is not None:
+        upstream = upstream.reshape(-1).float().contiguous()
+        if upstream.numel() != (N if upstream_per_image else 1):
+            raise ValueError("upstream must hold one value (or one per image)")
+    elif upstream_per_image:
+        raise ValueError("a per-image upstream needs upstream")
+    t0 = _timer.begin() if _timer is not None else None
+    check(lib().unet_ssim_grad(_ptr(pred), _ptr(target), 1 if target_u8 else 0, g, c1, c2,
+                               _ptr(upstream), 1 if upstream_per_image else 0, w_ssim, w_mse,
+                               _ptr(dpred), N, C, H, W, _stream()))
+    if t0 is not None:
+        _timer.end("ssim_grad", 0.0, 1, t0, nbytes=8.0 * pred.numel() + target.element_size() *
+                   target.numel())
+    return dpred
