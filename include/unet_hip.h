@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UNET_ABI_VERSION 10
+#define UNET_ABI_VERSION 11
 
 #define UNET_OK 0
 #define UNET_E_INVALID (-1) /* bad argument / unsupported shape */
@@ -323,9 +323,6 @@ int unet_sgd_nesterov_step(float* params, const float* grads, float* momentum, i
 int unet_sgd_nesterov_step_dev(float* params, const float* grads, float* momentum, int64_t n,
                                const float* hyper, int first_step, unet_stream_t stream);
 
-/* out[i] = a[i] + b[i] (gradient accumulation of skip tensors, test helper) */
-int unet_add_inplace(float* a, const float* b, int64_t n, unet_stream_t stream);
-
 /* ---- fused layer pipeline -------------------------------------------------- */
 /*
  * One ConvBlock unit of the reference is conv -> InstanceNorm2d -> LeakyReLU -> SpatialDropout2d
@@ -527,21 +524,6 @@ int unet_conv_c32_is_winograd(int N, int H, int W, int Cin, int Cout, int stride
  * chunks, the bilinear up-sampling folded into the input transform (1: with an 8 x 32 tile for
  * every CU, 2: every shape with H % 8 == 0 and W % 32 == 0).  1 when this shape takes it: */
 int unet_conv_up_c32_is_winograd(int N, int H, int W, int C0, int C1, int Cout);
-/* unet_conv_in_bwd_weight of a 32 -> 32 channel layer with the layer's InstanceNorm + LeakyReLU +
- * dropout backward (Our_UNet/models/unet.py:118-127 under autograd) applied ON LOAD by the dy side
- * of the Winograd weight-gradient kernel, which reads every pixel exactly once: g = dL/da [N][H][W]
- * [Cout] (w.r.t. the layer's activated output), y = the layer's raw convolution output, coef5 /
- * sums from unet_instnorm_bwd_coefs.  Writes dz = dL/dy to dz_out (may alias g) for the layer's
- * data gradient, fills dgamma / dbeta / dbias (each may be null) and the weight gradient as
- * unet_conv_in_bwd_weight does: the elementwise unet_instnorm_lrelu_drop_bwd pass of such a
- * layer disappears.  x must be activated on load (alpha / beta).  (csrc/conv_wgrad.hip) */
-int unet_conv_in_bwd_weight_dz_supported(int N, int H, int W, int Cx, int Cout);
-int unet_conv_in_bwd_weight_dz(const unet_act_src* x, float slope, const float* g, const float* y,
-                               const float* coef5, const float* sums, const float* gamma,
-                               const float* rstd, float dz_slope, float* dz_out, float* dgamma,
-                               float* dbeta, float* dbias, float* dw_oihw, int ci_offset,
-                               int Cin_total, void* workspace, size_t workspace_bytes, int N, int H,
-                               int W, int Cout, unet_stream_t stream);
 size_t unet_wino_weight_floats(int Cout, int Cin);
 int unet_pack_wino_weights(const float* w_oihw, float* uf, float* ud, int Cout, int Cin,
                            unet_stream_t stream);
@@ -576,25 +558,6 @@ int unet_conv_up_in_fwd_wino(const unet_act_src* low, const unet_act_src* skip, 
 /* unet_conv3x3_bwd_data_bs (stride 1, accumulate 0) on the Winograd kernel; ud covers the whole
  * weight [Cout][Cin_total], ci_offset % 64 == 0; bs may be NULL. */
 int unet_conv3x3_bwd_data_bs_wino(const float* dy, const float* ud, int Cin_total, int ci_offset,
-                                  float* dx, int N, int H, int W, int Cout, int Ccols,
-                                  unet_bwd_stats* bs, unet_stream_t stream);
-/* Apply-on-load InstanceNorm backward (round 3).  unet_instnorm_bwd_coefs turns the per-tile
- * reductions a data-gradient epilogue left (unet_bwd_stats.partial, `tiles` per image) into the
- * coefficient planes coef5 = [5][N][C] (a1, b1, P, Q, R) of
- *   dz = (z > 0 ? P : P slope) g + (Q y + R),  z = y a1 + b1,
- * and sums = [N][C][2] (S1, S2).  unet_conv3x3_bwd_data_dz_wino is unet_conv3x3_bwd_data_bs_wino
- * whose loader forms dz from (g, y) with them - the elementwise unet_instnorm_lrelu_drop_bwd
- * pass of the layer is not run - and which also writes dz (dz_out, must not alias g) for the
- * layer's weight gradient and the layer's dgamma / dbeta / dbias (each may be null).
- * Replaces the InstanceNorm2d / LeakyReLU / dropout backward of ConvBlock
- * (Our_UNet/models/unet.py:118-123 under autograd). */
-int unet_instnorm_bwd_coefs(const void* partial, int tiles, const float* mean, const float* rstd,
-                            const float* gamma, const float* beta, const float* mask,
-                            float* coef5, float* sums, int N, int HW, int C, unet_stream_t stream);
-int unet_conv3x3_bwd_data_dz_wino(const float* g, const float* y, const float* coef5,
-                                  const float* sums, const float* gamma, const float* rstd,
-                                  float slope, float* dz_out, float* dgamma, float* dbeta,
-                                  float* dbias, const float* ud, int Cin_total, int ci_offset,
                                   float* dx, int N, int H, int W, int Cout, int Ccols,
                                   unet_bwd_stats* bs, unet_stream_t stream);
 /* unet_instnorm_lrelu_drop_bwd with the reductions already summarised per tile

@@ -191,7 +191,8 @@ def test_conv_in_fwd_winograd(ua, case, with_mask):
 
 
 @pytest.mark.parametrize("case", [(4, 128, 128, 64, 64, 0), (4, 64, 64, 256, 256, 0),
-                                  (2, 128, 128, 128, 128, 0), (4, 64, 64, 256, 256, 512)])
+                                  (2, 128, 128, 128, 128, 0), (4, 64, 64, 256, 256, 512),
+                                  (4, 128, 128, 256, 64, 128)])
 def test_data_gradient_winograd(ua, case):
     """Winograd data gradient vs the direct kernel, with the BSTATS epilogue (reductions of the
     next InstanceNorm backward) and with a column slice of a wider weight (the skip half of a
@@ -262,7 +263,8 @@ def test_c32_winograd_forward(ua, case):
     check(st[2], st32[2], 5e-5, "alpha: Winograd vs direct")
 
 
-@pytest.mark.parametrize("case", [(2, 64, 64, 0), (1, 8, 32, 0), (3, 40, 96, 0), (2, 64, 96, 64)])
+@pytest.mark.parametrize("case", [(2, 64, 64, 0), (1, 8, 32, 0), (3, 40, 96, 0), (2, 256, 256, 0),
+                                  (2, 64, 96, 64)])
 def test_c32_winograd_data_gradient(ua, case):
     """Its data-gradient side: with the BSTATS epilogue (reductions of the next InstanceNorm
     backward on the same y), accumulating into an existing gradient, and as the skip half of the
@@ -304,7 +306,7 @@ def test_c32_winograd_data_gradient(ua, case):
 
 
 @pytest.mark.parametrize("case", [(2, 64, 64, True), (1, 8, 32, True), (3, 40, 96, False),
-                                  (2, 256, 256, True)])
+                                  (3, 40, 96, True), (2, 256, 256, True)])
 def test_c32_winograd_weight_gradient(ua, case):
     """The 32 -> 32 channel layers' Winograd F(3x3,2x2) weight gradient (csrc/conv_wgrad.hip:
     conv_wgrad_wino32_kernel - both operands transformed on chip, all 16 xi accumulated over a
@@ -339,51 +341,6 @@ def test_c32_winograd_weight_gradient(ua, case):
     check(dw, dw_d, 2e-5, "Winograd vs direct weight gradient")
     assert torch.equal(wide[:, 64:], dw) and bool((wide[:, :64] == 7.0).all())
     assert torch.equal(wide_d[:, 64:], dw_d)
-
-
-@pytest.mark.parametrize("case", [(2, 64, 64), (1, 8, 32), (3, 40, 96), (2, 256, 256)])
-def test_c32_weight_gradient_applies_the_instnorm_backward_on_load(ua, case):
-    """unet_conv_in_bwd_weight_dz: the dy side of the 32 -> 32 channel Winograd weight gradient
-    forms dz = dL/dy from (g, y) on load and writes it for the data gradient - against the
-    elementwise pass (unet_instnorm_lrelu_drop_bwd) followed by the plain weight gradient: dz,
-    dgamma, dbeta, dbias and dw."""
-    N, H, W = case
-    C = 32
-    x = rnd(N, C, H, W, seed=1)
-    c0 = coeffs(N, C, 10)
-    src = make_src(ua, x, c0)
-    y, st, gamma, beta, mask = _next_norm(ua, N, C, H, W, 10)
-    ua.ops.set_c32_winograd("always")
-    try:
-        assert ua.ops.conv_in_bwd_weight_dz_supported(N, H, W, C, C)
-        # g = dL/da of the layer and its per-tile reductions, as the net gets them: from the
-        # data gradient of the layer behind it (BSTATS epilogue)
-        w2 = rnd(C, C, 3, 3, seed=7, scale=0.1)
-        _, wd2 = ua.ops.pack_conv3x3_weights(w2.to(DEV))
-        nn = ua.ops.NextNorm(y, st, gamma, beta, mask, SLOPE)
-        g = ua.ops.conv3x3_bwd_data(to_nhwc(rnd(N, C, H, W, seed=2)), wd2, 0, C, H, W, 1, nxt=nn)
-        assert nn.tiles == H * W // 256
-        # reference: elementwise pass, then the (Winograd) weight gradient of its result
-        dgam, dbet, dbia = (torch.zeros(C, device=DEV) for _ in range(3))
-        dz_ref = ua.ops.instnorm_lrelu_drop_bwd(g.clone(), y, st[0], st[1], gamma, beta, mask, SLOPE,
-                                                dgam, dbet, dbia)
-        dw_ref = torch.zeros(C, C, 3, 3, device=DEV)
-        ua.ops.conv_in_bwd_weight(src, SLOPE, dz_ref, dw_ref, 0, 3, 1)
-        coef5, sums = ua.ops.instnorm_bwd_coefs(y, st[0], st[1], gamma, beta, mask,
-                                                (nn.partial, nn.tiles))
-        dgam2, dbet2, dbia2 = (torch.zeros(C, device=DEV) for _ in range(3))
-        dw = torch.zeros(C, C, 3, 3, device=DEV)
-        g2 = g.clone()
-        dz = ua.ops.conv_in_bwd_weight_dz(src, SLOPE, g2, y, coef5, sums, gamma, st[1], SLOPE,
-                                          dgam2, dbet2, dbia2, dw, 0)
-    finally:
-        ua.ops.set_c32_winograd(True)
-    assert dz.data_ptr() == g2.data_ptr()          # written over g
-    check(dz, dz_ref, 2e-5, "dz formed on load vs the elementwise pass")
-    check(dw, dw_ref, 5e-5, "weight gradient")
-    check(dgam2, dgam, 5e-5, "dgamma")
-    check(dbet2, dbet, 5e-5, "dbeta")
-    assert (dbia2 - dbia).abs().max() <= 1e-3 * (1 + dbet.abs().max())   # both ~0 (closed form)
 
 
 X3_FUSED_CASES = [  # shapes the split patch kernel takes in the fused pipeline
@@ -969,40 +926,3 @@ def test_winograd_weight_packing_in_one_launch(ua):
             assert torch.equal(uf, rf.view(-1))
         if fd:
             assert torch.equal(ud, rd.view(-1))
-
-
-@pytest.mark.parametrize("case", [(4, 128, 128, 128, 128, 0), (2, 256, 256, 64, 64, 0),
-                                  (4, 128, 128, 256, 64, 128)])
-def test_instnorm_backward_applied_on_load_by_the_winograd_data_gradient(ua, case):
-    """unet_instnorm_bwd_coefs + unet_conv3x3_bwd_data_dz_wino (the loader forms dL/dy from
-    (g, y) and five coefficient planes, writes it for the weight gradient, emits the layer's
-    parameter gradients) against the elementwise pass + the plain Winograd data gradient.
-    Third case: a column slice of a wider weight (the skip half of a decoder stage's first
-    convolution: ci_offset > 0)."""
-    N, H, W, C, Ccols, ci_off = case
-    cin_total = ci_off + Ccols
-    y, st, gamma, beta, mask = _next_norm(ua, N, C, H, W, 30)
-    # g = dL/da of that layer with its reductions, as a producing data gradient leaves them
-    dyn = to_nhwc(rnd(N, 64, H, W, seed=1))
-    _, wdn = ua.ops.pack_conv3x3_weights(rnd(64, C, 3, 3, seed=2, scale=0.1).to(DEV))
-    nn = ua.ops.NextNorm(y, st, gamma, beta, mask, SLOPE)
-    g = ua.ops.conv3x3_bwd_data(dyn, wdn, 0, C, H, W, 1, nxt=nn)
-    assert nn.tiles > 0
-    w = rnd(C, cin_total, 3, 3, seed=3, scale=0.1).to(DEV)
-    _, wd = ua.ops.pack_conv3x3_weights(w)
-    _, ud = ua.ops.pack_wino_weights(w, want_f=False)
-    # the two-pass way
-    dg0, db0, dbi0 = (torch.empty(C, device=DEV) for _ in range(3))
-    dz0 = ua.ops.instnorm_lrelu_drop_bwd(g.clone(), y, st[0], st[1], gamma, beta, mask, SLOPE, dg0,
-                                         db0, dbi0, partials=(nn.partial, nn.tiles))
-    dx0 = ua.ops.conv3x3_bwd_data(dz0, wd, ci_off, Ccols, H, W, 1, ud=ud)
-    # applied on load
-    coef5, sums = ua.ops.instnorm_bwd_coefs(y, st[0], st[1], gamma, beta, mask,
-                                            (nn.partial, nn.tiles))
-    dg1, db1, dbi1 = (torch.empty(C, device=DEV) for _ in range(3))
-    dx1, dz1 = ua.ops.conv3x3_bwd_data_dz(g, y, coef5, sums, gamma, st[1], SLOPE, dg1, db1, dbi1,
-                                          ud, cin_total, ci_off, Ccols)
-    check(dz1, dz0, 1e-5, "dz written by the data gradient")
-    check(dx1, dx0, 2e-5, "dx")
-    assert torch.equal(dg1, dg0) and torch.equal(db1, db0)
-    assert (dbi1 - dbi0).abs().max() <= 1e-6 * (dz0.abs().max() * H * W)

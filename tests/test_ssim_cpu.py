@@ -163,12 +163,12 @@ def test_argument_validation(ua):
     assert isinstance(ua.ReconstructionLoss(ssim_weight=0.1).ssim_loss, ua.SSIMLoss)
 
 
-def test_ssim_abi_symbols_and_host_checks(ua):
+def test_ssim_symbols_abi_version_and_host_checks(ua):
     handle = ctypes.CDLL(ua.LIB_PATH)
     for name in ("unet_ssim_workspace_bytes", "unet_ssim_fwd", "unet_ssim_grad"):
         assert hasattr(handle, name) and name in ua._lib.SIGNATURES
     lib = ua.lib()
-    assert lib.unet_abi_version() == ua._lib.ABI_VERSION == 10
+    assert lib.unet_abi_version() == ua._lib.ABI_VERSION == 11
     # 2 doubles per (image, channel, 32 x 32 tile)
     assert lib.unet_ssim_workspace_bytes(8, 3, 512, 512) == 8 * 3 * 256 * 16
     assert lib.unet_ssim_workspace_bytes(1, 3, 37, 50) == 3 * 4 * 16

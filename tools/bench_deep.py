@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
 """The 1/32-resolution layers (M = 2048 rows at bs 8): fused forward and data gradient, HIP events.
-Environment knobs of the gather-GEMM dispatcher apply (UNET_IGEMM_KG, UNET_IGEMM_NGROUP).
 Usage: python tools/bench_deep.py [reps]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -31,4 +30,4 @@ for H, stride in ((16, 1), (32, 2)):
     dx = torch.empty(N, H, H, C, device="cuda")
     t = timeit(lambda: ops.conv3x3_bwd_data(dy, wd, 0, C, H, H, stride, out=dx))
     out.append(f"dgrad{H}s{stride} {t:6.1f}")
-print(f"KG={os.environ.get('UNET_IGEMM_KG', '-')} NGROUP={os.environ.get('UNET_IGEMM_NGROUP', '-')}: " + "  ".join(out))
+print("  ".join(out))

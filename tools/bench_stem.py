@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times of the RGB stem (3 -> 32 channels, bs 8, 512 x 512): fused forward and weight gradient, fp32
-and bf16 layer tensors.  Usage: [UNET_STEM_WALK=0] python tools/bench_stem.py [reps]"""
+and bf16 layer tensors.  Usage: python tools/bench_stem.py [reps]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UNET_HIP_LIB") or os.path.join(_HERE, "libunet_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 
-ABI_VERSION = 10     # UNET_ABI_VERSION of include/unet_hip.h this binding was written against
+ABI_VERSION = 11     # UNET_ABI_VERSION of include/unet_hip.h this binding was written against
 
 _c = ctypes
 _p = _c.c_void_p
@@ -95,7 +95,6 @@ SIGNATURES = {
     "unet_preprocess_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _c.POINTER(_f), _c.POINTER(_f), _p]),
     "unet_sgd_nesterov_step": (_i, [_p, _p, _p, _i64, _f, _f, _f, _i, _f, _p]),
     "unet_sgd_nesterov_step_dev": (_i, [_p, _p, _p, _i64, _p, _i, _p]),
-    "unet_add_inplace": (_i, [_p, _p, _i64, _p]),
     "unet_conv_in_fwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "unet_conv_in_fwd": (_i, [_ps, _ps, _f, _p, _p, _i, _i, _p, _p, _sz, _c.POINTER(_i), _i, _i, _i,
                               _i, _p]),
@@ -111,9 +110,6 @@ SIGNATURES = {
     "unet_stem_u8_bwd_weight": (_i, [_p, _c.POINTER(_f), _c.POINTER(_f), _p, _p, _p, _sz, _i, _i,
                                      _i, _i, _p]),
     "unet_conv_in_bwd_weight": (_i, [_ps, _f, _p, _p, _i, _i, _i, _i, _p, _sz, _i, _i, _i, _i, _p]),
-    "unet_conv_in_bwd_weight_dz_supported": (_i, [_i, _i, _i, _i, _i]),
-    "unet_conv_in_bwd_weight_dz": (_i, [_ps, _f, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _i, _i,
-                                        _p, _sz, _i, _i, _i, _i, _p]),
     "unet_conv_in_bwd_weight_bf16x3": (_i, [_ps, _f, _p, _p, _i, _i, _i, _i, _p, _sz, _i, _i, _i, _i,
                                             _p]),
     "unet_upsample2x_in_fwd": (_i, [_ps, _f, _p, _i, _i, _i, _p]),
@@ -132,9 +128,6 @@ SIGNATURES = {
     "unet_conv_up_in_fwd_wino": (_i, [_ps, _ps, _f, _p, _p, _p, _p, _sz, _c.POINTER(_i), _i, _i,
                                       _i, _i, _p]),
     "unet_conv3x3_bwd_data_bs_wino": (_i, [_p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _pbs, _p]),
-    "unet_instnorm_bwd_coefs": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
-    "unet_conv3x3_bwd_data_dz_wino": (_i, [_p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _i, _i,
-                                           _p, _i, _i, _i, _i, _i, _pbs, _p]),
     "unet_conv3x3_bwd_data_bs_b16": (_i, [_p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _pbs, _p]),
     "unet_conv3x3_bwd_data_bs_b16_wb": (_i, [_p, _p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _pbs,
                                              _p]),

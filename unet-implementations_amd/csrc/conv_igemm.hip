@@ -17,7 +17,6 @@
 // Replaces nn.Conv2d forward / aten::convolution_backward(data) of
 // Our_UNet/models/unet.py:106-115 (reference is NCHW via oneDNN/cuDNN).
 #include "conv_params.h"
-#include <stdlib.h>
 
 namespace unet_conv {
 namespace {
@@ -1329,8 +1328,7 @@ constexpr int STEM_WALK_ROWS = 8;
 template <typename T, typename TO>
 void launch_stem_fwd_rows(const T* x, const float* wf, const float* bias, TO* y, int N, int H, int W,
                           int Cout, float2* stats, const StemNorm& nm, hipStream_t stream) {
-  static const bool walk_off = [] { const char* e = getenv("UNET_STEM_WALK"); return e && e[0] == '0'; }();
-  if (!walk_off && H % STEM_WALK_ROWS == 0 &&
+  if (H % STEM_WALK_ROWS == 0 &&
       (long long)N * H * W * 3 * (long long)sizeof(T) < (1LL << 31)) {   // (buffer descriptor)
     dim3 grid((unsigned)((long long)N * (H / STEM_WALK_ROWS) * (W / STEM_ROW_PIX)), Cout / 32);
     hipLaunchKernelGGL((conv_stem_fwd_walk_kernel<T, TO, STEM_WALK_ROWS>), grid, dim3(256), 0, stream,

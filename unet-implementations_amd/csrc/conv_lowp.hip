@@ -3,7 +3,6 @@
 // split-bf16 form used where the patch-staged kernel does not apply (stride-2 forward, per-class
 // stride-2 data gradient).
 #include "conv_params.h"
-#include <stdlib.h>
 
 namespace unet_conv {
 namespace {
@@ -809,8 +808,7 @@ int dispatch_igemm_b16(const IgemmParams& p, hipStream_t stream, int* stats_px, 
   // workgroups of the CU (measured against 128 x 128 / 128 x 64 tiles at two per CU: 72 -> 60 us
   // at K = 576, 202 -> 140 at K = 288; profiles/r04_bf16_experiments.txt); four K groups per
   // tile where the tiles do not fill the chip.
-  static const bool dense_off = [] { const char* e = getenv("UNET_B16_DENSE_TAPS"); return e && e[0] == '0'; }();
-  if (!dense_off && !stats_px && p.w3 && p.tap_cstride == p.C0 && p.src0_pitch == 9 * p.C0 &&
+  if (!stats_px && p.w3 && p.tap_cstride == p.C0 && p.src0_pitch == 9 * p.C0 &&
       p.C1 == 0 && p.ntaps == 9 && (p.C0 & (p.C0 - 1)) == 0 && p.C0 >= 32 && p.sin == 1 &&
       p.sout == 1 && p.Hl == p.Hout && p.Wl == p.Wout && M % 64 == 0 && nc % 64 == 0) {
     if ((M / 64) * (nc / 64) <= 256 && (9 * p.C0) % 256 == 0)
@@ -823,8 +821,7 @@ int dispatch_igemm_b16(const IgemmParams& p, hipStream_t stream, int* stats_px, 
     return launch_igemm_b16<128, 64, 64, 32>(p, stream, stats_px, bs_px);
   // data gradients of the 1/32-resolution stage (at most one 64 x 64 tile per CU) with the bf16
   // weight plane: the gather form on 64-wide K steps (WIDE), four K groups
-  static const bool wide_off = [] { const char* e = getenv("UNET_B16_WIDE_GATHER"); return e && e[0] == '0'; }();
-  if (!wide_off && p.w3 && p.tap_cstride == 0 && nc % 64 == 0 && p.C0 % 64 == 0 &&
+  if (p.w3 && p.tap_cstride == 0 && nc % 64 == 0 && p.C0 % 64 == 0 &&
       p.C1 % 64 == 0 && ceil_div64(M, 64) * (nc / 64) <= 256 &&
       (p.ntaps * ((p.C0 + p.C1) / 64)) % 4 == 0 && p.ntaps * ((p.C0 + p.C1) / 64) >= 8)
     return launch_igemm_b16<64, 64, 32, 32, 4, 1>(p, stream, stats_px, bs_px);

@@ -7,7 +7,6 @@
 // Replaces nn.Conv2d forward / aten::convolution_backward(data) of
 // Our_UNet/models/unet.py:106-115 for every stride-1 layer whose image tiles as TH x 32.
 #include "conv_params.h"
-#include <stdlib.h>
 
 #include <utility>
 
@@ -2211,8 +2210,7 @@ template <int BN, int WM, int WN, int TH>
 int launch_dgrad_s2_patch_b16(const IgemmParams& p, hipStream_t stream) {
   constexpr size_t lds = ((size_t)((TH + 1) * 33) * 40 + 2 * 3 * (size_t)BN * 40) * sizeof(__bf16);
   const long long tiles = (long long)p.N * (p.Hl / TH) * (p.Wl / 32) * (p.Ncols / BN);
-  static const bool one_set = [] { const char* e = getenv("UNET_B16_S2_DGRAD_WB"); return e && e[0] == '0'; }();
-  if (p.w3 && !one_set) {   // the weights pre-rounded to bf16: two panel sets
+  if (p.w3) {   // the weights pre-rounded to bf16: two panel sets
     auto kern = conv_dgrad_s2_patch_b16_kernel<BN, WM, WN, TH, true>;
     UNET_SET_DYN_LDS(kern, lds);
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, stream, p);
@@ -2420,9 +2418,8 @@ int launch_patch_b16_s2_t(const IgemmParams& p, hipStream_t stream) {
   return UNET_OK;
 }
 int launch_patch_s2_b16_auto(const IgemmParams& p0, hipStream_t stream, int* stats_px) {
-  static const bool off = [] { const char* e = getenv("UNET_B16_S2_PATCH"); return e && e[0] == '0'; }();
   IgemmParams p = p0;
-  if (off || !p.w3 || !patch_s2_applicable(p) || p.C0 % 32 || p.C1 % 32 || (p.ldo & 7) ||
+  if (!p.w3 || !patch_s2_applicable(p) || p.C0 % 32 || p.C1 % 32 || (p.ldo & 7) ||
       (reinterpret_cast<uintptr_t>(p.out) & 15))
     return 1;
   const long long mt = (long long)p.N * p.Hl * p.Wl / 128;

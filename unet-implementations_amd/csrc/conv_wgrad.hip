@@ -50,19 +50,6 @@ struct WgradParams {
   const float* beta;   // [N][Cx]
   float slope;
   int b16;             // x and dy are bf16 tensors (mixed-precision pipeline)
-  // conv_wgrad_wino32_kernel<.., DZ>: `dy` holds g = dL/da (gradient w.r.t. the layer's ACTIVATED
-  // output); the kernel forms dz = dL/dy of the layer's InstanceNorm + LeakyReLU + dropout
-  // backward while it loads its dy tiles - dz = (z > 0 ? P : P slope) g + (Q y + R),
-  // z = y a1 + b1, coefficient planes [5][N][C] from unet_instnorm_bwd_coefs - uses it, and
-  // WRITES it to dz_out (may alias dy: every pixel is read once) for the data gradient.
-  const float* dz_y;      // raw conv output y of the layer, [N][H][W][Cout]
-  const float* dz_coef;   // [5][N][Cout]: a1, b1, P, Q, R
-  float* dz_out;
-  const float2* dz_sums;  // [N][Cout] (S1, S2)
-  const float* dz_gamma;  // [Cout]
-  const float* dz_rstd;   // [N][Cout]
-  float* dz_dgamma; float* dz_dbeta; float* dz_dbias;   // [Cout] each (may be null)
-  float dz_slope;
 };
 
 // Epilogue shared by the weight-gradient kernels.  A wave holds nine 32x32 accumulator blocks
@@ -2049,7 +2036,7 @@ constexpr int WQ_V = 16 * 16 * WQ_VP;                       // [xi][tile slot 16
 constexpr size_t WQ_LDS = ((size_t)WQ_PPIX * WQ_LDA + 2 * WQ_V) * sizeof(float);
 static_assert(16 * 1024 <= 2 * WQ_V, "the epilogue exchange lives in the V / E stages");
 
-template <bool ACT, bool DZ>
+template <bool ACT>
 __global__ __launch_bounds__(512, 1) void conv_wgrad_wino32_kernel(const WgradParams p, int ntiles) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* const Pb = smem;
@@ -2071,21 +2058,6 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_wino32_kernel(const WgradPa
   }
   const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(p.x), 0, (int)p.x_bytes, 0x00020000);
-  if (DZ && blockIdx.x == 0) {   // parameter gradients of the layer's norm / bias (N x 32 sums)
-    const float hw = (float)(H * W), inv = 1.f / hw;
-    if (tid < 32) {
-      float dg = 0.f, db = 0.f, dbi = 0.f;
-      for (int q = 0; q < p.N; ++q) {
-        const float2 v = p.dz_sums[(size_t)q * 32 + tid];
-        db += v.x;
-        dg += v.y;
-        dbi += p.dz_gamma[tid] * p.dz_rstd[(size_t)q * 32 + tid] * (v.x - hw * (v.x * inv));
-      }
-      if (p.dz_dgamma) p.dz_dgamma[tid] = dg;
-      if (p.dz_dbeta) p.dz_dbeta[tid] = db;
-      if (p.dz_dbias) p.dz_dbias[tid] = dbi;
-    }
-  }
 
   // ---- patch slots of this thread ----
   int pp_rel[WQ_PASSES], pp_lds[WQ_PASSES], pp_rc[WQ_PASSES];
@@ -2117,10 +2089,6 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_wino32_kernel(const WgradPa
   const unsigned t_srca = lds_addr(Pb + ((2 * t_ty) * WQ_PW + 2 * t_tx) * WQ_LDA + 2 * cp);
   float* const t_dst = (xside ? Vs : Es) + tt * WQ_VP + 2 * cp;
   f32x2v en[4];   // dy side: the next unit's 2 x 2 tile (channel pair cp)
-  f32x2v yn[4];   // DZ: the same of the layer's raw output y
-  f32x2v cz[5];   // DZ: a1, b1, P, Q, R of image n_cz for this channel pair
-  int n_cz = -1;
-  size_t en_off = 0;   // element offset of the tile in the registers (DZ: where dz goes)
   auto load_unit = [&](int n, int yu, int xu) {   // patch of x (all threads) + dy tile (waves 4-7)
     const int base = ((n * H + yu - 1) * W + xu - 1) * 128;
     okm = 0;
@@ -2139,39 +2107,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_wino32_kernel(const WgradPa
       en[1] = *reinterpret_cast<const f32x2v*>(d + 32);
       en[2] = *reinterpret_cast<const f32x2v*>(d + (size_t)W * 32);
       en[3] = *reinterpret_cast<const f32x2v*>(d + (size_t)W * 32 + 32);
-      if (DZ) {
-        const float* yy = p.dz_y + o;
-        yn[0] = *reinterpret_cast<const f32x2v*>(yy);
-        yn[1] = *reinterpret_cast<const f32x2v*>(yy + 32);
-        yn[2] = *reinterpret_cast<const f32x2v*>(yy + (size_t)W * 32);
-        yn[3] = *reinterpret_cast<const f32x2v*>(yy + (size_t)W * 32 + 32);
-        en_off = o;
-      }
     }
-  };
-  // DZ: dz of the tile in (e, y) with the coefficients of image n; written out, returned in e
-  auto apply_dz = [&](f32x2v (&e)[4], const f32x2v (&y)[4], size_t off, int n) {
-    if (n != n_cz) {   // uniform: once per image
-      const size_t plane = (size_t)p.N * 32;
-#pragma unroll
-      for (int k = 0; k < 5; ++k)
-        cz[k] = *reinterpret_cast<const f32x2v*>(p.dz_coef + k * plane + (size_t)n * 32 + 2 * cp);
-      n_cz = n;
-    }
-    const f32x2v ps = cz[2] * p.dz_slope;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const f32x2v z = y[k] * cz[0] + cz[1];
-      f32x2v sel;
-      sel[0] = z[0] > 0.f ? cz[2][0] : ps[0];
-      sel[1] = z[1] > 0.f ? cz[2][1] : ps[1];
-      e[k] = sel * e[k] + (cz[3] * y[k] + cz[4]);
-    }
-    float* o = p.dz_out + off;
-    *reinterpret_cast<f32x2v*>(o) = e[0];
-    *reinterpret_cast<f32x2v*>(o + 32) = e[1];
-    *reinterpret_cast<f32x2v*>(o + (size_t)W * 32) = e[2];
-    *reinterpret_cast<f32x2v*>(o + (size_t)W * 32 + 32) = e[3];
   };
   auto load_act = [&](int n) {
     if (ACT) {
@@ -2271,10 +2207,9 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_wino32_kernel(const WgradPa
       tile_pos(tile, n, y0, x0);
       for_range<0, 4>([&](auto uc) {
         constexpr int u = decltype(uc)::value;
-        f32x2v ec[4], yc[4];
+        f32x2v ec[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { ec[k] = en[k]; yc[k] = yn[k]; }   // this unit's dy tile (loaded a unit ago)
-        const size_t ec_off = en_off;
+        for (int k = 0; k < 4; ++k) ec[k] = en[k];   // this unit's dy tile (loaded a unit ago)
         bool have_next = true;
         int nn = n;
         if constexpr (u < 3) {
@@ -2288,10 +2223,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_wino32_kernel(const WgradPa
           }
         }
         if (xside) transform_x();   // uniform
-        else {
-          if (DZ) apply_dz(ec, yc, ec_off, n);
-          transform_dy(ec);
-        }
+        else transform_dy(ec);
         __syncthreads();
         {
           f32x2v fa[2], fb[2];
@@ -2387,16 +2319,12 @@ WgradPlan make_plan_wino32(int N, int H, int W) {
 int launch_wgrad_wino32(const WgradParams& p, hipStream_t stream) {
   const int ntiles = p.N * (p.H / 8) * (p.W / 32);
   const unsigned grid = (unsigned)(ntiles < 256 ? ntiles : 256);
-  if (p.dz_y) {   // (the fused pipeline: the x operand is always activated on load)
-    auto kern = conv_wgrad_wino32_kernel<true, true>;
-    UNET_SET_DYN_LDS(kern, WQ_LDS);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), WQ_LDS, stream, p, ntiles);
-  } else if (p.alpha) {
-    auto kern = conv_wgrad_wino32_kernel<true, false>;
+  if (p.alpha) {
+    auto kern = conv_wgrad_wino32_kernel<true>;
     UNET_SET_DYN_LDS(kern, WQ_LDS);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), WQ_LDS, stream, p, ntiles);
   } else {
-    auto kern = conv_wgrad_wino32_kernel<false, false>;
+    auto kern = conv_wgrad_wino32_kernel<false>;
     UNET_SET_DYN_LDS(kern, WQ_LDS);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), WQ_LDS, stream, p, ntiles);
   }
@@ -2653,11 +2581,6 @@ WgradPlan make_plan_taps(long long Q, int Cx, int Cout, bool wide, bool b16 = fa
   return pl;
 }
 
-// UNET_WGRAD_RING=0: the segment kernels instead of the row-ring form (A/B measurements)
-bool ring_off() {
-  static const bool off = [] { const char* e = getenv("UNET_WGRAD_RING"); return e && e[0] == '0'; }();
-  return off;
-}
 // kernel instantiation for a plan (tile, segment length, stride, operand mode)
 int launch_wgrad_plan(const WgradParams& p, const WgradPlan& pl, int stride, int prec,
                       hipStream_t stream) {
@@ -2678,8 +2601,8 @@ int launch_wgrad_plan(const WgradParams& p, const WgradPlan& pl, int stride, int
     if (pl.ci_t == 32) return launch_wgrad_bf16<32, 64, 32, 3>(p, stream);
     return launch_wgrad_bf16<64, 64, 16, 3>(p, stream);
   }
-  if (p.b16 && prec == 1 && stride == 2 && (pl.S / 16) % pl.npp == 0 && wgrad_ring_ok(p, pl.rg) &&
-      !ring_off()) {   // the row-ring form with two input rows a step
+  if (p.b16 && prec == 1 && stride == 2 && (pl.S / 16) % pl.npp == 0 &&
+      wgrad_ring_ok(p, pl.rg)) {   // the row-ring form with two input rows a step
     if (pl.ci_t == 64 && pl.S == 16) return launch_wgrad_b16_ring<64, 64, 16, 2>(p, pl.rg, stream);
     if (pl.ci_t == 32 && pl.co_t == 64 && pl.S == 32) return launch_wgrad_b16_ring<32, 64, 32, 2>(p, pl.rg, stream);
   }
@@ -2687,7 +2610,7 @@ int launch_wgrad_plan(const WgradParams& p, const WgradPlan& pl, int stride, int
     if (pl.ci_t == 64 && pl.S == 16) return launch_wgrad_b16_s2<64, 64, 16>(p, stream);
     if (pl.ci_t == 32 && pl.co_t == 64 && pl.S == 32) return launch_wgrad_b16_s2<32, 64, 32>(p, stream);
   }
-  if (use_bf16 && prec == 1 && wgrad_ring_ok(p, pl.rg) && !ring_off()) {
+  if (use_bf16 && prec == 1 && wgrad_ring_ok(p, pl.rg)) {
     if (pl.ci_t == 32 && pl.co_t == 32 && pl.S == 64) return launch_wgrad_b16_ring<32, 32, 64>(p, pl.rg, stream);
     if (pl.ci_t == 32 && pl.co_t == 64 && pl.S == 32) return launch_wgrad_b16_ring<32, 64, 32>(p, pl.rg, stream);
     if (pl.ci_t == 64 && pl.S == 32) return launch_wgrad_b16_ring<64, 64, 32>(p, pl.rg, stream);
@@ -2804,8 +2727,7 @@ static int conv_bwd_weight_impl(const float* x, int Cx, const float* dy, float* 
                                 bool center_only, hipStream_t stream, int prec = 0,
                                 const float* act_alpha = nullptr, const float* act_beta = nullptr,
                                 float slope = 0.f, const unsigned char* x_u8 = nullptr,
-                                const float* u8_mean_std = nullptr, int b16 = 0,
-                                const WgradParams* dz = nullptr) {
+                                const float* u8_mean_std = nullptr, int b16 = 0) {
   // b16: x (except the RGB image) and dy are bf16 tensors; prec is then 1 (bf16 matrix cores
   // for the stride-1 layers, fp32 matrix cores on bf16 storage for the rest)
   const long long es = b16 ? 2 : 4;
@@ -2829,11 +2751,10 @@ static int conv_bwd_weight_impl(const float* x, int Cx, const float* dy, float* 
   const bool wino32 = prec == 0 && !b16 && !center_only && wgrad_wino32_ok(N, H, W, Cx, Cout, stride) &&
                       wgrad_batch_chunk(N, H, W, Cx, Cout, stride) >= N;
   // bf16 tensors, stride 1: the eight-wave row-ring kernel where the plan finds rows for it
-  static const bool ring8_off = [] { const char* e = getenv("UNET_WGRAD_RING8"); return e && e[0] == '0'; }();
   // (64 x 64 channel tiles only: measured per layer - 32 x 32 tiles, enc0 / dec4 at 512 x 512,
   // lose 20 % in the eight-wave form, the 64- and 128-channel layers gain 15 %, deeper ones +-0)
   const bool ring_s2 = b16 && prec == 1 && stride == 2;
-  const bool ring8 = b16 && (pprec == 1 || ring_s2) && !ring8_off && Cx % 64 == 0 && Cout % 64 == 0;
+  const bool ring8 = b16 && (pprec == 1 || ring_s2) && Cx % 64 == 0 && Cout % 64 == 0;
   const WgradPlan pl = wino32 ? make_plan_wino32(N, H, W)
                        : wino ? make_plan_wino(N, H, W, Cx, Cout)
                               : make_plan(N, H, W, Cx, Cout, stride, pprec, wide, ring8, ring_s2);
@@ -2905,12 +2826,6 @@ static int conv_bwd_weight_impl(const float* x, int Cx, const float* dy, float* 
       p.alpha = act_alpha ? act_alpha + (size_t)nb * Cx : nullptr;
       p.beta = act_alpha ? act_beta + (size_t)nb * Cx : nullptr;
       p.slope = slope;
-      if (dz) {   // the InstanceNorm backward applied by the dy side of the Winograd kernel
-        UNET_REQUIRE(wino32 && act_alpha, "conv_in_bwd_weight_dz: shape not taken by conv_wgrad_wino32_kernel");
-        p.dz_y = dz->dz_y; p.dz_coef = dz->dz_coef; p.dz_out = dz->dz_out; p.dz_sums = dz->dz_sums;
-        p.dz_gamma = dz->dz_gamma; p.dz_rstd = dz->dz_rstd; p.dz_dgamma = dz->dz_dgamma;
-        p.dz_dbeta = dz->dz_dbeta; p.dz_dbias = dz->dz_dbias; p.dz_slope = dz->dz_slope;
-      }
       const int rc = wino32 ? launch_wgrad_wino32(p, stream)
                      : wino ? launch_wgrad_wino(p, stream) : launch_wgrad_plan(p, pc, stride, prec, stream);
       if (rc != UNET_OK) return rc;
@@ -2997,36 +2912,6 @@ extern "C" int unet_conv_in_bwd_weight(const unet_act_src* x, float slope, const
   return conv_bwd_weight_impl(x->x, x->C, dy, dw_oihw, ci_offset, Cin_total, nullptr, workspace,
                               workspace_bytes, N, H, W, Cout, stride, ksize == 1,
                               (hipStream_t)stream, 0, x->alpha, x->beta, slope);
-}
-
-// unet_conv_in_bwd_weight of a 32 -> 32 channel layer with the layer's InstanceNorm + LeakyReLU +
-// dropout backward applied ON LOAD: `g` = dL/da (w.r.t. the activated output), y / coef5 / sums as
-// for unet_conv3x3_bwd_data_dz_wino (unet_instnorm_bwd_coefs).  Writes dz = dL/dy to dz_out (may
-// alias g) for the layer's data gradient, dgamma / dbeta / dbias, and the weight gradient.
-// Shapes: unet_conv_in_bwd_weight_dz_supported.
-extern "C" int unet_conv_in_bwd_weight_dz_supported(int N, int H, int W, int Cx, int Cout) {
-  return (N > 0 && H > 0 && W > 0 && wgrad_wino32_ok(N, H, W, Cx, Cout, 1) &&
-          wgrad_batch_chunk(N, H, W, Cx, Cout, 1) >= N) ? 1 : 0;
-}
-extern "C" int unet_conv_in_bwd_weight_dz(const unet_act_src* x, float slope, const float* g,
-                                          const float* y, const float* coef5, const float* sums,
-                                          const float* gamma, const float* rstd, float dz_slope,
-                                          float* dz_out, float* dgamma, float* dbeta, float* dbias,
-                                          float* dw_oihw, int ci_offset, int Cin_total,
-                                          void* workspace, size_t workspace_bytes, int N, int H,
-                                          int W, int Cout, unet_stream_t stream) {
-  UNET_REQUIRE(x && x->x && x->alpha && x->beta && g && y && coef5 && sums && gamma && rstd && dz_out,
-               "conv_in_bwd_weight_dz: null pointer");
-  UNET_REQUIRE(unet_conv_in_bwd_weight_dz_supported(N, H, W, x->C, Cout),
-               "conv_in_bwd_weight_dz: shape N=%d %dx%d %d->%d not supported", N, H, W, x->C, Cout);
-  WgradParams dz{};
-  dz.dz_y = y; dz.dz_coef = coef5; dz.dz_out = dz_out;
-  dz.dz_sums = reinterpret_cast<const float2*>(sums);
-  dz.dz_gamma = gamma; dz.dz_rstd = rstd; dz.dz_slope = dz_slope;
-  dz.dz_dgamma = dgamma; dz.dz_dbeta = dbeta; dz.dz_dbias = dbias;
-  return conv_bwd_weight_impl(x->x, x->C, g, dw_oihw, ci_offset, Cin_total, nullptr, workspace,
-                              workspace_bytes, N, H, W, Cout, 1, false, (hipStream_t)stream, 0,
-                              x->alpha, x->beta, slope, nullptr, nullptr, 0, &dz);
 }
 
 // The same in the split-bf16 operand mode (fp32 tensors, fp32-class accuracy): stride-1 3x3

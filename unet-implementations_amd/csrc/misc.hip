@@ -602,13 +602,6 @@ __global__ __launch_bounds__(256) void sgd_nesterov_kernel(float* __restrict__ p
   }
 }
 
-__global__ __launch_bounds__(256) void add_inplace_kernel(float* __restrict__ a,
-                                                          const float* __restrict__ b,
-                                                          long long n) {
-  const long long stride = (long long)gridDim.x * 256;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) a[i] += b[i];
-}
-
 unsigned stream_grid(long long items) {
   long long b = ceil_div64(items, 256);
   if (b > 256 * 16) b = 256 * 16;
@@ -782,14 +775,6 @@ extern "C" int unet_sgd_nesterov_step_dev(float* params, const float* grads, flo
                      (hipStream_t)stream, params, grads, momentum, (long long)n, 0.f, 0.f, 0.f,
                      first_step, 1.f, hyper);
   UNET_CHECK_LAUNCH("sgd_nesterov(dev)");
-  return UNET_OK;
-}
-
-extern "C" int unet_add_inplace(float* a, const float* b, int64_t n, unet_stream_t stream) {
-  UNET_REQUIRE(a && b && n > 0, "add_inplace: bad argument");
-  hipLaunchKernelGGL(add_inplace_kernel, dim3(stream_grid(n)), dim3(256), 0, (hipStream_t)stream,
-                     a, b, (long long)n);
-  UNET_CHECK_LAUNCH("add_inplace");
   return UNET_OK;
 }
 

@@ -573,69 +573,6 @@ def instnorm_lrelu_drop_bwd(ga, y, mean, rstd, gamma, beta, mask, slope, dgamma,
     return dy
 
 
-def instnorm_bwd_coefs(y, mean, rstd, gamma, beta, mask, partials):
-    """Apply-on-load form of the InstanceNorm + LeakyReLU + dropout backward: from the per-tile
-    reductions `partials` = (buffer, tiles) the coefficient planes coef5 [5, N, C] and the sums
-    [N, C, 2] that `conv3x3_bwd_data_dz` consumes (no elementwise pass over the layer tensor)."""
-    N, H, W, C = y.shape
-    coef5 = _f32((5, N, C), y)
-    sums = _f32((N, C, 2), y)
-    check(lib().unet_instnorm_bwd_coefs(_ptr(partials[0]), partials[1], _ptr(mean), _ptr(rstd),
-                                        _ptr(gamma), _ptr(beta), _ptr(mask), _ptr(coef5),
-                                        _ptr(sums), N, H * W, C, _stream()))
-    return coef5, sums
-
-
-def conv_in_bwd_weight_dz_supported(N, H, W, Cx, Cout):
-    """The fp32 weight gradient of this (stride-1, 3x3) layer can apply the layer's InstanceNorm
-    backward on load (32 -> 32 channels on the Winograd kernel: csrc/conv_wgrad.hip)?"""
-    return bool(lib().unet_conv_in_bwd_weight_dz_supported(N, H, W, Cx, Cout))
-
-
-def conv_in_bwd_weight_dz(x, slope, g, y, coef5, sums, gamma, rstd, dz_slope, dgamma, dbeta, dbias,
-                          dw_oihw, ci_offset, in_place=True):
-    """Weight gradient of a fused 32 -> 32 channel layer whose dy side forms dz = dL/dy from
-    (g, y) on load (unet_conv_in_bwd_weight_dz).  Returns dz (written over g unless in_place is
-    False) for the layer's data gradient; dgamma / dbeta / dbias are filled."""
-    x, rx = _act(x)
-    N, H, W, Cx = x.shape
-    Cout = g.shape[3]
-    assert dw_oihw.shape[0] == Cout and dw_oihw.is_contiguous() and y.shape == g.shape
-    ws = _wgrad_ws(lib().unet_conv3x3_bwd_weight_workspace_bytes(N, H, W, Cx, Cout, 1), g)
-    dz = g if in_place else _f32(tuple(g.shape), g)
-    t0 = _timer.begin("wgrad") if _timer is not None else None
-    check(lib().unet_conv_in_bwd_weight_dz(
-        rx, slope, _ptr(g), _ptr(y), _ptr(coef5), _ptr(sums), _ptr(gamma), _ptr(rstd), dz_slope,
-        _ptr(dz), _ptr(dgamma), _ptr(dbeta), _ptr(dbias), _ptr(dw_oihw), ci_offset,
-        dw_oihw.shape[1], _ptr(ws), ws.numel(), N, H, W, Cout, _stream()))
-    if t0 is not None:
-        alg = 2.0 * N * H * W * 9 * Cx * Cout
-        _timer.end("conv_wgrad", alg, 2, t0, executed=alg * 16.0 / 36.0)
-    return dz
-
-
-def conv3x3_bwd_data_dz(g, y, coef5, sums, gamma, rstd, slope, dgamma, dbeta, dbias, ud,
-                        cin_total, ci_offset, ccols, nxt=None):
-    """Winograd data gradient whose loader applies the InstanceNorm backward of the layer to
-    (g, y) on the fly (unet_conv3x3_bwd_data_dz_wino).  Returns (dx, dz): dz = dL/dy of the
-    layer, written as a by-product for its weight gradient; dgamma / dbeta / dbias are filled."""
-    N, H, W, Cout = g.shape
-    dx = _f32((N, H, W, ccols), g)
-    dz = _f32((N, H, W, Cout), g)
-    bs = nxt.c_struct() if nxt is not None else None
-    t0 = _timer.begin("conv") if _timer is not None else None
-    check(lib().unet_conv3x3_bwd_data_dz_wino(
-        _ptr(g), _ptr(y), _ptr(coef5), _ptr(sums), _ptr(gamma), _ptr(rstd), slope, _ptr(dz),
-        _ptr(dgamma), _ptr(dbeta), _ptr(dbias), _ptr(ud), cin_total, ci_offset, _ptr(dx), N, H, W,
-        Cout, ccols, ctypes.byref(bs) if bs is not None else None, _stream()))
-    if nxt is not None:
-        nxt.tiles = bs.tiles_out
-    if t0 is not None:
-        alg = 2.0 * N * H * W * 9 * ccols * Cout
-        _timer.end("conv_igemm", alg, 1, t0, executed=alg * 16.0 / 36.0)
-    return dx, dz
-
-
 class _ResizeBilinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, H, W):
@@ -1183,11 +1120,6 @@ def sgd_nesterov_step_dev(params, grads, momentum, hyper, first_step):
     n = params.numel()
     check(lib().unet_sgd_nesterov_step_dev(_ptr(params), _ptr(grads), _ptr(momentum), n,
                                            _ptr(hyper), 1 if first_step else 0, _stream()))
-
-
-def add_inplace(a, b):
-    check(lib().unet_add_inplace(_ptr(a), _ptr(b), a.numel(), _stream()))
-    return a
 
 
 # ---- autoencoder pretraining step (recon.hip) ------------------------------------------------

@@ -333,12 +333,6 @@ class UNet(nn.Module):
         # fp32 fused pipeline: run the stride-1 3x3 layers the Winograd F(2x2,3x3) kernel tiles
         # on it (2.25x fewer matrix-core FLOPs, a few extra fp32 roundings: csrc/conv_wino.hip)
         self.winograd = True
-        # fp32 fused pipeline, OFF by default: where a layer's gradient dL/dy is consumed by a
-        # Winograd data gradient, apply the InstanceNorm + LeakyReLU + dropout backward in that
-        # kernel's loader (which also writes dL/dy for the weight gradient) instead of the
-        # elementwise pass.  Measured: 12 of the 22 elementwise passes go (-0.38
-        # ms) but the second operand in the loader costs the data gradients +0.43 ms.
-        self.fold_instnorm_backward = False
         # normalisation constants of forward(..., input_layout="nhwc_u8") (ImageNet, as the
         # reference's dataset: Our_UNet/src/train.py:303-308)
         self.input_mean, self.input_std = ops.IMAGENET_MEAN, ops.IMAGENET_STD
@@ -879,7 +873,6 @@ class _UNetFunction(torch.autograd.Function):
         touched = set()      # ids of parameters whose gradient this backward produced
         head = model._head_module()
         fused, slope = ctx.fused, ctx.slope
-        b16_bwd = ctx.bf16 == "bf16"
         x3_bwd = ctx.fused and ctx.bf16 == "bf16x3"
         g = model._head_bwd(ctx, saved, dlogits, fused, slope, gv)
         ctx.last = None
@@ -938,57 +931,15 @@ class _UNetFunction(torch.autograd.Function):
                                    pl_.norm.bias.detach(), pr_["mask"], pl_.slope)
             x0, x1 = rec["x0"], rec["x1"]
             low = rec.get("x0_low")
-            # InstanceNorm backward applied ON LOAD by the layer's Winograd data gradient (which
-            # also writes dy for the weight gradient): no elementwise pass over the layer tensor.
-            # Needs the reductions from the producer of g_a and a Winograd data gradient of this dy.
-            dx_fold = None
-            wgrad_done = False
-            fold_ud = rec.get("ud1") if low is not None else rec.get("ud")
-            if model.fold_instnorm_backward and nn_ is not None and nn_.tiles > 0 and \
-                    fold_ud is not None and not dx0_acc and dx0_out is None and \
-                    (need_dx1 if low is not None else (need_dx and x1 is None)):
-                coef5, sums = ops.instnorm_bwd_coefs(rec["y"], st[0], st[1], l.norm.weight.detach(),
-                                                     l.norm.bias.detach(), rec["mask"],
-                                                     (nn_.partial, nn_.tiles))
-                w_ = l.conv.weight
-                c0_ = low.shape[3] if low is not None else 0
-                cc_ = x1.shape[3] if low is not None else x0.shape[3]
-                dx_fold, dy = ops.conv3x3_bwd_data_dz(
-                    g_a, rec["y"], coef5, sums, l.norm.weight.detach(), st[1], l.slope,
-                    gv(l.norm.weight), gv(l.norm.bias), gv(l.conv.bias), fold_ud, w_.shape[1], c0_,
-                    cc_, nxt=None if low is not None else nxt)
-                if nxt is not None and low is None:
-                    saved[i - 1]["nxt"] = nxt
-            elif model.fold_instnorm_backward and fused and not b16_bwd and not x3_bwd and \
-                    model.winograd and low is None and \
-                    x1 is None and l.ksize == 3 and l.stride == 1 and l.conv.weight.requires_grad and \
-                    nn_ is not None and nn_.tiles > 0 and isinstance(x0, ops.Act) and \
-                    x0.alpha is not None and g_a.dtype == torch.float32 and \
-                    ops.conv_in_bwd_weight_dz_supported(*x0.shape, l.conv.weight.shape[0]):
-                # 32 -> 32 channel layers: the dy side of the Winograd weight gradient reads every
-                # pixel once, so IT applies the InstanceNorm backward on load and writes dz (over
-                # g) for the data gradient - no elementwise pass over the layer tensor.  (Off by
-                # default like the rest of the fold: measured -0.16 ms of elementwise pass against
-                # +0.09 ms in the weight gradient, whose traffic goes from 0.5 to 1.1 GB.)
-                coef5, sums = ops.instnorm_bwd_coefs(rec["y"], st[0], st[1], l.norm.weight.detach(),
-                                                     l.norm.bias.detach(), rec["mask"],
-                                                     (nn_.partial, nn_.tiles))
-                dy = ops.conv_in_bwd_weight_dz(x0, slope, g_a, rec["y"], coef5, sums,
-                                               l.norm.weight.detach(), st[1], l.slope,
-                                               gv(l.norm.weight), gv(l.norm.bias), gv(l.conv.bias),
-                                               gv(l.conv.weight), 0)
-                wgrad_done = True
-            else:
-                dy = ops.instnorm_lrelu_drop_bwd(g_a, rec["y"], st[0], st[1],
-                                                 l.norm.weight.detach(), l.norm.bias.detach(),
-                                                 rec["mask"], l.slope, gv(l.norm.weight),
-                                                 gv(l.norm.bias), gv(l.conv.bias),
-                                                 partials=(nn_.partial, nn_.tiles)
-                                                 if nn_ is not None and nn_.tiles > 0 else None)
+            dy = ops.instnorm_lrelu_drop_bwd(g_a, rec["y"], st[0], st[1], l.norm.weight.detach(),
+                                             l.norm.bias.detach(), rec["mask"], l.slope,
+                                             gv(l.norm.weight), gv(l.norm.bias), gv(l.conv.bias),
+                                             partials=(nn_.partial, nn_.tiles)
+                                             if nn_ is not None and nn_.tiles > 0 else None)
             if dbg is not None:
                 dbg.append((l.name, "dy", dy.clone()))
             dw = gv(l.conv.weight)
-            want_dw = l.conv.weight.requires_grad and not wgrad_done
+            want_dw = l.conv.weight.requires_grad
             if low is not None:
                 # conv3x3(upsample2x(act(low))): both gradients of the up-sampled operand are
                 # GEMMs over the LOW-resolution pixels once dy is reduced to its nine D_tap
@@ -1002,12 +953,10 @@ class _UNetFunction(torch.autograd.Function):
                     if need_dx else None
                 if nxt is not None:
                     saved[i - 1]["nxt"] = nxt
-                dx1 = dx_fold
-                if need_dx1 and dx1 is None:
-                    dx1 = ops.conv3x3_bwd_data(dy, rec["wd"], C0, x1.shape[3], x1.shape[1],
-                                               x1.shape[2], 1, wd3=rec["wd3"],
-                                               bf16="bf16x3" if rec["wd3"] is not None else False,
-                                               ud=rec.get("ud1"))
+                dx1 = ops.conv3x3_bwd_data(dy, rec["wd"], C0, x1.shape[3], x1.shape[1],
+                                           x1.shape[2], 1, wd3=rec["wd3"],
+                                           bf16="bf16x3" if rec["wd3"] is not None else False,
+                                           ud=rec.get("ud1")) if need_dx1 else None
                 return g_low, dx1
             if want_dw and fused:      # the weight gradient activates its operand on load
                 ops.conv_in_bwd_weight(x0, slope, dy, dw, 0, l.ksize, l.stride, x3=x3_bwd)
@@ -1029,9 +978,7 @@ class _UNetFunction(torch.autograd.Function):
                     ops.conv3x3_bwd_weight(x1, dy, dw, x0.shape[3], l.stride, bf16=ctx.bf16)
             dx0 = dx1 = None
             N, H, W, C0 = x0.shape
-            if dx_fold is not None:
-                dx0 = dx_fold
-            elif need_dx:
+            if need_dx:
                 dx0 = ops.conv3x3_bwd_data(dy, rec["wd"], 0, C0, H, W, l.stride, out=dx0_out,
                                            accumulate=dx0_acc, bf16=ctx.bf16, wd3=rec["wd3"],
                                            nxt=nxt, ud=rec.get("ud"))
