@@ -12,6 +12,12 @@ the time of one timed step.  `--dump-outputs DIR` also writes what the last step
 leg computed: DIR/eager_*.npy (eager loop) and DIR/graph_*.npy (HIP-graph replay, when it runs);
 `dumped` in the line maps `value_path` to its files.  Inputs and seeds are fixed, so runs of two
 builds compare output for output.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed eager steps and the
+HIP-graph replay leg.  `--full` adds the rest: the CPU baseline, the other two operand modes
+(`alt_modes`), the roofline and per-kernel-group figures (`roofline`, `kernel_groups`) and the
+host enqueue time (`enqueue_ms_per_step`).  The timed legs, their figures and the dumped arrays
+are the same in both.
 """
 import argparse
 import json
@@ -30,6 +36,8 @@ PEAK_F32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: dense fp32 matrix peak
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 matrix peak (spec)
 PEAK_HBM_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E
 CONV_GROUPS = ("conv_igemm", "conv_igemm_bf16", "conv_igemm_bf16x3")
+GROUPS_PASS_STEPS = 3   # --full: steps after the timed region with every entry point bracketed
+ENQUEUE_REPS = 5        # --full: steps whose enqueue time gives enqueue_ms_per_step (median)
 
 
 def hbm_traffic(args, matmul):
@@ -255,13 +263,20 @@ def main():
     ap.add_argument("--loss-sync", choices=["local", "global"], default="local",
                     help="N>1: per-shard loss + averaged gradients (default) or the loss of the "
                          "concatenated batch + summed gradients")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run and report the CPU baseline, the bf16x3 and "
+                         "bf16 operand modes, the roofline and per-kernel-group figures and the "
+                         "host enqueue time")
     ap.add_argument("--no-alt", action="store_true",
-                    help="skip the second timed loop that reports the bf16x3 operand mode beside "
-                         "the fp32 headline (same model, same K steps)")
+                    help="with --full: skip the timed loops that report the bf16x3 and bf16 "
+                         "operand modes beside the fp32 headline (same model, same K steps)")
     ap.add_argument("--no-graph", action="store_true",
                     help="skip the extra leg that replays the step from a HIP graph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timer", action="store_true",
+                    help="no HIP events in the timed region; with --full: no roofline or "
+                         "per-kernel-group figures")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write what the last step of each timed leg computed (loss, and a fixed "
                          "seeded sample of the updated parameters and their gradients): the eager "
@@ -322,7 +337,7 @@ def main():
     # the CPU baseline (the oracle on the host cores) runs BEFORE the GPU legs: the GPU phases
     # then form one contiguous stretch that a coarse utilisation sampler can see
     cpu_base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_base = cpu_baseline()
 
     torch.manual_seed(1234)          # same initial replica on every rank
@@ -360,12 +375,14 @@ def main():
     for _ in range(args.warmup):
         loss = step()
     # HIP events on the launch stream bracket the roofline group (3x3 forward / data gradient)
-    # inside the timed region; the other groups are timed in a separate short pass below
+    # inside the timed region; the other groups are timed in a separate short pass below.  A
+    # plain run brackets the group too, so the timed steps are the same in both modes; only
+    # --full reports what the events measured
     timer = None
     if not args.no_kernel_timer:
         timer = ua.ops.KernelTimer(only={"conv"})
 
-    def groups_pass(nsteps=3):
+    def groups_pass(nsteps=GROUPS_PASS_STEPS):
         gt = ua.ops.KernelTimer()
         fence()
         ua.ops.set_timer(gt)
@@ -402,9 +419,8 @@ def main():
         # before any other leg steps the model on
         dump_outputs(args.dump_outputs, "eager_", model, loss)
         dumped["eager"] = "eager_*.npy"
-    gsumm, gsteps = groups_pass() if timer is not None else (None, None)
 
-    def enqueue_ms(reps=5):
+    def enqueue_ms(reps=ENQUEUE_REPS):
         """Host time to ENQUEUE one step onto an idle stream (median of `reps`): the Python /
         ctypes walk over the ~330 entry points, no HIP events, no waiting on the device."""
         ts = []
@@ -416,7 +432,17 @@ def main():
         fence()
         return 1e3 * sorted(ts)[len(ts) // 2]
 
-    enqueue = enqueue_ms()
+    gsumm = gsteps = enqueue = None
+    if args.full:
+        if timer is not None:
+            gsumm, gsteps = groups_pass()
+        enqueue = enqueue_ms()
+    else:
+        # the steps of those two passes, untimed: the graph leg below then starts from the model
+        # state (and dropout stream) of a --full run, so it dumps the same graph_*.npy
+        for _ in range((GROUPS_PASS_STEPS if timer is not None else 0) + ENQUEUE_REPS):
+            step()
+        fence()
 
     # ---- the line as it stands after the EAGER timed region (rank 0 only) ----
     result = None
@@ -445,11 +471,12 @@ def main():
             # step); the other one is reported under its own key
             "value_path": "eager",
             "final_loss": final_loss,
+        }
+        if enqueue is not None:
             # host time to enqueue one step (Python + ctypes, idle stream); the step is
             # launch-bound when this approaches ms_per_step
-            "enqueue_ms_per_step": enqueue,
-        }
-        if timer is not None:
+            result["enqueue_ms_per_step"] = enqueue
+        if gsumm is not None:
             roof, groups = roofline_of(timer.summary(), args.steps, args.matmul, args, gsumm, gsteps)
             if roof:
                 result["roofline"] = roof
@@ -564,7 +591,7 @@ def main():
             result["value"], result["ms_per_step"] = graph["value"], graph["ms_per_step"]
             result["value_path"] = "hip_graph_replay"
 
-    # Beside the fp32-matrix-core headline, the same K steps in the two other operand modes
+    # --full: beside the fp32-matrix-core headline, the same K steps in the two other operand modes
     # (reported, never `value`): the split-bf16 ("bf16x3") mode, which holds the same reference
     # fixtures and tolerances as fp32 (tests/test_net_gpu.py,
     # profiles/r01_bf16x3_accuracy_vs_fp64.txt), and BASELINE config 4, bf16 mixed precision
@@ -585,7 +612,7 @@ def main():
                note="peak = dense bf16 MFMA peak; this mode is bound by HBM / the gather-GEMM "
                     "loaders, not by the matrix cores")}
     alt = None
-    if args.matmul == "fp32" and not args.no_alt and not args.clip:
+    if args.full and args.matmul == "fp32" and not args.no_alt and not args.clip:
         alt = {}
         for mode in ("bf16x3", "bf16"):
             model.matmul_precision = mode

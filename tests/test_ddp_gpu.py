@@ -208,12 +208,31 @@ def test_two_ranks_at_full_size_share_one_gpu():
 
 def test_bench_single_gpu_through_a_one_rank_rccl_group():
     """UNET_BENCH_RCCL=1: the N=1 bench runs its fence barrier, the MAX all-reduce of the step
-    time and the bucketed gradient all-reduces through RCCL (backend nccl, one rank)."""
+    time and the bucketed gradient all-reduces through RCCL (backend nccl, one rank); --full adds
+    the roofline and the enqueue time to the line."""
     r = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--hw", "64",
-                    "--no-alt", "--no-cpu-baseline"], dict(UNET_BENCH_RCCL="1"))
+                    "--full", "--no-alt", "--no-cpu-baseline"], dict(UNET_BENCH_RCCL="1"))
     assert r["n_gpus"] == 1 and r["config"]["world"] == 1
     assert r["config"]["dist_backend"] == "nccl (RCCL)" and r["value"] > 0
     assert r["roofline"]["frac"] > 0 and "enqueue_ms_per_step" in r
+
+
+def test_bench_plain_and_full_runs_dump_the_same_arrays(tmp_path):
+    """A plain run skips the passes --full adds after the timed region but still takes their
+    steps, so both timed legs of the two runs end on the same parameters, gradients and loss."""
+    import numpy as np
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--hw", "64"]
+    plain = _run_bench(args + ["--dump-outputs", str(tmp_path / "plain")], {})
+    full = _run_bench(args + ["--full", "--no-alt", "--no-cpu-baseline",
+                              "--dump-outputs", str(tmp_path / "full")], {})
+    assert "roofline" not in plain and "enqueue_ms_per_step" not in plain
+    assert "roofline" in full and "enqueue_ms_per_step" in full
+    assert plain["dumped"] == full["dumped"] == {"eager": "eager_*.npy",
+                                                 "hip_graph_replay": "graph_*.npy"}
+    for leg in ("eager_", "graph_"):
+        for name in ("loss", "params", "grads"):
+            np.testing.assert_array_equal(np.load(tmp_path / "plain" / f"{leg}{name}.npy"),
+                                          np.load(tmp_path / "full" / f"{leg}{name}.npy"))
 
 
 def _worker_rccl(rank, world, port, out):
