@@ -239,7 +239,8 @@ int unet_head1x1_bwd(const float* a, const float* dlogits_nchw, const float* w, 
  * so far as 2-3 batched launches (all layers side by side; the same arithmetic in the same
  * order: bit-identical gradients).  While a reduction is queued its `workspace` must stay
  * allocated and dw_oihw is NOT yet valid.  The stand-alone bias gradient (db != NULL) cannot be
- * deferred.  No reference counterpart (aten::convolution_backward returns finished gradients). */
+ * deferred: such a call fails before it launches or queues anything.  No reference counterpart
+ * (aten::convolution_backward returns finished gradients). */
 int unet_wgrad_defer_begin(void);
 int unet_wgrad_defer_pending(void);
 int unet_wgrad_defer_flush(unet_stream_t stream);

@@ -2736,6 +2736,10 @@ static int conv_bwd_weight_impl(const float* x, int Cx, const float* dy, float* 
   UNET_REQUIRE(Cout > 0 && Cout % 32 == 0, "conv3x3_bwd_weight: Cout %d not a multiple of 32", Cout);
   UNET_REQUIRE(Cx == 3 || (Cx > 0 && Cx % 32 == 0), "conv3x3_bwd_weight: Cx %d unsupported", Cx);
   UNET_REQUIRE(ci_offset >= 0 && ci_offset + Cx <= Cin_total, "conv3x3_bwd_weight: bad ci slice");
+  // (checked before anything is launched or queued: a refused call leaves no job behind)
+  UNET_REQUIRE(!(db && b16), "conv_bwd_weight: db is not produced on the bf16-storage path");
+  UNET_REQUIRE(!(db && reduce_queue().on), "conv_bwd_weight: the bias gradient reuses the slab "
+                                           "workspace and cannot be combined with deferred reductions");
   const int pprec = (prec == 3 && stride == 1) ? 3 : ((prec == 1 && stride == 1) ? 1 : 0);
   // fp32 tensors on the fp32 matrix cores: the 8-wave kernel (parts merged in LDS)
   // fp32 tensors on the fp32 matrix cores: with >= 4 channel tiles the 8-wave kernel (one
@@ -2837,10 +2841,7 @@ static int conv_bwd_weight_impl(const float* x, int Cx, const float* dy, float* 
       if (rc != UNET_OK) return rc;
     }
   }
-  UNET_REQUIRE(!(db && b16), "conv_bwd_weight: db is not produced on the bf16-storage path");
   if (db) {
-    UNET_REQUIRE(!reduce_queue().on, "conv_bwd_weight: the bias gradient reuses the slab workspace "
-                                     "and cannot be combined with deferred reductions");
     // the slab workspace is free again at this point of the stream; reuse its head as scratch
     const long long M = (long long)N * Ho * Wo;
     const int chunks = M >= 4096 ? 64 : 1;

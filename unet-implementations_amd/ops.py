@@ -128,13 +128,16 @@ class wgrad_deferral:
     """`with wgrad_deferral() as d:` - the weight-gradient entry points called inside only queue
     the reductions of their slabs; `d.flush()` (and the end of the block) launches everything
     queued so far as 2-3 batched launches instead of 2-3 per layer.  A weight gradient is valid
-    only after the flush that follows its call.  Per thread; not re-entrant."""
+    only after the flush that follows its call.  Per thread and nestable: an inner scope (a
+    nested backward on the same thread) joins the outer one - its flush and its exit launch
+    what is queued and leave the queue on; only the outermost exit turns deferral off."""
 
     def __enter__(self):
-        if getattr(_defer, "held", None) is not None:
-            raise RuntimeError("wgrad_deferral is not re-entrant")
-        check(lib().unet_wgrad_defer_begin())
-        _defer.held = []
+        depth = getattr(_defer, "depth", 0)
+        if depth == 0:
+            check(lib().unet_wgrad_defer_begin())
+            _defer.held = []
+        _defer.depth = depth + 1
         return self
 
     def flush(self):
@@ -149,6 +152,10 @@ class wgrad_deferral:
         return n
 
     def __exit__(self, *exc):
+        _defer.depth -= 1
+        if _defer.depth:
+            self.flush()
+            return False
         try:
             check(lib().unet_wgrad_defer_end(_stream()))
         finally:
