@@ -50,6 +50,16 @@ int unet_device_count(void);
  * exercised on small tensors; bytes <= 0 restores 2^31 - 1. */
 int unet_debug_set_chunk_limit(int64_t bytes);
 
+/* Test hook: a record of the kernels the library launches, so tests can assert which
+ * instantiation a call selected.  unet_debug_record_launches clears the record and turns it on
+ * (on != 0) or off; while off a launch costs one relaxed atomic load.  The record holds host
+ * data only (harmless during graph capture).  unet_debug_recorded_launches writes the demangled
+ * kernel names launched since the record was turned on, one per line in launch order (the
+ * mangled name where the demangler gives up), NUL-terminated and truncated to cap - 1 bytes;
+ * returns the length of the whole text (call with cap = 0 to size the buffer). */
+int unet_debug_record_launches(int on);
+size_t unet_debug_recorded_launches(char* buf, size_t cap);
+
 /* ---- layout helpers ------------------------------------------------------ */
 
 /* NCHW -> NHWC (module boundary for the input image, Our_UNet/models/unet.py:399) */

@@ -47,6 +47,8 @@ SIGNATURES = {
     "unet_abi_version": (_i, []),
     "unet_device_count": (_i, []),
     "unet_debug_set_chunk_limit": (_i, [_i64]),
+    "unet_debug_record_launches": (_i, [_i]),
+    "unet_debug_recorded_launches": (_sz, [_p, _sz]),
     "unet_nchw_to_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "unet_nhwc_to_nchw": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "unet_pack_conv3x3_weights": (_i, [_p, _p, _p, _i, _i, _p]),

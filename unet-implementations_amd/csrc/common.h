@@ -62,6 +62,22 @@ static inline hipError_t unet_set_max_dyn_lds(const void* kern, size_t bytes,
     UNET_HIP_CALL(unet_set_max_dyn_lds(reinterpret_cast<const void*>(kern), bytes, done__)); \
   } while (0)
 
+// ---- launch record (unet_debug_record_launches) ----------------------------------------------
+// Every launch of the library goes through hipLaunchKernelGGL; while the record is on, the
+// kernel's host pointer is appended to a mutex-guarded host list (names are resolved only when
+// the record is read).  Off, a launch pays one relaxed atomic load.
+extern std::atomic<int> unet_launch_record_on;
+void unet_record_launch_slow(const void* kern);
+static inline void unet_record_launch(const void* kern) {
+  if (unet_launch_record_on.load(std::memory_order_relaxed)) unet_record_launch_slow(kern);
+}
+#undef hipLaunchKernelGGL
+#define hipLaunchKernelGGL(kernelName, ...)                                 \
+  do {                                                                      \
+    unet_record_launch(reinterpret_cast<const void*>(kernelName));          \
+    hipLaunchKernelGGLInternal((kernelName), __VA_ARGS__);                  \
+  } while (0)
+
 // ---- library-internal entry points shared between translation units (instnorm.hip) ----------
 int unet_in_finalize_tiles(const void* partial, int tiles, int px_per_tile, const float* gamma,
                            const float* beta, float eps, const float* mask, float* mean,

@@ -3,6 +3,14 @@
 // All kernels here are HBM-bound streaming kernels (float4 per lane).
 #include "conv_params.h"
 
+#include <cxxabi.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <mutex>
+#include <string>
+#include <vector>
+
 static thread_local char g_err[512] = "";
 
 void unet_set_error(const char* fmt, ...) {
@@ -25,6 +33,50 @@ extern "C" int unet_debug_set_chunk_limit(int64_t bytes) {
   unet_conv::chunk_limit_bytes() = (bytes > 0 && bytes < (1LL << 31)) ? bytes : (1LL << 31) - 1;
   return UNET_OK;
 }
+std::atomic<int> unet_launch_record_on{0};
+static std::mutex g_launch_mu;
+static std::vector<const void*> g_launches;
+
+void unet_record_launch_slow(const void* kern) {
+  std::lock_guard<std::mutex> lk(g_launch_mu);
+  g_launches.push_back(kern);
+}
+
+extern "C" int unet_debug_record_launches(int on) {
+  std::lock_guard<std::mutex> lk(g_launch_mu);
+  g_launches.clear();
+  unet_launch_record_on.store(on ? 1 : 0, std::memory_order_relaxed);
+  return UNET_OK;
+}
+
+extern "C" size_t unet_debug_recorded_launches(char* buf, size_t cap) {
+  std::string text;
+  {
+    std::lock_guard<std::mutex> lk(g_launch_mu);
+    for (const void* k : g_launches) {
+      const char* raw = hipKernelNameRefByPtr(k, nullptr);
+      if (raw == nullptr) {
+        (void)hipGetLastError();
+        char tmp[32];
+        snprintf(tmp, sizeof(tmp), "%p", k);
+        text += tmp;
+      } else {
+        int status = 0;
+        char* dem = abi::__cxa_demangle(raw, nullptr, nullptr, &status);
+        text += (status == 0 && dem != nullptr) ? dem : raw;   // (mangled where the
+        free(dem);                                              //  demangler gives up)
+      }
+      text += '\n';
+    }
+  }
+  if (buf != nullptr && cap > 0) {
+    const size_t n = text.size() < cap - 1 ? text.size() : cap - 1;
+    memcpy(buf, text.data(), n);
+    buf[n] = '\0';
+  }
+  return text.size();
+}
+
 extern "C" int unet_abi_version(void) { return UNET_ABI_VERSION; }
 extern "C" int unet_device_count(void) {
   int n = 0;

@@ -163,6 +163,28 @@ class wgrad_deferral:
         return False
 
 
+# ---- launch record (unet_debug_record_launches) ------------------------------------------------
+class record_launches:
+    """`with record_launches() as rec: ...` - afterwards `rec.names` lists the kernels the library
+    launched inside the block (demangled names, launch order, launches from every thread).  A
+    test hook: the record is process-wide, so two blocks must not overlap."""
+
+    def __init__(self):
+        self.names = None
+
+    def __enter__(self):
+        check(lib().unet_debug_record_launches(1))
+        return self
+
+    def __exit__(self, *exc):
+        n = lib().unet_debug_recorded_launches(None, 0)
+        buf = ctypes.create_string_buffer(n + 1)
+        lib().unet_debug_recorded_launches(buf, n + 1)
+        check(lib().unet_debug_record_launches(0))
+        self.names = buf.value.decode().splitlines()
+        return False
+
+
 # ---- layout -------------------------------------------------------------------
 def nchw_to_nhwc(x):
     N, C, H, W = x.shape
