@@ -72,31 +72,23 @@ class Autoencoder(UNet):
             raise NotImplementedError("the HIP reconstruction head is the 32 -> 3 3x3 convolution "
                                       "(pad 1, bias) followed by a sigmoid")
 
-    def _head_fwd(self, ctx, cur, fused, slope, need_grad):
+    def _head_fwd(self, walk, cur):
         conv = self.reconstruction_output[0]
-        out = ops.recon3x3_fwd(cur if fused else ops.Act(cur), slope, conv.weight.detach(),
-                               conv.bias.detach())
-        if need_grad:
-            ctx.head_out = out.detach()      # (an alias without grad_fn: no reference cycle)
+        out = ops.recon3x3_fwd(cur if walk.fused else ops.Act(cur), walk.slope,
+                               conv.weight.detach(), conv.bias.detach())
+        if walk.need_grad:
+            walk.head_out = out.detach()     # (an alias without grad_fn: no reference cycle)
         return out
 
-    def _head_bwd(self, ctx, saved, dout, fused, slope, gv):
+    def _head_bwd(self, walk, rec, dout):
         conv = self.reconstruction_output[0]
-        out, ctx.head_out = ctx.head_out, None
-        nxt = None
-        if fused and isinstance(ctx.last, ops.Act) and ctx.last.alpha is not None:
-            # da is the final gradient of the last decoder layer's output: the head's backward
-            # also leaves the reductions of that layer's InstanceNorm backward
-            pr_ = saved[-1]
-            pl_ = pr_["layer"]
-            nxt = ops.NextNorm(pr_["y"], pr_["st"], pl_.norm.weight.detach(),
-                               pl_.norm.bias.detach(), pr_["mask"], pl_.slope)
-        src = ctx.last if fused else ops.Act(saved[-1]["a"])
-        g = ops.recon3x3_bwd(src, slope, dout, out, conv.weight.detach(), gv(conv.weight),
-                             gv(conv.bias), nxt=nxt)
-        if nxt is not None and nxt.tiles > 0:
-            saved[-1]["nxt"] = nxt
-        return g
+        out, walk.head_out = walk.head_out, None
+        # fused pipeline: da is the final gradient of the last decoder layer's output, so the
+        # head's backward also leaves the reductions of that layer's InstanceNorm backward
+        return ops.recon3x3_bwd(rec.output() if walk.fused else ops.Act(rec.a), walk.slope, dout,
+                                out, conv.weight.detach(), self._grad_view(conv.weight),
+                                self._grad_view(conv.bias),
+                                nxt=rec.next_norm() if walk.fused else None)
 
     # -- reference API ---------------------------------------------------------------------------
     def get_encoder(self):

@@ -246,6 +246,44 @@ class _Layer:
         self.ksize = ksize
 
 
+class _Rec:
+    """What the forward of one layer leaves for its backward (`_Walk.saved`, forward order).
+    Every field is set by the `_Walk.run_*` call that made the record; None = does not apply.
+
+    Operands: `x0` / `x1` (tensors, or ops.Act on the fused pipeline); `low` replaces `x0` where
+    the first operand was up-sampled while the convolution loaded it.  Results: raw output `y`,
+    statistics `st`, dropout `mask`, and the activated output `a` (stand-alone pipeline only).
+    Backward weight forms: `wd` / `wd3` (packed fp32 / bf16 planes), `ud` / `ud1` (Winograd form
+    of the data gradient into x0 / into the skip half x1).
+    Place in the backward schedule: `bwd_hooks` = the modules this layer is the last of (their
+    backward hooks see its output gradient), `completes` = the module this layer is the first of
+    (its gradients are final once this layer's backward ran), `skip_dst` = index of the record
+    whose input x1 is (first convolution of a decoder stage: dx1 goes there).
+    `nxt` alone is written later: by `next_norm()`, read by this layer's `_Walk.layer_bwd`."""
+
+    __slots__ = ("layer", "x0", "x1", "low", "y", "st", "mask", "a", "wd", "wd3", "ud", "ud1",
+                 "bwd_hooks", "completes", "skip_dst", "nxt")
+
+    def __init__(self, layer, x0, x1, y, st, mask, bwd_forms, place, low=None, a=None):
+        self.layer, self.x0, self.x1, self.low, self.a = layer, x0, x1, low, a
+        self.y, self.st, self.mask = y, st, mask
+        self.wd, self.wd3, self.ud, self.ud1 = bwd_forms
+        self.bwd_hooks, self.completes, self.skip_dst = place
+        self.nxt = None
+
+    def next_norm(self):
+        """For the kernel that produces the FINAL gradient of this layer's output: it also leaves
+        the reductions of this layer's InstanceNorm backward in the returned ops.NextNorm."""
+        l = self.layer
+        self.nxt = ops.NextNorm(self.y, self.st, l.norm.weight.detach(), l.norm.bias.detach(),
+                                self.mask, l.slope)
+        return self.nxt
+
+    def output(self):
+        """This layer's output as its consumers take it."""
+        return self.a if self.a is not None else ops.Act(self.y, self.st[2], self.st[3])
+
+
 def _as_int(v):
     if isinstance(v, (tuple, list)):
         if len(set(v)) != 1:
@@ -353,36 +391,27 @@ class UNet(nn.Module):
         if _as_int(head.kernel_size) != 1 or head.in_channels != 32 or head.out_channels != 3:
             raise NotImplementedError("the HIP head kernel is the 32 -> 3 1x1 convolution")
 
-    def _head_fwd(self, ctx, cur, fused, slope, need_grad):
+    def _head_fwd(self, walk, cur):
         """NCHW fp32 output of the head over the last decoder layer's output `cur` (ops.Act on the
         fused pipeline, the activated NHWC tensor otherwise)."""
         head = self.segmentation_output
         hw = head.weight.detach().view(head.out_channels, -1)
-        if fused:
-            return ops.head1x1_in_fwd(cur, slope, hw, head.bias.detach())
+        if walk.fused:
+            return ops.head1x1_in_fwd(cur, walk.slope, hw, head.bias.detach())
         return ops.head1x1_fwd(cur, hw, head.bias.detach())
 
-    def _head_bwd(self, ctx, saved, dout, fused, slope, gv):
-        """dL/da of the last decoder layer's output; writes the head's weight gradients."""
+    def _head_bwd(self, walk, rec, dout):
+        """dL/da of the last decoder layer's output (`rec`: its record); writes the head's weight
+        gradients."""
         head = self.segmentation_output
         hw = head.weight.detach().view(head.out_channels, -1)
-        if fused:
+        dw, db = self._grad_view(head.weight).view(head.out_channels, -1), self._grad_view(head.bias)
+        if walk.fused:
             # g is the final gradient of the last decoder layer's output: the head's backward
             # also leaves the reductions of that layer's InstanceNorm backward (NextNorm)
-            pr_ = saved[-1]
-            pl_ = pr_["layer"]
-            nxt_h = ops.NextNorm(pr_["y"], pr_["st"], pl_.norm.weight.detach(),
-                                 pl_.norm.bias.detach(), pr_["mask"], pl_.slope) \
-                if isinstance(ctx.last, ops.Act) and ctx.last.alpha is not None else None
-            g = ops.head1x1_in_bwd(ctx.last, slope, dout, hw,
-                                   gv(head.weight).view(head.out_channels, -1), gv(head.bias),
-                                   nxt=nxt_h)
-            if nxt_h is not None and nxt_h.tiles > 0:
-                pr_["nxt"] = nxt_h
-        else:
-            g = ops.head1x1_bwd(saved[-1]["a"], dout, hw,
-                                gv(head.weight).view(head.out_channels, -1), gv(head.bias))
-        return g
+            return ops.head1x1_in_bwd(rec.output(), walk.slope, dout, hw, dw, db,
+                                      nxt=rec.next_norm())
+        return ops.head1x1_bwd(rec.a, dout, hw, dw, db)
 
     # -- reference: Our_UNet/models/unet.py:386-397 --------------------------------------
     def initialize_weights(self):
@@ -625,6 +654,235 @@ def _fire_backward_hooks(mods, make_grad):
             hook(m, (None,), (g,))
 
 
+class _Walk:
+    """State of one walk over the plan: made by the forward and, where a gradient is needed, kept
+    for its backward.  The methods run ONE layer; which layer runs when, and which hooks fire, is
+    the schedule in `_UNetFunction._forward` / `._backward`."""
+
+    def __init__(self, model, x, fusion, need_grad):
+        mode = model.matmul_precision      # operand mode handed to every conv call
+        if mode not in ("fp32", "bf16", "bf16x3"):
+            raise ValueError("matmul_precision must be 'fp32', 'bf16' or 'bf16x3'")
+        enc, dec = model._plan
+        layers = [l for blk in enc for l in blk] + ([fusion] if fusion is not None else []) + \
+            [l for blk in dec for l in blk]
+        self.model, self.mode = model, mode
+        self.need_grad = need_grad         # False under no_grad / frozen parameters: no records
+        self.saved = []                    # one _Rec per layer, forward order
+        self.head_out = None               # what a head keeps for its own backward (Autoencoder)
+        # The fused pipeline serves the fp32 mode and the mixed-precision mode ("bf16": there the
+        # layer tensors themselves are bf16 in HBM); 0 <= slope <= 1 (lrelu(z) = max(z, slope z)),
+        # one slope for the whole net.  Anything else runs the stand-alone passes.
+        self.slope = layers[0].slope
+        self.fused = model.fused_pipeline and \
+            len({l.slope for l in layers}) == 1 and 0.0 <= self.slope <= 1.0 and \
+            not (mode == "bf16" and fusion is not None)
+        self.b16 = self.fused and mode == "bf16"
+        # split-bf16 mode on the fused pipeline: the stride-1 3x3 layers that tile as 4 x 32
+        # pixels run the split patch kernel (forward + data gradient), the rest the fp32 kernels
+        self.x3 = self.fused and mode == "bf16x3"
+        # test hook: a list that receives (layer name, raw conv output y, statistics [4,N,C]) of
+        # every fused layer in forward order (tests/test_net_gpu.py: the LeakyReLU branch pattern)
+        self.dbg_fwd = getattr(model, "_debug_forward", None)
+
+        dev = x.x.device if isinstance(x, ops.U8Image) else x.device
+        use_masks = model.training or model.dropout_mask_override is not None
+        masks = _draw_masks(model, layers, x.shape[0], dev) if use_masks else [None] * len(layers)
+        self.mask_of = {id(l): m for l, m in zip(layers, masks)}
+
+        # one launch packs every 3x3 weight into the kernels' layouts (persistent buffers); in
+        # the fp32 mode the stride-1 layers with >= 64 channels also get their Winograd forms
+        # U = G g G^T (forward, incl. the up-sampling loader of the decoder's first convolutions;
+        # data gradient: the C -> C layers and the skip halves of the decoder's first
+        # convolutions) - `weight_forms` picks per call
+        convs = [l.conv.weight for l in layers if l.ksize == 3]
+        wino = None
+        if mode == "fp32" and model.fused_pipeline and model.winograd:
+            wino = []
+            for l in layers:
+                if l.ksize != 3:
+                    continue
+                co, ci = l.conv.weight.shape[0], l.conv.weight.shape[1]
+                s1 = l.stride == 1 and min(co, ci) >= 64
+                wino.append((s1 and co % 64 == 0 and ci % 8 == 0,
+                             s1 and ci % 64 == 0 and co % 8 == 0))
+        # (the 32 -> 32 channel layers' Winograd form needs no weight form of its own: a switch)
+        table = model.__dict__.get("_pack_table")
+        # (the bf16 planes: all three terms in the split mode; in the mixed-precision mode their
+        # first plane is the bf16-rounded weight the patch kernels stage without a conversion)
+        planes = 3 if mode == "bf16x3" else (1 if (mode == "bf16" and model.fused_pipeline) else False)
+        if table is None or not table.matches(convs, planes, wino):
+            table = model.__dict__["_pack_table"] = ops.PackTable(convs, planes, wino)
+        table.run()
+        self.table = table
+        self.row = {id(w): k for k, w in enumerate(convs)}    # weight -> its PackTable row
+
+    def weight_forms(self, l, s0, s1, up=False):
+        """THE place that picks a layer's weight forms -> ((w, w3, wu), (wd, wd3, ud, ud1)): what
+        the forward call takes and what its record keeps for the backward (`_Rec`).  w / wd are
+        the packed fp32 layouts (1x1: the matrix and its transpose), w3 / wd3 the PackTable's bf16
+        planes (None in the fp32 mode), wu / ud / ud1 the Winograd forms where the table holds one
+        AND the library tiles this call's shape.  s0, s1: the operands as the call gets them;
+        up: s0 is the low-resolution operand that the convolution up-samples on load."""
+        w = l.conv.weight
+        if l.ksize == 1:
+            w2d = w.detach().view(w.shape[0], w.shape[1])
+            return (w2d, None, None), \
+                (ops.transpose2d(w2d) if self.need_grad else None, None, None, None)
+        t, k = self.table, self.row[id(w)]
+        wu = ud = ud1 = None
+        if self.fused and self.mode == "fp32":
+            n, h, w_ = (s1 if up else s0).shape[:3]       # the convolution's output grid
+            c0, c1, cout = s0.shape[3], 0 if s1 is None else s1.shape[3], w.shape[0]
+            # forward: every source must be activated on load
+            if t.uf[k] is not None and s0.alpha is not None and \
+                    (s1 is None or s1.alpha is not None) and \
+                    (ops.conv_up_wino_supported if up else ops.conv_wino_supported)(
+                        n, h, w_, c0, c1, cout):
+                wu = t.uf[k]
+            # data gradient: into the skip half of an up-sampling layer, or into a lone source
+            if t.ud[k] is not None:
+                if up:
+                    if self.need_grad and ops.conv_wino_supported(n, h, w_, cout, 0, c1):
+                        ud1 = t.ud[k]
+                elif c1 == 0 and ops.conv_wino_supported(n, h, w_, cout, 0, c0):
+                    ud = t.ud[k]
+        return (t.wf[k], t.wf3[k], wu), (t.wd[k], t.wd3[k], ud, ud1)
+
+    def run_layer(self, l, x0, x1, place):
+        """Stand-alone pipeline: convolution, statistics and activation as three passes over NHWC
+        fp32 tensors; returns the activated output."""
+        (w, w3, _), bwd_forms = self.weight_forms(l, x0, x1)
+        if l.ksize == 1:
+            y = ops.conv1x1_fwd(x0, x1, w, l.conv.bias.detach())
+        else:
+            y = ops.conv3x3_fwd(x0, x1, w, l.conv.bias.detach(), l.stride, bf16=self.mode, wf3=w3)
+        st = ops.instnorm_stats(y, l.norm.weight.detach(), l.norm.bias.detach(), l.norm.eps)
+        m = self.mask_of[id(l)]
+        a = ops.instnorm_lrelu_drop_fwd(y, st[2], st[3], m, l.slope)
+        if self.need_grad:
+            self.saved.append(_Rec(l, x0, x1, y, st, m, bwd_forms, place, a=a))
+        return a
+
+    def run_layer_fused(self, l, s0, s1, place, low=None):
+        """s0 / s1: ops.Act operands; returns the Act of this layer's output.  low: s0 is only the
+        up-sampling of this Act - the backward works on `low` and s0 is not kept."""
+        (w, w3, wu), bwd_forms = self.weight_forms(l, s0, s1)
+        m = self.mask_of[id(l)]
+        y, st = ops.conv_in_fwd(s0, s1, self.slope, w, l.conv.bias.detach(), l.ksize, l.stride,
+                                l.norm.weight.detach(), l.norm.bias.detach(), l.norm.eps, m,
+                                b16=self.b16, w3=w3, wu=wu)
+        return self._fused_output(l, None if low is not None else s0, s1, low, y, st, m,
+                                  bwd_forms, place)
+
+    def run_up_layer(self, l, low, skip, place):
+        """First conv of a decoder stage: conv3x3(cat(upsample2x(act(low)), act(skip)))."""
+        if not self.fused:
+            return self.run_layer(l, ops.upsample2x_fwd(low), skip, place)
+        if self.x3 or l.ksize != 3 or \
+                not ops.conv_up_in_fwd_supported(low, skip, l.conv.weight.shape[0]):
+            return self.run_layer_fused(l, ops.Act(ops.upsample2x_in_fwd(low, self.slope)), skip,
+                                        place, low=low)
+        # the bilinear gather runs inside the conv's patch loader: the up-sampled tensor never
+        # exists, and the backward works on `low` (ops.conv3x3_up_bwd_weight / _data)
+        (w, w3, wu), bwd_forms = self.weight_forms(l, low, skip, up=True)
+        m = self.mask_of[id(l)]
+        y, st = ops.conv_up_in_fwd(low, skip, self.slope, w, l.conv.bias.detach(),
+                                   l.norm.weight.detach(), l.norm.bias.detach(), l.norm.eps, m,
+                                   wu=wu, w3=w3)
+        return self._fused_output(l, None, skip, low, y, st, m, bwd_forms, place)
+
+    def _fused_output(self, l, x0, x1, low, y, st, m, bwd_forms, place):
+        if self.need_grad:
+            self.saved.append(_Rec(l, x0, x1, y, st, m, bwd_forms, place, low=low))
+        if self.dbg_fwd is not None:
+            self.dbg_fwd.append((l.name, y, st))
+        return ops.Act(y, st[2], st[3])
+
+    def stage_output(self, v):
+        """activated stage output as an NCHW fp32 tensor (only materialised for hooks)"""
+        if isinstance(v, ops.Act):
+            if v.x.dtype != torch.float32:
+                raise NotImplementedError("sub-module hooks on the bf16 pipeline")
+            a = v.x if v.alpha is None else ops.instnorm_lrelu_drop_fwd(v.x, v.alpha, v.beta,
+                                                                        None, self.slope)
+            return ops.nhwc_to_nchw(a)
+        return ops.nhwc_to_nchw(v)
+
+    def layer_bwd(self, i, g_a, stop, dx0_acc=None):
+        """Backward of layer `i` from g_a = dL/d(its activated output) -> (dx0, dx1): the gradients
+        of its operands (dx0 on the low-resolution grid where the layer up-sampled on load).
+        stop: index of the first trainable layer - the gradient into layer j's input is needed
+        only for j > stop.  dx0_acc: the gradient another consumer of x0 already wrote (a skip):
+        dx0 is accumulated into it."""
+        rec = self.saved[i]
+        l, st, x0, x1, low = rec.layer, rec.st, rec.x0, rec.x1, rec.low
+        fused, slope, gv = self.fused, self.slope, self.model._grad_view
+        need_dx = i > stop
+        need_dx1 = rec.skip_dst is not None and rec.skip_dst > stop
+        dbg = getattr(self.model, "_debug_capture", None)
+        if dbg is not None:
+            dbg.append((l.name, "ga", g_a.clone()))
+        nn_, rec.nxt = rec.nxt, None       # reductions left by the kernel that produced g_a
+        # dx0 of this layer is the final gradient of the previous layer's output (the skip
+        # halves dx1 are accumulated into later, by the encoder): its producer also emits
+        # that layer's InstanceNorm-backward reductions
+        nxt = self.saved[i - 1].next_norm() if fused and need_dx else None
+        dy = ops.instnorm_lrelu_drop_bwd(g_a, rec.y, st[0], st[1], l.norm.weight.detach(),
+                                         l.norm.bias.detach(), rec.mask, l.slope,
+                                         gv(l.norm.weight), gv(l.norm.bias), gv(l.conv.bias),
+                                         partials=(nn_.partial, nn_.tiles)
+                                         if nn_ is not None and nn_.tiles > 0 else None)
+        if dbg is not None:
+            dbg.append((l.name, "dy", dy.clone()))
+        dw = gv(l.conv.weight)
+        want_dw = l.conv.weight.requires_grad
+        if low is not None:
+            # conv3x3(upsample2x(act(low))): both gradients of the up-sampled operand are
+            # GEMMs over the LOW-resolution pixels once dy is reduced to its nine D_tap
+            C0 = low.shape[3]
+            D = ops.upsample2x_bwd_taps(dy) if (want_dw or need_dx) else None
+            if want_dw:
+                ops.conv3x3_up_bwd_weight(low, slope, D, dw, 0)
+                ops.conv_in_bwd_weight(x1, slope, dy, dw, C0, 3, 1, x3=self.x3)
+            g_low = ops.conv3x3_up_bwd_data(D, rec.wd, 0, C0, nxt=nxt,
+                                            wd3=rec.wd3 if ops._is_b16(D) else None) \
+                if need_dx else None
+            dx1 = ops.conv3x3_bwd_data(dy, rec.wd, C0, x1.shape[3], x1.shape[1], x1.shape[2], 1,
+                                       wd3=rec.wd3,
+                                       bf16="bf16x3" if rec.wd3 is not None else False,
+                                       ud=rec.ud1) if need_dx1 else None
+            return g_low, dx1
+        if want_dw and fused:      # the weight gradient activates its operand on load
+            ops.conv_in_bwd_weight(x0, slope, dy, dw, 0, l.ksize, l.stride, x3=self.x3)
+            if x1 is not None:
+                ops.conv_in_bwd_weight(x1, slope, dy, dw, x0.shape[3], l.ksize, l.stride,
+                                       x3=self.x3)
+            want_dw = False
+        if l.ksize == 1:
+            if want_dw:
+                dw2d = dw.view(dw.shape[0], dw.shape[1])
+                ops.conv1x1_bwd_weight(x0, dy, dw2d, 0)
+                if x1 is not None:
+                    ops.conv1x1_bwd_weight(x1, dy, dw2d, x0.shape[3])
+            dx0 = ops.conv1x1_bwd_data(dy, rec.wd, 0, x0.shape[3]) if need_dx else None
+            return dx0, None      # the second source (frozen CLIP features) needs no gradient
+        if want_dw:
+            ops.conv3x3_bwd_weight(x0, dy, dw, 0, l.stride, bf16=self.mode)
+            if x1 is not None:
+                ops.conv3x3_bwd_weight(x1, dy, dw, x0.shape[3], l.stride, bf16=self.mode)
+        dx0 = dx1 = None
+        N, H, W, C0 = x0.shape
+        if need_dx:
+            dx0 = ops.conv3x3_bwd_data(dy, rec.wd, 0, C0, H, W, l.stride, out=dx0_acc,
+                                       accumulate=dx0_acc is not None, bf16=self.mode,
+                                       wd3=rec.wd3, nxt=nxt, ud=rec.ud)
+        if x1 is not None and need_dx1:
+            dx1 = ops.conv3x3_bwd_data(dy, rec.wd, C0, x1.shape[3], H, W, l.stride,
+                                       bf16=self.mode, wd3=rec.wd3)
+        return dx0, dx1
+
+
 class _UNetFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, x, extra, *params):
@@ -650,208 +908,52 @@ class _UNetFunction(torch.autograd.Function):
     def _forward(ctx, model, x, extra, params):
         enc, dec = model._plan
         fusion = model._fusion_layer if extra is not None else None
-        layers = [l for blk in enc for l in blk] + ([fusion] if fusion is not None else []) + \
-            [l for blk in dec for l in blk]
-        need_grad = any(ctx.needs_input_grad)  # False under no_grad / frozen parameters
-        N = x.shape[0]
-        dev = x.x.device if isinstance(x, ops.U8Image) else x.device
-        use_masks = model.training or model.dropout_mask_override is not None
-        masks = _draw_masks(model, layers, N, dev) if use_masks else [None] * len(layers)
-        mask_of = {id(l): m for l, m in zip(layers, masks)}
-        saved = []  # per layer: dict(inputs, y, stats, mask, a)
-        if model.matmul_precision not in ("fp32", "bf16", "bf16x3"):
-            raise ValueError("matmul_precision must be 'fp32', 'bf16' or 'bf16x3'")
-        bf16 = model.matmul_precision      # operand mode handed to every conv call
-
-        # one launch packs every 3x3 weight into the kernels' layouts (persistent buffers); in
-        # the fp32 mode the stride-1 layers with >= 64 channels also get their Winograd forms
-        # U = G g G^T (forward, incl. the up-sampling loader of the decoder's first convolutions;
-        # data gradient: the C -> C layers and the skip halves of the decoder's first
-        # convolutions) - ops.conv_wino_supported / conv_up_wino_supported decide per call
-        convs = [l.conv.weight for l in layers if l.ksize == 3]
-        wino = None
-        if bf16 == "fp32" and model.fused_pipeline and model.winograd:
-            wino = []
-            for l in layers:
-                if l.ksize != 3:
-                    continue
-                co, ci = l.conv.weight.shape[0], l.conv.weight.shape[1]
-                s1 = l.stride == 1 and min(co, ci) >= 64
-                wino.append((s1 and co % 64 == 0 and ci % 8 == 0,
-                             s1 and ci % 64 == 0 and co % 8 == 0))
-        # (the 32 -> 32 channel layers' Winograd form needs no weight form of its own: a switch)
-        table = model.__dict__.get("_pack_table")
-        # (the bf16 planes: all three terms in the split mode; in the mixed-precision mode their
-        # first plane is the bf16-rounded weight the patch kernels stage without a conversion)
-        planes = 3 if bf16 == "bf16x3" else (1 if (bf16 == "bf16" and model.fused_pipeline) else False)
-        if table is None or not table.matches(convs, planes, wino):
-            table = model.__dict__["_pack_table"] = ops.PackTable(convs, planes, wino)
-        table.run()
-        packed = {id(w): k for k, w in enumerate(convs)}
-
-        def run_layer(l, x0, x1):
-            w = l.conv.weight
-            if l.ksize == 1:
-                w2d = w.detach().view(w.shape[0], w.shape[1])
-                wd = ops.transpose2d(w2d) if need_grad else None
-                y = ops.conv1x1_fwd(x0, x1, w2d, l.conv.bias.detach())
-            else:
-                k = packed[id(w)]
-                wf, wd, wf3, wd3 = table.wf[k], table.wd[k], table.wf3[k], table.wd3[k]
-                y = ops.conv3x3_fwd(x0, x1, wf, l.conv.bias.detach(), l.stride, bf16=bf16,
-                                    wf3=wf3)
-            st = ops.instnorm_stats(y, l.norm.weight.detach(), l.norm.bias.detach(), l.norm.eps)
-            m = mask_of[id(l)]
-            a = ops.instnorm_lrelu_drop_fwd(y, st[2], st[3], m, l.slope)
-            if need_grad:
-                saved.append(dict(layer=l, x0=x0, x1=x1, y=y, st=st, mask=m, a=a, wd=wd,
-                                  wd3=wd3 if l.ksize == 3 else None))
-            return a
-
-        # The fused pipeline serves the fp32 mode and the mixed-precision mode ("bf16": there the
-        # layer tensors themselves are bf16 in HBM); 0 <= slope <= 1 (lrelu(z) = max(z, slope z)),
-        # one slope for the whole net.  Anything else runs the stand-alone passes.
-        slope = layers[0].slope
-        fused = model.fused_pipeline and \
-            len({l.slope for l in layers}) == 1 and 0.0 <= slope <= 1.0 and \
-            not (bf16 == "bf16" and fusion is not None)
-        b16 = fused and bf16 == "bf16"
-        # split-bf16 mode on the fused pipeline: the stride-1 3x3 layers that tile as 4 x 32
-        # pixels run the split patch kernel (forward + data gradient), the rest the fp32 kernels
-        x3 = fused and bf16 == "bf16x3"
-
-        # test hook: a list that receives (layer name, raw conv output y, statistics [4,N,C]) of
-        # every fused layer in forward order (tests/test_net_gpu.py: the LeakyReLU branch pattern)
-        dbg_fwd = getattr(model, "_debug_forward", None)
-
-        def run_layer_fused(l, s0, s1):
-            """s0 / s1: ops.Act operands; returns the Act of this layer's output."""
-            w = l.conv.weight
-            if l.ksize == 1:
-                wk = w.detach().view(w.shape[0], w.shape[1])
-                wd = ops.transpose2d(wk) if need_grad else None
-            else:
-                k = packed[id(w)]
-                wk, wd = table.wf[k], table.wd[k]
-            w3 = table.wf3[k] if ((x3 or b16) and l.ksize == 3) else None
-            m = mask_of[id(l)]
-            wu = ud = None
-            if l.ksize == 3 and not b16 and not x3:
-                n_, h_, w_, c0_ = s0.shape
-                c1_ = 0 if s1 is None else s1.shape[3]
-                if table.uf[k] is not None and s0.alpha is not None and \
-                        (s1 is None or s1.alpha is not None) and \
-                        ops.conv_wino_supported(n_, h_, w_, c0_, c1_, w.shape[0]):
-                    wu = table.uf[k]
-                if table.ud[k] is not None and c1_ == 0 and \
-                        ops.conv_wino_supported(n_, h_, w_, w.shape[0], 0, c0_):
-                    ud = table.ud[k]
-            y, st = ops.conv_in_fwd(s0, s1, slope, wk, l.conv.bias.detach(), l.ksize, l.stride,
-                                    l.norm.weight.detach(), l.norm.bias.detach(), l.norm.eps, m,
-                                    b16=b16, w3=w3, wu=wu)
-            if need_grad:
-                saved.append(dict(layer=l, x0=s0, x1=s1, y=y, st=st, mask=m, wd=wd,
-                                  wd3=table.wd3[k] if w3 is not None else None, ud=ud))
-            if dbg_fwd is not None:
-                dbg_fwd.append((l.name, y, st))
-            return ops.Act(y, st[2], st[3])
-
-        def run_up_layer_fused(l, low, skip):
-            """First conv of a decoder stage: conv3x3(cat(upsample2x(act(low)), act(skip))).
-            The up-sampled tensor only lives for this call: backward works on `low`
-            (ops.conv3x3_up_bwd_weight / _data)."""
-            w = l.conv.weight
-            if not x3 and l.ksize == 3 and ops.conv_up_in_fwd_supported(low, skip, w.shape[0]):
-                # the bilinear gather runs inside the conv's patch loader: no up-sampled tensor
-                # (fp32 tensors; bf16 tensors since round 4)
-                k = packed[id(w)]
-                m = mask_of[id(l)]
-                n_, h_, w_, c1_ = skip.shape
-                wu = table.uf[k] if (not b16 and table.uf[k] is not None and
-                                     low.alpha is not None and
-                                     skip.alpha is not None and ops.conv_up_wino_supported(
-                                         n_, h_, w_, low.shape[3], c1_, w.shape[0])) else None
-                y, st = ops.conv_up_in_fwd(low, skip, slope, table.wf[k], l.conv.bias.detach(),
-                                           l.norm.weight.detach(), l.norm.bias.detach(),
-                                           l.norm.eps, m, wu=wu,
-                                           w3=table.wf3[k] if b16 else None)
-                if need_grad:
-                    # Winograd form of the data gradient into the skip half
-                    n_, h_, w_, c1_ = skip.shape
-                    ud1 = table.ud[k] if (table.ud[k] is not None and ops.conv_wino_supported(
-                        n_, h_, w_, w.shape[0], 0, c1_)) else None
-                    saved.append(dict(layer=l, x0=None, x1=skip, y=y, st=st, mask=m,
-                                      wd=table.wd[k], wd3=table.wd3[k] if b16 else None,
-                                      x0_low=low, ud1=ud1))
-                if dbg_fwd is not None:
-                    dbg_fwd.append((l.name, y, st))
-                return ops.Act(y, st[2], st[3])
-            out = run_layer_fused(l, ops.Act(ops.upsample2x_in_fwd(low, slope)), skip)
-            if need_grad:
-                saved[-1]["x0"] = None
-                saved[-1]["x0_low"] = low
-            return out
-
-        if isinstance(x, ops.U8Image) and (not fused or b16):
+        walk = _Walk(model, x, fusion, any(ctx.needs_input_grad))
+        fused = walk.fused
+        if isinstance(x, ops.U8Image) and (not fused or walk.b16):
             raise RuntimeError("the uint8 stem needs the fused fp32 pipeline")
-        if fused:
-            run_layer = run_layer_fused
-            cur = x if isinstance(x, ops.U8Image) else ops.Act(x)   # the image: a plain operand
-        else:
-            cur = x          # NHWC image
-        def stage_output(v):
-            """activated stage output as an NCHW fp32 tensor (only materialised for hooks)"""
-            if isinstance(v, ops.Act):
-                if v.x.dtype != torch.float32:
-                    raise NotImplementedError("sub-module hooks on the bf16 pipeline")
-                a = v.x if v.alpha is None else ops.instnorm_lrelu_drop_fwd(v.x, v.alpha, v.beta,
-                                                                            None, slope)
-                return ops.nhwc_to_nchw(a)
-            return ops.nhwc_to_nchw(v)
+        run = walk.run_layer_fused if fused else walk.run_layer
+        # (the image is a plain operand of the fused pipeline)
+        cur = ops.Act(x) if fused and not isinstance(x, ops.U8Image) else x
 
-        skips = []
+        def place(blk, li, hooked, owner, skip_dst=None):
+            """(bwd_hooks, completes, skip_dst) of layer li of a stage: see _Rec"""
+            return (hooked if li == len(blk) - 1 else (), owner if li == 0 else None, skip_dst)
+
+        skips = []      # (stage output, index of the record that will take it as x0)
         for bi, blk in enumerate(enc):
-            for l in blk:
-                cur = run_layer(l, cur, None)
+            stage = model.encoder_stages[bi]
+            for li, l in enumerate(blk):
+                cur = run(l, cur, None, place(blk, li, (stage,), stage))
             if bi < len(enc) - 1:
-                skips.append(cur)
-            _fire_forward_hooks([model.encoder_stages[bi]], lambda: stage_output(cur))
+                skips.append((cur, len(walk.saved)))
+            _fire_forward_hooks([stage], lambda: walk.stage_output(cur))
         if fusion is not None:
             if extra.shape[:3] != cur.shape[:3]:
                 raise NotImplementedError("bottleneck features must match the 1/32-resolution "
                                           f"grid {tuple(cur.shape[1:3])} (got {tuple(extra.shape[1:3])})")
-            cur = run_layer(fusion, cur, ops.Act(extra) if fused else extra)
+            cur = run(fusion, cur, ops.Act(extra) if fused else extra,
+                      ((), model.clip_fusion_conv, None))
         for di, blk in enumerate(dec):
-            skip = skips[len(skips) - 1 - di]
+            stage = model.decoder_stages[di]
+            hooked = (stage, stage.conv_block)
+            skip, skip_dst = skips[len(skips) - 1 - di]
             if cur.shape[1] * 2 != skip.shape[1] or cur.shape[2] * 2 != skip.shape[2]:
                 raise NotImplementedError("decoder up-sampling must be exactly 2x")
-            if fused:
-                for li, l in enumerate(blk):
-                    cur = run_up_layer_fused(l, cur, skip) if li == 0 else run_layer(l, cur, None)
-            else:
-                up = ops.upsample2x_fwd(cur)
-                for li, l in enumerate(blk):
-                    cur = run_layer(l, up, skip) if li == 0 else run_layer(l, cur, None)
-            _fire_forward_hooks([model.decoder_stages[di], model.decoder_stages[di].conv_block],
-                                lambda: stage_output(cur))
-        logits = model._head_fwd(ctx, cur, fused, slope, need_grad)
+            cur = walk.run_up_layer(blk[0], cur, skip, place(blk, 0, hooked, stage, skip_dst))
+            for li in range(1, len(blk)):
+                cur = run(blk[li], cur, None, place(blk, li, hooked, stage))
+            _fire_forward_hooks(hooked, lambda: walk.stage_output(cur))
+        logits = model._head_fwd(walk, cur)
         _fire_forward_hooks([model._head_module()], lambda: logits)
-        if need_grad:
-            ctx.model = model
-            ctx.saved = saved
-            ctx.fused = fused
-            ctx.slope = slope
-            ctx.last = cur
-            ctx.n_enc_blocks = len(enc)
-            ctx.params = params
-            ctx.bf16 = bf16
-            ctx.fusion = fusion
+        if walk.need_grad:
+            ctx.walk, ctx.params = walk, params
         return logits
 
     @staticmethod
     def _backward(ctx, dlogits, deferred):
-        model, saved, params = ctx.model, ctx.saved, ctx.params
-        enc, dec = model._plan
+        walk, params = ctx.walk, ctx.params
+        model, saved = walk.model, walk.saved
         gv = model._grad_view
         dlogits = dlogits.contiguous()
         # The kernels WRITE the gradient arena and the returned views normally become p.grad.
@@ -870,16 +972,8 @@ class _UNetFunction(torch.autograd.Function):
                 "the bucketed all-reduce hook: the buckets would ship before the old gradient is "
                 "added.  Clear model.grad_ready_hook for the accumulation micro-steps, or call "
                 "optimizer.zero_grad() (set_to_none=True) before each backward.")
-        touched = set()      # ids of parameters whose gradient this backward produced
         head = model._head_module()
-        fused, slope = ctx.fused, ctx.slope
-        x3_bwd = ctx.fused and ctx.bf16 == "bf16x3"
-        g = model._head_bwd(ctx, saved, dlogits, fused, slope, gv)
-        ctx.last = None
-        touched.update(id(q) for q in head.parameters())
-
-        idx = len(saved) - 1
-        skip_grads = {}
+        g = model._head_bwd(walk, saved[-1], dlogits)
         hook = model.grad_ready_hook
 
         def ready(module):
@@ -896,158 +990,34 @@ class _UNetFunction(torch.autograd.Function):
                 raise NotImplementedError("sub-module hooks on the bf16 pipeline")
             return ops.nhwc_to_nchw(t)
 
-        def trainable(l):
-            return any(q.requires_grad for q in (l.conv.weight, l.conv.bias, l.norm.weight,
-                                                 l.norm.bias))
+        def layer_params(l):
+            return (l.conv.weight, l.conv.bias, l.norm.weight, l.norm.bias)
 
         # Frozen layers (AE-transfer freezes encoder_stages): nothing upstream of
         # the first trainable layer needs a backward pass, and frozen layers in between only
         # propagate the data gradient (no weight-gradient kernels).
-        stop = min((i for i, r in enumerate(saved) if trainable(r["layer"])), default=len(saved))
-        skip_src = {}        # encoder stage e -> index in `saved` of the layer producing skip e
-        pos = 0
-        for bi, blk in enumerate(enc):
-            pos += len(blk)
-            skip_src[bi] = pos - 1
-
-        def layer_bwd(i, g_a, dx0_out=None, dx0_acc=False, need_dx=True, need_dx1=True):
+        stop = min((i for i, r in enumerate(saved)
+                    if any(q.requires_grad for q in layer_params(r.layer))), default=len(saved))
+        skip_grads = {}      # index of a record -> the skip gradient its dx0 is accumulated into
+        for i in range(len(saved) - 1, stop - 1, -1):
             rec = saved[i]
-            l = rec["layer"]
-            st = rec["st"]
-            touched.update(id(q) for q in (l.conv.weight, l.conv.bias, l.norm.weight, l.norm.bias))
-            need_dx = need_dx and i > stop       # the first trainable layer needs no dx
-            dbg = getattr(model, "_debug_capture", None)
-            if dbg is not None:
-                dbg.append((l.name, "ga", g_a.clone()))
-            nn_ = rec.pop("nxt", None)     # reductions left by the kernel that produced g_a
-            # dx0 of this layer is the final gradient of the previous layer's output (the skip
-            # halves dx1 are accumulated into later, by the encoder): its producer also emits
-            # that layer's InstanceNorm-backward reductions
-            nxt = None
-            if fused and need_dx and i > 0:
-                pr_ = saved[i - 1]
-                pl_ = pr_["layer"]
-                nxt = ops.NextNorm(pr_["y"], pr_["st"], pl_.norm.weight.detach(),
-                                   pl_.norm.bias.detach(), pr_["mask"], pl_.slope)
-            x0, x1 = rec["x0"], rec["x1"]
-            low = rec.get("x0_low")
-            dy = ops.instnorm_lrelu_drop_bwd(g_a, rec["y"], st[0], st[1], l.norm.weight.detach(),
-                                             l.norm.bias.detach(), rec["mask"], l.slope,
-                                             gv(l.norm.weight), gv(l.norm.bias), gv(l.conv.bias),
-                                             partials=(nn_.partial, nn_.tiles)
-                                             if nn_ is not None and nn_.tiles > 0 else None)
-            if dbg is not None:
-                dbg.append((l.name, "dy", dy.clone()))
-            dw = gv(l.conv.weight)
-            want_dw = l.conv.weight.requires_grad
-            if low is not None:
-                # conv3x3(upsample2x(act(low))): both gradients of the up-sampled operand are
-                # GEMMs over the LOW-resolution pixels once dy is reduced to its nine D_tap
-                C0 = low.shape[3]
-                D = ops.upsample2x_bwd_taps(dy) if (want_dw or need_dx) else None
-                if want_dw:
-                    ops.conv3x3_up_bwd_weight(low, slope, D, dw, 0)
-                    ops.conv_in_bwd_weight(x1, slope, dy, dw, C0, 3, 1, x3=x3_bwd)
-                g_low = ops.conv3x3_up_bwd_data(D, rec["wd"], 0, C0, nxt=nxt,
-                                                wd3=rec["wd3"] if ops._is_b16(D) else None) \
-                    if need_dx else None
-                if nxt is not None:
-                    saved[i - 1]["nxt"] = nxt
-                dx1 = ops.conv3x3_bwd_data(dy, rec["wd"], C0, x1.shape[3], x1.shape[1],
-                                           x1.shape[2], 1, wd3=rec["wd3"],
-                                           bf16="bf16x3" if rec["wd3"] is not None else False,
-                                           ud=rec.get("ud1")) if need_dx1 else None
-                return g_low, dx1
-            if want_dw and fused:      # the weight gradient activates its operand on load
-                ops.conv_in_bwd_weight(x0, slope, dy, dw, 0, l.ksize, l.stride, x3=x3_bwd)
-                if x1 is not None:
-                    ops.conv_in_bwd_weight(x1, slope, dy, dw, x0.shape[3], l.ksize, l.stride,
-                                           x3=x3_bwd)
-                want_dw = False
-            if l.ksize == 1:
-                if want_dw:
-                    dw2d = dw.view(dw.shape[0], dw.shape[1])
-                    ops.conv1x1_bwd_weight(x0, dy, dw2d, 0)
-                    if x1 is not None:
-                        ops.conv1x1_bwd_weight(x1, dy, dw2d, x0.shape[3])
-                dx0 = ops.conv1x1_bwd_data(dy, rec["wd"], 0, x0.shape[3]) if need_dx else None
-                return dx0, None      # the second source (frozen CLIP features) needs no gradient
-            if want_dw:
-                ops.conv3x3_bwd_weight(x0, dy, dw, 0, l.stride, bf16=ctx.bf16)
-                if x1 is not None:
-                    ops.conv3x3_bwd_weight(x1, dy, dw, x0.shape[3], l.stride, bf16=ctx.bf16)
-            dx0 = dx1 = None
-            N, H, W, C0 = x0.shape
-            if need_dx:
-                dx0 = ops.conv3x3_bwd_data(dy, rec["wd"], 0, C0, H, W, l.stride, out=dx0_out,
-                                           accumulate=dx0_acc, bf16=ctx.bf16, wd3=rec["wd3"],
-                                           nxt=nxt, ud=rec.get("ud"))
-                if nxt is not None:
-                    saved[i - 1]["nxt"] = nxt
-            if x1 is not None and need_dx1:
-                dx1 = ops.conv3x3_bwd_data(dy, rec["wd"], C0, x1.shape[3], H, W, l.stride,
-                                           bf16=ctx.bf16, wd3=rec["wd3"])
-            return dx0, dx1
-
-        done = False
-        # decoder stages, last to first
-        for di in range(len(dec) - 1, -1, -1):
-            blk = dec[di]
-            if done or idx < stop:
-                done = True
-                break
-            _fire_backward_hooks([model.decoder_stages[di], model.decoder_stages[di].conv_block],
-                                 lambda: grad_nchw(g))
-            for li in range(len(blk) - 1, 0, -1):
-                if idx < stop:
-                    done = True
-                    break
-                g, _ = layer_bwd(idx, g)
-                idx -= 1
-            if done or idx < stop:
-                done = True
-                break
-            e = len(enc) - 2 - di
-            g_up, g_skip = layer_bwd(idx, g, need_dx1=skip_src[e] >= stop)
-            idx -= 1
+            _fire_backward_hooks(rec.bwd_hooks, lambda: grad_nchw(g))
+            g, g_skip = walk.layer_bwd(i, g, stop, dx0_acc=skip_grads.pop(i, None))
             if g_skip is not None:
-                skip_grads[e] = g_skip
-            if g_up is not None:   # fused pipeline: already the low-resolution gradient
-                g = g_up if "x0_low" in saved[idx + 1] else ops.upsample2x_bwd(g_up)
-            ready(model.decoder_stages[di])
-        if ctx.fusion is not None and not done and idx >= stop:
-            g, _ = layer_bwd(idx, g)
-            idx -= 1
-            ready(model.clip_fusion_conv)
-        # encoder stages, last to first
-        for bi in range(len(enc) - 1, -1, -1):
-            blk = enc[bi]
-            if done or idx < stop:
-                break
-            _fire_backward_hooks([model.encoder_stages[bi]], lambda: grad_nchw(g))
-            for li in range(len(blk) - 1, -1, -1):
-                if idx < stop:
-                    done = True
-                    break
-                first_layer_of_net = (bi == 0 and li == 0)
-                if first_layer_of_net:
-                    layer_bwd(idx, g, need_dx=False)
-                    g = None
-                elif li == 0 and (bi - 1) in skip_grads:
-                    # input of this layer is the skip tensor of stage bi-1: accumulate into the
-                    # gradient the decoder already wrote for it
-                    g, _ = layer_bwd(idx, g, dx0_out=skip_grads.pop(bi - 1), dx0_acc=True)
-                else:
-                    g, _ = layer_bwd(idx, g)
-                idx -= 1
-            if not done:
-                ready(model.encoder_stages[bi])
+                skip_grads[rec.skip_dst] = g_skip
+            if rec.layer.first_of_decoder and rec.low is None and g is not None:
+                g = ops.upsample2x_bwd(g)     # the up-sampled operand was materialised
+            if rec.completes is not None:
+                ready(rec.completes)
         deferred.flush()
         if hook is not None:
             # everything below the first trainable parameter is a frozen prefix: no gradient,
             # nothing to exchange
             hook(next((off for p, off in zip(params, model._offsets) if p.requires_grad), 0))
-        ctx.saved = None
+        # ids of the parameters whose gradient this backward produced
+        touched = {id(q) for q in head.parameters()}
+        touched.update(id(q) for r in saved[stop:] for q in layer_params(r.layer))
+        walk.saved = None
         grads = []
         for p in params:
             # no gradient for frozen parameters and for layers that did not run (e.g. the CLIP
