@@ -312,6 +312,32 @@ int unet_argmax_dice_counts(const float* logits_nchw, const int64_t* target, uin
                             uint64_t* counts, int N, int H, int W, int ignore_index,
                             unet_stream_t stream);
 
+/* ---- test-set evaluation (Our_UNet/src/evaluate.py:150-268) -------------------------------- */
+
+/* cm[B][3][3] (uint64, device; zeroed here) = per image, the confusion matrix
+ * [target class][predicted class] of the argmax map (first maximum wins) and the mask, BOTH
+ * resized with nearest-neighbour interpolation to that image's original size: the integers
+ * behind every metric of evaluate_model (src/evaluate.py:189-211) and behind its
+ * plot_confusion_matrix.  dims[B][2] = (orig_h, orig_w) is a DEVICE array (what the default
+ * collate makes of the dataset's original_dims, src/train.py:314) and is never read on the host;
+ * NULL = at network size.  The source index of output index d is ATen's, in fp32:
+ * min((int)floorf((float)d * ((float)in / (float)out)), in - 1).  Pixels whose (resized) target
+ * is ignore_index, or is not a class, are excluded.  An entry of dims outside 1..16384 gives
+ * that image zero counts.  H * W <= 2^30; ignore_index must not be 0, 1 or 2. */
+int unet_eval_confusion(const float* logits_nchw, const int64_t* target, const int64_t* dims,
+                        uint64_t* cm, int B, int H, int W, int ignore_index,
+                        unet_stream_t stream);
+
+/* One read of the logits, any subset of (NULL skips an output):
+ *   probs[B][3][H][W]  fp32 softmax over the classes (visualize_confidence_maps_batch,
+ *                      utils/visualize.py:117-119)
+ *   classes[B][H][W]   uint8 argmax
+ *   errors[B][H][W]    uint8 category of create_error_visualization (utils/visualize.py:205-222),
+ *                      255 in the mask read as background: 0 none, 1 true positive, 2 false
+ *                      positive, 3 false negative, 4 wrong class.  Needs target. */
+int unet_eval_maps(const float* logits_nchw, const int64_t* target, float* probs,
+                   uint8_t* classes, uint8_t* errors, int B, int H, int W, unet_stream_t stream);
+
 /* uint8 HWC image (+ uint8 mask) -> ((v/255) - mean)/std NHWC fp32 (+ int64 target with values
  * > 2 other than 255 mapped to 0): PetSegmentationDataset.__getitem__, src/train.py:300-311.
  * mean3 / std3 are HOST pointers to 3 floats. */

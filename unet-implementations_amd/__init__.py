@@ -9,6 +9,7 @@ from . import _lib, ops  # noqa: F401
 from ._lib import LIB_PATH, UNetHipError, build, lib  # noqa: F401
 from .losses import MSELoss, ReconstructionLoss, SimpleLoss, SSIMLoss  # noqa: F401
 from .metrics import (SegmentationMetrics, calculate_psnr, calculate_ssim,  # noqa: F401
+                      compute_dice, compute_iou, compute_pixel_accuracy, evaluate_model_metrics,
                       evaluate_reconstructions)
 from .optim import FusedAdam, FusedSGD  # noqa: F401
 from .train import (create_lr_scheduler, create_model, create_optimizer,  # noqa: F401
@@ -18,7 +19,8 @@ from .clip_unet import CLIPUNet  # noqa: F401
 from .unet import ConvBlock, SpatialDropout2d, UNet, UpBlock  # noqa: F401
 from .autoencoder import Autoencoder  # noqa: F401
 from . import ae  # noqa: F401
+from . import evaluate  # noqa: F401
 
-__all__ = ["UNet", "Autoencoder", "CLIPUNet", "ConvBlock", "UpBlock", "SpatialDropout2d", "SimpleLoss", "MSELoss", "SSIMLoss", "ReconstructionLoss", "calculate_psnr", "calculate_ssim", "evaluate_reconstructions", "SegmentationMetrics", "FusedSGD", "FusedAdam", "ae",
+__all__ = ["UNet", "Autoencoder", "CLIPUNet", "ConvBlock", "UpBlock", "SpatialDropout2d", "SimpleLoss", "MSELoss", "SSIMLoss", "ReconstructionLoss", "calculate_psnr", "calculate_ssim", "evaluate_reconstructions", "SegmentationMetrics", "compute_dice", "compute_iou", "compute_pixel_accuracy", "evaluate_model_metrics", "evaluate", "FusedSGD", "FusedAdam", "ae",
            "create_model", "create_optimizer", "create_lr_scheduler", "get_loss_function",
            "train_step", "GraphedTrainStep", "train_one_epoch", "save_checkpoint", "load_checkpoint", "validate", "predict_masks", "ops", "build", "lib", "UNetHipError", "LIB_PATH"]

@@ -94,6 +94,8 @@ SIGNATURES = {
     "unet_wgrad_defer_end": (_i, [_p]),
     "unet_dice_wce_loss_grad": (_i, [_p, _p, _p, _sz, _p, _p, _i, _i, _i, _i, _p]),
     "unet_argmax_dice_counts": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "unet_eval_confusion": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "unet_eval_maps": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "unet_preprocess_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _c.POINTER(_f), _c.POINTER(_f), _p]),
     "unet_sgd_nesterov_step": (_i, [_p, _p, _p, _i64, _f, _f, _f, _i, _f, _p]),
     "unet_sgd_nesterov_step_dev": (_i, [_p, _p, _p, _i64, _p, _i, _p]),

@@ -13,7 +13,9 @@ The reconstruction metrics of AE_pretrained/reconstruction/utils/metrics.py (`ca
 each is one fused forward (`unet_ssim_fwd`, or `unet_mse_loss_fwd` for PSNR alone).
 
 `update_from_logits(logits, target)` takes the network output itself (argmax inside the
-kernel); `update(pred, target)` takes class maps like the reference's method (device tensors;
+kernel); with `original_dims` it counts at every image's original size, as the reference's
+test-set evaluation does, through `unet_eval_confusion` (argmax, both nearest resizes and the
+3 x 3 confusion matrix in one launch), and `confusion_matrix` holds the accumulated matrix; `update(pred, target)` takes class maps like the reference's method (device tensors;
 routed through the same kernel as one-hot scores).  Targets hold {0, 1, 2, ignore_index}
 (Our_UNet/src/train.py:300: everything else was mapped to 0 by the dataset).
 """
@@ -30,29 +32,74 @@ class SegmentationMetrics:
         self.num_classes = num_classes
         self.ignore_index = ignore_index
         self._counts = None      # int64 [3, 3] on the device: {inter, predicted, labelled} per class
+        self._cm = None          # int64 [3, 3]: target class x predicted class (original-size path)
+        self._cm_complete = True  # False once an update arrived without its confusion matrix
         self.reset()
 
     # reference: utils/metrics.py:25-34
     def reset(self):
         if self._counts is not None:
             self._counts.zero_()
+        if self._cm is not None:
+            self._cm.zero_()
+        self._cm_complete = True
 
     def _add(self, counts):
         if self._counts is None:
             self._counts = counts.clone()
         else:
+            if self._counts.device != counts.device:
+                self._counts = self._counts.to(counts.device)
             self._counts += counts
 
-    def update_from_logits(self, logits, target):
-        """logits fp32 [B, 3, H, W], target int64 [B, H, W], both on the device."""
+    def update_from_confusion(self, cm):
+        """Adds confusion matrices [3, 3] or [B, 3, 3] (integers, target class x predicted class;
+        tensor on any device, or array): what `update_from_logits(..., original_dims)` does with
+        the output of `unet_eval_confusion`.  Intersections are the diagonal, predicted pixels the
+        column sums, labelled pixels the row sums; no host sync."""
+        cm = torch.as_tensor(cm)
+        if cm.dtype != torch.int64:
+            cm = cm.to(torch.int64)
+        cm = cm.reshape(-1, 3, 3).sum(dim=0)
+        if self._cm is None:
+            self._cm = cm.clone()
+        else:
+            if self._cm.device != cm.device:
+                self._cm = self._cm.to(cm.device)
+            self._cm += cm
+        self._add(torch.stack([torch.diagonal(cm), cm.sum(dim=0), cm.sum(dim=1)], dim=1))
+
+    def update_from_logits(self, logits, target, original_dims=None):
+        """logits fp32 [B, 3, H, W], target int64 [B, H, W], both on the device.
+        original_dims (int64 [B, 2] of (orig_h, orig_w), as the default collate builds it from the
+        dataset's `original_dims`; a host tensor is copied over): count at each image's original
+        size, both maps nearest-resized as evaluate_model does (src/evaluate.py:189-211)."""
         if not logits.is_cuda:
             raise RuntimeError("unet-implementations_amd.SegmentationMetrics runs on MI355X only "
                                "(no CPU fallback exists)")
         if target.dtype != torch.int64:
             target = target.long()
+        if original_dims is not None:
+            dims = torch.as_tensor(original_dims).to(device=logits.device, dtype=torch.int64,
+                                                     non_blocking=True)
+            self.update_from_confusion(ops.eval_confusion(logits.float(), target, dims,
+                                                          self.ignore_index))
+            return
         _, counts = ops.argmax_dice_counts(logits.float(), target, self.ignore_index,
                                            want_preds=False)
+        self._cm_complete = False
         self._add(counts)
+
+    @property
+    def confusion_matrix(self):
+        """int64 [3, 3] (numpy), target class x predicted class, accumulated by the updates that
+        carried one (`update_from_logits` with `original_dims`, `update_from_confusion`)."""
+        if not self._cm_complete:
+            raise RuntimeError("confusion_matrix: some updates came without original_dims (the "
+                               "network-size kernel counts per class only)")
+        if self._cm is None:
+            return np.zeros((3, 3), dtype=np.int64)
+        return self._cm.cpu().numpy()
 
     # reference: utils/metrics.py:36-57
     def update(self, pred, target):
@@ -149,6 +196,50 @@ class SegmentationMetrics:
                 "precision": self.compute_precision(cls), "recall": self.compute_recall(cls),
                 "f1_score": self.compute_f1_score(cls)}
         return results
+
+
+# ---- stand-alone forms (reference: utils/metrics.py:244-358) -------------------------------------
+def _single(pred, target, ignore_index):
+    metrics = SegmentationMetrics(num_classes=3, ignore_index=ignore_index)
+    metrics.update(pred, target)
+    return metrics
+
+
+def compute_dice(pred, target, cls, ignore_index=255):
+    """Dice of class `cls` for one prediction / target pair of class maps (device tensors)."""
+    return _single(pred, target, ignore_index).compute_dice(cls)
+
+
+def compute_iou(pred, target, cls, ignore_index=255):
+    """IoU of class `cls` for one prediction / target pair of class maps (device tensors)."""
+    return _single(pred, target, ignore_index).compute_iou(cls)
+
+
+def compute_pixel_accuracy(pred, target, ignore_index=255):
+    """Pixel accuracy of one prediction / target pair of class maps (device tensors)."""
+    return _single(pred, target, ignore_index).compute_pixel_accuracy()
+
+
+@torch.no_grad()
+def accumulate_test_metrics(model, data_loader, device, ignore_index=255):
+    """The loop of evaluate_model / evaluate_model_metrics: eval-mode forward, then one launch per
+    batch for argmax, both nearest resizes to `original_dims` and all counting.  Nothing is read
+    on the host until the returned SegmentationMetrics is asked for a value."""
+    model.eval()
+    metrics = SegmentationMetrics(num_classes=3, ignore_index=ignore_index)
+    for batch in data_loader:
+        images = batch["image"].to(device, non_blocking=True)
+        masks = batch["mask"].to(device, non_blocking=True)
+        metrics.update_from_logits(model(images), masks, batch["original_dims"])
+    return metrics
+
+
+def evaluate_model_metrics(model, data_loader, device, num_classes=3, ignore_index=255):
+    """utils/metrics.py:305-358: `get_all_metrics()` over a dataset, every image counted at its
+    original size."""
+    if num_classes != 3:
+        raise NotImplementedError("the HIP count kernel handles exactly 3 classes")
+    return accumulate_test_metrics(model, data_loader, device, ignore_index).get_all_metrics()
 
 
 # ---- reconstruction metrics (reference: AE_pretrained/reconstruction/utils/metrics.py) ----------

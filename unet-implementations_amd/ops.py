@@ -1112,6 +1112,64 @@ def argmax_classes(logits):
     return preds
 
 
+def _eval_operands(name, logits, target):
+    if not torch.is_tensor(logits) or not logits.is_cuda:
+        raise RuntimeError(f"unet-implementations_amd.{name} runs on MI355X only "
+                           "(no CPU fallback exists)")
+    if logits.dim() != 4 or logits.shape[1] != 3:
+        raise ValueError("3 classes expected (logits [B, 3, H, W])")
+    if logits.dtype != torch.float32:
+        raise TypeError(f"{name} takes fp32 logits")
+    if target is not None:
+        if target.dtype != torch.int64:
+            raise TypeError(f"{name} takes int64 targets")
+        if tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:]):
+            raise ValueError("target must be [B, H, W] of the logits' size")
+        target = target.contiguous()
+    return logits.contiguous(), target
+
+
+def eval_confusion(logits, target, dims=None, ignore_index=255):
+    """Per-image confusion matrices int64 [B, 3, 3] = [target class][predicted class] of the
+    argmax map and the mask, both nearest-resized to dims[b] = (orig_h, orig_w): the counting of
+    evaluate_model (src/evaluate.py:189-211) in one launch.  dims: int64 [B, 2] on the device
+    (never read on the host), or None for "at network size".  A size outside 1..16384 gives that
+    image zero counts."""
+    logits, target = _eval_operands("eval_confusion", logits, target)
+    if target is None:
+        raise TypeError("eval_confusion needs the target")
+    B, _, H, W = logits.shape
+    if dims is not None:
+        if not torch.is_tensor(dims) or dims.dtype != torch.int64 or tuple(dims.shape) != (B, 2):
+            raise TypeError("dims must be an int64 [B, 2] tensor of (orig_h, orig_w)")
+        dims = dims.contiguous()
+    cm = torch.empty((B, 3, 3), dtype=torch.int64, device=logits.device)
+    check(lib().unet_eval_confusion(_ptr(logits), _ptr(target), _ptr(dims), cm.data_ptr(), B, H,
+                                    W, int(ignore_index), _stream()))
+    return cm
+
+
+def eval_maps(logits, target=None, want_probs=True, want_classes=True, want_errors=None):
+    """(probs fp32 [B,3,H,W], classes uint8 [B,H,W], errors uint8 [B,H,W]) from one read of the
+    logits; an output that was not asked for is None.  errors (default: when a target is given)
+    holds the categories of create_error_visualization (utils/visualize.py:205-222): 0 none,
+    1 true positive, 2 false positive, 3 false negative, 4 wrong class, 255 read as background."""
+    logits, target = _eval_operands("eval_maps", logits, target)
+    if want_errors is None:
+        want_errors = target is not None
+    if want_errors and target is None:
+        raise TypeError("eval_maps: the error map needs the target")
+    B, _, H, W = logits.shape
+    probs = torch.empty_like(logits) if want_probs else None
+    classes = torch.empty((B, H, W), dtype=torch.uint8, device=logits.device) \
+        if want_classes else None
+    errors = torch.empty((B, H, W), dtype=torch.uint8, device=logits.device) \
+        if want_errors else None
+    check(lib().unet_eval_maps(_ptr(logits), _ptr(target) if want_errors else None, _ptr(probs),
+                               _ptr(classes), _ptr(errors), B, H, W, _stream()))
+    return probs, classes, errors
+
+
 def preprocess_u8(image_hwc_u8, mask_u8=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """uint8 [N,H,W,3] (+ uint8 [N,H,W]) on the device -> (fp32 NHWC image, int64 target)."""
     import ctypes

@@ -175,16 +175,39 @@ def validate(model, val_loader, loss_function, device, ignore_label=255):
     return (val_loss / n).item(), scores
 
 
+def nearest_source_index(in_size, out_size):
+    """int64 [out_size] (numpy): the source index F.interpolate(mode="nearest") reads for every
+    output index - ATen's rule in fp32, min(floor(d * (in / out)), in - 1), the one
+    `unet_eval_confusion` applies on the device."""
+    import numpy as np
+    scale = np.float32(in_size) / np.float32(out_size)
+    src = np.floor(np.arange(out_size, dtype=np.float32) * scale).astype(np.int64)
+    return np.minimum(src, in_size - 1)
+
+
 @torch.no_grad()
-def predict_masks(model, images):
+def predict_masks(model, images, original_dims=None):
     """Inference as in Our_UNet/src/evaluate.py:185-207: eval-mode forward and per-pixel argmax,
-    returned as a uint8 class map on the device (the reference resizes on the CPU afterwards)."""
+    returned as a uint8 class map on the device.  With `original_dims` ([B, 2] of (orig_h,
+    orig_w)) the result is a list of B uint8 device maps, each nearest-resized to its original
+    size as the reference does on the CPU; the sizes are read on the host (output shapes depend on
+    them), so this is the visual path, not the metric path (see `evaluate.evaluate_model`)."""
     was_training = model.training
     model.eval()
     try:
-        return ops.argmax_classes(model(images))
+        preds = ops.argmax_classes(model(images))
     finally:
         model.train(was_training)
+    if original_dims is None:
+        return preds
+    H, W = preds.shape[1:]
+    dims = torch.as_tensor(original_dims).cpu().tolist()
+    out = []
+    for b, (oh, ow) in enumerate(dims):
+        rows = torch.from_numpy(nearest_source_index(H, int(oh))).to(preds.device)
+        cols = torch.from_numpy(nearest_source_index(W, int(ow))).to(preds.device)
+        out.append(preds[b].index_select(0, rows).index_select(1, cols))
+    return out
 
 
 def save_checkpoint(model, optimizer, scheduler, epoch, best_dice, output_dir, is_best=False):
