@@ -1,13 +1,25 @@
-"""Thin torch-tensor wrappers over the C ABI (one Python function per export).
+"""Thin torch-tensor wrappers over the C ABI: one Python function per operation.
 
 Tensors are plumbing only: device memory, the current HIP stream and nothing
-else.  Activations are NHWC fp32 (`[N, H, W, C]` contiguous).  Every function
-launches asynchronously on `torch.cuda.current_stream()`.
-"""
-import torch
+else.  Activations are NHWC (`[N, H, W, C]` contiguous), fp32 or - on the
+mixed-precision pipeline - bf16; statistics, weights and gradients of weights are
+fp32.  Every function launches asynchronously on torch's current stream.
 
+An operation whose C entry point comes in several forms (storage type of the
+tensors, matrix-core operand mode, Winograd form, with or without the
+InstanceNorm-backward epilogue) has a `_sel_<operation>` function that names the
+entry point (resolved once per combination), says which optional arguments it
+takes and gives the KernelTimer tag; the wrapper then allocates, calls and
+brackets once.  The accounting rules of the timer records live in `_end_conv`
+(Winograd 16/36), `_end_lowres` (1/4) and `_sel_conv3x3_bwd_data` (stride-2
+launches).
+"""
 import ctypes
 import functools
+import struct
+import threading
+
+import torch
 
 from ._lib import ActSrc, BwdStats, check, lib
 
@@ -79,6 +91,27 @@ def set_timer(timer):
     _timer = timer
 
 
+def _begin(kind=None):
+    """Opening half of the timer bracket: the start event, or None when no timer is installed or
+    it does not take call sites of `kind`.  The closing half stays at the call site as
+    `if t0 is not None: _timer.end(...)`, so that the FLOP and byte arithmetic of a record runs
+    only when the record is kept."""
+    return _timer.begin(kind) if _timer is not None else None
+
+
+def _end_conv(t0, tag, alg, launches, wino):
+    """Record of a 3x3 matrix-core launch: a Winograd form F(2x2, 3x3) issues 16/36 of the
+    algorithmic MFMA FLOPs."""
+    _timer.end(tag, alg, launches, t0, executed=alg * 16.0 / 36.0 if wino else None)
+
+
+def _end_lowres(t0, tag, N, h, w, Cin, Cout, launches):
+    """Record of a gradient of conv3x3(upsample2x(.)) reassociated onto the low-resolution grid
+    (from the taps D): algorithmic FLOPs are those on the up-sampled grid, 1/4 of them execute."""
+    alg = 2.0 * N * 4 * h * w * 9 * Cin * Cout
+    _timer.end(tag, alg, launches, t0, executed=alg / 4)
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -108,9 +141,30 @@ def _ws(nbytes, like):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=like.device)
 
 
-# ---- deferred weight-gradient reductions (unet_wgrad_defer_*) -----------------------------------
-import threading
+@functools.lru_cache(maxsize=None)
+def _export(name):
+    """The entry point `name`, resolved once (the selectors below build names from parts)."""
+    return getattr(lib(), name)
 
+
+@functools.lru_cache(maxsize=None)
+def _twin(name, b16):
+    """The export `name`, or its twin for bf16 tensors (`name_b16`)."""
+    return getattr(lib(), name + "_b16" if b16 else name)
+
+
+def _call_nxt(fn, args, nxt):
+    """fn(*args, unet_bwd_stats* of the NextNorm `nxt` or NULL, stream); afterwards `nxt.tiles`
+    says whether the launch left that layer's InstanceNorm-backward reductions."""
+    if nxt is None:
+        check(fn(*args, None, _stream()))
+        return
+    bs = nxt.c_struct()
+    check(fn(*args, ctypes.byref(bs), _stream()))
+    nxt.tiles = bs.tiles_out
+
+
+# ---- deferred weight-gradient reductions (unet_wgrad_defer_*) -----------------------------------
 _defer = threading.local()
 
 
@@ -143,7 +197,7 @@ class wgrad_deferral:
     def flush(self):
         n = lib().unet_wgrad_defer_pending()
         if n:
-            t0 = _timer.begin("wgrad") if _timer is not None else None
+            t0 = _begin("wgrad")
             check(lib().unet_wgrad_defer_flush(_stream()))
             if t0 is not None:
                 _timer.end("conv_wgrad_reduce", 0.0, 2, t0)
@@ -232,7 +286,6 @@ class PackTable:
     def __init__(self, weights, planes, wino=None):
         """wino: per weight a pair (forward, data gradient) of flags - also keep the Winograd
         forms U = G g G^T of that layer (csrc/conv_wino.hip), refreshed by run()."""
-        import struct
         self.wf, self.wd, self.wf3, self.wd3 = [], [], [], []
         self.src_ptrs = [w.data_ptr() for w in weights]
         self.planes = planes
@@ -296,8 +349,7 @@ class PackTable:
 
 # ---- convolution ---------------------------------------------------------------
 _PREC = {False: 0, True: 1, 0: 0, 1: 1, 3: 3, "fp32": 0, "bf16": 1, "bf16x3": 3}
-_SUFFIX = {0: "", 1: "_bf16", 3: "_bf16x3"}
-_GROUP = {0: "", 1: "_bf16", 3: "_bf16x3"}
+_SUFFIX = {0: "", 1: "_bf16", 3: "_bf16x3"}   # of an operand mode: in export names and timer tags
 
 
 def _prec(bf16):
@@ -309,6 +361,15 @@ def _prec(bf16):
         raise ValueError("precision must be 'fp32', 'bf16' or 'bf16x3'") from None
 
 
+@functools.lru_cache(maxsize=None)
+def _sel_conv3x3_fwd(pr, C0):
+    """-> (entry point, takes the weight planes wf3, timer tag)"""
+    if pr == 3 and C0 == 3:
+        pr = 0                      # the RGB stem has no split form (K = 27, HBM-bound)
+    return (_export("unet_conv3x3_fwd" + _SUFFIX[pr]), pr == 3,
+            "conv_stem_fwd" if C0 == 3 else "conv_igemm" + _SUFFIX[pr])
+
+
 def conv3x3_fwd(x0, x1, wf, bias, stride, out=None, bf16=False, wf3=None):
     N, H, W, C0 = x0.shape
     C1 = 0 if x1 is None else x1.shape[3]
@@ -318,22 +379,15 @@ def conv3x3_fwd(x0, x1, wf, bias, stride, out=None, bf16=False, wf3=None):
     assert wf.shape[0] == 9 and wf.shape[2] == C0 + C1
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     y = out if out is not None else _f32((N, Ho, Wo, Cout), x0)
-    t0 = _timer.begin("conv") if _timer is not None else None
-    pr = _prec(bf16)
-    if pr == 3 and C0 == 3:
-        pr = 0                      # the RGB stem has no split form (K = 27, HBM-bound)
-    fn = getattr(lib(), "unet_conv3x3_fwd" + _SUFFIX[pr])
-    if pr == 3:
-        if wf3 is None:
-            raise ValueError("bf16x3 needs wf3 from pack_conv3x3_weights_bf16x3")
-        check(fn(_ptr(x0), C0, _ptr(x1), C1, _ptr(wf), _ptr(wf3), _ptr(bias), _ptr(y), N, H, W,
-                 Cout, stride, _stream()))
-    else:
-        check(fn(_ptr(x0), C0, _ptr(x1), C1, _ptr(wf), _ptr(bias), _ptr(y), N, H, W, Cout, stride,
-                 _stream()))
+    fn, planes, tag = _sel_conv3x3_fwd(_prec(bf16), C0)
+    if planes and wf3 is None:
+        raise ValueError("bf16x3 needs wf3 from pack_conv3x3_weights_bf16x3")
+    w3 = (_ptr(wf3),) if planes else ()
+    t0 = _begin("conv")
+    check(fn(_ptr(x0), C0, _ptr(x1), C1, _ptr(wf), *w3, _ptr(bias), _ptr(y), N, H, W, Cout, stride,
+             _stream()))
     if t0 is not None:
-        _timer.end("conv_stem_fwd" if C0 == 3 else "conv_igemm" + _GROUP[pr],
-                   2.0 * N * Ho * Wo * 9 * (C0 + C1) * Cout, 1, t0)
+        _timer.end(tag, 2.0 * N * Ho * Wo * 9 * (C0 + C1) * Cout, 1, t0)
     return y
 
 
@@ -404,92 +458,55 @@ def set_c32_winograd(on, override=True):
     return "always" if prev == 2 else bool(prev)
 
 
+@functools.lru_cache(maxsize=None)
+def _sel_conv3x3_bwd_data(b16, pr, has_wd3, has_nxt, wino):
+    """-> (entry point, takes the weight planes wd3, takes unet_bwd_stats, timer tag, launches at
+    stride 2: 4 = one per output parity class, 1 = one kernel covers them, 0 = the plain fp32
+    kernel: 1 when it has >= 512 tiles, else 4)"""
+    if wino:
+        return _export("unet_conv3x3_bwd_data_bs_wino"), False, True, "conv_igemm", 1
+    if b16:     # mixed-precision pipeline: bf16 tensors, bf16 matrix cores
+        if has_nxt or has_wd3:
+            # (wd3: the weights also pre-rounded to bf16 - plane 0 of the pack's planes)
+            return _export("unet_conv3x3_bwd_data_bs_b16_wb"), True, True, "conv_igemm_bf16", 4
+        return _export("unet_conv3x3_bwd_data_b16"), False, False, "conv_igemm_bf16", 4
+    bs = has_nxt and pr != 1
+    return (_export("unet_conv3x3_bwd_data" + ("_bs" if bs else "") + _SUFFIX[pr]), pr == 3, bs,
+            "conv_igemm" + _SUFFIX[pr], 1 if bs else (0 if pr == 0 else 4))
+
+
 def conv3x3_bwd_data(dy, wd, ci_offset, ccols, H, W, stride, out=None, accumulate=False,
                      bf16=False, wd3=None, nxt=None, ud=None):
     """dx[N,H,W,ccols] (+)= transpose-conv of dy for input channels [ci_offset, ci_offset+ccols).
-    nxt (NextNorm, fp32 path): dx is final for that layer - also emit its backward reductions.
+    nxt (NextNorm): dx is final for that layer - also emit its backward reductions.
     ud: the Winograd data-gradient form of the weight (fp32 tensors, stride 1, no accumulate,
     shape checked by the caller with conv_wino_supported)."""
     N, Ho, Wo, Cout = dy.shape
     cin_total = wd.shape[1]
     assert wd.shape[0] == 9 and wd.shape[2] == Cout
-    if ud is not None and not _is_b16(dy) and stride == 1 and not accumulate and _prec(bf16) == 0:
-        dx = out if out is not None else _f32((N, H, W, ccols), dy)
-        assert dx.shape == (N, H, W, ccols)
-        bs = nxt.c_struct() if nxt is not None else None
-        t0 = _timer.begin("conv") if _timer is not None else None
-        check(lib().unet_conv3x3_bwd_data_bs_wino(_ptr(dy), _ptr(ud), cin_total, ci_offset,
-                                                  _ptr(dx), N, H, W, Cout, ccols,
-                                                  ctypes.byref(bs) if bs is not None else None,
-                                                  _stream()))
-        if nxt is not None:
-            nxt.tiles = bs.tiles_out
-        if t0 is not None:
-            alg = 2.0 * N * H * W * 9 * ccols * Cout
-            _timer.end("conv_igemm", alg, 1, t0, executed=alg * 16.0 / 36.0)
-        return dx
-    if _is_b16(dy):     # mixed-precision pipeline: bf16 tensors, bf16 matrix cores
-        dx = out if out is not None else _b16((N, H, W, ccols), dy)
-        assert dx.shape == (N, H, W, ccols) and _is_b16(dx)
-        t0 = _timer.begin("conv") if _timer is not None else None
-        if nxt is not None or wd3 is not None:
-            # (wd3: the weights also pre-rounded to bf16 - plane 0 of the pack's planes)
-            bs = nxt.c_struct() if nxt is not None else None
-            check(lib().unet_conv3x3_bwd_data_bs_b16_wb(
-                _ptr(dy), _ptr(wd), _ptr(wd3), cin_total, ci_offset, _ptr(dx), N, H, W, Cout, ccols,
-                stride, 1 if accumulate else 0, ctypes.byref(bs) if bs is not None else None,
-                _stream()))
-            if nxt is not None:
-                nxt.tiles = bs.tiles_out
-        else:
-            check(lib().unet_conv3x3_bwd_data_b16(_ptr(dy), _ptr(wd), cin_total, ci_offset, _ptr(dx),
-                                                  N, H, W, Cout, ccols, stride,
-                                                  1 if accumulate else 0, _stream()))
-        if t0 is not None:
-            _timer.end("conv_igemm_bf16", 2.0 * N * Ho * Wo * 9 * ccols * Cout,
-                       1 if stride == 1 else 4, t0)
-        return dx
-    dx = out if out is not None else _f32((N, H, W, ccols), dy)
-    assert dx.shape == (N, H, W, ccols)
-    pr = _prec(bf16)
-    if nxt is not None and pr in (0, 3):
-        bs = nxt.c_struct()
-        t0 = _timer.begin("conv") if _timer is not None else None
-        if pr == 3:
-            check(lib().unet_conv3x3_bwd_data_bs_bf16x3(
-                _ptr(dy), _ptr(wd), _ptr(wd3), cin_total, ci_offset, _ptr(dx), N, H, W, Cout,
-                ccols, stride, 1 if accumulate else 0, ctypes.byref(bs), _stream()))
-        else:
-            check(lib().unet_conv3x3_bwd_data_bs(_ptr(dy), _ptr(wd), cin_total, ci_offset, _ptr(dx),
-                                                 N, H, W, Cout, ccols, stride,
-                                                 1 if accumulate else 0, ctypes.byref(bs),
-                                                 _stream()))
-        nxt.tiles = bs.tiles_out
-        if t0 is not None:
-            alg = 2.0 * N * Ho * Wo * 9 * ccols * Cout
-            c32w = pr == 0 and _c32_winograd(N, H, W, ccols, Cout, stride)
-            _timer.end("conv_igemm" + _GROUP[pr], alg, 1, t0,
-                       executed=alg * 16.0 / 36.0 if c32w else None)
-        return dx
-    t0 = _timer.begin("conv") if _timer is not None else None
-    fn = getattr(lib(), "unet_conv3x3_bwd_data" + _SUFFIX[pr])
-    if pr == 3:
-        if wd3 is None:
-            raise ValueError("bf16x3 needs wd3 from pack_conv3x3_weights_bf16x3")
-        check(fn(_ptr(dy), _ptr(wd), _ptr(wd3), cin_total, ci_offset, _ptr(dx), N, H, W, Cout,
-                 ccols, stride, 1 if accumulate else 0, _stream()))
+    b16 = _is_b16(dy)
+    pr = 1 if b16 else _prec(bf16)
+    wino = ud is not None and not b16 and stride == 1 and not accumulate and pr == 0
+    fn, planes, takes_bs, tag, stride2 = _sel_conv3x3_bwd_data(b16, pr, wd3 is not None,
+                                                               nxt is not None, wino)
+    dx = out if out is not None else (_b16 if b16 else _f32)((N, H, W, ccols), dy)
+    assert dx.shape == (N, H, W, ccols) and (not b16 or _is_b16(dx))
+    if planes and wd3 is None and not takes_bs:
+        raise ValueError("bf16x3 needs wd3 from pack_conv3x3_weights_bf16x3")
+    w3 = (_ptr(wd3),) if planes else ()
+    form = () if wino else (stride, 1 if accumulate else 0)
+    args = (_ptr(dy), _ptr(ud if wino else wd), *w3, cin_total, ci_offset, _ptr(dx), N, H, W, Cout,
+            ccols, *form)
+    t0 = _begin("conv")
+    if takes_bs:
+        _call_nxt(fn, args, nxt)
     else:
-        check(fn(_ptr(dy), _ptr(wd), cin_total, ci_offset, _ptr(dx), N, H, W, Cout, ccols, stride,
-                 1 if accumulate else 0, _stream()))
+        check(fn(*args, _stream()))
     if t0 is not None:
-        launches = 1
-        if stride == 2:  # fp32: one launch when >= 512 tiles, else one per output parity class
-            tiles = -(-(N * Ho * Wo) // 128) * (ccols // 32)
-            launches = 1 if (pr == 0 and tiles >= 512) else 4
-        alg = 2.0 * N * Ho * Wo * 9 * ccols * Cout
-        c32w = pr == 0 and _c32_winograd(N, H, W, ccols, Cout, stride)
-        _timer.end("conv_igemm" + _GROUP[pr], alg, launches, t0,
-                   executed=alg * 16.0 / 36.0 if c32w else None)
+        launches = 1 if stride == 1 else stride2 or \
+            (1 if -(-(N * Ho * Wo) // 128) * (ccols // 32) >= 512 else 4)
+        _end_conv(t0, tag, 2.0 * N * Ho * Wo * 9 * ccols * Cout, launches,
+                  wino or (not b16 and pr == 0 and _c32_winograd(N, H, W, ccols, Cout, stride)))
     return dx
 
 
@@ -500,15 +517,14 @@ def conv3x3_bwd_weight(x, dy, dw_oihw, ci_offset, stride, db=None, bf16=False):
     assert dw_oihw.shape[0] == Cout and dw_oihw.is_contiguous()
     nbytes = lib().unet_conv3x3_bwd_weight_workspace_bytes(N, H, W, Cx, Cout, stride)
     ws = _wgrad_ws(nbytes, x)
-    t0 = _timer.begin("wgrad") if _timer is not None else None
-    pr = _prec(bf16)
-    fn = getattr(lib(), "unet_conv3x3_bwd_weight" + _SUFFIX[pr])
-    check(fn(_ptr(x), Cx, _ptr(dy), _ptr(dw_oihw), ci_offset, cin_total, _ptr(db), _ptr(ws),
-             ws.numel(), N, H, W, Cout, stride, _stream()))
+    sfx = _SUFFIX[_prec(bf16)]
+    t0 = _begin("wgrad")
+    check(_export("unet_conv3x3_bwd_weight" + sfx)(
+        _ptr(x), Cx, _ptr(dy), _ptr(dw_oihw), ci_offset, cin_total, _ptr(db), _ptr(ws), ws.numel(),
+        N, H, W, Cout, stride, _stream()))
     if t0 is not None:  # wgrad kernel + slab reduce
-        Ho, Wo = dy.shape[1], dy.shape[2]
-        _timer.end("conv_stem_wgrad" if Cx == 3 else "conv_wgrad" + _GROUP[pr],
-                   2.0 * N * Ho * Wo * 9 * Cx * Cout, 2, t0)
+        _timer.end("conv_stem_wgrad" if Cx == 3 else "conv_wgrad" + sfx,
+                   2.0 * N * dy.shape[1] * dy.shape[2] * 9 * Cx * Cout, 2, t0)
     return dw_oihw
 
 
@@ -579,26 +595,20 @@ def instnorm_lrelu_drop_bwd(ga, y, mean, rstd, gamma, beta, mask, slope, dgamma,
     N, H, W, C = y.shape
     dy = ga if out is None else out
     ws = _ws(lib().unet_instnorm_workspace_bytes(N, H * W, C), y)
-    if partials is not None:
-        fnp = lib().unet_instnorm_lrelu_drop_bwd_partials_b16 if _is_b16(y) else \
-            lib().unet_instnorm_lrelu_drop_bwd_partials
-        t0 = _timer.begin() if _timer is not None else None
-        check(fnp(
-            _ptr(ga), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(mask), slope,
-            _ptr(dy), _ptr(dgamma), _ptr(dbeta), _ptr(dbias), _ptr(partials[0]), partials[1],
-            _ptr(ws), ws.numel(), N, H * W, C, _stream()))
-        if t0 is not None:   # apply pass only: ga + y in, dy out
-            _timer.end("instnorm_bwd", 0.0, 2, t0, nbytes=y.element_size() * 3.0 * y.numel())
-        return dy
-    fn = lib().unet_instnorm_lrelu_drop_bwd_b16 if _is_b16(y) else lib().unet_instnorm_lrelu_drop_bwd
-    if _is_b16(y) != _is_b16(ga):
-        raise TypeError("ga and y must share their storage type")
-    t0 = _timer.begin() if _timer is not None else None
-    check(fn(_ptr(ga), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(mask),
-             slope, _ptr(dy), _ptr(dgamma), _ptr(dbeta), _ptr(dbias), _ptr(ws), ws.numel(), N,
-             H * W, C, _stream()))
-    if t0 is not None:   # reduce pass: ga + y; apply pass: ga + y in, dy out (+ tiny finalizers)
-        _timer.end("instnorm_bwd", 0.0, 5, t0, nbytes=y.element_size() * 5 * y.numel())
+    if partials is not None:    # apply pass only: ga + y in, dy out
+        name, part, launches, passes = "unet_instnorm_lrelu_drop_bwd_partials", \
+            (_ptr(partials[0]), partials[1]), 2, 3.0
+    else:       # reduce pass: ga + y; apply pass: ga + y in, dy out (+ tiny finalizers)
+        name, part, launches, passes = "unet_instnorm_lrelu_drop_bwd", (), 5, 5
+        if _is_b16(y) != _is_b16(ga):
+            raise TypeError("ga and y must share their storage type")
+    t0 = _begin()
+    check(_twin(name, _is_b16(y))(
+        _ptr(ga), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(mask), slope,
+        _ptr(dy), _ptr(dgamma), _ptr(dbeta), _ptr(dbias), *part, _ptr(ws), ws.numel(), N, H * W, C,
+        _stream()))
+    if t0 is not None:
+        _timer.end("instnorm_bwd", 0.0, launches, t0, nbytes=y.element_size() * passes * y.numel())
     return dy
 
 
@@ -696,6 +706,44 @@ def pack_wino_weights(w_oihw, want_f=True, want_d=True):
     return uf, ud
 
 
+def _conv_stats_launch(fn, head, b16, like, N, H, W, Cout, stride):
+    """First half of the tail shared by the fused forwards "convolution + InstanceNorm statistics":
+    allocates y, the statistics and the workspace and launches `fn(*head, y, workspace, &px, N, H,
+    W, Cout, stream)` behind the opened timer bracket.  -> (y, st, ws, px, t0)"""
+    y = (_b16 if b16 else _f32)((N, (H - 1) // stride + 1, (W - 1) // stride + 1, Cout), like)
+    st = _f32((4, N, Cout), like)
+    ws = _ws(lib().unet_conv_in_fwd_workspace_bytes(N, H, W, Cout, stride), like)
+    px = ctypes.c_int(0)
+    t0 = _begin("conv")
+    check(fn(*head, _ptr(y), _ptr(ws), ws.numel(), ctypes.byref(px), N, H, W, Cout, _stream()))
+    return y, st, ws, px, t0
+
+
+def _conv_stats_finalize(b16, y, st, ws, px, gamma, beta, eps, mask):
+    """Second half: the statistics of y from the partial sums the convolution left in ws."""
+    N, Ho, Wo, Cout = y.shape
+    check(_twin("unet_conv_in_stats_finalize", b16)(
+        _ptr(y), _ptr(ws), ws.numel(), px.value, _ptr(gamma), _ptr(beta), eps, _ptr(mask),
+        _ptr(st[0]), _ptr(st[1]), _ptr(st[2]), _ptr(st[3]), N, Ho * Wo, Cout, _stream()))
+    return y, st
+
+
+@functools.lru_cache(maxsize=None)
+def _sel_conv_in_fwd(b16, u8, wino, has_w3, ksize, C0):
+    """-> (entry point, form: "u8" (normalising RGB stem) / "wino" (takes wu, no ksize / stride) /
+    "planes" (takes w3) / "plain", timer tag)"""
+    tag = "conv_stem_fwd" if C0 == 3 else \
+        "conv_igemm" + _SUFFIX[1 if b16 else (3 if has_w3 else 0)]
+    if u8:
+        return _export("unet_stem_u8_fwd"), "u8", tag
+    if wino:    # Winograd F(2x2, 3x3) form (the caller checked conv_wino_supported)
+        return _export("unet_conv_in_fwd_wino"), "wino", tag
+    # planes on bf16 tensors: the weights also pre-rounded to bf16 (plane 0 of the planes)
+    planes = has_w3 and C0 != 3 and (ksize == 3 or not b16)
+    mark = ("_b16_wb" if b16 else "_bf16x3") if planes else ("_b16" if b16 else "")
+    return _export("unet_conv_in_fwd" + mark), "planes" if planes else "plain", tag
+
+
 def conv_in_fwd(s0, s1, slope, w, bias, ksize, stride, gamma, beta, eps, mask, b16=False,
                 w3=None, wu=None):
     """Fused layer forward: y = conv(cat(act(s0), act(s1))) + bias and the InstanceNorm
@@ -714,52 +762,32 @@ def conv_in_fwd(s0, s1, slope, w, bias, ksize, stride, gamma, beta, eps, mask, b
         assert s1.shape[:3] == s0.shape[:3]
     Cout = w.shape[1] if ksize == 3 else w.shape[0]
     assert (w.shape[0] == 9 and w.shape[2] == C0 + C1) if ksize == 3 else w.shape[1] == C0 + C1
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     if b16:
         for src in (s0, s1):
             if src is not None and src.shape[3] != 3 and not _is_b16(src.x):
                 raise TypeError("the bf16 pipeline takes bf16 layer tensors")
         if u8 is not None:
             raise NotImplementedError("uint8 stem on the bf16 pipeline")
-    y = (_b16 if b16 else _f32)((N, Ho, Wo, Cout), s0.x)
-    st = _f32((4, N, Cout), s0.x)
-    ws = _ws(lib().unet_conv_in_fwd_workspace_bytes(N, H, W, Cout, stride), s0.x)
-    fwd = lib().unet_conv_in_fwd_b16 if b16 else lib().unet_conv_in_fwd
-    fin = lib().unet_conv_in_stats_finalize_b16 if b16 else lib().unet_conv_in_stats_finalize
-    px = ctypes.c_int(0)
-    t0 = _timer.begin("conv") if _timer is not None else None
-    if u8 is not None:
+    wino = wu is not None and not b16 and ksize == 3 and stride == 1
+    fn, form, tag = _sel_conv_in_fwd(b16, u8 is not None, wino, w3 is not None, ksize, C0)
+    if form == "u8":
         assert s1 is None and ksize == 3 and stride == 1
-        m3, s3 = u8.c_mean_std()
-        check(lib().unet_stem_u8_fwd(_ptr(u8.x), m3, s3, _ptr(w), _ptr(bias), _ptr(y), _ptr(ws),
-                                     ws.numel(), ctypes.byref(px), N, H, W, Cout, _stream()))
-    elif wu is not None and not b16 and ksize == 3 and stride == 1:
-        # Winograd F(2x2, 3x3) form (the caller checked conv_wino_supported)
-        check(lib().unet_conv_in_fwd_wino(r0, r1, slope, _ptr(wu), _ptr(bias), _ptr(y), _ptr(ws),
-                                          ws.numel(), ctypes.byref(px), N, H, W, Cout, _stream()))
-    elif w3 is not None and b16 and ksize == 3 and C0 != 3:
-        # mixed precision with the weights also pre-rounded to bf16 (plane 0 of the planes)
-        check(lib().unet_conv_in_fwd_b16_wb(r0, r1, slope, _ptr(w), _ptr(w3), _ptr(bias), ksize,
-                                            stride, _ptr(y), _ptr(ws), ws.numel(),
-                                            ctypes.byref(px), N, H, W, Cout, _stream()))
-    elif w3 is not None and not b16 and C0 != 3:
-        check(lib().unet_conv_in_fwd_bf16x3(r0, r1, slope, _ptr(w), _ptr(w3), _ptr(bias), ksize,
-                                            stride, _ptr(y), _ptr(ws), ws.numel(),
-                                            ctypes.byref(px), N, H, W, Cout, _stream()))
+        head = (_ptr(u8.x), *u8.c_mean_std(), _ptr(w), _ptr(bias))
+    elif form == "wino":
+        head = (r0, r1, slope, _ptr(wu), _ptr(bias))
+    elif form == "planes":
+        head = (r0, r1, slope, _ptr(w), _ptr(w3), _ptr(bias), ksize, stride)
     else:
-        check(fwd(r0, r1, slope, _ptr(w), _ptr(bias), ksize, stride, _ptr(y), _ptr(ws),
-                  ws.numel(), ctypes.byref(px), N, H, W, Cout, _stream()))
+        head = (r0, r1, slope, _ptr(w), _ptr(bias), ksize, stride)
+    y, st, ws, px, t0 = _conv_stats_launch(fn, head, b16, s0.x, N, H, W, Cout, stride)
     if t0 is not None:   # the convolution launch alone (its epilogue includes the statistics)
-        alg = 2.0 * N * Ho * Wo * ksize * ksize * (C0 + C1) * Cout
-        wino = wu is not None and not b16 and ksize == 3 and stride == 1
-        if not wino and not b16 and w3 is None and u8 is None and ksize == 3 and s1 is None:
+        # (a U8Image handed wu as well is recorded as a Winograd launch, which it is not: kept
+        # as it always was, the network never makes that call)
+        if form == "plain" and not b16 and w3 is None and ksize == 3 and s1 is None:
             wino = _c32_winograd(N, H, W, C0, Cout, stride)
-        _timer.end("conv_stem_fwd" if C0 == 3 else
-                   ("conv_igemm_bf16" if b16 else ("conv_igemm_bf16x3" if w3 is not None else "conv_igemm")),
-                   alg, 1, t0, executed=alg * 16.0 / 36.0 if wino else None)
-    check(fin(_ptr(y), _ptr(ws), ws.numel(), px.value, _ptr(gamma), _ptr(beta), eps, _ptr(mask),
-              _ptr(st[0]), _ptr(st[1]), _ptr(st[2]), _ptr(st[3]), N, Ho * Wo, Cout, _stream()))
-    return y, st
+        _end_conv(t0, tag, 2.0 * N * y.shape[1] * y.shape[2] * ksize * ksize * (C0 + C1) * Cout, 1,
+                  wino)
+    return _conv_stats_finalize(b16, y, st, ws, px, gamma, beta, eps, mask)
 
 
 def conv_up_in_fwd_supported(low, skip, Cout):
@@ -787,77 +815,51 @@ def conv_up_in_fwd(low, skip, slope, wf, bias, gamma, beta, eps, mask, wu=None, 
     assert low.shape[1] * 2 == H and low.shape[2] * 2 == W and low.shape[0] == N
     Cout = wf.shape[1]
     assert wf.shape[0] == 9 and wf.shape[2] == C0 + C1
-    if _is_b16(skip.x):
-        y = _b16((N, H, W, Cout), skip.x)
-        st = _f32((4, N, Cout), skip.x)
-        ws = _ws(lib().unet_conv_in_fwd_workspace_bytes(N, H, W, Cout, 1), skip.x)
-        px = ctypes.c_int(0)
-        t0 = _timer.begin("conv") if _timer is not None else None
-        check(lib().unet_conv_up_in_fwd_b16(rl, rs, slope, _ptr(wf), _ptr(w3), _ptr(bias), _ptr(y),
-                                            _ptr(ws), ws.numel(), ctypes.byref(px), N, H, W, Cout,
-                                            _stream()))
-        if t0 is not None:
-            _timer.end("conv_igemm_bf16", 2.0 * N * H * W * 9 * (C0 + C1) * Cout, 1, t0)
-        check(lib().unet_conv_in_stats_finalize_b16(_ptr(y), _ptr(ws), ws.numel(), px.value,
-                                                    _ptr(gamma), _ptr(beta), eps, _ptr(mask),
-                                                    _ptr(st[0]), _ptr(st[1]), _ptr(st[2]),
-                                                    _ptr(st[3]), N, H * W, Cout, _stream()))
-        return y, st
-    y = _f32((N, H, W, Cout), skip.x)
-    st = _f32((4, N, Cout), skip.x)
-    ws = _ws(lib().unet_conv_in_fwd_workspace_bytes(N, H, W, Cout, 1), skip.x)
-    px = ctypes.c_int(0)
-    t0 = _timer.begin("conv") if _timer is not None else None
-    if wu is not None:
-        check(lib().unet_conv_up_in_fwd_wino(rl, rs, slope, _ptr(wu), _ptr(bias), _ptr(y),
-                                             _ptr(ws), ws.numel(), ctypes.byref(px), N, H, W, Cout,
-                                             _stream()))
+    b16 = _is_b16(skip.x)
+    if b16:     # takes the bf16-rounded weight plane (or NULL), has no Winograd form
+        fn, head = lib().unet_conv_up_in_fwd_b16, (rl, rs, slope, _ptr(wf), _ptr(w3), _ptr(bias))
+    elif wu is not None:
+        fn, head = lib().unet_conv_up_in_fwd_wino, (rl, rs, slope, _ptr(wu), _ptr(bias))
     else:
-        check(lib().unet_conv_up_in_fwd(rl, rs, slope, _ptr(wf), _ptr(bias), _ptr(y), _ptr(ws),
-                                        ws.numel(), ctypes.byref(px), N, H, W, Cout, _stream()))
+        fn, head = lib().unet_conv_up_in_fwd, (rl, rs, slope, _ptr(wf), _ptr(bias))
+    y, st, ws, px, t0 = _conv_stats_launch(fn, head, b16, skip.x, N, H, W, Cout, 1)
     if t0 is not None:
-        alg = 2.0 * N * H * W * 9 * (C0 + C1) * Cout
-        wino = wu is not None or (low.alpha is not None and skip.alpha is not None and bool(
-            lib().unet_conv_up_c32_is_winograd(N, H, W, C0, C1, Cout)))
-        _timer.end("conv_igemm", alg, 1, t0, executed=alg * 16.0 / 36.0 if wino else None)
-    check(lib().unet_conv_in_stats_finalize(_ptr(y), _ptr(ws), ws.numel(), px.value, _ptr(gamma),
-                                            _ptr(beta), eps, _ptr(mask), _ptr(st[0]), _ptr(st[1]),
-                                            _ptr(st[2]), _ptr(st[3]), N, H * W, Cout, _stream()))
-    return y, st
+        wino = not b16 and (wu is not None or (
+            low.alpha is not None and skip.alpha is not None and
+            bool(lib().unet_conv_up_c32_is_winograd(N, H, W, C0, C1, Cout))))
+        _end_conv(t0, "conv_igemm_bf16" if b16 else "conv_igemm",
+                  2.0 * N * H * W * 9 * (C0 + C1) * Cout, 1, wino)
+    return _conv_stats_finalize(b16, y, st, ws, px, gamma, beta, eps, mask)
 
 
 def conv_in_bwd_weight(x, slope, dy, dw_oihw, ci_offset, ksize, stride, x3=False):
     """Weight gradient of a fused layer: dw[:, ci_offset : ci_offset + Cx] = act(x) (x) dy.
-    x3: the split-bf16 operand mode (fp32 tensors)."""
-    if isinstance(x, U8Image):
-        N, H, W, _ = x.shape
-        Cout = dy.shape[3]
-        ws = _wgrad_ws(lib().unet_conv3x3_bwd_weight_workspace_bytes(N, H, W, 3, Cout, 1), dy)
-        m3, s3 = x.c_mean_std()
-        t0 = _timer.begin("wgrad") if _timer is not None else None
-        check(lib().unet_stem_u8_bwd_weight(_ptr(x.x), m3, s3, _ptr(dy), _ptr(dw_oihw), _ptr(ws),
-                                            ws.numel(), N, H, W, Cout, _stream()))
-        if t0 is not None:
-            _timer.end("conv_stem_wgrad", 2.0 * N * H * W * 27 * Cout, 2, t0)
-        return dw_oihw
-    x, rx = _act(x)
+    x3: the split-bf16 operand mode (fp32 tensors).  x a U8Image: the whole weight gradient of
+    the normalising RGB stem (3x3, stride 1)."""
+    u8 = isinstance(x, U8Image)
+    if not u8:
+        x, rx = _act(x)
     N, H, W, Cx = x.shape
     Cout = dy.shape[3]
-    assert dw_oihw.shape[0] == Cout and dw_oihw.is_contiguous()
-    ws = _wgrad_ws(lib().unet_conv3x3_bwd_weight_workspace_bytes(N, H, W, Cx, Cout, stride), dy)
     b16 = _is_b16(dy)
-    fn = lib().unet_conv_in_bwd_weight_b16 if b16 else \
-        (lib().unet_conv_in_bwd_weight_bf16x3 if x3 else lib().unet_conv_in_bwd_weight)
-    t0 = _timer.begin("wgrad") if _timer is not None else None
-    check(fn(rx, slope, _ptr(dy), _ptr(dw_oihw), ci_offset, dw_oihw.shape[1], ksize, stride,
-             _ptr(ws), ws.numel(), N, H, W, Cout, _stream()))
+    sfx = "_bf16" if b16 else ("_bf16x3" if x3 else "")     # of the timer tag
+    if u8:
+        ksize, stride = 3, 1
+        fn, head = lib().unet_stem_u8_bwd_weight, \
+            (_ptr(x.x), *x.c_mean_std(), _ptr(dy), _ptr(dw_oihw))
+    else:
+        assert dw_oihw.shape[0] == Cout and dw_oihw.is_contiguous()
+        fn = _export("unet_conv_in_bwd_weight" + ("_b16" if b16 else sfx))
+        head = (rx, slope, _ptr(dy), _ptr(dw_oihw), ci_offset, dw_oihw.shape[1], ksize, stride)
+    ws = _wgrad_ws(lib().unet_conv3x3_bwd_weight_workspace_bytes(N, H, W, Cx, Cout, stride), dy)
+    t0 = _begin("wgrad")
+    check(fn(*head, _ptr(ws), ws.numel(), N, H, W, Cout, _stream()))
     if t0 is not None:
-        alg = 2.0 * N * dy.shape[1] * dy.shape[2] * ksize * ksize * Cx * Cout
-        wino = not b16 and not x3 and ksize == 3 and \
+        wino = not u8 and not b16 and not x3 and ksize == 3 and \
             bool(lib().unet_conv3x3_bwd_weight_is_winograd(N, H, W, Cx, Cout, stride))
-        _timer.end("conv_stem_wgrad" if Cx == 3 else
-                   ("conv_wgrad_bf16" if b16 else ("conv_wgrad_bf16x3" if x3 else "conv_wgrad")),
-                   alg, 2, t0, executed=alg * 16.0 / 36.0 if wino else None)
+        Ho, Wo = (H, W) if u8 else dy.shape[1:3]
+        _end_conv(t0, "conv_stem_wgrad" if Cx == 3 else "conv_wgrad" + sfx,
+                  2.0 * N * Ho * Wo * ksize * ksize * Cx * Cout, 2, wino)
     return dw_oihw
 
 
@@ -866,9 +868,8 @@ def upsample2x_in_fwd(x, slope):
     N, h, w, C = x.shape
     b16 = _is_b16(x.x)
     up = (_b16 if b16 else _f32)((N, 2 * h, 2 * w, C), x.x)
-    t0 = _timer.begin() if _timer is not None else None
-    fn = lib().unet_upsample2x_in_fwd_b16 if b16 else lib().unet_upsample2x_in_fwd
-    check(fn(rx, slope, _ptr(up), N, h, w, _stream()))
+    t0 = _begin()
+    check(_twin("unet_upsample2x_in_fwd", b16)(rx, slope, _ptr(up), N, h, w, _stream()))
     if t0 is not None:
         _timer.end("upsample2x_fwd", 0.0, 1, t0,
                    nbytes=x.x.element_size() * (x.x.numel() + up.numel()))
@@ -880,9 +881,9 @@ def upsample2x_bwd_taps(dy):
     N, H2, W2, C = dy.shape
     b16 = _is_b16(dy)
     D = (_b16 if b16 else _f32)((N, H2 // 2, W2 // 2, 9 * C), dy)
-    t0 = _timer.begin() if _timer is not None else None
-    fn = lib().unet_upsample2x_bwd_taps_b16 if b16 else lib().unet_upsample2x_bwd_taps
-    check(fn(_ptr(dy), _ptr(D), N, H2 // 2, W2 // 2, C, _stream()))
+    t0 = _begin()
+    check(_twin("unet_upsample2x_bwd_taps", b16)(_ptr(dy), _ptr(D), N, H2 // 2, W2 // 2, C,
+                                                 _stream()))
     if t0 is not None:   # reads dy once, writes 9/4 of it
         _timer.end("upsample2x_bwd_taps", 0.0, 1, t0,
                    nbytes=dy.element_size() * dy.numel() * (1 + 9 / 4))
@@ -896,15 +897,23 @@ def conv3x3_up_bwd_weight(x, slope, D, dw_oihw, ci_offset):
     Cout = D.shape[3] // 9
     assert D.shape[:3] == x.shape[:3] and dw_oihw.shape[0] == Cout and dw_oihw.is_contiguous()
     ws = _wgrad_ws(lib().unet_conv3x3_up_bwd_weight_workspace_bytes(N, h, w, Cx, Cout), D)
-    fn = lib().unet_conv3x3_up_bwd_weight_b16 if _is_b16(D) else lib().unet_conv3x3_up_bwd_weight
-    t0 = _timer.begin("wgrad") if _timer is not None else None
-    check(fn(rx, slope, _ptr(D), _ptr(dw_oihw), ci_offset, dw_oihw.shape[1], _ptr(ws), ws.numel(),
-             N, h, w, Cout, _stream()))
-    if t0 is not None:   # algorithmic FLOPs: the 3x3 weight gradient on the up-sampled grid
-        _timer.end("conv_wgrad_bf16" if _is_b16(D) else "conv_wgrad",
-                   2.0 * N * 4 * h * w * 9 * Cx * Cout, 2, t0,
-                   executed=2.0 * N * h * w * 9 * Cx * Cout)
+    b16 = _is_b16(D)
+    t0 = _begin("wgrad")
+    check(_twin("unet_conv3x3_up_bwd_weight", b16)(
+        rx, slope, _ptr(D), _ptr(dw_oihw), ci_offset, dw_oihw.shape[1], _ptr(ws), ws.numel(), N, h,
+        w, Cout, _stream()))
+    if t0 is not None:
+        _end_lowres(t0, "conv_wgrad_bf16" if b16 else "conv_wgrad", N, h, w, Cx, Cout, 2)
     return dw_oihw
+
+
+@functools.lru_cache(maxsize=None)
+def _sel_conv3x3_up_bwd_data(b16, has_wd3, has_nxt):
+    """-> (entry point, takes the bf16-rounded weights wd3, takes unet_bwd_stats, timer tag)"""
+    wb = b16 and has_wd3
+    bs = wb or has_nxt
+    return (_export("unet_conv3x3_up_bwd_data" + ("_bs" if bs else "") + ("_b16" if b16 else "") +
+                    ("_wb" if wb else "")), wb, bs, "conv_igemm_bf16" if b16 else "conv_igemm")
 
 
 def conv3x3_up_bwd_data(D, wd, ci_offset, ccols, out=None, accumulate=False, nxt=None, wd3=None):
@@ -917,28 +926,17 @@ def conv3x3_up_bwd_data(D, wd, ci_offset, ccols, out=None, accumulate=False, nxt
     assert wd.shape[0] == 9 and wd.shape[2] == Cout
     b16 = _is_b16(D)
     g = out if out is not None else (_b16 if b16 else _f32)((N, h, w, ccols), D)
-    fn = lib().unet_conv3x3_up_bwd_data_b16 if b16 else lib().unet_conv3x3_up_bwd_data
-    t0 = _timer.begin("conv") if _timer is not None else None
-    if b16 and wd3 is not None:
-        bs = nxt.c_struct() if nxt is not None else None
-        check(lib().unet_conv3x3_up_bwd_data_bs_b16_wb(
-            _ptr(D), _ptr(wd), _ptr(wd3), cin_total, ci_offset, _ptr(g), N, h, w, Cout, ccols,
-            1 if accumulate else 0, ctypes.byref(bs) if bs is not None else None, _stream()))
-        if nxt is not None:
-            nxt.tiles = bs.tiles_out
-    elif nxt is not None:
-        bs = nxt.c_struct()
-        fbs = lib().unet_conv3x3_up_bwd_data_bs_b16 if b16 else lib().unet_conv3x3_up_bwd_data_bs
-        check(fbs(_ptr(D), _ptr(wd), cin_total, ci_offset, _ptr(g), N, h, w, Cout, ccols,
-                  1 if accumulate else 0, ctypes.byref(bs), _stream()))
-        nxt.tiles = bs.tiles_out
+    fn, planes, takes_bs, tag = _sel_conv3x3_up_bwd_data(b16, wd3 is not None, nxt is not None)
+    w3 = (_ptr(wd3),) if planes else ()
+    args = (_ptr(D), _ptr(wd), *w3, cin_total, ci_offset, _ptr(g), N, h, w, Cout, ccols,
+            1 if accumulate else 0)
+    t0 = _begin("conv")
+    if takes_bs:
+        _call_nxt(fn, args, nxt)
     else:
-        check(fn(_ptr(D), _ptr(wd), cin_total, ci_offset, _ptr(g), N, h, w, Cout, ccols,
-                 1 if accumulate else 0, _stream()))
-    if t0 is not None:   # algorithmic FLOPs: the 3x3 data gradient on the up-sampled grid
-        _timer.end("conv_igemm_bf16" if b16 else "conv_igemm",
-                   2.0 * N * 4 * h * w * 9 * ccols * Cout, 1, t0,
-                   executed=2.0 * N * h * w * 9 * ccols * Cout)
+        check(fn(*args, _stream()))
+    if t0 is not None:
+        _end_lowres(t0, tag, N, h, w, ccols, Cout, 1)
     return g
 
 
@@ -947,9 +945,9 @@ def head1x1_in_fwd(x, slope, w, b):
     N, H, W, C = x.shape
     K = w.shape[0]
     logits = _f32((N, K, H, W), x.x)
-    fn = lib().unet_head1x1_in_fwd_b16 if _is_b16(x.x) else lib().unet_head1x1_in_fwd
-    t0 = _timer.begin() if _timer is not None else None
-    check(fn(rx, slope, _ptr(w), _ptr(b), _ptr(logits), N, H * W, K, _stream()))
+    t0 = _begin()
+    check(_twin("unet_head1x1_in_fwd", _is_b16(x.x))(rx, slope, _ptr(w), _ptr(b), _ptr(logits), N,
+                                                     H * W, K, _stream()))
     if t0 is not None:
         _timer.end("head_fwd", 0.0, 1, t0,
                    nbytes=x.x.element_size() * x.x.numel() + 4.0 * logits.numel())
@@ -964,18 +962,14 @@ def head1x1_in_bwd(x, slope, dlogits, w, dw, db, nxt=None):
     K = w.shape[0]
     da = torch.empty_like(x.x)
     ws = _ws(lib().unet_head1x1_bwd_workspace_bytes(N, H * W, C, K), x.x)
-    b16 = _is_b16(x.x)
-    t0 = _timer.begin() if _timer is not None else None
+    args = (rx, slope, _ptr(dlogits), _ptr(w), _ptr(da), _ptr(dw), _ptr(db), _ptr(ws), ws.numel(),
+            N, H * W, K)
+    fn = _twin("unet_head1x1_in_bwd" + ("_bs" if nxt is not None else ""), _is_b16(x.x))
+    t0 = _begin()
     if nxt is not None:
-        bs = nxt.c_struct()
-        fn = lib().unet_head1x1_in_bwd_bs_b16 if b16 else lib().unet_head1x1_in_bwd_bs
-        check(fn(rx, slope, _ptr(dlogits), _ptr(w), _ptr(da), _ptr(dw), _ptr(db), _ptr(ws),
-                 ws.numel(), N, H * W, K, ctypes.byref(bs), _stream()))
-        nxt.tiles = bs.tiles_out
+        _call_nxt(fn, args, nxt)
     else:
-        fn = lib().unet_head1x1_in_bwd_b16 if b16 else lib().unet_head1x1_in_bwd
-        check(fn(rx, slope, _ptr(dlogits), _ptr(w), _ptr(da), _ptr(dw), _ptr(db), _ptr(ws),
-                 ws.numel(), N, H * W, K, _stream()))
+        check(fn(*args, _stream()))
     if t0 is not None:
         _timer.end("head_bwd", 0.0, 2, t0,
                    nbytes=da.element_size() * 2 * da.numel() + 4.0 * dlogits.numel())
@@ -1172,7 +1166,6 @@ def eval_maps(logits, target=None, want_probs=True, want_classes=True, want_erro
 
 def preprocess_u8(image_hwc_u8, mask_u8=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """uint8 [N,H,W,3] (+ uint8 [N,H,W]) on the device -> (fp32 NHWC image, int64 target)."""
-    import ctypes
     N, H, W, C = image_hwc_u8.shape
     if C != 3 or image_hwc_u8.dtype != torch.uint8 or not image_hwc_u8.is_contiguous():
         raise TypeError("preprocess_u8 takes a contiguous uint8 [N,H,W,3] tensor")
@@ -1193,7 +1186,7 @@ def preprocess_u8(image_hwc_u8, mask_u8=None, mean=IMAGENET_MEAN, std=IMAGENET_S
 # ---- optimizer -------------------------------------------------------------------------
 def sgd_nesterov_step(params, grads, momentum, lr, mu, weight_decay, first_step, grad_scale=1.0):
     n = params.numel()
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _begin()
     check(lib().unet_sgd_nesterov_step(_ptr(params), _ptr(grads), _ptr(momentum), n, lr, mu,
                                        weight_decay, 1 if first_step else 0, grad_scale,
                                        _stream()))
@@ -1217,7 +1210,7 @@ def recon3x3_fwd(x, slope, w, b):
     N, H, W, C = x.shape
     K = w.shape[0]
     out = _f32((N, K, H, W), x.x)
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _begin()
     check(lib().unet_recon3x3_fwd(rx, 1 if _is_b16(x.x) else 0, slope, _ptr(w), _ptr(b),
                                   _ptr(out), N, H, W, K, _stream()))
     if t0 is not None:
@@ -1241,14 +1234,10 @@ def recon3x3_bwd(x, slope, dout, out, w, dw, db, nxt=None):
     ws = _recon_ws.get(key)
     if ws is None:
         ws = _recon_ws[key] = _ws(lib().unet_recon3x3_bwd_workspace_bytes(N, H, W), x.x)
-    bs = nxt.c_struct() if nxt is not None else None
-    t0 = _timer.begin() if _timer is not None else None
-    check(lib().unet_recon3x3_bwd(rx, 1 if _is_b16(x.x) else 0, slope, _ptr(dout), _ptr(out),
-                                  _ptr(w), _ptr(da), _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), N,
-                                  H, W, K, ctypes.byref(bs) if bs is not None else None,
-                                  _stream()))
-    if nxt is not None:
-        nxt.tiles = bs.tiles_out
+    t0 = _begin()
+    _call_nxt(lib().unet_recon3x3_bwd,
+              (rx, 1 if _is_b16(x.x) else 0, slope, _ptr(dout), _ptr(out), _ptr(w), _ptr(da),
+               _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), N, H, W, K), nxt)
     if t0 is not None:   # x in, da out, dout + out in
         _timer.end("recon_bwd", 4.0 * N * H * W * K * C * 9, 2, t0,
                    nbytes=da.element_size() * 2.0 * da.numel() + 8.0 * dout.numel())
@@ -1272,7 +1261,7 @@ def mse_loss_fwd(out, target, target_u8=False):
     loss = _f32((1,), out)
     per_image = torch.empty((N,), dtype=torch.float64, device=out.device)
     ws = _ws(lib().unet_mse_loss_workspace_bytes(N, C, H, W), out)
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _begin()
     check(lib().unet_mse_loss_fwd(_ptr(out), _ptr(target), 1 if target_u8 else 0, _ptr(loss),
                                   per_image.data_ptr(), _ptr(ws), ws.numel(), N, C, H, W,
                                   _stream()))
@@ -1289,7 +1278,7 @@ def mse_loss_grad(out, target, upstream=None, target_u8=False):
     dout = torch.empty_like(out)
     if upstream is not None:
         upstream = upstream.reshape(1).float().contiguous()
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _begin()
     check(lib().unet_mse_loss_grad(_ptr(out), _ptr(target), 1 if target_u8 else 0, _ptr(upstream),
                                    _ptr(dout), N, C, H, W, _stream()))
     if t0 is not None:
@@ -1304,7 +1293,7 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, hyper, advance_step):
     n = params.numel()
     if hyper.dtype != torch.float64 or not hyper.is_cuda or hyper.numel() < 8:
         raise TypeError("hyper must be an fp64 [8] device tensor")
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _begin()
     check(lib().unet_adam_step(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n,
                                hyper.data_ptr(), 1 if advance_step else 0, _stream()))
     if t0 is not None:   # p, g, m, v in; p, m, v out
@@ -1339,7 +1328,7 @@ def ssim_fwd(pred, target, target_u8=False, window=None, c1=1e-4, c2=9e-4, w_ssi
     ssim = torch.empty((N,), dtype=torch.float64, device=pred.device)
     sq = torch.empty((N,), dtype=torch.float64, device=pred.device)
     ws = _ws(lib().unet_ssim_workspace_bytes(N, C, H, W), pred)
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _begin()
     check(lib().unet_ssim_fwd(_ptr(pred), _ptr(target), 1 if target_u8 else 0, g, c1, c2,
                               ssim.data_ptr(), sq.data_ptr(), _ptr(loss), w_ssim, w_mse, _ptr(ws),
                               ws.numel(), N, C, H, W, _stream()))
@@ -1364,7 +1353,7 @@ def ssim_grad(pred, target, upstream=None, upstream_per_image=False, target_u8=F
             raise ValueError("upstream must hold one value (or one per image)")
     elif upstream_per_image:
         raise ValueError("a per-image upstream needs upstream")
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _begin()
     check(lib().unet_ssim_grad(_ptr(pred), _ptr(target), 1 if target_u8 else 0, g, c1, c2,
                                _ptr(upstream), 1 if upstream_per_image else 0, w_ssim, w_mse,
                                _ptr(dpred), N, C, H, W, _stream()))
