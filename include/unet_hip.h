@@ -807,6 +807,31 @@ int unet_ssim_grad(const float* pred_nchw, const void* target, int target_u8,
                    int upstream_per_image, double w_ssim, double w_mse, float* dpred_nchw, int N,
                    int C, int H, int W, unet_stream_t stream);
 
+/* ---- Grad-CAM (Our_UNet/utils/visualize.py:372-439) ---------------------------------------- *
+ * The tail of generate_gradcam_heatmap after the backward pass, for a whole batch: A = the output
+ * of the target stage, G = dL/dA, both NHWC [N][HW][C] in the layer tensors' storage type
+ * (*_bf16: 0 = fp32, 1 = bf16; the arithmetic is fp32).  C = 4..256 a power of two, 512 or 1024;
+ * HW <= 2^30.  Fixed-order sums, no floating-point atomics (two runs are bit-identical), nothing
+ * is read back to the host.  One workspace of unet_gradcam_workspace_bytes(N, HW, C) serves the
+ * three calls, in this order on one stream. */
+size_t unet_gradcam_workspace_bytes(int N, int HW, int C);
+/* w[N][C] = mean over the pixels of g (visualize.py:424), correctly divided by HW. */
+int unet_gradcam_weights(const void* g, int g_bf16, float* w, void* workspace,
+                         size_t workspace_bytes, int N, int HW, int C, unet_stream_t stream);
+/* cam[N][HW] = max(0, sum_c w[n][c] * act(a)[n][p][c]) (:427-428); a is activated while it is
+ * loaded, as every consumer of a fused layer does (a->alpha == NULL: a plain tensor; eval mode,
+ * so the coefficients carry no dropout mask).  Leaves per-workgroup (min, max) of cam in the
+ * workspace for unet_gradcam_heatmap. */
+int unet_gradcam_map(const unet_act_src* a, int a_bf16, float slope, const float* w, float* cam,
+                     void* workspace, size_t workspace_bytes, int N, int HW, unet_stream_t stream);
+/* heatmap[N][H][W] = bilinear resize (align_corners = False, the rule of
+ * unet_resize_bilinear_fwd) of the per-image normalisation of cam[N][h][w] (:431-437):
+ * (cam - min) / max(cam - min), each tap normalised as it is read; an image whose
+ * max(cam - min) is 0 stays all zero (the reference's `if cam.max() != 0`, decided on the
+ * device, no division).  workspace: as left by unet_gradcam_map with the same N and HW = h * w. */
+int unet_gradcam_heatmap(const float* cam, const void* workspace, size_t workspace_bytes,
+                         float* heatmap, int N, int h, int w, int H, int W, unet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

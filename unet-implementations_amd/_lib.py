@@ -96,6 +96,10 @@ SIGNATURES = {
     "unet_argmax_dice_counts": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "unet_eval_confusion": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "unet_eval_maps": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "unet_gradcam_workspace_bytes": (_sz, [_i, _i, _i]),
+    "unet_gradcam_weights": (_i, [_p, _i, _p, _p, _sz, _i, _i, _i, _p]),
+    "unet_gradcam_map": (_i, [_ps, _i, _f, _p, _p, _p, _sz, _i, _i, _p]),
+    "unet_gradcam_heatmap": (_i, [_p, _p, _sz, _p, _i, _i, _i, _i, _i, _p]),
     "unet_preprocess_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _c.POINTER(_f), _c.POINTER(_f), _p]),
     "unet_sgd_nesterov_step": (_i, [_p, _p, _p, _i64, _f, _f, _f, _i, _f, _p]),
     "unet_sgd_nesterov_step_dev": (_i, [_p, _p, _p, _i64, _p, _i, _p]),

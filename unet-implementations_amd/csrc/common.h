@@ -189,6 +189,18 @@ __device__ __forceinline__ f32x4 blend2x2(const f32x4 p00, const f32x4 p01, cons
   return v;
 }
 
+// PyTorch's bilinear source index for align_corners = False (the general resize of misc.hip and
+// the Grad-CAM heatmap): src = max((dst + 0.5) * (in / out) - 0.5, 0), i0 = floor(src),
+// i1 = min(i0 + 1, in - 1), weights (1 - l, l) with l = src - i0.  scale = (float)in / (float)out.
+__device__ __forceinline__ void bil_src(int dst, float scale, int in, int& i0, int& i1, float& l) {
+  float src = ((float)dst + 0.5f) * scale - 0.5f;
+  src = src < 0.f ? 0.f : src;
+  i0 = (int)src;
+  i0 = i0 > in - 1 ? in - 1 : i0;
+  i1 = i0 + 1 > in - 1 ? in - 1 : i0 + 1;
+  l = src - (float)i0;
+}
+
 // Chan/Welford merge of (count, mean, M2) pairs.
 __device__ __forceinline__ void wf_merge(float& n, float& mean, float& m2, float nb, float mb,
                                          float m2b) {

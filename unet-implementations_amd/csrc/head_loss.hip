@@ -755,6 +755,7 @@ static int head1x1_bwd_impl(const float* a, const float* dlogits, const float* w
     hipLaunchKernelGGL(head_bwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a,
                        dlogits, w, da, partial, M, HW, K, tiles, alpha, beta, slope, hb);
   UNET_CHECK_LAUNCH("head_bwd");
+  if (!dw && !db) return UNET_OK;     // data gradient only (Grad-CAM): no parameter gradients
   hipLaunchKernelGGL(head_bwd_finalize_kernel, dim3(K * 32 + K), dim3(256), 0, (hipStream_t)stream,
                      partial, dw, db, blocks, K);
   UNET_CHECK_LAUNCH("head_bwd_finalize");

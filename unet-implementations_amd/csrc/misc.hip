@@ -542,14 +542,7 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_taps_kernel(const TS* __re
 // to the bottleneck features (CLIP_UNet/models/unet.py:444-450).  PyTorch's source index:
 // src = max((dst + 0.5) * (in / out) - 0.5, 0), i0 = floor(src), i1 = min(i0 + 1, in - 1),
 // weights (1 - l, l) with l = src - i0; blend order w0y (w0x p00 + w1x p01) + w1y (...).
-__device__ __forceinline__ void bil_src(int dst, float scale, int in, int& i0, int& i1, float& l) {
-  float src = ((float)dst + 0.5f) * scale - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  i0 = i0 > in - 1 ? in - 1 : i0;
-  i1 = i0 + 1 > in - 1 ? in - 1 : i0 + 1;
-  l = src - (float)i0;
-}
+// (bil_src: common.h - unet_gradcam_heatmap samples by the same rule)
 __global__ __launch_bounds__(256) void resize_bilinear_fwd_kernel(const float* __restrict__ x,
                                                                   float* __restrict__ y, int h,
                                                                   int w, int H, int W,

@@ -9,14 +9,19 @@ a batch in one launch and the loop has no host sync until the results are read.
 
 `confidence_maps` / `error_maps` return what `visualize_confidence_maps_batch` and
 `create_error_visualization` (utils/visualize.py:96-238) compute before they plot, as device
-tensors (`unet_eval_maps`).  Plotting itself (matplotlib) is not part of this package.
+tensors (`unet_eval_maps`).  `gradcam` / `gradcam_batch` / `generate_gradcam_heatmap` are the
+tensors behind `visualize_gradcam` (utils/visualize.py:372-516): a gradient-only backward that
+stops at the target stage and three small kernels (`unet_gradcam_*`), for a whole batch.
+Plotting itself (matplotlib) is not part of this package.
 """
 import numpy as np
 import torch
+import torch.nn as nn
 
 from . import ops
 from .metrics import accumulate_test_metrics
 from .train import create_model
+from .unet import stage_feature_and_gradient
 
 
 def load_model(model_path, device):
@@ -39,7 +44,8 @@ def evaluate_model(model, test_loader, device, visualize_samples=0):
     matplotlib: `visualize_samples > 0` is not supported (see confidence_maps / error_maps)."""
     if visualize_samples > 0:
         raise NotImplementedError("plots are not part of the HIP path (use visualize_samples=0; "
-                                  "confidence_maps / error_maps return the plotted tensors)")
+                                  "confidence_maps / error_maps / gradcam return the plotted "
+                                  "tensors)")
     metrics = accumulate_test_metrics(model, test_loader, device)
     results = {"pixel_accuracy": metrics.compute_pixel_accuracy(),
                "mean_iou": metrics.compute_mean_iou()}
@@ -76,3 +82,87 @@ def error_maps(model, images, masks):
         masks = masks.long()
     return ops.eval_maps(_eval_logits(model, images), masks, want_probs=False,
                          want_classes=False)[2]
+
+
+def _gradcam_target(model, target_layer):
+    """The stage module whose output the walk holds for `target_layer`, or ValueError."""
+    if target_layer is None:
+        return model.decoder_stages[0]
+    for stage in model.encoder_stages:
+        if target_layer is stage:
+            return stage
+    for stage in model.decoder_stages:
+        if target_layer is stage or target_layer is stage.conv_block:
+            return stage
+    name = next((n for n, m in model.named_modules() if m is target_layer), None)
+    if name is None:
+        raise ValueError("target_layer is not a module of this model")
+    msg = (f"target_layer {name} ({type(target_layer).__name__}) is an inner module: the fused "
+           "HIP walk never holds that tensor (a layer exists in memory only as its raw "
+           "convolution output plus InstanceNorm coefficients).  Use encoder_stages[i], "
+           "decoder_stages[i] or decoder_stages[i].conv_block; target_layer=None is "
+           "decoder_stages[0].")
+    if isinstance(target_layer, nn.Conv2d) and target_layer is not model.segmentation_output:
+        msg += ("  For this convolution the request is also empty: its output feeds an "
+                "InstanceNorm, the gradient with respect to an InstanceNorm input sums to zero "
+                "over every (image, channel) plane, so the Grad-CAM channel weights - that "
+                "spatial mean - are identically zero in exact arithmetic and the reference's "
+                "picture for this target is rounding noise.")
+    raise ValueError(msg)
+
+
+def gradcam(model, images, target_class, target_layer=None, precision="fp32"):
+    """Grad-CAM heatmaps of a whole batch: fp32 [B, H, W] on the device, no host sync - per image
+    what the reference's generate_gradcam_heatmap (utils/visualize.py:372-439) returns for
+    images[b:b+1].
+
+    target_layer: encoder_stages[i], decoder_stages[i] or decoder_stages[i].conv_block (the same
+    tensor as its stage); None = decoder_stages[0], the "first decoder stage" of the reference's
+    docstring.  (The reference's code default, the inner Conv2d decoder_stages[0].conv_block.
+    block[0], raises ValueError like every inner module: see the message.)
+    precision: "fp32" (default) runs this pass in the fp32 operand mode whatever
+    model.matmul_precision is (the master weights are fp32); None runs it in the model's own mode,
+    bf16 layer tensors included.  Grad-CAM through many InstanceNorms is ill-conditioned for deep
+    targets: no accuracy is claimed for the bf16 mode.
+
+    Unlike the reference (model.zero_grad() + a full backward per image) this leaves every .grad,
+    the gradient arena, model.training and dropout_mask_override as they were."""
+    if precision not in (None, "fp32"):
+        raise ValueError("precision must be 'fp32' or None (the model's own mode)")
+    target = _gradcam_target(model, target_layer)
+    K = model.segmentation_output.out_channels
+    if not 0 <= int(target_class) < K:
+        raise ValueError(f"target_class {target_class} is outside [0, {K})")
+    if not torch.is_tensor(images) or not images.is_cuda:
+        raise RuntimeError("unet-implementations_amd.evaluate.gradcam runs on MI355X only "
+                           "(no CPU fallback exists)")
+    mode = model.matmul_precision
+    if precision is not None:
+        model.matmul_precision = precision
+    try:
+        feature, grad, slope = stage_feature_and_gradient(model, images, target_class, target)
+    finally:
+        model.matmul_precision = mode
+    N, h, w, C = grad.shape
+    ws = ops.gradcam_workspace(N, h * w, C, grad)
+    weights = ops.gradcam_weights(grad, ws)
+    cam, ws = ops.gradcam_map(feature, slope, weights, ws)
+    return ops.gradcam_heatmap(cam, ws, images.shape[2:])
+
+
+def generate_gradcam_heatmap(model, input_tensor, target_class, target_layer, device):
+    """The reference's helper with its signature (utils/visualize.py:372-439): the squeezed numpy
+    heatmap of `input_tensor` ([1, C, H, W] -> [H, W]), so its visualize_gradcam can import this
+    one instead.  One device-to-host copy, at the end."""
+    heat = gradcam(model, input_tensor.to(device), target_class, target_layer)
+    return heat.squeeze().cpu().numpy()
+
+
+def gradcam_batch(model, batch, device, target_class=1, target_layer=None):
+    """(heatmaps fp32 [B, H, W], present bool [B]) on the device for a loader batch: what
+    visualize_gradcam (utils/visualize.py:442-516) computes before it plots.  present[b] says
+    whether batch["mask"][b] contains target_class - the images the reference's np.unique test
+    (:474-476) does not skip."""
+    images, masks = batch["image"].to(device), batch["mask"].to(device)
+    present = (masks == target_class).flatten(1).any(dim=1)
+    return gradcam(model, images, target_class, target_layer), present

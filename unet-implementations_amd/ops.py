@@ -1164,6 +1164,56 @@ def eval_maps(logits, target=None, want_probs=True, want_classes=True, want_erro
     return probs, classes, errors
 
 
+# ---- Grad-CAM (gradcam.hip) ------------------------------------------------------------------
+def gradcam_workspace(N, HW, C, like):
+    """The workspace the three Grad-CAM calls of one heatmap share."""
+    return _ws(lib().unet_gradcam_workspace_bytes(N, HW, C), like)
+
+
+def gradcam_weights(g, ws=None):
+    """w fp32 [N, C] = mean over the pixels of g [N, h, w, C] (NHWC, fp32 or bf16)."""
+    N, h, w_, C = g.shape
+    ws = gradcam_workspace(N, h * w_, C, g) if ws is None else ws
+    w = _f32((N, C), g)
+    t0 = _begin()
+    check(lib().unet_gradcam_weights(_ptr(g), 1 if _is_b16(g) else 0, _ptr(w), _ptr(ws),
+                                     ws.numel(), N, h * w_, C, _stream()))
+    if t0 is not None:
+        _timer.end("gradcam_weights", 0.0, 2, t0, nbytes=float(g.element_size() * g.numel()))
+    return w
+
+
+def gradcam_map(a, slope, w, ws=None):
+    """cam fp32 [N, h, w] = relu(sum_c w[n, c] * act(a)[n, :, :, c]); a: ops.Act (activated on
+    load) or a plain NHWC tensor.  The per-workgroup minima / maxima stay in `ws` for
+    gradcam_heatmap."""
+    a, ra = _act(a)
+    N, h, w_, C = a.shape
+    if tuple(w.shape) != (N, C) or w.dtype != torch.float32:
+        raise ValueError("w must be an fp32 [N, C] tensor")
+    ws = gradcam_workspace(N, h * w_, C, a.x) if ws is None else ws
+    cam = _f32((N, h, w_), a.x)
+    t0 = _begin()
+    check(lib().unet_gradcam_map(ra, 1 if _is_b16(a.x) else 0, slope, _ptr(w), _ptr(cam), _ptr(ws),
+                                 ws.numel(), N, h * w_, _stream()))
+    if t0 is not None:
+        _timer.end("gradcam_map", 0.0, 1, t0,
+                   nbytes=float(a.x.element_size() * a.x.numel() + 4 * cam.numel()))
+    return cam, ws
+
+
+def gradcam_heatmap(cam, ws, size):
+    """fp32 [N, H, W]: cam [N, h, w] normalised per image (minus its minimum, over its range unless
+    that is 0: then all zero) and resized bilinearly (align_corners=False) to size = (H, W).
+    ws: what gradcam_map returned for this cam."""
+    N, h, w_ = cam.shape
+    H, W = int(size[0]), int(size[1])
+    out = _f32((N, H, W), cam)
+    check(lib().unet_gradcam_heatmap(_ptr(cam), _ptr(ws), ws.numel(), _ptr(out), N, h, w_, H, W,
+                                     _stream()))
+    return out
+
+
 def preprocess_u8(image_hwc_u8, mask_u8=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """uint8 [N,H,W,3] (+ uint8 [N,H,W]) on the device -> (fp32 NHWC image, int64 target)."""
     N, H, W, C = image_hwc_u8.shape

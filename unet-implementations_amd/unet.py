@@ -400,17 +400,22 @@ class UNet(nn.Module):
             return ops.head1x1_in_fwd(cur, walk.slope, hw, head.bias.detach())
         return ops.head1x1_fwd(cur, hw, head.bias.detach())
 
-    def _head_bwd(self, walk, rec, dout):
+    def _head_bwd(self, walk, rec, dout, grad_only=False):
         """dL/da of the last decoder layer's output (`rec`: its record); writes the head's weight
-        gradients."""
+        gradients (grad_only: the data gradient alone, nothing is written but the result; `rec`
+        is then also the last layer that gets one when it is the walk's `stop`)."""
         head = self.segmentation_output
         hw = head.weight.detach().view(head.out_channels, -1)
-        dw, db = self._grad_view(head.weight).view(head.out_channels, -1), self._grad_view(head.bias)
+        dw = db = None
+        if not grad_only:
+            dw = self._grad_view(head.weight).view(head.out_channels, -1)
+            db = self._grad_view(head.bias)
         if walk.fused:
             # g is the final gradient of the last decoder layer's output: the head's backward
             # also leaves the reductions of that layer's InstanceNorm backward (NextNorm)
+            last = grad_only and rec is walk.saved[walk.stop_at]
             return ops.head1x1_in_bwd(rec.output(), walk.slope, dout, hw, dw, db,
-                                      nxt=rec.next_norm())
+                                      nxt=None if last else rec.next_norm())
         return ops.head1x1_bwd(rec.a, dout, hw, dw, db)
 
     # -- reference: Our_UNet/models/unet.py:386-397 --------------------------------------
@@ -533,17 +538,7 @@ class UNet(nn.Module):
             x = x.permute(0, 3, 1, 2)      # a view: the shape checks below see NCHW sizes
         elif input_layout != "nchw":
             raise ValueError("input_layout must be 'nchw', 'nhwc' or 'nhwc_u8'")
-        if not x.is_cuda:
-            raise RuntimeError("unet-implementations_amd.UNet runs on MI355X only: move the model "
-                               "and the input to a ROCm device (no CPU fallback exists)")
-        if x.dim() != 4 or x.shape[1] != self.in_channels or self.in_channels != 3:
-            raise ValueError("expected an NCHW batch with 3 channels")
-        n_down = self.n_stages - 1
-        if x.shape[2] % (1 << n_down) or x.shape[3] % (1 << n_down) or \
-                min(x.shape[2], x.shape[3]) < (2 << n_down):
-            raise ValueError(f"H and W must be multiples of {1 << n_down} and >= {2 << n_down}")
-        if self._plan is None:
-            self._build_plan()
+        self._check_input(x)
         self._check_hooks()
         params = list(self.parameters())
         self._ensure_arena(params)
@@ -555,6 +550,20 @@ class UNet(nn.Module):
         else:
             x_nhwc = ops.nchw_to_nhwc(x.contiguous().float())
         return _UNetFunction.apply(self, x_nhwc, self._bottleneck_input(x, extra), *params)
+
+    def _check_input(self, x):
+        """The checks every walk starts with (x: NCHW sizes); builds the plan."""
+        if not x.is_cuda:
+            raise RuntimeError("unet-implementations_amd.UNet runs on MI355X only: move the model "
+                               "and the input to a ROCm device (no CPU fallback exists)")
+        if x.dim() != 4 or x.shape[1] != self.in_channels or self.in_channels != 3:
+            raise ValueError("expected an NCHW batch with 3 channels")
+        n_down = self.n_stages - 1
+        if x.shape[2] % (1 << n_down) or x.shape[3] % (1 << n_down) or \
+                min(x.shape[2], x.shape[3]) < (2 << n_down):
+            raise ValueError(f"H and W must be multiples of {1 << n_down} and >= {2 << n_down}")
+        if self._plan is None:
+            self._build_plan()
 
     def _check_hooks(self):
         """The fused walk fires hooks of the stage-level modules only (encoder_stages[i],
@@ -670,6 +679,7 @@ class _Walk:
         self.need_grad = need_grad         # False under no_grad / frozen parameters: no records
         self.saved = []                    # one _Rec per layer, forward order
         self.head_out = None               # what a head keeps for its own backward (Autoencoder)
+        self.stop_at = None                # gradient-only backward: index of the target's record
         # The fused pipeline serves the fp32 mode and the mixed-precision mode ("bf16": there the
         # layer tensors themselves are bf16 in HBM); 0 <= slope <= 1 (lrelu(z) = max(z, slope z)),
         # one slope for the whole net.  Anything else runs the stand-alone passes.
@@ -809,15 +819,18 @@ class _Walk:
             return ops.nhwc_to_nchw(a)
         return ops.nhwc_to_nchw(v)
 
-    def layer_bwd(self, i, g_a, stop, dx0_acc=None):
+    def layer_bwd(self, i, g_a, stop, dx0_acc=None, grad_only=False):
         """Backward of layer `i` from g_a = dL/d(its activated output) -> (dx0, dx1): the gradients
         of its operands (dx0 on the low-resolution grid where the layer up-sampled on load).
         stop: index of the first trainable layer - the gradient into layer j's input is needed
         only for j > stop.  dx0_acc: the gradient another consumer of x0 already wrote (a skip):
-        dx0 is accumulated into it."""
+        dx0 is accumulated into it.  grad_only: the data gradients and the InstanceNorm backward
+        alone - no weight, bias or affine gradient is formed and the gradient arena is not
+        touched; layer `stop` itself gets no backward (its output gradient is the result)."""
         rec = self.saved[i]
         l, st, x0, x1, low = rec.layer, rec.st, rec.x0, rec.x1, rec.low
-        fused, slope, gv = self.fused, self.slope, self.model._grad_view
+        fused, slope = self.fused, self.slope
+        gv = (lambda p: None) if grad_only else self.model._grad_view
         need_dx = i > stop
         need_dx1 = rec.skip_dst is not None and rec.skip_dst > stop
         dbg = getattr(self.model, "_debug_capture", None)
@@ -827,7 +840,8 @@ class _Walk:
         # dx0 of this layer is the final gradient of the previous layer's output (the skip
         # halves dx1 are accumulated into later, by the encoder): its producer also emits
         # that layer's InstanceNorm-backward reductions
-        nxt = self.saved[i - 1].next_norm() if fused and need_dx else None
+        nxt = self.saved[i - 1].next_norm() \
+            if fused and need_dx and not (grad_only and i - 1 == stop) else None
         dy = ops.instnorm_lrelu_drop_bwd(g_a, rec.y, st[0], st[1], l.norm.weight.detach(),
                                          l.norm.bias.detach(), rec.mask, l.slope,
                                          gv(l.norm.weight), gv(l.norm.bias), gv(l.conv.bias),
@@ -836,7 +850,7 @@ class _Walk:
         if dbg is not None:
             dbg.append((l.name, "dy", dy.clone()))
         dw = gv(l.conv.weight)
-        want_dw = l.conv.weight.requires_grad
+        want_dw = l.conv.weight.requires_grad and not grad_only
         if low is not None:
             # conv3x3(upsample2x(act(low))): both gradients of the up-sampled operand are
             # GEMMs over the LOW-resolution pixels once dy is reduced to its nine D_tap
@@ -905,7 +919,8 @@ class _UNetFunction(torch.autograd.Function):
             return _UNetFunction._backward(ctx, dlogits, deferred)
 
     @staticmethod
-    def _forward(ctx, model, x, extra, params):
+    def _forward(ctx, model, x, extra, params, fire_hooks=True):
+        fire = _fire_forward_hooks if fire_hooks else (lambda mods, make_output: None)
         enc, dec = model._plan
         fusion = model._fusion_layer if extra is not None else None
         walk = _Walk(model, x, fusion, any(ctx.needs_input_grad))
@@ -927,7 +942,7 @@ class _UNetFunction(torch.autograd.Function):
                 cur = run(l, cur, None, place(blk, li, (stage,), stage))
             if bi < len(enc) - 1:
                 skips.append((cur, len(walk.saved)))
-            _fire_forward_hooks([stage], lambda: walk.stage_output(cur))
+            fire([stage], lambda: walk.stage_output(cur))
         if fusion is not None:
             if extra.shape[:3] != cur.shape[:3]:
                 raise NotImplementedError("bottleneck features must match the 1/32-resolution "
@@ -943,9 +958,9 @@ class _UNetFunction(torch.autograd.Function):
             cur = walk.run_up_layer(blk[0], cur, skip, place(blk, 0, hooked, stage, skip_dst))
             for li in range(1, len(blk)):
                 cur = run(blk[li], cur, None, place(blk, li, hooked, stage))
-            _fire_forward_hooks(hooked, lambda: walk.stage_output(cur))
+            fire(hooked, lambda: walk.stage_output(cur))
         logits = model._head_fwd(walk, cur)
-        _fire_forward_hooks([model._head_module()], lambda: logits)
+        fire([model._head_module()], lambda: logits)
         if walk.need_grad:
             ctx.walk, ctx.params = walk, params
         return logits
@@ -1030,3 +1045,64 @@ class _UNetFunction(torch.autograd.Function):
             else:
                 grads.append(gv(p))
         return (None, None, None, *grads)
+
+
+class _GradOnlyCtx:
+    """What `_UNetFunction._forward` needs of an autograd context when the walk is run by hand."""
+    needs_input_grad = (True,)
+
+
+def stage_feature_and_gradient(model, x, target_class, target):
+    """(A, G, slope) for Grad-CAM: A = the output of the stage module `target` in eval mode, as the
+    walk holds it (ops.Act: raw convolution output + folded InstanceNorm coefficients; the
+    activated NHWC tensor on the stand-alone pipeline), and G = d mean_hw(logits[b, target_class])
+    / dA, an NHWC tensor of the walk's storage type - the tensors a forward hook and a backward
+    hook on `target` see (for an encoder stage G includes the skip path's share).  The images of a
+    batch are independent (InstanceNorm, no dropout), so one seed dlogits[b, c] = 1 / (H W) gives
+    every image's own gradient.
+
+    The backward walks from the head down to the target only, with the data-gradient and
+    InstanceNorm-backward kernels alone: no weight, bias or affine gradient, no write to the
+    gradient arena or to any .grad, no hook is fired or needed.  model.training and
+    dropout_mask_override are put back."""
+    if type(model)._head_bwd is not UNet._head_bwd or model._fusion_layer is not None:
+        raise NotImplementedError("Grad-CAM on the HIP path covers UNet (not CLIPUNet / Autoencoder)")
+    model._check_input(x)
+    K = model._head_module().out_channels
+    if not 0 <= int(target_class) < K:
+        raise ValueError(f"target_class {target_class} is outside [0, {K})")
+    was_training, override = model.training, model.dropout_mask_override
+    # the mode of this pass may differ from the model's (evaluate.gradcam): keep the model's own
+    # packed weights for its next step
+    table = model.__dict__.get("_pack_table")
+    model.eval()
+    model.dropout_mask_override = None
+    c32_mode = "always" if ops.c32_winograd_override() == "always" else bool(model.winograd)
+    try:
+        with torch.no_grad(), ops.c32_winograd_scope(c32_mode):
+            ctx = _GradOnlyCtx()
+            logits = _UNetFunction._forward(ctx, model, ops.nchw_to_nhwc(x.contiguous().float()),
+                                            None, None, fire_hooks=False)
+            walk, saved = ctx.walk, ctx.walk.saved
+            t = next(i for i, r in enumerate(saved) if any(m is target for m in r.bwd_hooks))
+            walk.stop_at = t
+            dlogits = torch.zeros_like(logits)
+            dlogits[:, int(target_class)] = 1.0 / (logits.shape[2] * logits.shape[3])
+            g = model._head_bwd(walk, saved[-1], dlogits, grad_only=True)
+            skip_grads = {}
+            for i in range(len(saved) - 1, t, -1):
+                rec = saved[i]
+                g, g_skip = walk.layer_bwd(i, g, t, dx0_acc=skip_grads.pop(i, None),
+                                           grad_only=True)
+                if g_skip is not None:
+                    skip_grads[rec.skip_dst] = g_skip
+                if rec.layer.first_of_decoder and rec.low is None:
+                    g = ops.upsample2x_bwd(g)     # the up-sampled operand was materialised
+            feature = saved[t].output()
+            walk.saved = None
+            return feature, g, walk.slope
+    finally:
+        model.train(was_training)
+        model.dropout_mask_override = override
+        if table is not None:
+            model.__dict__["_pack_table"] = table
