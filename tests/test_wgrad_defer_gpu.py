@@ -12,6 +12,7 @@ asserted, so each case provably reaches the 1, 2 or 3 stages it was chosen for. 
 table itself: mixed kinds and stage counts in one flush, more than 56 jobs in a stage, a flush in
 the middle of a scope, the workspaces held until the flush, disjoint column slices of one
 gradient, nested scopes, a refused call, and the whole network with and without deferral."""
+import re
 from collections import namedtuple
 
 import pytest
@@ -74,40 +75,120 @@ def pending(ua):
 # entry: conv3x3 (ops.conv3x3_bwd_weight, plain operand), in (ops.conv_in_bwd_weight, activated on
 # load), 1x1 (ops.conv1x1_bwd_weight), stem (Cx = 3 through conv_in_bwd_weight), u8 (the stem from
 # a U8Image), up (ops.conv3x3_up_bwd_weight; H, W = the low-resolution size).
-# mode: fp32, x3 (split bf16 on fp32 tensors), b16 (bf16 tensors).  dw has off + Cx + extra
+# mode: fp32, bf16 (bf16 matrix cores on fp32 tensors whose values are bf16 numbers, conv3x3
+# only), x3 (split bf16 on fp32 tensors), b16 (bf16 tensors).  dw has off + Cx + extra
 # input channels, the layer writes [off, off + Cx).  stages / kind: what the plan of the shape
-# queues (emit_wgrad_reduction in csrc/conv_wgrad.hip).
-Spec = namedtuple("Spec", "entry mode N H W Cx Cout stride ks off extra stages kind c32",
-                  defaults=(1, 3, 0, 0, 1, "TAP", None))
+# queues (emit_wgrad_reduction in csrc/conv_wgrad.hip).  chunk: images per launch, forced with
+# the debug chunk limit (0: the whole batch).  kernel: the compute launches of the call, in
+# order, as short_name() writes them: the instantiation wgrad_select / launch_wgrad_plan of
+# csrc/conv_wgrad.hip pick for the shape (one name per launch, so one per chunk).
+Spec = namedtuple("Spec", "entry mode N H W Cx Cout stride ks off extra stages kind c32 chunk "
+                          "kernel", defaults=(1, 3, 0, 0, 1, "TAP", None, 0, None))
+
+
+def wg(targs, nw=4):
+    """conv_wgrad_kernel<CI_T, CO_T, S, STRIDE, ACT, TX, TD, NW> on fp32 tensors"""
+    return (f"conv_wgrad_kernel<{targs}, float, float, {nw}>",)
+
+
+def wg_bf16(targs, act="true"):
+    """conv_wgrad_bf16_kernel<CI_T, CO_T, S, NPL, SB, TX, TD, ACT, STRIDE> on fp32 tensors"""
+    return (f"conv_wgrad_bf16_kernel<{targs}, float, float, {act}, 1>",)
+
+
+def wg_b16(S, stride):
+    """conv_wgrad_bf16_kernel<64, 64, S, 1, false, __bf16, __bf16, true, stride> (mangled: the
+    demangler gives up on __bf16 template arguments)"""
+    return (f"_ZN12_GLOBAL__N_122conv_wgrad_bf16_kernelILi64ELi64ELi{S}ELi1ELb0EDF16bDF16bLb1ELi"
+            f"{stride}EEEvNS_11WgradParamsE",)
+
+
+def ring(targs):
+    """conv_wgrad_b16_ring_kernel<CI_T, CO_T, S, ACT, DEPTH, RG, STRIDE>"""
+    return (f"conv_wgrad_b16_ring_kernel<{targs}>",)
+
+
+def taps(targs, nw=4):
+    """conv_wgrad_taps_kernel<CI_T, CO_T, S, ACT, TX, TD, NW> on fp32 tensors"""
+    return (f"conv_wgrad_taps_kernel<{targs}, true, float, float, {nw}>",)
+
+
+def taps_b16(targs):
+    return (f"conv_wgrad_taps_b16_kernel<{targs}, true>",)
+
 
 CASES = {
     # conv3x3_bwd_weight, fp32
-    "conv3x3-4wave": Spec("conv3x3", "fp32", 2, 24, 40, 32, 32, stages=2),          # 24 slabs
-    "conv3x3-8wave": Spec("conv3x3", "fp32", 2, 16, 24, 128, 128),                   # wide, 8 slabs
-    "conv3x3-winograd": Spec("conv3x3", "fp32", 2, 64, 64, 64, 64, stages=2),       # 32 slabs
-    "conv3x3-wino32": Spec("conv3x3", "fp32", 2, 64, 64, 32, 32, stages=2, c32="always"),
-    "conv3x3-stride2": Spec("conv3x3", "fp32", 2, 64, 64, 32, 64, stride=2),         # 16 slabs
-    "conv3x3-slice": Spec("conv3x3", "fp32", 2, 32, 48, 64, 32, off=32, extra=32, stages=2),
+    "conv3x3-4wave": Spec("conv3x3", "fp32", 2, 24, 40, 32, 32, stages=2,           # 24 slabs
+                          kernel=wg("32, 32, 32, 1, false")),
+    "conv3x3-8wave": Spec("conv3x3", "fp32", 2, 16, 24, 128, 128,                    # wide, 8 slabs
+                          kernel=wg("64, 64, 32, 1, false", nw=8)),
+    "conv3x3-winograd": Spec("conv3x3", "fp32", 2, 64, 64, 64, 64, stages=2,        # 32 slabs
+                             kernel=("conv_wgrad_wino_kernel<false>",)),
+    "conv3x3-wino32": Spec("conv3x3", "fp32", 2, 64, 64, 32, 32, stages=2, c32="always",
+                           kernel=("conv_wgrad_wino32_kernel<false>",)),
+    "conv3x3-stride2": Spec("conv3x3", "fp32", 2, 64, 64, 32, 64, stride=2,          # 16 slabs
+                            kernel=wg("32, 64, 32, 2, false")),
+    "conv3x3-slice": Spec("conv3x3", "fp32", 2, 32, 48, 64, 32, off=32, extra=32, stages=2,
+                          kernel=wg("32, 32, 32, 1, false")),
     # conv_in_bwd_weight (activation on load)
-    "in-fp32": Spec("in", "fp32", 2, 24, 40, 32, 64, off=32, stages=2),              # 24 slabs
-    "in-bf16x3": Spec("in", "x3", 2, 24, 40, 32, 64, off=32, stages=2),              # 24 slabs
-    "in-bf16x3-3stages": Spec("in", "x3", 2, 256, 256, 32, 32, stages=3),            # 512 slabs
-    "in-b16-ring": Spec("in", "b16", 2, 64, 64, 64, 64, off=32, stages=2),           # 64 slabs
-    "in-b16-stride2": Spec("in", "b16", 2, 64, 64, 64, 128, stride=2, stages=2),     # 32 slabs
-    "generic": Spec("in", "fp32", 2, 16, 16, 256, 96, kind="GENERIC"),               # 8 slabs
-    "generic-bf16x3": Spec("in", "x3", 2, 48, 32, 256, 96, stages=2, kind="GENERIC"),  # 20 slabs
-    "wide8": Spec("in", "fp32", 2, 8, 16, 256, 128, kind="WIDE8"),                   # 4 slabs
-    "wide16": Spec("in", "fp32", 1, 8, 8, 512, 512, kind="WIDE16"),                  # 2 slabs
-    "center-ksize1": Spec("in", "fp32", 2, 4, 4, 256, 64, ks=1, off=64, kind="CENTER"),  # 2 slabs
-    "conv1x1": Spec("1x1", "fp32", 2, 16, 16, 64, 64, ks=1, off=64, extra=32, kind="CENTER"),
+    "in-fp32": Spec("in", "fp32", 2, 24, 40, 32, 64, off=32, stages=2,               # 24 slabs
+                    kernel=wg("32, 64, 32, 1, true")),
+    "in-bf16x3": Spec("in", "x3", 2, 24, 40, 32, 64, off=32, stages=2,               # 24 slabs
+                      kernel=wg_bf16("32, 64, 32, 3, false")),
+    "in-bf16x3-3stages": Spec("in", "x3", 2, 256, 256, 32, 32, stages=3,             # 512 slabs
+                              kernel=wg_bf16("32, 32, 64, 3, true")),
+    "in-b16-ring": Spec("in", "b16", 2, 64, 64, 64, 64, off=32, stages=2,            # 64 slabs
+                        kernel=ring("64, 64, 32, true, 2, 2, 1")),
+    "in-b16-stride2": Spec("in", "b16", 2, 64, 64, 64, 128, stride=2, stages=2,      # 32 slabs
+                           kernel=ring("64, 64, 16, true, 2, 2, 2")),
+    "generic": Spec("in", "fp32", 2, 16, 16, 256, 96, kind="GENERIC",                # 8 slabs
+                    kernel=wg("32, 32, 16, 1, true", nw=8)),
+    "generic-bf16x3": Spec("in", "x3", 2, 48, 32, 256, 96, stages=2, kind="GENERIC",  # 20 slabs
+                           kernel=wg("32, 32, 32, 1, true")),
+    "wide8": Spec("in", "fp32", 2, 8, 16, 256, 128, kind="WIDE8",                    # 4 slabs
+                  kernel=wg("64, 64, 16, 1, true", nw=8)),
+    "wide16": Spec("in", "fp32", 1, 8, 8, 512, 512, kind="WIDE16",                   # 2 slabs
+                   kernel=wg("64, 64, 16, 1, true", nw=8)),
+    "center-ksize1": Spec("in", "fp32", 2, 4, 4, 256, 64, ks=1, off=64, kind="CENTER",  # 2 slabs
+                          kernel=wg("64, 64, 16, 1, true", nw=8)),
+    "conv1x1": Spec("1x1", "fp32", 2, 16, 16, 64, 64, ks=1, off=64, extra=32, kind="CENTER",
+                    kernel=wg("64, 64, 16, 1, false")),
     # the RGB stem: 1 x 256 x 256 = 512 blocks, 1 x 256 x 192 = 384: three stages
-    "stem-rows": Spec("stem", "fp32", 1, 256, 256, 3, 32, stages=3, kind="STEM"),    # W % 128 == 0
-    "stem-generic": Spec("stem", "fp32", 1, 256, 192, 3, 32, stages=3, kind="STEM"),
-    "stem-u8": Spec("u8", "fp32", 1, 256, 256, 3, 32, stages=3, kind="STEM"),
+    "stem-rows": Spec("stem", "fp32", 1, 256, 256, 3, 32, stages=3, kind="STEM",     # W % 128 == 0
+                      kernel=("conv_stem_wgrad_rows_kernel<float, float>",)),
+    "stem-generic": Spec("stem", "fp32", 1, 256, 192, 3, 32, stages=3, kind="STEM",
+                         kernel=("conv_stem_wgrad_kernel<float>",)),
+    "stem-u8": Spec("u8", "fp32", 1, 256, 256, 3, 32, stages=3, kind="STEM",
+                    kernel=("conv_stem_wgrad_rows_kernel<unsigned char, float>",)),
     # conv3x3(upsample2x(.)) at low resolution
-    "up-fp32": Spec("up", "fp32", 2, 8, 16, 64, 64, extra=32),                       # 4 slabs
-    "up-fp32-8wave": Spec("up", "fp32", 2, 16, 16, 128, 128),                        # wide, 4 slabs
-    "up-b16": Spec("up", "b16", 2, 32, 32, 64, 64, off=32, stages=2),                # 32 slabs
+    "up-fp32": Spec("up", "fp32", 2, 8, 16, 64, 64, extra=32,                        # 4 slabs
+                    kernel=taps("64, 64, 16")),
+    "up-fp32-8wave": Spec("up", "fp32", 2, 16, 16, 128, 128,                         # wide, 4 slabs
+                          kernel=taps("64, 64, 32", nw=8)),
+    "up-b16": Spec("up", "b16", 2, 32, 32, 64, 64, off=32, stages=2,                 # 32 slabs
+                   kernel=taps_b16("64, 64, 16")),
+    # bf16 tensors with an odd number of output rows: no whole ring rounds, so the segment
+    # kernels of the bf16 matrix cores
+    "in-b16-segments": Spec("in", "b16", 2, 25, 40, 64, 64, stages=2,                # 25 slabs
+                            kernel=wg_b16(32, 1)),
+    "in-b16-stride2-segments": Spec("in", "b16", 2, 50, 40, 64, 128, stride=2, stages=2,
+                                    kernel=wg_b16(16, 2)),
+    # unet_conv3x3_bwd_weight_bf16 (fp32 tensors), bf16x3 on the 64x64 and the single-buffered
+    # 32x32 tile, the bf16 tap kernel on the 32x32 tile
+    "conv3x3-bf16": Spec("conv3x3", "bf16", 2, 16, 24, 32, 64,                       # 8 slabs
+                         kernel=wg_bf16("32, 64, 32, 1, false", act="false")),
+    "in-bf16x3-64x64": Spec("in", "x3", 2, 16, 24, 64, 64,                           # 16 slabs
+                            kernel=wg_bf16("64, 64, 16, 3, false")),
+    "in-bf16x3-32x32": Spec("in", "x3", 2, 16, 64, 32, 32,                           # 8 slabs
+                            kernel=wg_bf16("32, 32, 64, 3, true")),
+    "up-b16-32x32": Spec("up", "b16", 2, 16, 16, 32, 32,                             # 2 slabs
+                         kernel=taps_b16("32, 32, 64")),
+    # batches split by the chunk limit: 2 + 1 images, a launch each
+    "conv3x3-chunked": Spec("conv3x3", "fp32", 3, 24, 40, 32, 32, stages=2, chunk=2,  # 24 + 12
+                            kernel=wg("32, 32, 32, 1, false") * 2),
+    "up-chunked": Spec("up", "fp32", 3, 8, 16, 64, 64, chunk=2,                      # 4 + 2 slabs
+                       kernel=taps("64, 64, 16") * 2),
 }
 
 
@@ -121,13 +202,14 @@ class Layer:
         self.total = s.off + s.Cx + s.extra
         self.Ho, self.Wo = (s.H - 1) // s.stride + 1, (s.W - 1) // s.stride + 1
         b16 = s.mode == "b16"
+        rounded = b16 or s.mode == "bf16"      # operand values are bf16 numbers
         if s.entry == "u8":
             self.u8 = torch.randint(0, 256, (s.N, s.H, s.W, 3), dtype=torch.uint8,
                                     generator=torch.Generator().manual_seed(seed))
             self.src = ua.ops.U8Image(self.u8.to(DEV))
         else:
             self.x = rnd(s.N, s.Cx, s.H, s.W, seed=seed)
-            if b16:
+            if rounded:
                 self.x = r16(self.x)
             self.coef = coeffs(s.N, s.Cx, seed + 10) if s.entry in ("in", "up") else None
             xd = to_nhwc_b16(self.x) if b16 else to_nhwc(self.x)
@@ -143,7 +225,7 @@ class Layer:
             self.dyd = ua.ops.upsample2x_bwd_taps(to_nhwc_b16(self.dy) if b16 else to_nhwc(self.dy))
         else:
             self.dy = rnd(s.N, s.Cout, self.Ho, self.Wo, seed=seed + 1)
-            if b16:
+            if rounded:
                 self.dy = r16(self.dy)
             self.dyd = to_nhwc_b16(self.dy) if b16 else to_nhwc(self.dy)
 
@@ -158,11 +240,29 @@ class Layer:
             return lib.unet_conv3x3_up_bwd_weight_workspace_bytes(s.N, s.H, s.W, s.Cx, s.Cout)
         return lib.unet_conv3x3_bwd_weight_workspace_bytes(s.N, s.H, s.W, s.Cx, s.Cout, s.stride)
 
+    def chunk_limit_bytes(self):
+        """The debug chunk limit under which the call takes s.chunk images a launch; a tensor's
+        image is counted at four bytes an element."""
+        s = self.s
+        dy_image = s.H * s.W * 9 * s.Cout if s.entry == "up" else self.Ho * self.Wo * s.Cout
+        return int((s.chunk + 0.5) * 4 * max(s.H * s.W * s.Cx, dy_image))
+
     def __call__(self, dw):
+        if not self.s.chunk:
+            return self._call(dw)
+        lib = self.ua._lib.lib()
+        lib.unet_debug_set_chunk_limit(self.chunk_limit_bytes())
+        try:
+            return self._call(dw)
+        finally:
+            lib.unet_debug_set_chunk_limit(0)      # (0: back to the default)
+
+    def _call(self, dw):
         s, ops = self.s, self.ua.ops
         with ops.c32_winograd_scope(s.c32 if s.c32 is not None else True):
             if s.entry == "conv3x3":
-                ops.conv3x3_bwd_weight(self.src, self.dyd, dw, s.off, s.stride)
+                ops.conv3x3_bwd_weight(self.src, self.dyd, dw, s.off, s.stride,
+                                       bf16=s.mode == "bf16")
             elif s.entry == "1x1":
                 ops.conv1x1_bwd_weight(self.src, self.dyd, dw, s.off)
             elif s.entry == "up":
@@ -212,6 +312,19 @@ def immediate(layer):
     return dw
 
 
+def short_name(name):
+    """A recorded launch without what every weight-gradient kernel shares: the return type, the
+    anonymous namespace and the parameter list.  Names the demangler gives up on (__bf16 template
+    arguments) stay mangled."""
+    if name.startswith("_Z"):
+        return name
+    return re.sub(r"\(.*\)$", "", name.replace("void ", "").replace("(anonymous namespace)::", ""))
+
+
+def compute_launches(names):
+    return tuple(short_name(n) for n in names if "wgrad_reduce_batched_kernel" not in n)
+
+
 def outside_cols_kept(layer, dw):
     s = layer.s
     return bool((dw[:, :s.off] == SENTINEL).all()) and \
@@ -242,7 +355,9 @@ def test_deferred_equals_immediate(ua, name):
             wino = bool(ua._lib.lib().unet_conv3x3_bwd_weight_is_winograd(s.N, s.H, s.W, s.Cx,
                                                                            s.Cout, 1))
         assert wino == (name in ("conv3x3-winograd", "conv3x3-wino32")), "the case misses its form"
-    dw_i = immediate(L)
+    with ua.ops.record_launches() as rec:
+        dw_i = immediate(L)
+    assert compute_launches(rec.names) == s.kernel, f"{name}: launched {rec.names}"
     e = relerr(L.cols(dw_i), L.ref())
     assert e <= L.tol(), f"{name}: per-call dw vs fp64: rel err {e:.3e} > {L.tol():.1e}"
     assert outside_cols_kept(L, dw_i)

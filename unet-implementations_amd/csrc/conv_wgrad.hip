@@ -18,6 +18,7 @@
 #include "conv_params.h"
 #include <vector>
 #include "lds_asm.h"
+#include <type_traits>
 #include <utility>
 
 namespace {
@@ -1562,66 +1563,92 @@ int emit_wgrad_reduction(float* ws, int nslab, size_t E, float* dw, int Cx, int 
 }
 
 struct WgradPlan {
-  int npp;   // pixel-pair parts per segment (waves that share a sub-block)
-  int sps;   // slabs per pixel split: 1 (the parts of a sub-block are merged in LDS)
+  int npp;   // pixel-pair parts per segment (waves that share a sub-block, merged in LDS: a
+             // workgroup leaves ONE slab, so a plan's slab count is its `split`)
   int nw;    // waves per workgroup: 4, or 8 (fp32 tensors, one workgroup per CU, LDS merge)
   int ci_t, co_t, S, split, segs_per_row, total_segs, segs_per_block;
   int rg;    // conv_wgrad_b16_ring_kernel: row groups of a workgroup (2 = eight waves), 0 = not planned for it
   size_t ws_floats;
-  bool stem;
   int stem_blocks, stem_spb;
   long long stem_stages;
 };
 
+// What the selector (wgrad_select) decided for make_plan / make_plan_taps.
+struct PlanOpts {
+  int prec;       // matrix cores the plan is for: 0 fp32, 1 bf16, 3 bf16x3 (stride 1 only)
+  bool wide;      // the 8-wave kernel (fp32 tensors on the fp32 matrix cores)
+  bool ring8;     // bf16 tensors: the eight-wave row-ring kernel where the rows allow it
+  bool ring_s2;   // bf16 tensors, stride 2: the row-ring kernel with two input rows a step
+  bool taps_b16;  // low-resolution taps, bf16 tensors: conv_wgrad_taps_b16_kernel's segments
+};
+
 int stem_grid(long long stages) { return (int)(stages < 1024 ? stages : 1024); }
 
-int wgrad_tiles(int Cx, int Cout) {
+// slabs + ping-pong room for the staged reduction (each stage shrinks 16x)
+size_t slab_ws_floats(size_t slabs, size_t E) {
+  return slabs * E + 2 * (size_t)ceil_div((int)slabs, kSlabChunk) * E;
+}
+
+// channel tile of a layer (instantiated: 32x32, 32x64, 64x64) and the number of such tiles
+struct WgradTile { int ci_t, co_t, tiles; };
+WgradTile wgrad_tile(int Cx, int Cout) {
   int ci_t = (Cx % 64 == 0) ? 64 : 32;
   const int co_t = (Cout % 64 == 0) ? 64 : 32;
   if (ci_t == 64 && co_t == 32) ci_t = 32;
-  return (Cx / ci_t) * (Cout / co_t);
+  return {ci_t, co_t, (Cx / ci_t) * (Cout / co_t)};
 }
 
-// wide: the 8-wave kernel (fp32 tensors on the fp32 matrix cores)
-// (2: measured against 4 per layer - equal or 5-8 % faster, and 24 registers fewer)
-constexpr int kRingDepth = 2;   // steps whose operands are in flight in conv_wgrad_b16_ring_kernel
-WgradPlan make_plan(int N, int H, int W, int Cx, int Cout, int stride, int prec = 0,
-                    bool wide = false, bool ring8 = false, bool ring_s2 = false) {
+// pixel splits for `target_blocks` workgroups over the channel tiles, within [1, max_split]
+int wgrad_split(int target_blocks, int tiles, int max_split) {
+  int split = ceil_div(target_blocks, tiles);
+  if (split > max_split) split = max_split;
+  return split < 1 ? 1 : split;
+}
+
+// closes a plan whose segs_per_block is set: the split and the workspace of its slabs
+WgradPlan with_slabs(WgradPlan pl, int Cx, int Cout) {
+  pl.split = ceil_div(pl.total_segs, pl.segs_per_block);
+  pl.ws_floats = slab_ws_floats(pl.split, (size_t)9 * Cx * Cout);
+  return pl;
+}
+
+WgradPlan make_plan_stem(int N, int H, int W, int Cout) {
   WgradPlan pl{};
   pl.nw = 4;
-  if (Cx == 3) {
-    pl.stem = true;
-    const long long M = (long long)N * H * W;
-    pl.stem_stages = ceil_div64(M, SW_PIX);
-    pl.stem_blocks = stem_grid(pl.stem_stages);
-    pl.stem_spb = (int)ceil_div64(pl.stem_stages, pl.stem_blocks);
-    pl.stem_blocks = (int)ceil_div64(pl.stem_stages, pl.stem_spb);
-    pl.ws_floats = (size_t)pl.stem_blocks * 27 * Cout +
-                   2 * (size_t)ceil_div(pl.stem_blocks, kSlabChunk) * 27 * Cout;
-    return pl;
-  }
+  const long long M = (long long)N * H * W;
+  pl.stem_stages = ceil_div64(M, SW_PIX);
+  pl.stem_blocks = stem_grid(pl.stem_stages);
+  pl.stem_spb = (int)ceil_div64(pl.stem_stages, pl.stem_blocks);
+  pl.stem_blocks = (int)ceil_div64(pl.stem_stages, pl.stem_spb);
+  pl.ws_floats = slab_ws_floats(pl.stem_blocks, (size_t)27 * Cout);
+  return pl;
+}
+
+// (2: measured against 4 per layer - equal or 5-8 % faster, and 24 registers fewer)
+constexpr int kRingDepth = 2;   // steps whose operands are in flight in conv_wgrad_b16_ring_kernel
+WgradPlan make_plan(int N, int H, int W, int Cx, int Cout, int stride, const PlanOpts& o) {
+  WgradPlan pl{};
+  pl.nw = 4;
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-  pl.ci_t = (Cx % 64 == 0) ? 64 : 32;
-  pl.co_t = (Cout % 64 == 0) ? 64 : 32;
-  if (pl.ci_t == 64 && pl.co_t == 32) pl.ci_t = 32;  // instantiated: 32x32, 32x64, 64x64
+  const WgradTile t = wgrad_tile(Cx, Cout);
+  pl.ci_t = t.ci_t;
+  pl.co_t = t.co_t;
   const int nsb = (pl.ci_t / 32) * (pl.co_t / 32);
-  if (wide && prec == 0) {
+  if (o.wide) {
     // one 8-wave workgroup per CU; a segment as long as the image row and 133 KB of stages
     // allow (16 pixel pairs per wave per barrier on 64x64 tiles at S = 64)
     pl.nw = 8;
     pl.npp = 8 / nsb;
-    pl.sps = 1;
     const int smax = nsb == 1 ? (stride == 1 ? 128 : 32)
                    : nsb == 2 ? 64
                               : (stride == 1 ? 64 : 32);
     pl.S = 16;
     while (pl.S < smax && pl.S < Wo) pl.S *= 2;
   } else {
-    pl.npp = 4 / nsb;  // pixel-pair parts per segment, each with a slab of its own
-    pl.sps = 1;
+    pl.npp = 4 / nsb;  // pixel-pair parts per segment
     // segment length: enough pixel pairs per wave per stage, within the LDS budget
     if (Wo <= 16) pl.S = 16;
-    else if (pl.ci_t == 64) pl.S = (stride == 2 || prec == 3) ? 16 : 32;  // bf16x3: 3 planes in LDS
+    else if (pl.ci_t == 64) pl.S = (stride == 2 || o.prec == 3) ? 16 : 32;  // bf16x3: 3 planes in LDS
     else if (pl.co_t == 64) pl.S = 32;                       // 32x64 tile
     else pl.S = (stride == 1 && Wo >= 64) ? 64 : 32;         // 32x32 tile
     // (tried for the bf16 operands, whose stages are half as large: segments of 64 / 128 pixels
@@ -1630,39 +1657,55 @@ WgradPlan make_plan(int N, int H, int W, int Cx, int Cout, int stride, int prec 
   }
   pl.segs_per_row = ceil_div(Wo, pl.S);
   pl.total_segs = N * Ho * pl.segs_per_row;
-  const int tiles = (Cx / pl.ci_t) * (Cout / pl.co_t);
   // aim for two 4-wave workgroups / one 8-wave workgroup per CU, at least 4 segments per block
-  int split = ceil_div(pl.nw == 8 ? 256 : 512, tiles);
   const int max_split = ceil_div(pl.total_segs, 4);
-  if (split > max_split) split = max_split;
-  if (split < 1) split = 1;
-  pl.segs_per_block = ceil_div(pl.total_segs, split);
-  if (((prec == 1 && stride == 1) || (ring_s2 && stride == 2)) && pl.nw == 4) {
+  pl.segs_per_block =
+      ceil_div(pl.total_segs, wgrad_split(pl.nw == 8 ? 256 : 512, t.tiles, max_split));
+  if (((o.prec == 1 && stride == 1) || (o.ring_s2 && stride == 2)) && pl.nw == 4) {
     // the row-ring kernel (bf16 tensors) walks down a column strip: a workgroup's range must
     // lie inside one strip and be a whole number of prefetch rounds.  Harmless to the segment
     // kernels, which enumerate the same g differently.  ring8: its eight-wave form - one
     // workgroup per CU, two rows a step, half the slabs - where the rows allow it.
     auto rows_for = [&](int target_blocks, int rg) {
-      int sp = ceil_div(target_blocks, tiles);
-      if (sp > max_split) sp = max_split;
-      if (sp < 1) sp = 1;
-      int r = ceil_div(pl.total_segs, sp);
+      int r = ceil_div(pl.total_segs, wgrad_split(target_blocks, t.tiles, max_split));
       const int q = kRingDepth * rg;
       while (r < Ho && (Ho % r || r % q)) ++r;
       return (r <= Ho && Ho % r == 0 && r % q == 0) ? r : 0;
     };
-    const int r2 = ring8 ? rows_for(256, 2) : 0;
+    const int r2 = o.ring8 ? rows_for(256, 2) : 0;
     const int r1 = rows_for(512, 1);
     if (r2) { pl.segs_per_block = r2; pl.rg = 2; }
     else if (r1) { pl.segs_per_block = r1; pl.rg = 1; }
   }
-  pl.split = ceil_div(pl.total_segs, pl.segs_per_block);
-  // slabs + ping-pong room for the staged reduction (each stage shrinks 16x)
-  const size_t E = (size_t)9 * Cx * Cout;
-  const int slabs = pl.split * pl.sps;
-  pl.ws_floats = (size_t)slabs * E + 2 * (size_t)ceil_div(slabs, kSlabChunk) * E;
-  return pl;
+  return with_slabs(pl, Cx, Cout);
 }
+
+// ---- launching --------------------------------------------------------------------------------
+// f(std::true_type | std::false_type) for a run-time bool: how a launcher picks the ACT / bf16
+// instantiation of its kernel
+template <typename F>
+int with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+template <typename F>
+int with_bools(bool a, bool b, F&& f) {
+  return with_bool(a, [&](auto ca) { return with_bool(b, [&](auto cb) { return f(ca, cb); }); });
+}
+
+// One launch of the kernel instantiation Kern: raises its dynamic-LDS limit (remembered per
+// instantiation and device), goes through the recording hipLaunchKernelGGL and reports a failed
+// launch under `label`.
+template <auto Kern, typename... Args>
+int launch_kernel(const char* label, dim3 grid, unsigned threads, size_t lds, hipStream_t stream,
+                  const Args&... args) {
+  if (lds) UNET_SET_DYN_LDS(Kern, lds);
+  hipLaunchKernelGGL(Kern, grid, dim3(threads), lds, stream, args...);
+  UNET_CHECK_LAUNCH(label);
+  return UNET_OK;
+}
+
+// one workgroup per (pixel split, channel tile)
+dim3 wgrad_grid(const WgradParams& p) { return dim3((unsigned)(p.split * p.ci_tiles * p.co_tiles)); }
 
 // 8-wave form: LDS = the two stages, at least the 96 KB the merge epilogue uses
 template <int CI_T, int CO_T, int S, int STRIDE>
@@ -1671,18 +1714,11 @@ int launch_wgrad8(const WgradParams& p, hipStream_t stream) {
   constexpr size_t stages = 2 * (size_t)(3 * PW * CI_T + S * CO_T) * sizeof(float);
   constexpr size_t lds = stages > kWgradMergeLds8 ? stages : kWgradMergeLds8;
   static_assert(lds <= 160 * 1024, "stages exceed the CU's LDS");
-  const unsigned grid = (unsigned)(p.split * p.ci_tiles * p.co_tiles);
-  if (p.alpha) {
-    auto kern = conv_wgrad_kernel<CI_T, CO_T, S, STRIDE, true, float, float, 8>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, p);
-  } else {
-    auto kern = conv_wgrad_kernel<CI_T, CO_T, S, STRIDE, false, float, float, 8>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, p);
-  }
-  UNET_CHECK_LAUNCH("conv_wgrad(8 waves)");
-  return UNET_OK;
+  return with_bool(p.alpha != nullptr, [&](auto act) {
+    return launch_kernel<
+        conv_wgrad_kernel<CI_T, CO_T, S, STRIDE, decltype(act)::value, float, float, 8>>(
+        "conv_wgrad(8 waves)", wgrad_grid(p), 512, lds, stream, p);
+  });
 }
 
 template <int CI_T, int CO_T, int STRIDE>
@@ -2298,53 +2334,36 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_wino32_kernel(const WgradPa
 
 // shapes it takes: the layer is ONE 32 x 32 channel tile, stride 1, whole 8 x 32-pixel tiles,
 // enough of them for one workgroup per CU
-// (unet_set_c32_winograd: 1 = when there is a tile for every CU, 2 = always, 0 = never)
-bool wgrad_wino32_ok(int N, int H, int W, int Cx, int Cout, int stride) {
-  const int f = unet_conv::c32_winograd_flag();
-  if (!(f && stride == 1 && Cx == 32 && Cout == 32 && H % 8 == 0 && W % 32 == 0 &&
+// (c32 = unet_set_c32_winograd: 1 = when there is a tile for every CU, 2 = always, 0 = never)
+bool wgrad_wino32_ok(int N, int H, int W, int Cx, int Cout, int stride, int c32) {
+  if (!(c32 && stride == 1 && Cx == 32 && Cout == 32 && H % 8 == 0 && W % 32 == 0 &&
         (long long)N * H * W * 128 < (1LL << 31)))
     return false;
-  return f == 2 || (long long)N * (H / 8) * (W / 32) >= 256;
+  return c32 == 2 || (long long)N * (H / 8) * (W / 32) >= 256;
 }
 WgradPlan make_plan_wino32(int N, int H, int W) {
   WgradPlan pl{};
   const long long t = (long long)N * (H / 8) * (W / 32);
-  pl.nw = 8; pl.ci_t = pl.co_t = 32; pl.npp = 1; pl.sps = 1; pl.S = 16;
+  pl.nw = 8; pl.ci_t = pl.co_t = 32; pl.npp = 1; pl.S = 16;
   pl.split = (int)(t < 256 ? t : 256);
   pl.total_segs = (int)t; pl.segs_per_block = 1; pl.segs_per_row = W / 32;
-  const size_t E = (size_t)9 * 32 * 32;
-  pl.ws_floats = (size_t)pl.split * E + 2 * (size_t)ceil_div(pl.split, kSlabChunk) * E;
+  pl.ws_floats = slab_ws_floats(pl.split, (size_t)9 * 32 * 32);
   return pl;
 }
 int launch_wgrad_wino32(const WgradParams& p, hipStream_t stream) {
   const int ntiles = p.N * (p.H / 8) * (p.W / 32);
-  const unsigned grid = (unsigned)(ntiles < 256 ? ntiles : 256);
-  if (p.alpha) {
-    auto kern = conv_wgrad_wino32_kernel<true>;
-    UNET_SET_DYN_LDS(kern, WQ_LDS);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), WQ_LDS, stream, p, ntiles);
-  } else {
-    auto kern = conv_wgrad_wino32_kernel<false>;
-    UNET_SET_DYN_LDS(kern, WQ_LDS);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), WQ_LDS, stream, p, ntiles);
-  }
-  UNET_CHECK_LAUNCH("conv_wgrad_wino32");
-  return UNET_OK;
+  return with_bool(p.alpha != nullptr, [&](auto act) {
+    return launch_kernel<conv_wgrad_wino32_kernel<decltype(act)::value>>(
+        "conv_wgrad_wino32", dim3((unsigned)(ntiles < 256 ? ntiles : 256)), 512, WQ_LDS, stream, p,
+        ntiles);
+  });
 }
 
 int launch_wgrad_wino(const WgradParams& p, hipStream_t stream) {
-  const unsigned grid = (unsigned)(p.split * p.ci_tiles * p.co_tiles);
-  if (p.alpha) {
-    auto kern = conv_wgrad_wino_kernel<true>;
-    UNET_SET_DYN_LDS(kern, WW_LDS);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), WW_LDS, stream, p);
-  } else {
-    auto kern = conv_wgrad_wino_kernel<false>;
-    UNET_SET_DYN_LDS(kern, WW_LDS);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), WW_LDS, stream, p);
-  }
-  UNET_CHECK_LAUNCH("conv_wgrad_wino");
-  return UNET_OK;
+  return with_bool(p.alpha != nullptr, [&](auto act) {
+    return launch_kernel<conv_wgrad_wino_kernel<decltype(act)::value>>(
+        "conv_wgrad_wino", wgrad_grid(p), 512, WW_LDS, stream, p);
+  });
 }
 
 // shapes the Winograd weight gradient tiles: stride 1, 64-wide channel tiles, an image that
@@ -2358,227 +2377,142 @@ bool wgrad_wino_ok(int N, int H, int W, int Cx, int Cout, int stride) {
 // plan: K chunks (`segments`) split over ~256 / tiles workgroups per channel tile
 WgradPlan make_plan_wino(int N, int H, int W, int Cx, int Cout) {
   WgradPlan pl{};
-  pl.nw = 8; pl.ci_t = pl.co_t = 64; pl.npp = 2; pl.sps = 1; pl.S = 16;
+  pl.nw = 8; pl.ci_t = pl.co_t = 64; pl.npp = 2; pl.S = 16;
   pl.segs_per_row = W / 16;
   pl.total_segs = N * (H / 2) * (W / 16);
-  const int tiles = (Cx / 64) * (Cout / 64);
-  int split = ceil_div(256, tiles);
-  const int max_split = ceil_div(pl.total_segs, 8);
-  if (split > max_split) split = max_split;
-  if (split < 1) split = 1;
-  pl.segs_per_block = ceil_div(pl.total_segs, split);
-  pl.split = ceil_div(pl.total_segs, pl.segs_per_block);
-  const size_t E = (size_t)9 * Cx * Cout;
-  pl.ws_floats = (size_t)pl.split * E + 2 * (size_t)ceil_div(pl.split, kSlabChunk) * E;
-  return pl;
+  pl.segs_per_block = ceil_div(
+      pl.total_segs, wgrad_split(256, (Cx / 64) * (Cout / 64), ceil_div(pl.total_segs, 8)));
+  return with_slabs(pl, Cx, Cout);
 }
 
-template <int CI_T, int CO_T, int S, int STRIDE, bool ACT, typename TS>
-int launch_wgrad_t(const WgradParams& p, hipStream_t stream);
-
+// 4-wave form: fp32 or bf16 tensors on the fp32 matrix cores
 template <int CI_T, int CO_T, int S, int STRIDE>
 int launch_wgrad(const WgradParams& p, hipStream_t stream) {
-  if (p.b16) {
-    if (p.alpha) return launch_wgrad_t<CI_T, CO_T, S, STRIDE, true, __bf16>(p, stream);
-    return launch_wgrad_t<CI_T, CO_T, S, STRIDE, false, __bf16>(p, stream);
-  }
-  if (p.alpha) return launch_wgrad_t<CI_T, CO_T, S, STRIDE, true, float>(p, stream);
-  return launch_wgrad_t<CI_T, CO_T, S, STRIDE, false, float>(p, stream);
-}
-
-template <int CI_T, int CO_T, int S, int STRIDE, bool ACT, typename TS>
-int launch_wgrad_t(const WgradParams& p, hipStream_t stream) {
   constexpr int PW = (S - 1) * STRIDE + 3;
   constexpr size_t stages = 2 * (size_t)(3 * PW * CI_T + S * CO_T) * sizeof(float);
-  constexpr bool merge = true;
-  constexpr size_t lds = (merge && stages < kWgradMergeLds4) ? kWgradMergeLds4 : stages;
-  constexpr int NT = 256;
-  auto kern = conv_wgrad_kernel<CI_T, CO_T, S, STRIDE, ACT, TS, TS>;
-  UNET_SET_DYN_LDS(kern, lds);
-  const unsigned grid = (unsigned)(p.split * p.ci_tiles * p.co_tiles);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, stream, p);
-  UNET_CHECK_LAUNCH("conv_wgrad");
-  return UNET_OK;
+  constexpr size_t lds = stages < kWgradMergeLds4 ? kWgradMergeLds4 : stages;
+  return with_bools(p.b16, p.alpha != nullptr, [&](auto b16, auto act) {
+    using TS = std::conditional_t<decltype(b16)::value, __bf16, float>;
+    return launch_kernel<conv_wgrad_kernel<CI_T, CO_T, S, STRIDE, decltype(act)::value, TS, TS>>(
+        "conv_wgrad", wgrad_grid(p), 256, lds, stream, p);
+  });
 }
 
+// mixed-precision pipeline: bf16 tensors in HBM on the bf16 matrix cores, the operand activated
+// on load when p.alpha is set
+template <int CI_T, int CO_T, int S, int STRIDE>
+int launch_wgrad_b16(const WgradParams& p, hipStream_t stream) {
+  constexpr int PW = (S - 1) * STRIDE + 3;
+  constexpr size_t stages = 2 * (size_t)(3 * PW * CI_T + S * CO_T) * sizeof(__bf16);
+  constexpr size_t lds = stages < kWgradMergeLds4 ? kWgradMergeLds4 : stages;
+  return with_bool(p.alpha != nullptr, [&](auto act) {
+    return launch_kernel<conv_wgrad_bf16_kernel<CI_T, CO_T, S, 1, false, __bf16, __bf16,
+                                                decltype(act)::value, STRIDE>>(
+        STRIDE == 2 ? "conv_wgrad_bf16(b16, stride 2)" : "conv_wgrad_bf16(b16)", wgrad_grid(p), 256,
+        lds, stream, p);
+  });
+}
+
+// fp32 tensors, stride 1, on the bf16 matrix cores: NPL = 1 plane (bf16) or 3 (bf16x3)
 template <int CI_T, int CO_T, int S, int NPL = 1, bool SB = false>
 int launch_wgrad_bf16(const WgradParams& p, hipStream_t stream) {
+  // (compiled for the NPL = 3 / SB instantiations too: their (CI_T, CO_T, S) are NPL = 1
+  // combinations of launch_wgrad_plan as well, so this names no kernel of its own - a tile only
+  // bf16x3 used would instantiate an unused bf16-storage kernel here)
+  if (p.b16) return launch_wgrad_b16<CI_T, CO_T, S, 1>(p, stream);
   constexpr int PW = S + 2;
   constexpr size_t stages = (SB ? 1 : 2) * NPL * (size_t)(3 * PW * CI_T + S * CO_T) * sizeof(__bf16);
-  constexpr bool merge = true;
-  constexpr size_t lds = (merge && stages < kWgradMergeLds4) ? kWgradMergeLds4 : stages;
-  const unsigned grid = (unsigned)(p.split * p.ci_tiles * p.co_tiles);
-  if constexpr (NPL == 1 && !SB) {
-    if (p.b16) {   // bf16 tensors in HBM, operand activated on load when p.alpha is set
-      if (p.alpha) {
-        auto kern = conv_wgrad_bf16_kernel<CI_T, CO_T, S, 1, false, __bf16, __bf16, true>;
-        UNET_SET_DYN_LDS(kern, lds);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
-      } else {
-        auto kern = conv_wgrad_bf16_kernel<CI_T, CO_T, S, 1, false, __bf16, __bf16, false>;
-        UNET_SET_DYN_LDS(kern, lds);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
-      }
-      UNET_CHECK_LAUNCH("conv_wgrad_bf16(b16)");
-      return UNET_OK;
-    }
-  }
-  if constexpr (NPL == 3) {
-    if (p.alpha) {   // split mode of the fused pipeline: activation on load, then the split
-      auto kern = conv_wgrad_bf16_kernel<CI_T, CO_T, S, 3, SB, float, float, true>;
-      UNET_SET_DYN_LDS(kern, lds);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
-      UNET_CHECK_LAUNCH("conv_wgrad_bf16x3(act)");
-      return UNET_OK;
-    }
-  }
-  auto kern = conv_wgrad_bf16_kernel<CI_T, CO_T, S, NPL, SB>;
-  UNET_SET_DYN_LDS(kern, lds);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
-  UNET_CHECK_LAUNCH("conv_wgrad_bf16");
-  return UNET_OK;
+  constexpr size_t lds = stages < kWgradMergeLds4 ? kWgradMergeLds4 : stages;
+  if constexpr (NPL == 3)
+    if (p.alpha)   // split mode of the fused pipeline: activation on load, then the split
+      return launch_kernel<conv_wgrad_bf16_kernel<CI_T, CO_T, S, 3, SB, float, float, true>>(
+          "conv_wgrad_bf16x3(act)", wgrad_grid(p), 256, lds, stream, p);
+  return launch_kernel<conv_wgrad_bf16_kernel<CI_T, CO_T, S, NPL, SB>>(
+      "conv_wgrad_bf16", wgrad_grid(p), 256, lds, stream, p);
 }
 
-// mixed-precision pipeline, stride 1, bf16 tensors: the row-ring form (plan: make_plan)
+// mixed-precision pipeline, bf16 tensors: the row-ring form (plan: make_plan)
 bool wgrad_ring_ok(const WgradParams& p, int rg) {
   return rg >= 1 && p.b16 &&
          p.segs_per_block % (kRingDepth * rg) == 0 && p.Ho % p.segs_per_block == 0 &&
          p.total_segs % p.segs_per_block == 0 && p.Cx % 8 == 0 && p.Cout % 8 == 0;
 }
-template <int CI_T, int CO_T, int S, int RG, int STRIDE>
-int launch_wgrad_b16_ring_t(const WgradParams& p, hipStream_t stream) {
-  constexpr size_t lds = RG == 2 ? kWgradMergeLds8 : kWgradMergeLds4;
-  const unsigned grid = (unsigned)(p.split * p.ci_tiles * p.co_tiles);
-  if (p.alpha) {
-    auto kern = conv_wgrad_b16_ring_kernel<CI_T, CO_T, S, true, kRingDepth, RG, STRIDE>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * RG), lds, stream, p);
-  } else {
-    auto kern = conv_wgrad_b16_ring_kernel<CI_T, CO_T, S, false, kRingDepth, RG, STRIDE>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * RG), lds, stream, p);
-  }
-  UNET_CHECK_LAUNCH("conv_wgrad_b16_ring");
-  return UNET_OK;
-}
 template <int CI_T, int CO_T, int S, int STRIDE = 1>
 int launch_wgrad_b16_ring(const WgradParams& p, int rg, hipStream_t stream) {
-  return rg == 2 ? launch_wgrad_b16_ring_t<CI_T, CO_T, S, 2, STRIDE>(p, stream)
-                 : launch_wgrad_b16_ring_t<CI_T, CO_T, S, 1, STRIDE>(p, stream);
+  return with_bools(rg == 2, p.alpha != nullptr, [&](auto eight, auto act) {
+    constexpr int RG = decltype(eight)::value ? 2 : 1;
+    constexpr size_t lds = RG == 2 ? kWgradMergeLds8 : kWgradMergeLds4;
+    return launch_kernel<conv_wgrad_b16_ring_kernel<CI_T, CO_T, S, decltype(act)::value,
+                                                    kRingDepth, RG, STRIDE>>(
+        "conv_wgrad_b16_ring", wgrad_grid(p), 256 * RG, lds, stream, p);
+  });
 }
 
-// mixed-precision pipeline, stride 2: bf16 tensors, bf16 matrix cores
-template <int CI_T, int CO_T, int S>
-int launch_wgrad_b16_s2(const WgradParams& p, hipStream_t stream) {
-  constexpr int PW = (S - 1) * 2 + 3;
-  constexpr size_t stages = 2 * (size_t)(3 * PW * CI_T + S * CO_T) * sizeof(__bf16);
-  constexpr bool merge = true;
-  constexpr size_t lds = (merge && stages < kWgradMergeLds4) ? kWgradMergeLds4 : stages;
-  const unsigned grid = (unsigned)(p.split * p.ci_tiles * p.co_tiles);
-  if (p.alpha) {
-    auto kern = conv_wgrad_bf16_kernel<CI_T, CO_T, S, 1, false, __bf16, __bf16, true, 2>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
-  } else {
-    auto kern = conv_wgrad_bf16_kernel<CI_T, CO_T, S, 1, false, __bf16, __bf16, false, 2>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
-  }
-  UNET_CHECK_LAUNCH("conv_wgrad_bf16(b16, stride 2)");
-  return UNET_OK;
-}
-
-// the 8-wave form (fp32 tensors)
+// low-resolution taps, the 8-wave form (fp32 tensors)
 template <int CI_T, int CO_T, int S>
 int launch_wgrad_taps8(const WgradParams& p, hipStream_t stream) {
   constexpr size_t lds = 2 * (size_t)S * (CI_T + 9 * CO_T) * sizeof(float);
   static_assert(lds <= 160 * 1024 && lds >= 96 * 1024, "8-wave stages / merge space");
-  const unsigned grid = (unsigned)(p.split * p.ci_tiles * p.co_tiles);
-  if (p.alpha) {
-    auto kern = conv_wgrad_taps_kernel<CI_T, CO_T, S, true, float, float, 8>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, p);
-  } else {
-    auto kern = conv_wgrad_taps_kernel<CI_T, CO_T, S, false, float, float, 8>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, p);
-  }
-  UNET_CHECK_LAUNCH("conv_wgrad_taps(8 waves)");
-  return UNET_OK;
+  return with_bool(p.alpha != nullptr, [&](auto act) {
+    return launch_kernel<
+        conv_wgrad_taps_kernel<CI_T, CO_T, S, decltype(act)::value, float, float, 8>>(
+        "conv_wgrad_taps(8 waves)", wgrad_grid(p), 512, lds, stream, p);
+  });
 }
 
-// bf16 tensors, bf16 matrix cores (64 x 64 tiles)
+// low-resolution taps, bf16 tensors on the bf16 matrix cores
 template <int CI_T, int CO_T, int S>
 int launch_wgrad_taps_b16(const WgradParams& p, hipStream_t stream) {
   constexpr size_t stages = 2 * (size_t)S * (CI_T + 9 * CO_T) * sizeof(__bf16);
   constexpr size_t lds = stages > kWgradMergeLds4 ? stages : kWgradMergeLds4;
-  const unsigned grid = (unsigned)(p.split * p.ci_tiles * p.co_tiles);
-  if (p.alpha) {
-    auto kern = conv_wgrad_taps_b16_kernel<CI_T, CO_T, S, true>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
-  } else {
-    auto kern = conv_wgrad_taps_b16_kernel<CI_T, CO_T, S, false>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
-  }
-  UNET_CHECK_LAUNCH("conv_wgrad_taps_b16");
-  return UNET_OK;
+  return with_bool(p.alpha != nullptr, [&](auto act) {
+    return launch_kernel<conv_wgrad_taps_b16_kernel<CI_T, CO_T, S, decltype(act)::value>>(
+        "conv_wgrad_taps_b16", wgrad_grid(p), 256, lds, stream, p);
+  });
 }
 
+// low-resolution taps on the fp32 matrix cores: fp32 tensors, or bf16 tensors in HBM (1/4 of
+// the FLOPs already)
 template <int CI_T, int CO_T, int S>
 int launch_wgrad_taps(const WgradParams& p, hipStream_t stream) {
   constexpr size_t lds = 2 * (size_t)S * (CI_T + 9 * CO_T) * sizeof(float);
-  const unsigned grid = (unsigned)(p.split * p.ci_tiles * p.co_tiles);
-  if (p.b16) {   // bf16 tensors in HBM (fp32 matrix cores: 1/4 of the FLOPs already)
-    if (p.alpha) {
-      auto kern = conv_wgrad_taps_kernel<CI_T, CO_T, S, true, __bf16, __bf16>;
-      UNET_SET_DYN_LDS(kern, lds);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
-    } else {
-      auto kern = conv_wgrad_taps_kernel<CI_T, CO_T, S, false, __bf16, __bf16>;
-      UNET_SET_DYN_LDS(kern, lds);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
-    }
-  } else if (p.alpha) {
-    auto kern = conv_wgrad_taps_kernel<CI_T, CO_T, S, true>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
-  } else {
-    auto kern = conv_wgrad_taps_kernel<CI_T, CO_T, S, false>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
-  }
-  UNET_CHECK_LAUNCH("conv_wgrad_taps");
-  return UNET_OK;
+  return with_bools(p.b16, p.alpha != nullptr, [&](auto b16, auto act) {
+    using TS = std::conditional_t<decltype(b16)::value, __bf16, float>;
+    return launch_kernel<conv_wgrad_taps_kernel<CI_T, CO_T, S, decltype(act)::value, TS, TS>>(
+        "conv_wgrad_taps", wgrad_grid(p), 256, lds, stream, p);
+  });
 }
 
 // plan of the low-resolution tap GEMM: Q pixels, (Cx x Cout) channel tiles
-// wide: the 8-wave kernel (fp32 tensors)
-WgradPlan make_plan_taps(long long Q, int Cx, int Cout, bool wide, bool b16 = false) {
+WgradPlan make_plan_taps(long long Q, int Cx, int Cout, const PlanOpts& o) {
   WgradPlan pl{};
-  pl.ci_t = (Cx % 64 == 0) ? 64 : 32;
-  pl.co_t = (Cout % 64 == 0) ? 64 : 32;
-  if (pl.ci_t == 64 && pl.co_t == 32) pl.ci_t = 32;  // instantiated: 32x32, 32x64, 64x64
+  const WgradTile t = wgrad_tile(Cx, Cout);
+  pl.ci_t = t.ci_t;
+  pl.co_t = t.co_t;
   const int nsb = (pl.ci_t / 32) * (pl.co_t / 32);
-  pl.nw = wide ? 8 : 4;
+  pl.nw = o.wide ? 8 : 4;
   pl.npp = pl.nw / nsb;
-  pl.sps = 1;
-  pl.S = (nsb == 1 ? 32 : 16) * (wide ? 2 : 1);
-  if (b16 && nsb == 1) pl.S = 64;   // conv_wgrad_taps_b16_kernel: four k-groups, one per wave
+  pl.S = (nsb == 1 ? 32 : 16) * (o.wide ? 2 : 1);
+  if (o.taps_b16 && nsb == 1) pl.S = 64;   // conv_wgrad_taps_b16_kernel: four k-groups, one per wave
   pl.segs_per_row = 0;
   pl.total_segs = (int)ceil_div64(Q, pl.S);
-  const int tiles = (Cx / pl.ci_t) * (Cout / pl.co_t);
-  int split = ceil_div(wide ? 256 : 512, tiles);
-  const int max_split = ceil_div(pl.total_segs, 4);
-  if (split > max_split) split = max_split;
-  if (split < 1) split = 1;
-  pl.segs_per_block = ceil_div(pl.total_segs, split);
-  pl.split = ceil_div(pl.total_segs, pl.segs_per_block);
-  const size_t E = (size_t)9 * Cx * Cout;
-  const int slabs = pl.split * pl.sps;
-  pl.ws_floats = (size_t)slabs * E + 2 * (size_t)ceil_div(slabs, kSlabChunk) * E;
-  return pl;
+  pl.segs_per_block = ceil_div(
+      pl.total_segs, wgrad_split(o.wide ? 256 : 512, t.tiles, ceil_div(pl.total_segs, 4)));
+  return with_slabs(pl, Cx, Cout);
+}
+
+// kernel instantiation for a plan of the low-resolution taps
+int launch_wgrad_taps_plan(const WgradParams& p, const WgradPlan& pl, hipStream_t stream) {
+  if (pl.nw == 8) {
+    if (pl.ci_t == 64) return launch_wgrad_taps8<64, 64, 32>(p, stream);
+    if (pl.co_t == 64) return launch_wgrad_taps8<32, 64, 32>(p, stream);
+    return launch_wgrad_taps8<32, 32, 64>(p, stream);
+  }
+  if (pl.ci_t == 64 && p.b16) return launch_wgrad_taps_b16<64, 64, 16>(p, stream);
+  if (pl.ci_t == 32 && pl.co_t == 32 && p.b16) return launch_wgrad_taps_b16<32, 32, 64>(p, stream);
+  if (pl.ci_t == 64) return launch_wgrad_taps<64, 64, 16>(p, stream);
+  if (pl.co_t == 64) return launch_wgrad_taps<32, 64, 16>(p, stream);
+  return launch_wgrad_taps<32, 32, 32>(p, stream);
 }
 
 // kernel instantiation for a plan (tile, segment length, stride, operand mode)
@@ -2607,8 +2541,8 @@ int launch_wgrad_plan(const WgradParams& p, const WgradPlan& pl, int stride, int
     if (pl.ci_t == 32 && pl.co_t == 64 && pl.S == 32) return launch_wgrad_b16_ring<32, 64, 32, 2>(p, pl.rg, stream);
   }
   if (p.b16 && prec == 1 && stride == 2 && (pl.S / 16) % pl.npp == 0) {
-    if (pl.ci_t == 64 && pl.S == 16) return launch_wgrad_b16_s2<64, 64, 16>(p, stream);
-    if (pl.ci_t == 32 && pl.co_t == 64 && pl.S == 32) return launch_wgrad_b16_s2<32, 64, 32>(p, stream);
+    if (pl.ci_t == 64 && pl.S == 16) return launch_wgrad_b16<64, 64, 16, 2>(p, stream);
+    if (pl.ci_t == 32 && pl.co_t == 64 && pl.S == 32) return launch_wgrad_b16<32, 64, 32, 2>(p, stream);
   }
   if (use_bf16 && prec == 1 && wgrad_ring_ok(p, pl.rg)) {
     if (pl.ci_t == 32 && pl.co_t == 32 && pl.S == 64) return launch_wgrad_b16_ring<32, 32, 64>(p, pl.rg, stream);
@@ -2643,28 +2577,177 @@ int launch_wgrad_plan(const WgradParams& p, const WgradPlan& pl, int stride, int
   return launch_wgrad<64, 64, 16, 2>(p, stream);
 }
 
+// ---- one weight-gradient request: record, selector, chunk driver ------------------------------
+enum WgradForm { WF_STEM, WF_WINO, WF_WINO32, WF_DIRECT, WF_TAPS };
+
+// What an entry point asks for.  The selector reads the shape and mode fields only, so the
+// workspace queries fill just those.
+struct WgradCall {
+  // operands: x (or the uint8 image with mean[3], std[3]) and dy - the tap gradients D
+  // [N][H][W][9][Cout] when `taps`; bf16 tensors when `b16` (never the RGB image)
+  const void* x = nullptr;
+  const unsigned char* x_u8 = nullptr;
+  const float* u8_mean_std = nullptr;
+  const void* dy = nullptr;
+  // activation on load: a = lrelu(x * alpha[n][c] + beta[n][c], slope); alpha == nullptr: plain x
+  const float* alpha = nullptr;
+  const float* beta = nullptr;
+  float slope = 0.f;
+  bool b16 = false;          // element storage of x and dy: bf16 (else fp32)
+  int prec = 0;              // matrix cores asked for: 0 fp32, 1 bf16, 3 bf16x3
+  bool center_only = false;  // 1x1 layer: keep the centre tap
+  bool taps = false;         // conv3x3(upsample2x(x)) at low resolution
+  // dw[Cout][Cin_total][3][3] (OIHW), columns ci_offset .. ci_offset + Cx; optional bias gradient
+  float* dw = nullptr;
+  int ci_offset = 0, Cin_total = 0;
+  float* db = nullptr;
+  void* workspace = nullptr;
+  size_t workspace_bytes = 0;
+  int N = 0, H = 0, W = 0, Cx = 0, Cout = 0, stride = 1;
+
+  int Ho() const { return (H - 1) / stride + 1; }
+  int Wo() const { return (W - 1) / stride + 1; }
+  int dy_channels() const { return taps ? 9 * Cout : Cout; }
+};
+
+struct WgradSel {
+  WgradForm form;
+  PlanOpts opt;
+  int nmax;   // images per launch
+};
+
 // x and dy are addressed through 2 GiB buffer descriptors: a larger batch is processed in
 // chunks of `nmax` images whose slabs are reduced together.
-int wgrad_batch_chunk(int N, int H, int W, int Cx, int Cout, int stride) {
-  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-  const long long a = (long long)H * W * Cx * 4, b = (long long)Ho * Wo * Cout * 4;
-  return unet_conv::batch_chunk(N, a > b ? a : b);
+int wgrad_batch_chunk(const WgradCall& c) {
+  const long long a = (long long)c.H * c.W * c.Cx * 4;
+  const long long b = (long long)c.Ho() * c.Wo() * c.dy_channels() * 4;
+  return unet_conv::batch_chunk(c.N, a > b ? a : b);
 }
 
-size_t wgrad_ws_floats(int N, int H, int W, int Cx, int Cout, int stride, int prec,
-                       bool wide = false) {
-  if (Cx == 3) return make_plan(N, H, W, Cx, Cout, stride, prec).ws_floats;
-  const int nmax = wgrad_batch_chunk(N, H, W, Cx, Cout, stride);
-  if (nmax < 1) return 0;
-  const size_t E = (size_t)9 * Cx * Cout;
-  size_t slabs = 0;
-  for (int nb = 0; nb < N; nb += nmax) {
-    const WgradPlan pl = make_plan(N - nb < nmax ? N - nb : nmax, H, W, Cx, Cout, stride, prec,
-                                   wide);
-    slabs += (size_t)pl.split * pl.sps;
+// THE rule for which form runs a request, and with which plan options.  c32: the calling
+// thread's unet_set_c32_winograd switch.
+WgradSel wgrad_select(const WgradCall& c, int c32) {
+  WgradSel s{};
+  s.nmax = wgrad_batch_chunk(c);
+  // fp32 tensors on the fp32 matrix cores: with >= 4 channel tiles the 8-wave kernel (one
+  // workgroup per CU, <= 64 pixel splits, 16 pixel pairs per barrier); the 32 / 64-channel layers
+  // keep two independent 4-wave workgroups per CU (measured 4-6 % faster there: their 128..256
+  // pixel splits leave the 8-wave form few MFMAs per barrier and long reductions)
+  const bool fp32 = c.prec == 0 && !c.b16;
+  s.opt.wide = fp32 && c.Cx != 3 && wgrad_tile(c.Cx, c.Cout).tiles >= 4;
+  if (c.taps) {
+    s.form = WF_TAPS;
+    s.opt.taps_b16 = c.b16;
+    return s;
   }
-  return slabs * E + 2 * (size_t)ceil_div((int)slabs, kSlabChunk) * E;
+  if (c.Cx == 3) {
+    s.form = WF_STEM;
+    return s;
+  }
+  // the bf16 operand modes are for the stride-1 layers; stride 2 runs the fp32 matrix cores
+  s.opt.prec = c.stride == 1 ? c.prec : 0;
+  // bf16 tensors: the row-ring kernel, in its eight-wave form where the plan finds rows for it
+  // (64 x 64 channel tiles only: measured per layer - 32 x 32 tiles, enc0 / dec4 at 512 x 512,
+  // lose 20 % in the eight-wave form, the 64- and 128-channel layers gain 15 %, deeper ones +-0)
+  s.opt.ring_s2 = c.b16 && c.prec == 1 && c.stride == 2;
+  s.opt.ring8 = c.b16 && (s.opt.prec == 1 || s.opt.ring_s2) && c.Cx % 64 == 0 && c.Cout % 64 == 0;
+  // fp32 tensors, stride-1 3x3 layers in one launch: the Winograd F(3x3,2x2) form for 64-wide
+  // channel tiles, and the 32 -> 32 channel layers their own (one workgroup per CU keeps the
+  // whole M)
+  const bool wino_able = fp32 && !c.center_only && s.nmax >= c.N;
+  s.form = wino_able && wgrad_wino32_ok(c.N, c.H, c.W, c.Cx, c.Cout, c.stride, c32) ? WF_WINO32
+         : wino_able && wgrad_wino_ok(c.N, c.H, c.W, c.Cx, c.Cout, c.stride)        ? WF_WINO
+                                                                                     : WF_DIRECT;
+  return s;
 }
+
+// plan of one launch over `nc` images
+WgradPlan wgrad_plan(const WgradCall& c, WgradForm form, const PlanOpts& o, int nc) {
+  switch (form) {
+    case WF_STEM: return make_plan_stem(nc, c.H, c.W, c.Cout);
+    case WF_WINO: return make_plan_wino(nc, c.H, c.W, c.Cx, c.Cout);
+    case WF_WINO32: return make_plan_wino32(nc, c.H, c.W);
+    case WF_TAPS: return make_plan_taps((long long)nc * c.H * c.W, c.Cx, c.Cout, o);
+    default: return make_plan(nc, c.H, c.W, c.Cx, c.Cout, c.stride, o);
+  }
+}
+
+// Workspace (floats) of a request: the slabs of every launch and the room of their staged
+// reduction; 0 when one image exceeds the 2 GiB range.  Sized for the plain plan of the mode: the
+// row-ring forms and the bf16 tap kernel only ever merge slabs of it, so one size serves both
+// storage types.
+size_t wgrad_ws_floats(const WgradCall& c, const WgradSel& s) {
+  PlanOpts o = s.opt;
+  o.ring8 = o.ring_s2 = o.taps_b16 = false;
+  if (s.form == WF_STEM) return wgrad_plan(c, s.form, o, c.N).ws_floats;
+  size_t slabs = 0;
+  for (int nb = 0; nb < c.N && s.nmax >= 1; nb += s.nmax)
+    slabs += (size_t)wgrad_plan(c, s.form, o, c.N - nb < s.nmax ? c.N - nb : s.nmax).split;
+  return slab_ws_floats(slabs, (size_t)9 * c.Cx * c.Cout);
+}
+
+// Walks the batch in chunks of s.nmax (>= 1) images: the chunk's plan, its WgradParams, its
+// launch.  *nslab: the slabs the launches left at ws, in launch order.
+int wgrad_launch_chunks(const WgradCall& c, const WgradSel& s, float* ws, int* nslab,
+                        hipStream_t stream) {
+  const long long es = c.b16 ? 2 : 4;
+  const size_t E = (size_t)9 * c.Cx * c.Cout;
+  const size_t x_img = (size_t)c.H * c.W * c.Cx * es;
+  const size_t dy_img = (size_t)c.Ho() * c.Wo() * c.dy_channels() * es;
+  *nslab = 0;
+  for (int nb = 0; nb < c.N; nb += s.nmax) {   // one pass unless a tensor exceeds 2 GiB
+    const int nc = c.N - nb < s.nmax ? c.N - nb : s.nmax;
+    const WgradPlan pl = wgrad_plan(c, s.form, s.opt, nc);
+    WgradParams p{};
+    p.x = reinterpret_cast<const float*>(static_cast<const char*>(c.x) + nb * x_img);
+    p.dy = reinterpret_cast<const float*>(static_cast<const char*>(c.dy) + nb * dy_img);
+    p.b16 = c.b16;
+    p.partial = ws + (size_t)*nslab * E; p.Cx = c.Cx; p.Cout = c.Cout;
+    p.N = nc; p.H = c.H; p.W = c.W; p.Ho = c.Ho(); p.Wo = c.Wo();
+    p.segs_per_row = pl.segs_per_row; p.total_segs = pl.total_segs;
+    p.segs_per_block = pl.segs_per_block; p.split = pl.split;
+    p.ci_tiles = c.Cx / pl.ci_t; p.co_tiles = c.Cout / pl.co_t;
+    p.x_bytes = (unsigned)(nc * x_img);
+    p.dy_bytes = (unsigned)(nc * dy_img);
+    p.alpha = c.alpha ? c.alpha + (size_t)nb * c.Cx : nullptr;
+    p.beta = c.alpha ? c.beta + (size_t)nb * c.Cx : nullptr;
+    p.slope = c.slope;
+    const int rc = s.form == WF_WINO32 ? launch_wgrad_wino32(p, stream)
+                   : s.form == WF_WINO ? launch_wgrad_wino(p, stream)
+                   : s.form == WF_TAPS ? launch_wgrad_taps_plan(p, pl, stream)
+                                       : launch_wgrad_plan(p, pl, c.stride, c.prec, stream);
+    if (rc != UNET_OK) return rc;
+    *nslab += pl.split;
+  }
+  return UNET_OK;
+}
+
+// the RGB stem: (fp32 | uint8 image) x (fp32 | bf16 dy), in the raw-row form when a 128-pixel
+// stage never straddles image rows
+int launch_wgrad_stem(const WgradCall& c, const WgradPlan& pl, float* ws, hipStream_t stream) {
+  StemNormW nm{};
+  if (c.x_u8) {
+    UNET_REQUIRE(c.W % SW_PIX == 0, "stem_u8_bwd_weight: needs W %% %d == 0", SW_PIX);
+    for (int k = 0; k < 3; ++k) { nm.mean[k] = c.u8_mean_std[k]; nm.std[k] = c.u8_mean_std[3 + k]; }
+  }
+  const dim3 grid(pl.stem_blocks, c.Cout / 32);
+  return with_bools(c.x_u8 != nullptr, c.b16, [&](auto u8, auto b16) {
+    using TX = std::conditional_t<decltype(u8)::value, unsigned char, float>;
+    using TD = std::conditional_t<decltype(b16)::value, __bf16, float>;
+    const TX* x = decltype(u8)::value ? reinterpret_cast<const TX*>(c.x_u8)
+                                      : static_cast<const TX*>(c.x);
+    const TD* dy = static_cast<const TD*>(c.dy);
+    if constexpr (!decltype(u8)::value)
+      if (c.W % SW_PIX != 0)
+        return launch_kernel<conv_stem_wgrad_kernel<TD>>("conv_stem_wgrad", grid, 256, 0, stream, x,
+                                                         dy, ws, c.N, c.H, c.W, c.Cout, pl.stem_spb,
+                                                         pl.stem_stages);
+    return launch_kernel<conv_stem_wgrad_rows_kernel<TX, TD>>("conv_stem_wgrad", grid, 256, 0,
+                                                              stream, x, dy, ws, c.N, c.H, c.W,
+                                                              c.Cout, pl.stem_spb, pl.stem_stages, nm);
+  });
+}
+
 
 // db[c] = sum over pixels of dy[.][c]: 64 row chunks per 32-channel group, then the chunk sums
 // (fixed order => deterministic).  out[chunk][C] when chunks > 1.
@@ -2693,168 +2776,90 @@ __global__ __launch_bounds__(256) void bias_grad_kernel(const float* __restrict_
 extern "C" size_t unet_conv3x3_bwd_weight_workspace_bytes(int N, int H, int W, int Cx, int Cout,
                                                           int stride) {
   if (N <= 0 || H <= 0 || W <= 0 || Cx <= 0 || Cout <= 0) return 0;
-  // one size for every operand mode (the bf16x3 plan uses shorter segments on 64x64 tiles)
-  const size_t a = wgrad_ws_floats(N, H, W, Cx, Cout, stride, 0);
-  const size_t b = wgrad_ws_floats(N, H, W, Cx, Cout, stride, 3);
-  const size_t c = wgrad_ws_floats(N, H, W, Cx, Cout, stride, 0, true);
-  const size_t e = wgrad_ws_floats(N, H, W, Cx, Cout, stride, 1);   // bf16: longer segments
-  size_t m = a > b ? a : b;
-  if (c > m) m = c;
-  if (e > m) m = e;
-  if (Cx != 3 && wgrad_wino_ok(N, H, W, Cx, Cout, stride)) {
-    const size_t d = make_plan_wino(N, H, W, Cx, Cout).ws_floats;
-    if (d > m) m = d;
-  }
-  if (stride == 1 && Cx == 32 && Cout == 32 && H % 8 == 0 && W % 32 == 0) {   // (whatever the switch says)
-    const size_t d = make_plan_wino32(N, H, W).ws_floats;
-    if (d > m) m = d;
+  // One size for whatever a caller may ask of the shape without asking again: the largest
+  // selector result over every request the 3x3 entry points make - element storage x matrix
+  // cores, the centre-tap (1x1) call, which keeps the direct kernels where a 3x3 call takes a
+  // Winograd form, and the c32 switch off and at "always" (1 selects a subset of 2).  No plan is
+  // assumed to bound another.  bf16 storage on the fp32 matrix cores is the stride-2 request; at
+  // stride 1 no entry point makes it, and it stays in the list because callers have always been
+  // given at least the 4-wave fp32 plan's size.
+  static constexpr struct { bool b16; int prec; bool center_only; int c32; } kRequests[] = {
+      {false, 0, false, 0}, {false, 0, false, 2}, {false, 0, true, 0}, {false, 3, false, 0},
+      {false, 1, false, 0}, {true, 0, false, 0},  {true, 1, false, 0}};
+  size_t m = 0;
+  for (const auto& r : kRequests) {
+    WgradCall c;
+    c.N = N; c.H = H; c.W = W; c.Cx = Cx; c.Cout = Cout; c.stride = stride;
+    c.b16 = r.b16; c.prec = r.prec; c.center_only = r.center_only;
+    const size_t f = wgrad_ws_floats(c, wgrad_select(c, r.c32));
+    if (f > m) m = f;
   }
   return m * sizeof(float);
 }
 
 // 1 when the fp32 entry points (unet_conv3x3_bwd_weight, unet_conv_in_bwd_weight with ksize 3)
-// run this shape on the Winograd F(3x3,2x2) kernel (16/36 of the direct matrix FLOPs)
+// run this shape on a Winograd F(3x3,2x2) kernel (16/36 of the direct matrix FLOPs)
 extern "C" int unet_conv3x3_bwd_weight_is_winograd(int N, int H, int W, int Cx, int Cout,
                                                    int stride) {
-  if (N <= 0 || H <= 0 || W <= 0 || Cx <= 3 || Cout <= 0) return 0;
-  return ((wgrad_wino_ok(N, H, W, Cx, Cout, stride) || wgrad_wino32_ok(N, H, W, Cx, Cout, stride)) &&
-          wgrad_batch_chunk(N, H, W, Cx, Cout, stride) >= N) ? 1 : 0;
+  if (N <= 0 || H <= 0 || W <= 0 || Cx <= 3 || Cout <= 0 || stride != 1) return 0;
+  WgradCall c;
+  c.N = N; c.H = H; c.W = W; c.Cx = Cx; c.Cout = Cout;
+  const WgradForm form = wgrad_select(c, unet_conv::c32_winograd_flag()).form;
+  return (form == WF_WINO || form == WF_WINO32) ? 1 : 0;
 }
 
-static int conv_bwd_weight_impl(const float* x, int Cx, const float* dy, float* dw_oihw,
-                                int ci_offset, int Cin_total, float* db, void* workspace,
-                                size_t workspace_bytes, int N, int H, int W, int Cout, int stride,
-                                bool center_only, hipStream_t stream, int prec = 0,
-                                const float* act_alpha = nullptr, const float* act_beta = nullptr,
-                                float slope = 0.f, const unsigned char* x_u8 = nullptr,
-                                const float* u8_mean_std = nullptr, int b16 = 0) {
+static int conv_bwd_weight_impl(const WgradCall& c, hipStream_t stream) {
   // b16: x (except the RGB image) and dy are bf16 tensors; prec is then 1 (bf16 matrix cores
   // for the stride-1 layers, fp32 matrix cores on bf16 storage for the rest)
-  const long long es = b16 ? 2 : 4;
-  UNET_REQUIRE((x || x_u8) && dy && dw_oihw && workspace, "conv3x3_bwd_weight: null pointer");
-  UNET_REQUIRE(stride == 1 || stride == 2, "conv3x3_bwd_weight: stride %d unsupported", stride);
-  UNET_REQUIRE(Cout > 0 && Cout % 32 == 0, "conv3x3_bwd_weight: Cout %d not a multiple of 32", Cout);
-  UNET_REQUIRE(Cx == 3 || (Cx > 0 && Cx % 32 == 0), "conv3x3_bwd_weight: Cx %d unsupported", Cx);
-  UNET_REQUIRE(ci_offset >= 0 && ci_offset + Cx <= Cin_total, "conv3x3_bwd_weight: bad ci slice");
+  UNET_REQUIRE((c.x || c.x_u8) && c.dy && c.dw && c.workspace, "conv3x3_bwd_weight: null pointer");
+  UNET_REQUIRE(c.stride == 1 || c.stride == 2, "conv3x3_bwd_weight: stride %d unsupported", c.stride);
+  UNET_REQUIRE(c.Cout > 0 && c.Cout % 32 == 0, "conv3x3_bwd_weight: Cout %d not a multiple of 32", c.Cout);
+  UNET_REQUIRE(c.Cx == 3 || (c.Cx > 0 && c.Cx % 32 == 0), "conv3x3_bwd_weight: Cx %d unsupported", c.Cx);
+  UNET_REQUIRE(c.ci_offset >= 0 && c.ci_offset + c.Cx <= c.Cin_total, "conv3x3_bwd_weight: bad ci slice");
   // (checked before anything is launched or queued: a refused call leaves no job behind)
-  UNET_REQUIRE(!(db && b16), "conv_bwd_weight: db is not produced on the bf16-storage path");
-  UNET_REQUIRE(!(db && reduce_queue().on), "conv_bwd_weight: the bias gradient reuses the slab "
-                                           "workspace and cannot be combined with deferred reductions");
-  const int pprec = (prec == 3 && stride == 1) ? 3 : ((prec == 1 && stride == 1) ? 1 : 0);
-  // fp32 tensors on the fp32 matrix cores: the 8-wave kernel (parts merged in LDS)
-  // fp32 tensors on the fp32 matrix cores: with >= 4 channel tiles the 8-wave kernel (one
-  // workgroup per CU, <= 64 pixel splits, 16 pixel pairs per barrier); the 32 / 64-channel layers
-  // keep two independent 4-wave workgroups per CU (measured 4-6 % faster there: their 128..256
-  // pixel splits leave the 8-wave form few MFMAs per barrier and long reductions)
-  const bool wide = prec == 0 && !b16 && Cx != 3 && wgrad_tiles(Cx, Cout) >= 4;
-  // fp32 tensors, stride-1 3x3 layers with 64-wide channel tiles: the Winograd F(3x3,2x2) form
-  const bool wino = prec == 0 && !b16 && !center_only && Cx != 3 &&
-                    wgrad_wino_ok(N, H, W, Cx, Cout, stride) &&
-                    wgrad_batch_chunk(N, H, W, Cx, Cout, stride) >= N;
-  // ... and the 32 -> 32 channel layers their own (one workgroup per CU keeps the whole M)
-  const bool wino32 = prec == 0 && !b16 && !center_only && wgrad_wino32_ok(N, H, W, Cx, Cout, stride) &&
-                      wgrad_batch_chunk(N, H, W, Cx, Cout, stride) >= N;
-  // bf16 tensors, stride 1: the eight-wave row-ring kernel where the plan finds rows for it
-  // (64 x 64 channel tiles only: measured per layer - 32 x 32 tiles, enc0 / dec4 at 512 x 512,
-  // lose 20 % in the eight-wave form, the 64- and 128-channel layers gain 15 %, deeper ones +-0)
-  const bool ring_s2 = b16 && prec == 1 && stride == 2;
-  const bool ring8 = b16 && (pprec == 1 || ring_s2) && Cx % 64 == 0 && Cout % 64 == 0;
-  const WgradPlan pl = wino32 ? make_plan_wino32(N, H, W)
-                       : wino ? make_plan_wino(N, H, W, Cx, Cout)
-                              : make_plan(N, H, W, Cx, Cout, stride, pprec, wide, ring8, ring_s2);
-  const size_t need = ((wino || wino32) ? pl.ws_floats
-                            : wgrad_ws_floats(N, H, W, Cx, Cout, stride, pprec, wide)) * sizeof(float);
-  if (workspace_bytes < need || need == 0) {
-    unet_set_error("conv3x3_bwd_weight: workspace %zu < %zu bytes", workspace_bytes, need);
+  UNET_REQUIRE(!(c.db && c.b16), "conv_bwd_weight: db is not produced on the bf16-storage path");
+  UNET_REQUIRE(!(c.db && reduce_queue().on), "conv_bwd_weight: the bias gradient reuses the slab "
+                                             "workspace and cannot be combined with deferred reductions");
+  const WgradSel sel = wgrad_select(c, unet_conv::c32_winograd_flag());
+  const size_t need = wgrad_ws_floats(c, sel) * sizeof(float);
+  if (c.workspace_bytes < need || need == 0) {
+    unet_set_error("conv3x3_bwd_weight: workspace %zu < %zu bytes", c.workspace_bytes, need);
     return UNET_E_WORKSPACE;
   }
-  float* ws = reinterpret_cast<float*>(workspace);
-  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-  if (pl.stem) {
-    UNET_REQUIRE(stride == 1 && Cin_total == 3 && ci_offset == 0, "conv3x3_bwd_weight: stem shape");
-    dim3 grid(pl.stem_blocks, Cout / 32);
-    if (x_u8) {
-      UNET_REQUIRE(W % SW_PIX == 0, "stem_u8_bwd_weight: needs W %% %d == 0", SW_PIX);
-      StemNormW nm;
-      for (int c = 0; c < 3; ++c) { nm.mean[c] = u8_mean_std[c]; nm.std[c] = u8_mean_std[3 + c]; }
-      if (b16)
-        hipLaunchKernelGGL((conv_stem_wgrad_rows_kernel<unsigned char, __bf16>), grid, dim3(256), 0,
-                           stream, x_u8, reinterpret_cast<const __bf16*>(dy), ws, N, H, W, Cout,
-                           pl.stem_spb, pl.stem_stages, nm);
-      else
-        hipLaunchKernelGGL((conv_stem_wgrad_rows_kernel<unsigned char, float>), grid, dim3(256), 0,
-                           stream, x_u8, dy, ws, N, H, W, Cout, pl.stem_spb, pl.stem_stages, nm);
-    } else if (W % SW_PIX == 0) {  // a 128-pixel stage never straddles image rows: raw-row form
-      if (b16)
-        hipLaunchKernelGGL((conv_stem_wgrad_rows_kernel<float, __bf16>), grid, dim3(256), 0, stream,
-                           x, reinterpret_cast<const __bf16*>(dy), ws, N, H, W, Cout, pl.stem_spb,
-                           pl.stem_stages, StemNormW{});
-      else
-        hipLaunchKernelGGL((conv_stem_wgrad_rows_kernel<float, float>), grid, dim3(256), 0, stream,
-                           x, dy, ws, N, H, W, Cout, pl.stem_spb, pl.stem_stages, StemNormW{});
-    } else if (b16)
-      hipLaunchKernelGGL(conv_stem_wgrad_kernel<__bf16>, grid, dim3(256), 0, stream, x,
-                         reinterpret_cast<const __bf16*>(dy), ws, N, H, W, Cout, pl.stem_spb,
-                         pl.stem_stages);
-    else
-      hipLaunchKernelGGL(conv_stem_wgrad_kernel<float>, grid, dim3(256), 0, stream, x, dy, ws, N, H,
-                         W, Cout, pl.stem_spb, pl.stem_stages);
-    UNET_CHECK_LAUNCH("conv_stem_wgrad");
-    {
-      const int rc = emit_wgrad_reduction(ws, pl.stem_blocks, (size_t)27 * Cout, dw_oihw, 3, Cout, 0, 3,
-                                          false, true, stream);
-      if (rc != UNET_OK) return rc;
-    }
+  float* ws = reinterpret_cast<float*>(c.workspace);
+  if (sel.form == WF_STEM) {
+    UNET_REQUIRE(c.stride == 1 && c.Cin_total == 3 && c.ci_offset == 0, "conv3x3_bwd_weight: stem shape");
+    const WgradPlan pl = wgrad_plan(c, sel.form, sel.opt, c.N);
+    int rc = launch_wgrad_stem(c, pl, ws, stream);
+    if (rc == UNET_OK)
+      rc = emit_wgrad_reduction(ws, pl.stem_blocks, (size_t)27 * c.Cout, c.dw, 3, c.Cout, 0, 3,
+                                false, true, stream);
+    if (rc != UNET_OK) return rc;
   } else {
-    UNET_REQUIRE(!act_alpha || (act_beta && (prec == 0 || prec == 3 || b16)),
+    UNET_REQUIRE(!c.alpha || (c.beta && (c.prec == 0 || c.prec == 3 || c.b16)),
                  "conv_bwd_weight: activation on load needs the fp32, split or bf16-storage path");
-    const size_t E = (size_t)9 * Cx * Cout;
-    const int nmax = wgrad_batch_chunk(N, H, W, Cx, Cout, stride);
     int nslab = 0;
-    for (int nb = 0; nb < N; nb += nmax) {   // one pass unless a tensor exceeds 2 GiB
-      const int nc = N - nb < nmax ? N - nb : nmax;
-      const WgradPlan pc = (wino || wino32) ? pl : make_plan(nc, H, W, Cx, Cout, stride, pprec, wide, ring8, ring_s2);
-      WgradParams p{};
-      p.x = reinterpret_cast<const float*>(reinterpret_cast<const char*>(x) +
-                                           (size_t)nb * H * W * Cx * es);
-      p.dy = reinterpret_cast<const float*>(reinterpret_cast<const char*>(dy) +
-                                            (size_t)nb * Ho * Wo * Cout * es);
-      p.b16 = b16;
-      p.partial = ws + (size_t)nslab * E; p.Cx = Cx; p.Cout = Cout;
-      p.N = nc; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-      p.segs_per_row = pc.segs_per_row; p.total_segs = pc.total_segs;
-      p.segs_per_block = pc.segs_per_block; p.split = pc.split;
-      p.ci_tiles = Cx / pc.ci_t; p.co_tiles = Cout / pc.co_t;
-      p.x_bytes = (unsigned)((long long)nc * H * W * Cx * es);
-      p.dy_bytes = (unsigned)((long long)nc * Ho * Wo * Cout * es);
-      p.alpha = act_alpha ? act_alpha + (size_t)nb * Cx : nullptr;
-      p.beta = act_alpha ? act_beta + (size_t)nb * Cx : nullptr;
-      p.slope = slope;
-      const int rc = wino32 ? launch_wgrad_wino32(p, stream)
-                     : wino ? launch_wgrad_wino(p, stream) : launch_wgrad_plan(p, pc, stride, prec, stream);
-      if (rc != UNET_OK) return rc;
-      nslab += pc.split * pc.sps;
-    }
-    {
-      const int rc = emit_wgrad_reduction(ws, nslab, E, dw_oihw, Cx, Cout, ci_offset, Cin_total,
-                                          center_only, false, stream);
-      if (rc != UNET_OK) return rc;
-    }
+    int rc = wgrad_launch_chunks(c, sel, ws, &nslab, stream);
+    if (rc == UNET_OK)
+      rc = emit_wgrad_reduction(ws, nslab, (size_t)9 * c.Cx * c.Cout, c.dw, c.Cx, c.Cout,
+                                c.ci_offset, c.Cin_total, c.center_only, false, stream);
+    if (rc != UNET_OK) return rc;
   }
-  if (db) {
+  if (c.db) {
     // the slab workspace is free again at this point of the stream; reuse its head as scratch
-    const long long M = (long long)N * Ho * Wo;
+    const float* dy = static_cast<const float*>(c.dy);
+    const long long M = (long long)c.N * c.Ho() * c.Wo();
     const int chunks = M >= 4096 ? 64 : 1;
     const long long rpc = ceil_div64(M, chunks);
     if (chunks == 1) {
-      hipLaunchKernelGGL(bias_grad_kernel, dim3(Cout / 32, 1), dim3(256), 0, stream, dy, db, M,
-                         Cout, rpc);
+      hipLaunchKernelGGL(bias_grad_kernel, dim3(c.Cout / 32, 1), dim3(256), 0, stream, dy, c.db, M,
+                         c.Cout, rpc);
     } else {
-      hipLaunchKernelGGL(bias_grad_kernel, dim3(Cout / 32, chunks), dim3(256), 0, stream, dy, ws, M,
-                         Cout, rpc);
+      hipLaunchKernelGGL(bias_grad_kernel, dim3(c.Cout / 32, chunks), dim3(256), 0, stream, dy, ws,
+                         M, c.Cout, rpc);
       UNET_CHECK_LAUNCH("bias_grad(stage)");
-      hipLaunchKernelGGL(bias_grad_kernel, dim3(Cout / 32, 1), dim3(256), 0, stream, ws, db,
-                         (long long)chunks, Cout, (long long)chunks);
+      hipLaunchKernelGGL(bias_grad_kernel, dim3(c.Cout / 32, 1), dim3(256), 0, stream, ws, c.db,
+                         (long long)chunks, c.Cout, (long long)chunks);
     }
     UNET_CHECK_LAUNCH("bias_grad");
   }
@@ -2865,8 +2870,12 @@ extern "C" int unet_conv3x3_bwd_weight(const float* x, int Cx, const float* dy, 
                                        int ci_offset, int Cin_total, float* db, void* workspace,
                                        size_t workspace_bytes, int N, int H, int W, int Cout,
                                        int stride, unet_stream_t stream) {
-  return conv_bwd_weight_impl(x, Cx, dy, dw_oihw, ci_offset, Cin_total, db, workspace,
-                              workspace_bytes, N, H, W, Cout, stride, false, (hipStream_t)stream);
+  WgradCall c;
+  c.x = x; c.dy = dy;
+  c.dw = dw_oihw; c.ci_offset = ci_offset; c.Cin_total = Cin_total; c.db = db;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.N = N; c.H = H; c.W = W; c.Cx = Cx; c.Cout = Cout; c.stride = stride;
+  return conv_bwd_weight_impl(c, (hipStream_t)stream);
 }
 
 // 1x1 weight gradient dw[Cout][Cin_total] (columns ci_offset .. +Cx).  Runs the 3x3 kernel and
@@ -2877,8 +2886,12 @@ extern "C" int unet_conv1x1_bwd_weight(const float* x, int Cx, const float* dy, 
                                        size_t workspace_bytes, int N, int H, int W, int Cout,
                                        unet_stream_t stream) {
   UNET_REQUIRE(Cx % 32 == 0, "conv1x1_bwd_weight: Cx %d must be a multiple of 32", Cx);
-  return conv_bwd_weight_impl(x, Cx, dy, dw, ci_offset, Cin_total, nullptr, workspace,
-                              workspace_bytes, N, H, W, Cout, 1, true, (hipStream_t)stream);
+  WgradCall c;
+  c.x = x; c.dy = dy; c.center_only = true;
+  c.dw = dw; c.ci_offset = ci_offset; c.Cin_total = Cin_total;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.N = N; c.H = H; c.W = W; c.Cx = Cx; c.Cout = Cout;
+  return conv_bwd_weight_impl(c, (hipStream_t)stream);
 }
 
 extern "C" int unet_conv3x3_bwd_weight_bf16(const float* x, int Cx, const float* dy,
@@ -2886,9 +2899,12 @@ extern "C" int unet_conv3x3_bwd_weight_bf16(const float* x, int Cx, const float*
                                             float* db, void* workspace, size_t workspace_bytes,
                                             int N, int H, int W, int Cout, int stride,
                                             unet_stream_t stream) {
-  return conv_bwd_weight_impl(x, Cx, dy, dw_oihw, ci_offset, Cin_total, db, workspace,
-                              workspace_bytes, N, H, W, Cout, stride, false, (hipStream_t)stream,
-                              1);
+  WgradCall c;
+  c.x = x; c.dy = dy; c.prec = 1;
+  c.dw = dw_oihw; c.ci_offset = ci_offset; c.Cin_total = Cin_total; c.db = db;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.N = N; c.H = H; c.W = W; c.Cx = Cx; c.Cout = Cout; c.stride = stride;
+  return conv_bwd_weight_impl(c, (hipStream_t)stream);
 }
 
 extern "C" int unet_conv3x3_bwd_weight_bf16x3(const float* x, int Cx, const float* dy,
@@ -2896,23 +2912,43 @@ extern "C" int unet_conv3x3_bwd_weight_bf16x3(const float* x, int Cx, const floa
                                               float* db, void* workspace, size_t workspace_bytes,
                                               int N, int H, int W, int Cout, int stride,
                                               unet_stream_t stream) {
-  return conv_bwd_weight_impl(x, Cx, dy, dw_oihw, ci_offset, Cin_total, db, workspace,
-                              workspace_bytes, N, H, W, Cout, stride, false, (hipStream_t)stream,
-                              3);
+  WgradCall c;
+  c.x = x; c.dy = dy; c.prec = 3;
+  c.dw = dw_oihw; c.ci_offset = ci_offset; c.Cin_total = Cin_total; c.db = db;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.N = N; c.H = H; c.W = W; c.Cx = Cx; c.Cout = Cout; c.stride = stride;
+  return conv_bwd_weight_impl(c, (hipStream_t)stream);
+}
+
+// What the unet_conv_in_bwd_weight* entry points require of their source and kernel size;
+// `name`: the entry point's, for the error text.
+static int check_conv_in(const char* name, const unet_act_src* x, int ksize, int stride) {
+  UNET_REQUIRE(x && x->x, "%s: null source", name);
+  UNET_REQUIRE(ksize == 3 || (ksize == 1 && stride == 1), "%s: kernel %d / stride %d unsupported",
+               name, ksize, stride);
+  UNET_REQUIRE(x->C == 3 ? !x->alpha : x->C % 32 == 0,
+               "%s: Cx %d unsupported (the RGB image is a plain operand)", name, x->C);
+  return UNET_OK;
+}
+// the operand of a record from a layer source (activated on load when x->alpha is set)
+static void set_source(WgradCall& c, const unet_act_src* x, float slope) {
+  if (!x) return;
+  c.x = x->x; c.Cx = x->C; c.alpha = x->alpha; c.beta = x->beta; c.slope = slope;
 }
 
 extern "C" int unet_conv_in_bwd_weight(const unet_act_src* x, float slope, const float* dy,
                                        float* dw_oihw, int ci_offset, int Cin_total, int ksize,
                                        int stride, void* workspace, size_t workspace_bytes, int N,
                                        int H, int W, int Cout, unet_stream_t stream) {
-  UNET_REQUIRE(x && x->x, "conv_in_bwd_weight: null source");
-  UNET_REQUIRE(ksize == 3 || (ksize == 1 && stride == 1),
-               "conv_in_bwd_weight: kernel %d / stride %d unsupported", ksize, stride);
-  UNET_REQUIRE(x->C == 3 ? !x->alpha : x->C % 32 == 0,
-               "conv_in_bwd_weight: Cx %d unsupported (the RGB image is a plain operand)", x->C);
-  return conv_bwd_weight_impl(x->x, x->C, dy, dw_oihw, ci_offset, Cin_total, nullptr, workspace,
-                              workspace_bytes, N, H, W, Cout, stride, ksize == 1,
-                              (hipStream_t)stream, 0, x->alpha, x->beta, slope);
+  const int rc = check_conv_in("conv_in_bwd_weight", x, ksize, stride);
+  if (rc != UNET_OK) return rc;
+  WgradCall c;
+  set_source(c, x, slope);
+  c.dy = dy; c.center_only = ksize == 1;
+  c.dw = dw_oihw; c.ci_offset = ci_offset; c.Cin_total = Cin_total;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.N = N; c.H = H; c.W = W; c.Cout = Cout; c.stride = stride;
+  return conv_bwd_weight_impl(c, (hipStream_t)stream);
 }
 
 // The same in the split-bf16 operand mode (fp32 tensors, fp32-class accuracy): stride-1 3x3
@@ -2923,127 +2959,15 @@ extern "C" int unet_conv_in_bwd_weight_bf16x3(const unet_act_src* x, float slope
                                               int ksize, int stride, void* workspace,
                                               size_t workspace_bytes, int N, int H, int W, int Cout,
                                               unet_stream_t stream) {
-  UNET_REQUIRE(x && x->x, "conv_in_bwd_weight_bf16x3: null source");
-  UNET_REQUIRE(ksize == 3 || (ksize == 1 && stride == 1),
-               "conv_in_bwd_weight_bf16x3: kernel %d / stride %d unsupported", ksize, stride);
-  UNET_REQUIRE(x->C == 3 ? !x->alpha : x->C % 32 == 0,
-               "conv_in_bwd_weight_bf16x3: Cx %d unsupported (the RGB image is a plain operand)",
-               x->C);
-  const int prec = (ksize == 3 && x->C != 3) ? 3 : 0;
-  return conv_bwd_weight_impl(x->x, x->C, dy, dw_oihw, ci_offset, Cin_total, nullptr, workspace,
-                              workspace_bytes, N, H, W, Cout, stride, ksize == 1,
-                              (hipStream_t)stream, prec, x->alpha, x->beta, slope);
-}
-
-// ---- conv3x3(upsample2x(a)): weight gradient w.r.t. the up-sampled operand at low resolution
-namespace {
-int up_wgrad_chunk(int N, int h, int w, int Cx, int Cout) {
-  const long long a = (long long)h * w * Cx * 4, b = (long long)h * w * 9 * Cout * 4;
-  return unet_conv::batch_chunk(N, a > b ? a : b);
-}
-size_t up_wgrad_ws_floats(int N, int h, int w, int Cx, int Cout, bool wide) {
-  const int nmax = up_wgrad_chunk(N, h, w, Cx, Cout);
-  if (nmax < 1) return 0;
-  const size_t E = (size_t)9 * Cx * Cout;
-  size_t slabs = 0;
-  for (int nb = 0; nb < N; nb += nmax) {
-    const WgradPlan pl =
-        make_plan_taps((long long)(N - nb < nmax ? N - nb : nmax) * h * w, Cx, Cout, wide);
-    slabs += (size_t)pl.split * pl.sps;
-  }
-  return slabs * E + 2 * (size_t)ceil_div((int)slabs, kSlabChunk) * E;
-}
-}  // namespace
-
-extern "C" size_t unet_conv3x3_up_bwd_weight_workspace_bytes(int N, int h, int w, int Cx, int Cout) {
-  if (N <= 0 || h <= 0 || w <= 0 || Cx <= 0 || Cout <= 0) return 0;
-  const size_t a = up_wgrad_ws_floats(N, h, w, Cx, Cout, false);
-  const size_t b = up_wgrad_ws_floats(N, h, w, Cx, Cout, true);
-  return (a > b ? a : b) * sizeof(float);
-}
-
-static int up_bwd_weight_impl(const unet_act_src* x, float slope, const float* D, float* dw_oihw,
-                              int ci_offset, int Cin_total, void* workspace,
-                              size_t workspace_bytes, int N, int h, int w, int Cout,
-                              hipStream_t stream, int b16);
-
-extern "C" int unet_conv3x3_up_bwd_weight(const unet_act_src* x, float slope, const float* D,
-                                          float* dw_oihw, int ci_offset, int Cin_total,
-                                          void* workspace, size_t workspace_bytes, int N, int h,
-                                          int w, int Cout, unet_stream_t stream) {
-  return up_bwd_weight_impl(x, slope, D, dw_oihw, ci_offset, Cin_total, workspace, workspace_bytes,
-                            N, h, w, Cout, (hipStream_t)stream, 0);
-}
-
-// x (activated on load) and D are bf16 tensors
-extern "C" int unet_conv3x3_up_bwd_weight_b16(const unet_act_src* x, float slope, const uint16_t* D,
-                                              float* dw_oihw, int ci_offset, int Cin_total,
-                                              void* workspace, size_t workspace_bytes, int N,
-                                              int h, int w, int Cout, unet_stream_t stream) {
-  return up_bwd_weight_impl(x, slope, reinterpret_cast<const float*>(D), dw_oihw, ci_offset,
-                            Cin_total, workspace, workspace_bytes, N, h, w, Cout,
-                            (hipStream_t)stream, 1);
-}
-
-static int up_bwd_weight_impl(const unet_act_src* x, float slope, const float* D, float* dw_oihw,
-                              int ci_offset, int Cin_total, void* workspace,
-                              size_t workspace_bytes, int N, int h, int w, int Cout,
-                              hipStream_t stream, int b16) {
-  const long long es = b16 ? 2 : 4;
-  UNET_REQUIRE(x && x->x && D && dw_oihw && workspace, "conv3x3_up_bwd_weight: null pointer");
-  const int Cx = x->C;
-  UNET_REQUIRE(Cx > 0 && Cx % 32 == 0 && Cout > 0 && Cout % 32 == 0 && N > 0 && h > 0 && w > 0,
-               "conv3x3_up_bwd_weight: bad shape Cx=%d Cout=%d", Cx, Cout);
-  UNET_REQUIRE(ci_offset >= 0 && ci_offset + Cx <= Cin_total, "conv3x3_up_bwd_weight: bad ci slice");
-  UNET_REQUIRE(!x->alpha || x->beta, "conv3x3_up_bwd_weight: alpha without beta");
-  const int nmax = up_wgrad_chunk(N, h, w, Cx, Cout);
-  UNET_REQUIRE(nmax >= 1, "conv3x3_up_bwd_weight: one image exceeds the 2 GiB buffer-descriptor range");
-  const bool wide = !b16 && wgrad_tiles(Cx, Cout) >= 4;   // as in conv_bwd_weight_impl
-  const size_t need = up_wgrad_ws_floats(N, h, w, Cx, Cout, wide) * sizeof(float);
-  if (workspace_bytes < need) {
-    unet_set_error("conv3x3_up_bwd_weight: workspace %zu < %zu bytes", workspace_bytes, need);
-    return UNET_E_WORKSPACE;
-  }
-  float* ws = reinterpret_cast<float*>(workspace);
-  const size_t E = (size_t)9 * Cx * Cout;
-  int nslab = 0;
-  for (int nb = 0; nb < N; nb += nmax) {   // one pass unless a tensor exceeds 2 GiB
-    const int nc = N - nb < nmax ? N - nb : nmax;
-    const long long Q = (long long)nc * h * w;
-    const WgradPlan pl = make_plan_taps(Q, Cx, Cout, wide, b16);
-    WgradParams p{};
-    p.x = reinterpret_cast<const float*>(reinterpret_cast<const char*>(x->x) +
-                                         (size_t)nb * h * w * Cx * es);
-    p.dy = reinterpret_cast<const float*>(reinterpret_cast<const char*>(D) +
-                                          (size_t)nb * h * w * 9 * Cout * es);
-    p.b16 = b16;
-    p.partial = ws + (size_t)nslab * E; p.Cx = Cx; p.Cout = Cout;
-    p.N = nc; p.H = h; p.W = w; p.Ho = h; p.Wo = w;
-    p.segs_per_row = 0; p.total_segs = pl.total_segs;
-    p.segs_per_block = pl.segs_per_block; p.split = pl.split;
-    p.ci_tiles = Cx / pl.ci_t; p.co_tiles = Cout / pl.co_t;
-    p.x_bytes = (unsigned)(Q * Cx * es);
-    p.dy_bytes = (unsigned)(Q * 9 * Cout * es);
-    p.alpha = x->alpha ? x->alpha + (size_t)nb * Cx : nullptr;
-    p.beta = x->alpha ? x->beta + (size_t)nb * Cx : nullptr;
-    p.slope = slope;
-    int rc;
-    if (wide) {
-      if (pl.ci_t == 64) rc = launch_wgrad_taps8<64, 64, 32>(p, stream);
-      else if (pl.co_t == 64) rc = launch_wgrad_taps8<32, 64, 32>(p, stream);
-      else rc = launch_wgrad_taps8<32, 32, 64>(p, stream);
-    } else {
-      if (pl.ci_t == 64 && b16) rc = launch_wgrad_taps_b16<64, 64, 16>(p, stream);
-      else if (pl.ci_t == 32 && pl.co_t == 32 && b16) rc = launch_wgrad_taps_b16<32, 32, 64>(p, stream);
-      else if (pl.ci_t == 64) rc = launch_wgrad_taps<64, 64, 16>(p, stream);
-      else if (pl.co_t == 64) rc = launch_wgrad_taps<32, 64, 16>(p, stream);
-      else rc = launch_wgrad_taps<32, 32, 32>(p, stream);
-    }
-    if (rc != UNET_OK) return rc;
-    nslab += pl.split * pl.sps;
-  }
-  return emit_wgrad_reduction(ws, nslab, E, dw_oihw, Cx, Cout, ci_offset, Cin_total, false, false,
-                              stream);
+  const int rc = check_conv_in("conv_in_bwd_weight_bf16x3", x, ksize, stride);
+  if (rc != UNET_OK) return rc;
+  WgradCall c;
+  set_source(c, x, slope);
+  c.dy = dy; c.center_only = ksize == 1; c.prec = (ksize == 3 && x->C != 3) ? 3 : 0;
+  c.dw = dw_oihw; c.ci_offset = ci_offset; c.Cin_total = Cin_total;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.N = N; c.H = H; c.W = W; c.Cout = Cout; c.stride = stride;
+  return conv_bwd_weight_impl(c, (hipStream_t)stream);
 }
 
 // Mixed-precision pipeline: x (activated on load) and dy are bf16 tensors; stride-1 layers on the
@@ -3053,15 +2977,15 @@ extern "C" int unet_conv_in_bwd_weight_b16(const unet_act_src* x, float slope, c
                                            float* dw_oihw, int ci_offset, int Cin_total, int ksize,
                                            int stride, void* workspace, size_t workspace_bytes,
                                            int N, int H, int W, int Cout, unet_stream_t stream) {
-  UNET_REQUIRE(x && x->x, "conv_in_bwd_weight_b16: null source");
-  UNET_REQUIRE(ksize == 3 || (ksize == 1 && stride == 1),
-               "conv_in_bwd_weight_b16: kernel %d / stride %d unsupported", ksize, stride);
-  UNET_REQUIRE(x->C == 3 ? !x->alpha : x->C % 32 == 0,
-               "conv_in_bwd_weight_b16: Cx %d unsupported (the RGB image is a plain operand)", x->C);
-  return conv_bwd_weight_impl(x->x, x->C, reinterpret_cast<const float*>(dy), dw_oihw, ci_offset,
-                              Cin_total, nullptr, workspace, workspace_bytes, N, H, W, Cout, stride,
-                              ksize == 1, (hipStream_t)stream, 1, x->alpha, x->beta, slope, nullptr,
-                              nullptr, 1);
+  const int rc = check_conv_in("conv_in_bwd_weight_b16", x, ksize, stride);
+  if (rc != UNET_OK) return rc;
+  WgradCall c;
+  set_source(c, x, slope);
+  c.dy = dy; c.center_only = ksize == 1; c.b16 = true; c.prec = 1;
+  c.dw = dw_oihw; c.ci_offset = ci_offset; c.Cin_total = Cin_total;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.N = N; c.H = H; c.W = W; c.Cout = Cout; c.stride = stride;
+  return conv_bwd_weight_impl(c, (hipStream_t)stream);
 }
 
 // Weight gradient of the RGB stem from the uint8 image (normalised on load, W % 128 == 0);
@@ -3072,9 +2996,76 @@ extern "C" int unet_stem_u8_bwd_weight(const uint8_t* image_hwc, const float* me
                                        int W, int Cout, unet_stream_t stream) {
   UNET_REQUIRE(image_hwc && mean3 && std3, "stem_u8_bwd_weight: null pointer");
   const float ms[6] = {mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]};
-  return conv_bwd_weight_impl(nullptr, 3, dy, dw_oihw, 0, 3, nullptr, workspace, workspace_bytes,
-                              N, H, W, Cout, 1, false, (hipStream_t)stream, 0, nullptr, nullptr,
-                              0.f, image_hwc, ms);
+  WgradCall c;
+  c.x_u8 = image_hwc; c.u8_mean_std = ms; c.dy = dy;
+  c.dw = dw_oihw; c.Cin_total = 3;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.N = N; c.H = H; c.W = W; c.Cx = 3; c.Cout = Cout;
+  return conv_bwd_weight_impl(c, (hipStream_t)stream);
+}
+
+// ---- conv3x3(upsample2x(a)): weight gradient w.r.t. the up-sampled operand at low resolution
+extern "C" size_t unet_conv3x3_up_bwd_weight_workspace_bytes(int N, int h, int w, int Cx, int Cout) {
+  if (N <= 0 || h <= 0 || w <= 0 || Cx <= 0 || Cout <= 0) return 0;
+  size_t m = 0;
+  for (const bool b16 : {false, true}) {   // the selector's choice for either element storage
+    WgradCall c;
+    c.taps = true; c.b16 = b16;
+    c.N = N; c.H = h; c.W = w; c.Cx = Cx; c.Cout = Cout;
+    const size_t f = wgrad_ws_floats(c, wgrad_select(c, 0));
+    if (f > m) m = f;
+  }
+  return m * sizeof(float);
+}
+
+// c: a `taps` record - dy holds the tap gradients D, H x W is the low resolution
+static int up_bwd_weight_impl(const WgradCall& c, hipStream_t stream) {
+  UNET_REQUIRE(c.x && c.dy && c.dw && c.workspace, "conv3x3_up_bwd_weight: null pointer");
+  UNET_REQUIRE(c.Cx > 0 && c.Cx % 32 == 0 && c.Cout > 0 && c.Cout % 32 == 0 && c.N > 0 && c.H > 0 &&
+                   c.W > 0,
+               "conv3x3_up_bwd_weight: bad shape Cx=%d Cout=%d", c.Cx, c.Cout);
+  UNET_REQUIRE(c.ci_offset >= 0 && c.ci_offset + c.Cx <= c.Cin_total, "conv3x3_up_bwd_weight: bad ci slice");
+  UNET_REQUIRE(!c.alpha || c.beta, "conv3x3_up_bwd_weight: alpha without beta");
+  const WgradSel sel = wgrad_select(c, 0);
+  UNET_REQUIRE(sel.nmax >= 1, "conv3x3_up_bwd_weight: one image exceeds the 2 GiB buffer-descriptor range");
+  const size_t need = wgrad_ws_floats(c, sel) * sizeof(float);
+  if (c.workspace_bytes < need) {
+    unet_set_error("conv3x3_up_bwd_weight: workspace %zu < %zu bytes", c.workspace_bytes, need);
+    return UNET_E_WORKSPACE;
+  }
+  float* ws = reinterpret_cast<float*>(c.workspace);
+  int nslab = 0;
+  const int rc = wgrad_launch_chunks(c, sel, ws, &nslab, stream);
+  if (rc != UNET_OK) return rc;
+  return emit_wgrad_reduction(ws, nslab, (size_t)9 * c.Cx * c.Cout, c.dw, c.Cx, c.Cout, c.ci_offset,
+                              c.Cin_total, false, false, stream);
+}
+
+extern "C" int unet_conv3x3_up_bwd_weight(const unet_act_src* x, float slope, const float* D,
+                                          float* dw_oihw, int ci_offset, int Cin_total,
+                                          void* workspace, size_t workspace_bytes, int N, int h,
+                                          int w, int Cout, unet_stream_t stream) {
+  WgradCall c;
+  set_source(c, x, slope);
+  c.dy = D; c.taps = true;
+  c.dw = dw_oihw; c.ci_offset = ci_offset; c.Cin_total = Cin_total;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.N = N; c.H = h; c.W = w; c.Cout = Cout;
+  return up_bwd_weight_impl(c, (hipStream_t)stream);
+}
+
+// x (activated on load) and D are bf16 tensors
+extern "C" int unet_conv3x3_up_bwd_weight_b16(const unet_act_src* x, float slope, const uint16_t* D,
+                                              float* dw_oihw, int ci_offset, int Cin_total,
+                                              void* workspace, size_t workspace_bytes, int N,
+                                              int h, int w, int Cout, unet_stream_t stream) {
+  WgradCall c;
+  set_source(c, x, slope);
+  c.dy = D; c.taps = true; c.b16 = true;
+  c.dw = dw_oihw; c.ci_offset = ci_offset; c.Cin_total = Cin_total;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.N = N; c.H = h; c.W = w; c.Cout = Cout;
+  return up_bwd_weight_impl(c, (hipStream_t)stream);
 }
 
 // ---- deferred reductions (include/unet_hip.h) ----
