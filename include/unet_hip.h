@@ -312,6 +312,41 @@ int unet_argmax_dice_counts(const float* logits_nchw, const int64_t* target, uin
                             uint64_t* counts, int N, int H, int W, int ignore_index,
                             unet_stream_t stream);
 
+/* uint8-target twins of the loss and metric entry points above: `target` is the dataset's uint8
+ * mask [N,H,W] itself (1 byte per pixel instead of 8), raw or cleaned - the dataset's rule
+ * v > 2 && v != 255 -> 0 (Our_UNet/src/train.py:300) is applied on load and is the identity on a
+ * cleaned mask.  Arguments, outputs and workspace layout are those of the int64 forms, and so are
+ * the results, bit for bit, on the cleaned mask widened to int64 (the kernels are the same
+ * templates; the workspaces of the two forms are interchangeable).  ignore_index must lie in
+ * 3..255: anything else is UNET_E_INVALID before a launch.  unet_argmax_dice_counts_u8 takes four
+ * pixels per lane - one 4-byte label load, 16-byte logit loads - when H*W % 4 == 0 and the
+ * tensors are 16- / 4-byte aligned; the loss kernels keep the int64 forms' one pixel per lane,
+ * whose summation order and fused multiply-adds are the bits of the loss and of dlogits. */
+int unet_dice_wce_loss_fwd_bwd_u8(const float* logits_nchw, const uint8_t* target, float* loss_out,
+                                  float* dlogits_nchw, void* workspace, size_t workspace_bytes,
+                                  int N, int H, int W, float smooth, float w_dice, float w_ce,
+                                  int ignore_index, int dynamic_weights,
+                                  const float* class_weights, float grad_scale,
+                                  unet_stream_t stream);
+int unet_dice_wce_loss_grad_u8(const float* logits_nchw, const uint8_t* target,
+                               const void* workspace, size_t workspace_bytes,
+                               const float* upstream, float* dlogits_nchw, int N, int H, int W,
+                               int ignore_index, unet_stream_t stream);
+int unet_dice_wce_loss_shard_stats_u8(const float* logits_nchw, const uint8_t* target,
+                                      double* stats, void* workspace, size_t workspace_bytes,
+                                      int N, int H, int W, float smooth, int ignore_index,
+                                      unet_stream_t stream);
+int unet_dice_wce_loss_shard_apply_u8(const float* logits_nchw, const uint8_t* target,
+                                      const double* global_stats, int N_global, float* loss_out,
+                                      float* dlogits, void* workspace, size_t workspace_bytes,
+                                      int N, int H, int W, float smooth, float w_dice, float w_ce,
+                                      int ignore_index, int dynamic_weights,
+                                      const float* class_weights, float grad_scale,
+                                      unet_stream_t stream);
+int unet_argmax_dice_counts_u8(const float* logits_nchw, const uint8_t* target, uint8_t* preds,
+                               uint64_t* counts, int N, int H, int W, int ignore_index,
+                               unet_stream_t stream);
+
 /* ---- test-set evaluation (Our_UNet/src/evaluate.py:150-268) -------------------------------- */
 
 /* cm[B][3][3] (uint64, device; zeroed here) = per image, the confusion matrix
@@ -442,6 +477,18 @@ int unet_stem_u8_bwd_weight(const uint8_t* image_hwc, const float* mean3, const 
                             const float* dy, float* dw_oihw, void* workspace,
                             size_t workspace_bytes, int N, int H, int W, int Cout,
                             unet_stream_t stream);
+/* The same on the mixed-precision pipeline: y / dy are bf16 tensors (statistics, workspace and
+ * *stats_px_out as unet_conv_in_fwd_b16; dw stays fp32).  The fp32 accumulators are those of
+ * the fp32 forms, so the results equal unet_conv_in_fwd_b16 / unet_conv_in_bwd_weight_b16 on the
+ * image unet_preprocess_u8 writes, bit for bit. */
+int unet_stem_u8_fwd_b16(const uint8_t* image_hwc, const float* mean3, const float* std3,
+                         const float* wf, const float* bias, uint16_t* y, void* workspace,
+                         size_t workspace_bytes, int* stats_px_out, int N, int H, int W, int Cout,
+                         unet_stream_t stream);
+int unet_stem_u8_bwd_weight_b16(const uint8_t* image_hwc, const float* mean3, const float* std3,
+                                const uint16_t* dy, float* dw_oihw, void* workspace,
+                                size_t workspace_bytes, int N, int H, int W, int Cout,
+                                unet_stream_t stream);
 
 /* Weight gradient with the activation applied to the input operand on load:
  * dw_oihw[Cout][Cin_total][k][k] (columns ci_offset .. +x->C) = sum_pixels act(x) (x) dy.

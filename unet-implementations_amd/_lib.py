@@ -190,7 +190,17 @@ SIGNATURES = {
                            _c.c_double, _p, _sz, _i, _i, _i, _i, _p]),
     "unet_ssim_grad": (_i, [_p, _p, _i, _c.POINTER(_f), _f, _f, _p, _i, _c.c_double, _c.c_double,
                             _p, _i, _i, _i, _i, _p]),
+    "unet_stem_u8_fwd_b16": (_i, [_p, _c.POINTER(_f), _c.POINTER(_f), _p, _p, _p, _p, _sz,
+                                  _c.POINTER(_i), _i, _i, _i, _i, _p]),
+    "unet_stem_u8_bwd_weight_b16": (_i, [_p, _c.POINTER(_f), _c.POINTER(_f), _p, _p, _p, _sz, _i,
+                                         _i, _i, _i, _p]),
 }
+# the uint8-target twins take the arguments of their int64 forms
+for _name in ("unet_dice_wce_loss_fwd_bwd", "unet_dice_wce_loss_grad",
+              "unet_dice_wce_loss_shard_stats", "unet_dice_wce_loss_shard_apply",
+              "unet_argmax_dice_counts"):
+    SIGNATURES[_name + "_u8"] = SIGNATURES[_name]
+del _name
 
 _lib = None
 

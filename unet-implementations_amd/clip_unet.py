@@ -44,8 +44,8 @@ class CLIPUNet(UNet):
                                         "clip_fusion_conv", ksize=1)
         return plan
 
-    def forward(self, x, clip_features=None):
-        return super().forward(x, clip_features)
+    def forward(self, x, clip_features=None, input_layout="nchw"):
+        return super().forward(x, clip_features, input_layout=input_layout)
 
     def _bottleneck_input(self, x, clip_features):
         if not self.with_clip_features or clip_features is None:

@@ -2184,10 +2184,11 @@ extern "C" int unet_conv_up_in_fwd_b16(const unet_act_src* low, const unet_act_s
 // RGB stem straight from the dataset's uint8 HWC image: normalisation fused into the loader
 // (Our_UNet/src/train.py:303-308 + the first Conv2d of encoder_stages.0), statistics epilogue as
 // unet_conv_in_fwd.  Needs W % 128 == 0 (the raw-row form); other widths: unet_preprocess_u8.
-extern "C" int unet_stem_u8_fwd(const uint8_t* image_hwc, const float* mean3, const float* std3,
-                                const float* wf, const float* bias, float* y, void* workspace,
-                                size_t workspace_bytes, int* stats_px_out, int N, int H, int W,
-                                int Cout, unet_stream_t stream) {
+template <typename TO>
+static int stem_u8_fwd_impl(const uint8_t* image_hwc, const float* mean3, const float* std3,
+                            const float* wf, const float* bias, TO* y, void* workspace,
+                            size_t workspace_bytes, int* stats_px_out, int N, int H, int W,
+                            int Cout, hipStream_t stream) {
   UNET_REQUIRE(image_hwc && mean3 && std3 && wf && y && workspace && stats_px_out,
                "stem_u8_fwd: null pointer");
   UNET_REQUIRE(N > 0 && H > 0 && W > 0 && W % STEM_ROW_PIX == 0 && Cout > 0 && Cout % 32 == 0,
@@ -2199,12 +2200,30 @@ extern "C" int unet_stem_u8_fwd(const uint8_t* image_hwc, const float* mean3, co
   }
   StemNorm nm;
   for (int c = 0; c < 3; ++c) { nm.mean[c] = mean3[c]; nm.std[c] = std3[c]; }
-  launch_stem_fwd_rows<unsigned char, float>(image_hwc, wf, bias, y, N, H, W, Cout,
-                                             reinterpret_cast<float2*>(workspace), nm,
-                                             (hipStream_t)stream);
+  launch_stem_fwd_rows<unsigned char, TO>(image_hwc, wf, bias, y, N, H, W, Cout,
+                                          reinterpret_cast<float2*>(workspace), nm, stream);
   UNET_CHECK_LAUNCH("conv_stem_fwd(u8)");
   *stats_px_out = STEM_ROW_PIX;
   return UNET_OK;
+}
+
+extern "C" int unet_stem_u8_fwd(const uint8_t* image_hwc, const float* mean3, const float* std3,
+                                const float* wf, const float* bias, float* y, void* workspace,
+                                size_t workspace_bytes, int* stats_px_out, int N, int H, int W,
+                                int Cout, unet_stream_t stream) {
+  return stem_u8_fwd_impl(image_hwc, mean3, std3, wf, bias, y, workspace, workspace_bytes,
+                          stats_px_out, N, H, W, Cout, (hipStream_t)stream);
+}
+
+// ... on the mixed-precision pipeline: y is a bf16 tensor (statistics, workspace and
+// *stats_px_out as unet_conv_in_fwd_b16) - the same accumulators, rounded once on the store
+extern "C" int unet_stem_u8_fwd_b16(const uint8_t* image_hwc, const float* mean3,
+                                    const float* std3, const float* wf, const float* bias,
+                                    uint16_t* y, void* workspace, size_t workspace_bytes,
+                                    int* stats_px_out, int N, int H, int W, int Cout,
+                                    unet_stream_t stream) {
+  return stem_u8_fwd_impl(image_hwc, mean3, std3, wf, bias, reinterpret_cast<__bf16*>(y), workspace,
+                          workspace_bytes, stats_px_out, N, H, W, Cout, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------

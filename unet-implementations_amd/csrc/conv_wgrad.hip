@@ -2990,18 +2990,38 @@ extern "C" int unet_conv_in_bwd_weight_b16(const unet_act_src* x, float slope, c
 
 // Weight gradient of the RGB stem from the uint8 image (normalised on load, W % 128 == 0);
 // workspace as unet_conv3x3_bwd_weight_workspace_bytes(N, H, W, 3, Cout, 1).
-extern "C" int unet_stem_u8_bwd_weight(const uint8_t* image_hwc, const float* mean3,
-                                       const float* std3, const float* dy, float* dw_oihw,
-                                       void* workspace, size_t workspace_bytes, int N, int H,
-                                       int W, int Cout, unet_stream_t stream) {
+static int stem_u8_bwd_weight_impl(const uint8_t* image_hwc, const float* mean3,
+                                   const float* std3, const void* dy, bool b16, float* dw_oihw,
+                                   void* workspace, size_t workspace_bytes, int N, int H, int W,
+                                   int Cout, hipStream_t stream) {
   UNET_REQUIRE(image_hwc && mean3 && std3, "stem_u8_bwd_weight: null pointer");
   const float ms[6] = {mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]};
   WgradCall c;
   c.x_u8 = image_hwc; c.u8_mean_std = ms; c.dy = dy;
+  if (b16) { c.b16 = true; c.prec = 1; }      // (as unet_conv_in_bwd_weight_b16)
   c.dw = dw_oihw; c.Cin_total = 3;
   c.workspace = workspace; c.workspace_bytes = workspace_bytes;
   c.N = N; c.H = H; c.W = W; c.Cx = 3; c.Cout = Cout;
-  return conv_bwd_weight_impl(c, (hipStream_t)stream);
+  return conv_bwd_weight_impl(c, stream);
+}
+
+extern "C" int unet_stem_u8_bwd_weight(const uint8_t* image_hwc, const float* mean3,
+                                       const float* std3, const float* dy, float* dw_oihw,
+                                       void* workspace, size_t workspace_bytes, int N, int H,
+                                       int W, int Cout, unet_stream_t stream) {
+  return stem_u8_bwd_weight_impl(image_hwc, mean3, std3, dy, false, dw_oihw, workspace,
+                                 workspace_bytes, N, H, W, Cout, (hipStream_t)stream);
+}
+
+// ... with a bf16 dy (mixed-precision pipeline); the width is checked before the workspace here
+extern "C" int unet_stem_u8_bwd_weight_b16(const uint8_t* image_hwc, const float* mean3,
+                                           const float* std3, const uint16_t* dy, float* dw_oihw,
+                                           void* workspace, size_t workspace_bytes, int N, int H,
+                                           int W, int Cout, unet_stream_t stream) {
+  UNET_REQUIRE(N > 0 && H > 0 && W > 0 && W % SW_PIX == 0,
+               "stem_u8_bwd_weight_b16: needs W %% %d == 0 (got W=%d)", SW_PIX, W);
+  return stem_u8_bwd_weight_impl(image_hwc, mean3, std3, dy, true, dw_oihw, workspace,
+                                 workspace_bytes, N, H, W, Cout, (hipStream_t)stream);
 }
 
 // ---- conv3x3(upsample2x(a)): weight gradient w.r.t. the up-sampled operand at low resolution

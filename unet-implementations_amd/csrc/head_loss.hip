@@ -289,19 +289,63 @@ __device__ __forceinline__ void softmax3(float z0, float z1, float z2, float& p0
   lse = m + logf(s);
 }
 
-__global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restrict__ logits,
-                                                          const long long* __restrict__ target,
-                                                          float* __restrict__ partial, int HW,
-                                                          int ignore_index) {
+// Labels of V consecutive pixels.  TT = long long: the int64 target as stored.  TT = unsigned
+// char: the dataset's raw uint8 mask, cleaned on load with its rule v > 2 && v != 255 -> 0
+// (Our_UNet/src/train.py:300; the identity on a cleaned mask) - V = 4 pixels are ONE 4-byte load.
+template <int V>
+__device__ __forceinline__ void load_targets(const long long* tg, long long (&t)[V]) {
+#pragma unroll
+  for (int j = 0; j < V; ++j) t[j] = tg[j];
+}
+template <int V>
+__device__ __forceinline__ void load_targets(const unsigned char* tg, long long (&t)[V]) {
+  static_assert(V == 1 || V == 4, "one byte or one 32-bit word");
+  unsigned w;
+  if constexpr (V == 4) w = *reinterpret_cast<const unsigned*>(tg);
+  else w = tg[0];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    const unsigned v = (w >> (8 * j)) & 0xffu;
+    t[j] = (v > 2u && v != 255u) ? 0 : (long long)v;
+    // the label's small range is hidden from the optimiser: knowing it, hipcc compares in 16 bits
+    // and then fuses other multiply-adds in the gradient kernel than in the int64 instantiation
+    // (one-ulp differences in dlogits); behind this the two instantiations are the same code
+    asm("" : "+v"(t[j]));
+  }
+}
+template <typename TT>
+__device__ __forceinline__ long long load_target(const TT* tg) {
+  long long t[1];
+  load_targets<1>(tg, t);
+  return t[0];
+}
+// V consecutive floats as one load (V = 4: 16 bytes, the address 16-byte aligned)
+template <int V>
+__device__ __forceinline__ void ldv(const float* p, float (&v)[V]) {
+  if constexpr (V == 4) {
+    const f32x4 q = *reinterpret_cast<const f32x4*>(p);
+    v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+  } else {
+    v[0] = p[0];
+  }
+}
+// One pixel per lane for either target type: the per-lane fp32 sums and their merge order are
+// what the loss value is made of, so the uint8 form keeps the int64 form's pixel-to-lane map (and
+// with it the same bits); the label is 1 of the 13 bytes a pixel costs here.
+template <typename TT>
+__device__ __forceinline__ void loss_reduce_body(const float* __restrict__ logits,
+                                                 const TT* __restrict__ target,
+                                                 float* __restrict__ partial, int HW,
+                                                 int ignore_index) {
   __shared__ float red[4][LQ];
   const int n = blockIdx.y;
   const float* z = logits + (size_t)n * 3 * HW;
-  const long long* tg = target + (size_t)n * HW;
+  const TT* tg = target + (size_t)n * HW;
   float q[LQ];
 #pragma unroll
   for (int i = 0; i < LQ; ++i) q[i] = 0.f;
   for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
-    const long long t = tg[p];
+    const long long t = load_target(tg + p);
     const bool valid = (t != (long long)ignore_index);
     float p0, p1, p2, lse;
     const float z0 = z[p], z1 = z[HW + p], z2 = z[2 * HW + p];
@@ -326,6 +370,20 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restric
     partial[((size_t)n * gridDim.x + blockIdx.x) * LQ + i] =
         (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
   }
+}
+
+// (the two instantiations as kernels of their own: the int64 one keeps its name)
+__global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restrict__ logits,
+                                                          const long long* __restrict__ target,
+                                                          float* __restrict__ partial, int HW,
+                                                          int ignore_index) {
+  loss_reduce_body(logits, target, partial, HW, ignore_index);
+}
+__global__ __launch_bounds__(256) void loss_reduce_u8_kernel(const float* __restrict__ logits,
+                                                             const unsigned char* __restrict__ target,
+                                                             float* __restrict__ partial, int HW,
+                                                             int ignore_index) {
+  loss_reduce_body(logits, target, partial, HW, ignore_index);
 }
 
 // Sum of one column over the slabs, in slab order, in double: 32 loads in flight, then their adds
@@ -489,20 +547,24 @@ __global__ void loss_shard_apply_kernel(const double* __restrict__ sums, int N,
   coef->wdice = w_dice * grad_scale;
 }
 
-__global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict__ logits,
-                                                        const long long* __restrict__ target,
-                                                        const LossCoef* __restrict__ coef,
-                                                        const float* __restrict__ dice_ab,
-                                                        float* __restrict__ dlogits, int HW,
-                                                        int ignore_index,
-                                                        const float* __restrict__ upstream) {
+// One pixel per lane for either target type as well: equal bits with the int64 form are the
+// contract of the uint8 twins, and a four-pixel form of this arithmetic is other code (the
+// compiler fuses other multiply-adds: one-ulp differences in dlogits).
+template <typename TT>
+__device__ __forceinline__ void loss_grad_body(const float* __restrict__ logits,
+                                               const TT* __restrict__ target,
+                                               const LossCoef* __restrict__ coef,
+                                               const float* __restrict__ dice_ab,
+                                               float* __restrict__ dlogits, int HW,
+                                               int ignore_index,
+                                               const float* __restrict__ upstream) {
   const int n = blockIdx.y;
   const float* z = logits + (size_t)n * 3 * HW;
   float* dz = dlogits + (size_t)n * 3 * HW;
   // dL/d(loss) handed down by autograd (a device scalar; 1 for loss.backward()): applied to the
   // finished gradient, i.e. the same rounding as a separate `dlogits *= g` pass
   const float up = upstream ? upstream[0] : 1.f;
-  const long long* tg = target + (size_t)n * HW;
+  const TT* tg = target + (size_t)n * HW;
   const float w0 = coef->w[0], w1 = coef->w[1], w2 = coef->w[2];
   const float iw = coef->inv_wsum, wd = coef->wdice;
   float A[3], B[3];
@@ -512,7 +574,7 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict_
     B[c] = dice_ab[(n * 3 + c) * 2 + 1];
   }
   for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
-    const long long t = tg[p];
+    const long long t = load_target(tg + p);
     float g0 = 0.f, g1 = 0.f, g2 = 0.f;
     if (t != (long long)ignore_index) {
       float p0, p1, p2, lse;
@@ -536,39 +598,78 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict_
   }
 }
 
+__global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict__ logits,
+                                                        const long long* __restrict__ target,
+                                                        const LossCoef* __restrict__ coef,
+                                                        const float* __restrict__ dice_ab,
+                                                        float* __restrict__ dlogits, int HW,
+                                                        int ignore_index,
+                                                        const float* __restrict__ upstream) {
+  loss_grad_body(logits, target, coef, dice_ab, dlogits, HW, ignore_index, upstream);
+}
+__global__ __launch_bounds__(256) void loss_grad_u8_kernel(const float* __restrict__ logits,
+                                                           const unsigned char* __restrict__ target,
+                                                           const LossCoef* __restrict__ coef,
+                                                           const float* __restrict__ dice_ab,
+                                                           float* __restrict__ dlogits, int HW,
+                                                           int ignore_index,
+                                                           const float* __restrict__ upstream) {
+  loss_grad_body(logits, target, coef, dice_ab, dlogits, HW, ignore_index, upstream);
+}
+
 // ------------------------------------------------------------------ validation metrics
 // argmax over the 3 class planes (lowest index wins ties, like torch.argmax) and, per class,
 // the exact integer counts the reference's validate() turns into Dice scores
 // (Our_UNet/src/train.py:556-577): counts[c] = {intersection, predicted, labelled}, pixels
 // labelled ignore_index excluded.
+// V pixels per lane (comparisons and integer counts: any pixel-to-lane map gives the same result).
+// V = 4 (uint8 targets, HW % 4 == 0, aligned tensors): one 4-byte label load, 16-byte logit loads
+// and the four predictions as one 32-bit word; V = 1: any shape.
+template <typename TT, int V>
 __global__ __launch_bounds__(256) void argmax_counts_kernel(const float* __restrict__ logits,
-                                                            const long long* __restrict__ target,
+                                                            const TT* __restrict__ target,
                                                             unsigned char* __restrict__ preds,
                                                             unsigned long long* __restrict__ counts,
                                                             int HW, int ignore_index) {
   __shared__ unsigned int red[4][9];
   const int n = blockIdx.y;
   const float* z = logits + (size_t)n * 3 * HW;
-  const long long* tg = target + (size_t)n * HW;
+  const TT* tg = target + (size_t)n * HW;
   unsigned int q[9];
 #pragma unroll
   for (int i = 0; i < 9; ++i) q[i] = 0;
-  for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
-    const float z0 = z[p], z1 = z[HW + p], z2 = z[2 * HW + p];
-    int am = 0;
-    float best = z0;
-    if (z1 > best) { best = z1; am = 1; }
-    if (z2 > best) { best = z2; am = 2; }
-    if (preds) preds[(size_t)n * HW + p] = (unsigned char)am;
-    if (!target) continue;           // prediction only (inference)
-    const long long t = tg[p];
-    if (t != (long long)ignore_index) {
+  for (int p = (blockIdx.x * 256 + threadIdx.x) * V; p < HW; p += gridDim.x * 256 * V) {
+    float zv[3][V];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const unsigned int pc = (am == c), mc = (t == c);
-        q[c * 3 + 0] += pc & mc;
-        q[c * 3 + 1] += pc;
-        q[c * 3 + 2] += mc;
+    for (int c = 0; c < 3; ++c) ldv<V>(z + (size_t)c * HW + p, zv[c]);
+    int am[V];
+    unsigned packed = 0;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      am[j] = 0;
+      float best = zv[0][j];
+      if (zv[1][j] > best) { best = zv[1][j]; am[j] = 1; }
+      if (zv[2][j] > best) { best = zv[2][j]; am[j] = 2; }
+      packed |= (unsigned)am[j] << (8 * j);
+    }
+    if (preds) {
+      if constexpr (V == 4) *reinterpret_cast<unsigned*>(preds + (size_t)n * HW + p) = packed;
+      else preds[(size_t)n * HW + p] = (unsigned char)am[0];
+    }
+    if (!target) continue;           // prediction only (inference)
+    long long tv[V];
+    load_targets<V>(tg + p, tv);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const long long t = tv[j];
+      if (t != (long long)ignore_index) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const unsigned int pc = (am[j] == c), mc = (t == c);
+          q[c * 3 + 0] += pc & mc;
+          q[c * 3 + 1] += pc;
+          q[c * 3 + 2] += mc;
+        }
       }
     }
   }
@@ -767,100 +868,142 @@ extern "C" size_t unet_dice_wce_loss_workspace_bytes(int N, int H, int W) {
   return loss_ws_layout(N, nullptr, nullptr);
 }
 
-extern "C" int unet_dice_wce_loss_fwd_bwd(const float* logits, const int64_t* target,
-                                          float* loss_out, float* dlogits, void* workspace,
-                                          size_t workspace_bytes, int N, int H, int W,
-                                          float smooth, float w_dice, float w_ce, int ignore_index,
-                                          int dynamic_weights, const float* class_weights,
-                                          float grad_scale, unet_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  UNET_REQUIRE(logits && target && loss_out && workspace, "dice_wce_loss: null pointer");
-  UNET_REQUIRE(N > 0 && N <= 1024 && H > 0 && W > 0, "dice_wce_loss: bad shape");
-  if (workspace_bytes < loss_ws_layout(N, nullptr, nullptr)) {
-    unet_set_error("dice_wce_loss: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
-  LossWs ws;
-  loss_ws_layout(N, &ws, reinterpret_cast<char*>(workspace));
-  const int HW = H * W;
-  int blocks = ceil_div(HW, 256 * 8);
-  if (blocks > LOSS_BLOCKS) blocks = LOSS_BLOCKS;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(loss_reduce_kernel, dim3(blocks, N), dim3(256), 0, stream, logits,
-                     reinterpret_cast<const long long*>(target), ws.partial, HW, ignore_index);
-  UNET_CHECK_LAUNCH("loss_reduce");
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), (size_t)N * LQ * sizeof(double),
-                     stream, ws.partial, N, blocks, smooth, w_dice, w_ce, dynamic_weights,
-                     class_weights, grad_scale, loss_out, ws.coef, ws.dice_ab);
-  UNET_CHECK_LAUNCH("loss_finalize");
-  if (dlogits) {
-    int gblocks = ceil_div(HW, 256 * 4);
-    if (gblocks < 1) gblocks = 1;
-    hipLaunchKernelGGL(loss_grad_kernel, dim3(gblocks, N), dim3(256), 0, stream, logits,
-                       reinterpret_cast<const long long*>(target), ws.coef, ws.dice_ab, dlogits, HW,
-                       ignore_index, nullptr);
-    UNET_CHECK_LAUNCH("loss_grad");
-  }
-  return UNET_OK;
-}
-
-extern "C" int unet_dice_wce_loss_grad(const float* logits, const int64_t* target,
-                                       const void* workspace, size_t workspace_bytes,
-                                       const float* upstream, float* dlogits, int N, int H, int W,
-                                       int ignore_index, unet_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  UNET_REQUIRE(logits && target && workspace && dlogits, "dice_wce_loss_grad: null pointer");
-  UNET_REQUIRE(N > 0 && N <= 1024 && H > 0 && W > 0, "dice_wce_loss_grad: bad shape");
-  if (workspace_bytes < loss_ws_layout(N, nullptr, nullptr)) {
-    unet_set_error("dice_wce_loss_grad: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
-  LossWs ws;
-  loss_ws_layout(N, &ws, reinterpret_cast<char*>(const_cast<void*>(workspace)));
-  const int HW = H * W;
-  int gblocks = ceil_div(HW, 256 * 4);
-  if (gblocks < 1) gblocks = 1;
-  hipLaunchKernelGGL(loss_grad_kernel, dim3(gblocks, N), dim3(256), 0, stream, logits,
-                     reinterpret_cast<const long long*>(target), ws.coef, ws.dice_ab, dlogits, HW,
-                     ignore_index, upstream);
-  UNET_CHECK_LAUNCH("loss_grad");
-  return UNET_OK;
-}
-
-extern "C" int unet_argmax_dice_counts(const float* logits_nchw, const int64_t* target,
-                                       uint8_t* preds, uint64_t* counts, int N, int H, int W,
-                                       int ignore_index, unet_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  UNET_REQUIRE(logits_nchw && ((target && counts) || (!target && preds)),
-               "argmax_dice_counts: needs target + counts, or preds alone");
-  UNET_REQUIRE(N > 0 && H > 0 && W > 0, "argmax_dice_counts: bad shape");
-  const int HW = H * W;
-  if (counts) UNET_HIP_CALL(hipMemsetAsync(counts, 0, 9 * sizeof(uint64_t), stream));
-  int blocks = ceil_div(HW, 256 * 4);
-  if (blocks > 256) blocks = 256;
-  hipLaunchKernelGGL(argmax_counts_kernel, dim3(blocks, N), dim3(256), 0, stream, logits_nchw,
-                     reinterpret_cast<const long long*>(target), preds,
-                     reinterpret_cast<unsigned long long*>(counts), HW, ignore_index);
-  UNET_CHECK_LAUNCH("argmax_counts");
-  return UNET_OK;
-}
-
 namespace {
 int loss_blocks_for(int HW) {
   int blocks = ceil_div(HW, 256 * 8);
   if (blocks > LOSS_BLOCKS) blocks = LOSS_BLOCKS;
   return blocks < 1 ? 1 : blocks;
 }
-}  // namespace
 
-extern "C" int unet_dice_wce_loss_shard_stats(const float* logits, const int64_t* target,
-                                              double* stats, void* workspace,
-                                              size_t workspace_bytes, int N, int H, int W,
-                                              float smooth, int ignore_index,
-                                              unet_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+// Target types of the loss / metric entry points: int64 labels, or (the `_u8` twins) the
+// dataset's uint8 mask.  A uint8 label cannot equal an ignore_index outside 0..255, and one in
+// 0..2 would ignore a class: both are refused before anything is launched.
+template <typename TT>
+int check_ignore_index(const char* name, int ignore_index) {
+  if constexpr (sizeof(TT) == 1)
+    UNET_REQUIRE(ignore_index >= 3 && ignore_index <= 255,
+                 "%s: a uint8 target needs ignore_index in 3..255 (got %d)", name, ignore_index);
+  return UNET_OK;
+}
+
+// four pixels per lane: uint8 targets on images of whole 4-pixel groups, every tensor aligned for
+// its 4- / 16-byte accesses (fresh allocations are; a view at an odd offset is not)
+template <typename TT>
+bool four_pixel_lanes(int HW, const void* f32_a, const void* f32_b, const void* u8_a,
+                      const void* u8_b) {
+  if (sizeof(TT) != 1 || HW % 4) return false;
+  return (reinterpret_cast<uintptr_t>(f32_a) | reinterpret_cast<uintptr_t>(f32_b)) % 16 == 0 &&
+         (reinterpret_cast<uintptr_t>(u8_a) | reinterpret_cast<uintptr_t>(u8_b)) % 4 == 0;
+}
+
+template <typename TT>
+int launch_loss_reduce(const float* logits, const TT* target, float* partial, int N, int HW,
+                       int blocks, int ignore_index, hipStream_t stream) {
+  if constexpr (sizeof(TT) == 1)
+    hipLaunchKernelGGL(loss_reduce_u8_kernel, dim3(blocks, N), dim3(256), 0, stream, logits,
+                       target, partial, HW, ignore_index);
+  else
+    hipLaunchKernelGGL(loss_reduce_kernel, dim3(blocks, N), dim3(256), 0, stream, logits, target,
+                       partial, HW, ignore_index);
+  UNET_CHECK_LAUNCH("loss_reduce");
+  return UNET_OK;
+}
+
+template <typename TT>
+int launch_loss_grad(const float* logits, const TT* target, const LossWs& ws, float* dlogits,
+                     int N, int HW, int ignore_index, const float* upstream, hipStream_t stream) {
+  int gblocks = ceil_div(HW, 256 * 4);
+  if (gblocks < 1) gblocks = 1;
+  if constexpr (sizeof(TT) == 1)
+    hipLaunchKernelGGL(loss_grad_u8_kernel, dim3(gblocks, N), dim3(256), 0, stream, logits, target,
+                       ws.coef, ws.dice_ab, dlogits, HW, ignore_index, upstream);
+  else
+    hipLaunchKernelGGL(loss_grad_kernel, dim3(gblocks, N), dim3(256), 0, stream, logits, target,
+                       ws.coef, ws.dice_ab, dlogits, HW, ignore_index, upstream);
+  UNET_CHECK_LAUNCH("loss_grad");
+  return UNET_OK;
+}
+
+template <typename TT>
+int loss_fwd_bwd_impl(const float* logits, const TT* target, float* loss_out, float* dlogits,
+                      void* workspace, size_t workspace_bytes, int N, int H, int W, float smooth,
+                      float w_dice, float w_ce, int ignore_index, int dynamic_weights,
+                      const float* class_weights, float grad_scale, hipStream_t stream) {
+  UNET_REQUIRE(logits && target && loss_out && workspace, "dice_wce_loss: null pointer");
+  UNET_REQUIRE(N > 0 && N <= 1024 && H > 0 && W > 0, "dice_wce_loss: bad shape");
+  int rc = check_ignore_index<TT>("dice_wce_loss", ignore_index);
+  if (rc != UNET_OK) return rc;
+  if (workspace_bytes < loss_ws_layout(N, nullptr, nullptr)) {
+    unet_set_error("dice_wce_loss: workspace too small");
+    return UNET_E_WORKSPACE;
+  }
+  LossWs ws;
+  loss_ws_layout(N, &ws, reinterpret_cast<char*>(workspace));
+  const int HW = H * W, blocks = loss_blocks_for(HW);
+  rc = launch_loss_reduce(logits, target, ws.partial, N, HW, blocks, ignore_index, stream);
+  if (rc != UNET_OK) return rc;
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), (size_t)N * LQ * sizeof(double),
+                     stream, ws.partial, N, blocks, smooth, w_dice, w_ce, dynamic_weights,
+                     class_weights, grad_scale, loss_out, ws.coef, ws.dice_ab);
+  UNET_CHECK_LAUNCH("loss_finalize");
+  if (dlogits)
+    return launch_loss_grad(logits, target, ws, dlogits, N, HW, ignore_index, nullptr, stream);
+  return UNET_OK;
+}
+
+template <typename TT>
+int loss_grad_impl(const float* logits, const TT* target, const void* workspace,
+                   size_t workspace_bytes, const float* upstream, float* dlogits, int N, int H,
+                   int W, int ignore_index, hipStream_t stream) {
+  UNET_REQUIRE(logits && target && workspace && dlogits, "dice_wce_loss_grad: null pointer");
+  UNET_REQUIRE(N > 0 && N <= 1024 && H > 0 && W > 0, "dice_wce_loss_grad: bad shape");
+  const int rc = check_ignore_index<TT>("dice_wce_loss_grad", ignore_index);
+  if (rc != UNET_OK) return rc;
+  if (workspace_bytes < loss_ws_layout(N, nullptr, nullptr)) {
+    unet_set_error("dice_wce_loss_grad: workspace too small");
+    return UNET_E_WORKSPACE;
+  }
+  LossWs ws;
+  loss_ws_layout(N, &ws, reinterpret_cast<char*>(const_cast<void*>(workspace)));
+  return launch_loss_grad(logits, target, ws, dlogits, N, H * W, ignore_index, upstream, stream);
+}
+
+template <typename TT>
+int argmax_counts_impl(const float* logits_nchw, const TT* target, uint8_t* preds,
+                       uint64_t* counts, int N, int H, int W, int ignore_index,
+                       hipStream_t stream) {
+  UNET_REQUIRE(logits_nchw && ((target && counts) || (!target && preds)),
+               "argmax_dice_counts: needs target + counts, or preds alone");
+  UNET_REQUIRE(N > 0 && H > 0 && W > 0, "argmax_dice_counts: bad shape");
+  const int rc = check_ignore_index<TT>("argmax_dice_counts", ignore_index);
+  if (rc != UNET_OK) return rc;
+  const int HW = H * W;
+  if (counts) UNET_HIP_CALL(hipMemsetAsync(counts, 0, 9 * sizeof(uint64_t), stream));
+  int blocks = ceil_div(HW, 256 * 4);
+  if (blocks > 256) blocks = 256;
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
+  bool v4 = false;
+  if constexpr (sizeof(TT) == 1) {
+    v4 = four_pixel_lanes<TT>(HW, logits_nchw, nullptr, target, preds);
+    if (v4)
+      hipLaunchKernelGGL((argmax_counts_kernel<TT, 4>), dim3(blocks, N), dim3(256), 0, stream,
+                         logits_nchw, target, preds, cnt, HW, ignore_index);
+  }
+  if (!v4)
+    hipLaunchKernelGGL((argmax_counts_kernel<TT, 1>), dim3(blocks, N), dim3(256), 0, stream,
+                       logits_nchw, target, preds, cnt, HW, ignore_index);
+  UNET_CHECK_LAUNCH("argmax_counts");
+  return UNET_OK;
+}
+
+template <typename TT>
+int loss_shard_stats_impl(const float* logits, const TT* target, double* stats, void* workspace,
+                          size_t workspace_bytes, int N, int H, int W, float smooth,
+                          int ignore_index, hipStream_t stream) {
   UNET_REQUIRE(logits && target && stats && workspace, "loss_shard_stats: null pointer");
   UNET_REQUIRE(N > 0 && N <= 1024 && H > 0 && W > 0, "loss_shard_stats: bad shape");
+  int rc = check_ignore_index<TT>("loss_shard_stats", ignore_index);
+  if (rc != UNET_OK) return rc;
   if (workspace_bytes < loss_ws_layout(N, nullptr, nullptr)) {
     unet_set_error("loss_shard_stats: workspace too small");
     return UNET_E_WORKSPACE;
@@ -868,46 +1011,128 @@ extern "C" int unet_dice_wce_loss_shard_stats(const float* logits, const int64_t
   LossWs ws;
   loss_ws_layout(N, &ws, reinterpret_cast<char*>(workspace));
   const int HW = H * W, blocks = loss_blocks_for(HW);
-  hipLaunchKernelGGL(loss_reduce_kernel, dim3(blocks, N), dim3(256), 0, stream, logits,
-                     reinterpret_cast<const long long*>(target), ws.partial, HW, ignore_index);
-  UNET_CHECK_LAUNCH("loss_reduce");
+  rc = launch_loss_reduce(logits, target, ws.partial, N, HW, blocks, ignore_index, stream);
+  if (rc != UNET_OK) return rc;
   hipLaunchKernelGGL(loss_shard_stats_kernel, dim3(1), dim3(256), 0, stream, ws.partial, N, blocks,
                      smooth, ws.sums, stats);
   UNET_CHECK_LAUNCH("loss_shard_stats");
   return UNET_OK;
 }
 
-extern "C" int unet_dice_wce_loss_shard_apply(const float* logits, const int64_t* target,
-                                              const double* global_stats, int N_global,
-                                              float* loss_out, float* dlogits, void* workspace,
-                                              size_t workspace_bytes, int N, int H, int W,
-                                              float smooth, float w_dice, float w_ce,
-                                              int ignore_index, int dynamic_weights,
-                                              const float* class_weights, float grad_scale,
-                                              unet_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+template <typename TT>
+int loss_shard_apply_impl(const float* logits, const TT* target, const double* global_stats,
+                          int N_global, float* loss_out, float* dlogits, void* workspace,
+                          size_t workspace_bytes, int N, int H, int W, float smooth, float w_dice,
+                          float w_ce, int ignore_index, int dynamic_weights,
+                          const float* class_weights, float grad_scale, hipStream_t stream) {
   UNET_REQUIRE(logits && target && global_stats && loss_out && workspace,
                "loss_shard_apply: null pointer");
   UNET_REQUIRE(N > 0 && N <= 1024 && N_global >= N && H > 0 && W > 0,
                "loss_shard_apply: bad shape");
+  const int rc = check_ignore_index<TT>("loss_shard_apply", ignore_index);
+  if (rc != UNET_OK) return rc;
   if (workspace_bytes < loss_ws_layout(N, nullptr, nullptr)) {
     unet_set_error("loss_shard_apply: workspace too small");
     return UNET_E_WORKSPACE;
   }
   LossWs ws;
   loss_ws_layout(N, &ws, reinterpret_cast<char*>(workspace));
-  const int HW = H * W;
   hipLaunchKernelGGL(loss_shard_apply_kernel, dim3(1), dim3(256), 0, stream, ws.sums, N,
                      global_stats, N_global, smooth, w_dice, w_ce, dynamic_weights, class_weights,
                      grad_scale, loss_out, ws.coef, ws.dice_ab);
   UNET_CHECK_LAUNCH("loss_shard_apply");
-  if (dlogits) {
-    int gblocks = ceil_div(HW, 256 * 4);
-    if (gblocks < 1) gblocks = 1;
-    hipLaunchKernelGGL(loss_grad_kernel, dim3(gblocks, N), dim3(256), 0, stream, logits,
-                       reinterpret_cast<const long long*>(target), ws.coef, ws.dice_ab, dlogits, HW,
-                       ignore_index, nullptr);
-    UNET_CHECK_LAUNCH("loss_grad");
-  }
+  if (dlogits)
+    return launch_loss_grad(logits, target, ws, dlogits, N, H * W, ignore_index, nullptr, stream);
   return UNET_OK;
 }
+
+inline const long long* i64(const int64_t* t) { return reinterpret_cast<const long long*>(t); }
+}  // namespace
+
+// The int64-target entry points and their uint8-target twins (`_u8`: the dataset's raw mask,
+// cleaned on load) - one implementation each, instantiated on the target type.
+#define UNET_LOSS_FWD_BWD_ARGS                                                                    \
+  float *loss_out, float *dlogits, void *workspace, size_t workspace_bytes, int N, int H, int W,  \
+      float smooth, float w_dice, float w_ce, int ignore_index, int dynamic_weights,              \
+      const float *class_weights, float grad_scale, unet_stream_t stream
+
+extern "C" int unet_dice_wce_loss_fwd_bwd(const float* logits, const int64_t* target,
+                                          UNET_LOSS_FWD_BWD_ARGS) {
+  return loss_fwd_bwd_impl(logits, i64(target), loss_out, dlogits, workspace, workspace_bytes, N, H,
+                           W, smooth, w_dice, w_ce, ignore_index, dynamic_weights, class_weights,
+                           grad_scale, (hipStream_t)stream);
+}
+extern "C" int unet_dice_wce_loss_fwd_bwd_u8(const float* logits, const uint8_t* target,
+                                             UNET_LOSS_FWD_BWD_ARGS) {
+  return loss_fwd_bwd_impl(logits, target, loss_out, dlogits, workspace, workspace_bytes, N, H, W,
+                           smooth, w_dice, w_ce, ignore_index, dynamic_weights, class_weights,
+                           grad_scale, (hipStream_t)stream);
+}
+#undef UNET_LOSS_FWD_BWD_ARGS
+
+extern "C" int unet_dice_wce_loss_grad(const float* logits, const int64_t* target,
+                                       const void* workspace, size_t workspace_bytes,
+                                       const float* upstream, float* dlogits, int N, int H, int W,
+                                       int ignore_index, unet_stream_t stream) {
+  return loss_grad_impl(logits, i64(target), workspace, workspace_bytes, upstream, dlogits, N, H, W,
+                        ignore_index, (hipStream_t)stream);
+}
+extern "C" int unet_dice_wce_loss_grad_u8(const float* logits, const uint8_t* target,
+                                          const void* workspace, size_t workspace_bytes,
+                                          const float* upstream, float* dlogits, int N, int H,
+                                          int W, int ignore_index, unet_stream_t stream) {
+  return loss_grad_impl(logits, target, workspace, workspace_bytes, upstream, dlogits, N, H, W,
+                        ignore_index, (hipStream_t)stream);
+}
+
+extern "C" int unet_argmax_dice_counts(const float* logits_nchw, const int64_t* target,
+                                       uint8_t* preds, uint64_t* counts, int N, int H, int W,
+                                       int ignore_index, unet_stream_t stream) {
+  return argmax_counts_impl(logits_nchw, i64(target), preds, counts, N, H, W, ignore_index,
+                            (hipStream_t)stream);
+}
+extern "C" int unet_argmax_dice_counts_u8(const float* logits_nchw, const uint8_t* target,
+                                          uint8_t* preds, uint64_t* counts, int N, int H, int W,
+                                          int ignore_index, unet_stream_t stream) {
+  return argmax_counts_impl(logits_nchw, target, preds, counts, N, H, W, ignore_index,
+                            (hipStream_t)stream);
+}
+
+extern "C" int unet_dice_wce_loss_shard_stats(const float* logits, const int64_t* target,
+                                              double* stats, void* workspace,
+                                              size_t workspace_bytes, int N, int H, int W,
+                                              float smooth, int ignore_index,
+                                              unet_stream_t stream) {
+  return loss_shard_stats_impl(logits, i64(target), stats, workspace, workspace_bytes, N, H, W,
+                               smooth, ignore_index, (hipStream_t)stream);
+}
+extern "C" int unet_dice_wce_loss_shard_stats_u8(const float* logits, const uint8_t* target,
+                                                 double* stats, void* workspace,
+                                                 size_t workspace_bytes, int N, int H, int W,
+                                                 float smooth, int ignore_index,
+                                                 unet_stream_t stream) {
+  return loss_shard_stats_impl(logits, target, stats, workspace, workspace_bytes, N, H, W, smooth,
+                               ignore_index, (hipStream_t)stream);
+}
+
+#define UNET_LOSS_SHARD_APPLY_ARGS                                                               \
+  const double *global_stats, int N_global, float *loss_out, float *dlogits, void *workspace,    \
+      size_t workspace_bytes, int N, int H, int W, float smooth, float w_dice, float w_ce,       \
+      int ignore_index, int dynamic_weights, const float *class_weights, float grad_scale,       \
+      unet_stream_t stream
+
+extern "C" int unet_dice_wce_loss_shard_apply(const float* logits, const int64_t* target,
+                                              UNET_LOSS_SHARD_APPLY_ARGS) {
+  return loss_shard_apply_impl(logits, i64(target), global_stats, N_global, loss_out, dlogits,
+                               workspace, workspace_bytes, N, H, W, smooth, w_dice, w_ce,
+                               ignore_index, dynamic_weights, class_weights, grad_scale,
+                               (hipStream_t)stream);
+}
+extern "C" int unet_dice_wce_loss_shard_apply_u8(const float* logits, const uint8_t* target,
+                                                 UNET_LOSS_SHARD_APPLY_ARGS) {
+  return loss_shard_apply_impl(logits, target, global_stats, N_global, loss_out, dlogits,
+                               workspace, workspace_bytes, N, H, W, smooth, w_dice, w_ce,
+                               ignore_index, dynamic_weights, class_weights, grad_scale,
+                               (hipStream_t)stream);
+}
+#undef UNET_LOSS_SHARD_APPLY_ARGS

@@ -2,7 +2,8 @@
 
 Dice + cross-entropy with per-batch inverse-frequency class weights and
 ignore_index handling.  `forward(logits[N,3,H,W] fp32, target[N,H,W] int64)`
-returns a 0-dim fp32 tensor supporting `.backward()` / `.item()`.  One fused
+returns a 0-dim fp32 tensor supporting `.backward()` / `.item()`; with
+`target_layout="u8"` the target is the dataset's uint8 mask itself.  One fused
 kernel sequence computes the loss AND dL/dlogits in the forward call; autograd's
 backward only scales that stored gradient.
 """
@@ -50,8 +51,14 @@ class _LossFunction(torch.autograd.Function):
 
 class SimpleLoss(nn.Module):
     def __init__(self, weight_dice=1.0, weight_ce=1.0, ignore_index=255, smooth=1e-5,
-                 class_weights=None, dynamic_weights=True, batch_sync="local", process_group=None):
-        """`batch_sync="global"` (data parallel only; not in the reference, which is
+                 class_weights=None, dynamic_weights=True, batch_sync="local", process_group=None,
+                 target_layout="int64"):
+        """`target_layout="u8"`: the target is the dataset's uint8 [N,H,W] mask on the device,
+        handed to the kernels untouched (1 byte a pixel instead of 8; a raw mask is cleaned on
+        load with the dataset's rule v > 2 and v != 255 -> 0).  The loss, `last_terms` and the
+        gradient equal those of the default layout on the cleaned mask bit for bit.
+
+        `batch_sync="global"` (data parallel only; not in the reference, which is
         single-process): every rank evaluates the loss of the CONCATENATED batch - class weights,
         CE denominator and the Dice batch mean taken over all ranks' images (equal per-rank batch
         sizes) - so that N ranks x batch b reproduce one process at batch N*b.  Gradients must
@@ -59,6 +66,9 @@ class SimpleLoss(nn.Module):
         super().__init__()
         if batch_sync not in ("local", "global"):
             raise ValueError("batch_sync must be 'local' or 'global'")
+        if target_layout not in ("int64", "u8"):
+            raise ValueError("target_layout must be 'int64' or 'u8'")
+        self.target_layout = target_layout
         self.batch_sync = batch_sync
         self.process_group = process_group
         self.weight_dice = weight_dice
@@ -85,7 +95,10 @@ class SimpleLoss(nn.Module):
         if input.shape[-2:] != target.shape[-2:]:
             # the reference resizes the logits to the target (Our_UNet/models/losses.py:66-68)
             input = ops.resize_bilinear(input, target.shape[-2:])
-        if target.dtype != torch.int64:
+        if self.target_layout == "u8":
+            if target.dtype != torch.uint8 or not target.is_cuda or not target.is_contiguous():
+                raise TypeError("target_layout='u8' takes a contiguous uint8 device tensor")
+        elif target.dtype != torch.int64:
             target = target.long()
         cw = None
         dynamic = bool(self.dynamic_weights) and target.size(0) > 0

@@ -661,7 +661,8 @@ class Act:
 class U8Image:
     """The dataset's uint8 HWC batch [N, H, W, 3] as the operand of the RGB stem: normalised
     ((v / 255) - mean) / std inside the loaders of the first convolution and of its weight
-    gradient (unet_stem_u8_fwd / _bwd_weight), never materialised as fp32."""
+    gradient (unet_stem_u8_fwd / _bwd_weight and their `_b16` twins for bf16 layer tensors), never
+    materialised as fp32."""
 
     __slots__ = ("x", "mean", "std")
 
@@ -729,13 +730,22 @@ def _conv_stats_finalize(b16, y, st, ws, px, gamma, beta, eps, mask):
 
 
 @functools.lru_cache(maxsize=None)
+def _sel_conv_in_bwd_weight(u8, b16, x3):
+    """-> entry point of a fused layer's weight gradient: the normalising RGB stem (U8Image) or a
+    layer source, for fp32 / bf16 dy; x3: the split-bf16 operand mode (fp32 tensors)"""
+    if u8:
+        return _twin("unet_stem_u8_bwd_weight", b16)
+    return _export("unet_conv_in_bwd_weight" + ("_b16" if b16 else ("_bf16x3" if x3 else "")))
+
+
+@functools.lru_cache(maxsize=None)
 def _sel_conv_in_fwd(b16, u8, wino, has_w3, ksize, C0):
     """-> (entry point, form: "u8" (normalising RGB stem) / "wino" (takes wu, no ksize / stride) /
     "planes" (takes w3) / "plain", timer tag)"""
     tag = "conv_stem_fwd" if C0 == 3 else \
         "conv_igemm" + _SUFFIX[1 if b16 else (3 if has_w3 else 0)]
     if u8:
-        return _export("unet_stem_u8_fwd"), "u8", tag
+        return _twin("unet_stem_u8_fwd", b16), "u8", tag
     if wino:    # Winograd F(2x2, 3x3) form (the caller checked conv_wino_supported)
         return _export("unet_conv_in_fwd_wino"), "wino", tag
     # planes on bf16 tensors: the weights also pre-rounded to bf16 (plane 0 of the planes)
@@ -749,8 +759,8 @@ def conv_in_fwd(s0, s1, slope, w, bias, ksize, stride, gamma, beta, eps, mask, b
     """Fused layer forward: y = conv(cat(act(s0), act(s1))) + bias and the InstanceNorm
     statistics of y.  Returns (y, st) with st = [mean, rstd, alpha, beta] as [4, N, Cout];
     alpha / beta carry the dropout `mask` [N, Cout] (or None) folded in.
-    b16: the mixed-precision pipeline - y (and the sources other than the fp32 RGB image) are
-    bf16 tensors, bf16 matrix cores, fp32 statistics.
+    b16: the mixed-precision pipeline - y (and the sources other than the RGB image, fp32 or a
+    U8Image) are bf16 tensors, bf16 matrix cores, fp32 statistics.
     w3 (pre-split weight planes): the split-bf16 operand mode on fp32 tensors."""
     u8 = s0 if isinstance(s0, U8Image) else None
     if u8 is None:
@@ -766,8 +776,6 @@ def conv_in_fwd(s0, s1, slope, w, bias, ksize, stride, gamma, beta, eps, mask, b
         for src in (s0, s1):
             if src is not None and src.shape[3] != 3 and not _is_b16(src.x):
                 raise TypeError("the bf16 pipeline takes bf16 layer tensors")
-        if u8 is not None:
-            raise NotImplementedError("uint8 stem on the bf16 pipeline")
     wino = wu is not None and not b16 and ksize == 3 and stride == 1
     fn, form, tag = _sel_conv_in_fwd(b16, u8 is not None, wino, w3 is not None, ksize, C0)
     if form == "u8":
@@ -835,7 +843,7 @@ def conv_up_in_fwd(low, skip, slope, wf, bias, gamma, beta, eps, mask, wu=None, 
 def conv_in_bwd_weight(x, slope, dy, dw_oihw, ci_offset, ksize, stride, x3=False):
     """Weight gradient of a fused layer: dw[:, ci_offset : ci_offset + Cx] = act(x) (x) dy.
     x3: the split-bf16 operand mode (fp32 tensors).  x a U8Image: the whole weight gradient of
-    the normalising RGB stem (3x3, stride 1)."""
+    the normalising RGB stem (3x3, stride 1), for an fp32 or a bf16 dy."""
     u8 = isinstance(x, U8Image)
     if not u8:
         x, rx = _act(x)
@@ -843,13 +851,12 @@ def conv_in_bwd_weight(x, slope, dy, dw_oihw, ci_offset, ksize, stride, x3=False
     Cout = dy.shape[3]
     b16 = _is_b16(dy)
     sfx = "_bf16" if b16 else ("_bf16x3" if x3 else "")     # of the timer tag
+    fn = _sel_conv_in_bwd_weight(u8, b16, bool(x3))
     if u8:
         ksize, stride = 3, 1
-        fn, head = lib().unet_stem_u8_bwd_weight, \
-            (_ptr(x.x), *x.c_mean_std(), _ptr(dy), _ptr(dw_oihw))
+        head = (_ptr(x.x), *x.c_mean_std(), _ptr(dy), _ptr(dw_oihw))
     else:
         assert dw_oihw.shape[0] == Cout and dw_oihw.is_contiguous()
-        fn = _export("unet_conv_in_bwd_weight" + ("_b16" if b16 else sfx))
         head = (rx, slope, _ptr(dy), _ptr(dw_oihw), ci_offset, dw_oihw.shape[1], ksize, stride)
     ws = _wgrad_ws(lib().unet_conv3x3_bwd_weight_workspace_bytes(N, H, W, Cx, Cout, stride), dy)
     t0 = _begin("wgrad")
@@ -1013,10 +1020,20 @@ def head1x1_bwd(a, dlogits, w, dw, db):
     return da
 
 
+def _target_twin(name, target):
+    """The export `name` for an int64 target, its `_u8` twin for the dataset's uint8 mask."""
+    if target.dtype == torch.uint8:
+        return _export(name + "_u8")
+    if target.dtype != torch.int64:
+        raise TypeError(f"{name}: the target is int64 or uint8 (got {target.dtype})")
+    return _export(name)
+
+
 def dice_wce_loss_fwd_bwd(logits, target, smooth, w_dice, w_ce, ignore_index, dynamic_weights,
                           class_weights=None, grad_scale=1.0, want_grad=True, ws=None):
     """ws: a caller-kept workspace (dice_wce_loss_workspace) - needed when the gradient is taken
-    later with dice_wce_loss_grad (want_grad=False here)."""
+    later with dice_wce_loss_grad (want_grad=False here).  target: int64 labels, or (here and in
+    the four functions below) the dataset's uint8 mask as it is - raw or cleaned, 1 byte a pixel."""
     N, K, H, W = logits.shape
     if K != 3:
         raise ValueError("the fused loss kernel handles exactly 3 classes")
@@ -1024,10 +1041,10 @@ def dice_wce_loss_fwd_bwd(logits, target, smooth, w_dice, w_ce, ignore_index, dy
     dl = torch.empty_like(logits) if want_grad else None
     if ws is None:
         ws = _ws(lib().unet_dice_wce_loss_workspace_bytes(N, H, W), logits)
-    check(lib().unet_dice_wce_loss_fwd_bwd(_ptr(logits), _ptr(target), _ptr(out), _ptr(dl),
-                                           _ptr(ws), ws.numel(), N, H, W, smooth, w_dice, w_ce,
-                                           ignore_index, 1 if dynamic_weights else 0,
-                                           _ptr(class_weights), grad_scale, _stream()))
+    check(_target_twin("unet_dice_wce_loss_fwd_bwd", target)(
+        _ptr(logits), _ptr(target), _ptr(out), _ptr(dl), _ptr(ws), ws.numel(), N, H, W, smooth,
+        w_dice, w_ce, ignore_index, 1 if dynamic_weights else 0, _ptr(class_weights), grad_scale,
+        _stream()))
     return out, dl
 
 
@@ -1044,9 +1061,9 @@ def dice_wce_loss_grad(logits, target, ws, upstream, ignore_index):
     dl = torch.empty_like(logits)
     if upstream is not None:
         upstream = upstream.reshape(1).float().contiguous()
-    check(lib().unet_dice_wce_loss_grad(_ptr(logits), _ptr(target), _ptr(ws), ws.numel(),
-                                        _ptr(upstream), _ptr(dl), N, H, W, ignore_index,
-                                        _stream()))
+    check(_target_twin("unet_dice_wce_loss_grad", target)(
+        _ptr(logits), _ptr(target), _ptr(ws), ws.numel(), _ptr(upstream), _ptr(dl), N, H, W,
+        ignore_index, _stream()))
     return dl
 
 
@@ -1057,9 +1074,9 @@ def dice_wce_loss_shard_stats(logits, target, smooth, ignore_index):
         raise ValueError("the fused loss kernel handles exactly 3 classes")
     stats = torch.empty((10,), dtype=torch.float64, device=logits.device)
     ws = _ws(lib().unet_dice_wce_loss_workspace_bytes(N, H, W), logits)
-    check(lib().unet_dice_wce_loss_shard_stats(_ptr(logits), _ptr(target), stats.data_ptr(),
-                                               _ptr(ws), ws.numel(), N, H, W, smooth, ignore_index,
-                                               _stream()))
+    check(_target_twin("unet_dice_wce_loss_shard_stats", target)(
+        _ptr(logits), _ptr(target), stats.data_ptr(), _ptr(ws), ws.numel(), N, H, W, smooth,
+        ignore_index, _stream()))
     return stats, ws
 
 
@@ -1070,7 +1087,7 @@ def dice_wce_loss_shard_apply(logits, target, global_stats, n_global, ws, smooth
     N, K, H, W = logits.shape
     out = _f32((8,), logits)
     dl = torch.empty_like(logits) if want_grad else None
-    check(lib().unet_dice_wce_loss_shard_apply(
+    check(_target_twin("unet_dice_wce_loss_shard_apply", target)(
         _ptr(logits), _ptr(target), global_stats.data_ptr(), int(n_global), _ptr(out), _ptr(dl),
         _ptr(ws), ws.numel(), N, H, W, smooth, w_dice, w_ce, ignore_index,
         1 if dynamic_weights else 0, _ptr(class_weights), grad_scale, _stream()))
@@ -1080,17 +1097,19 @@ def dice_wce_loss_shard_apply(logits, target, global_stats, n_global, ws, smooth
 # ---- validation metrics / input pipeline ---------------------------------------------------
 def argmax_dice_counts(logits, target, ignore_index=255, want_preds=True):
     """Returns (preds uint8 [N,H,W] or None, counts int64 [3,3] = per class
-    {intersection, predicted, labelled}); everything stays on the device."""
+    {intersection, predicted, labelled}); everything stays on the device.  target: int64 labels
+    or the dataset's uint8 mask."""
     N, K, H, W = logits.shape
     if K != 3:
         raise ValueError("3 classes expected")
     logits, target = logits.contiguous(), target.contiguous()
-    if logits.dtype != torch.float32 or target.dtype != torch.int64:
-        raise TypeError("argmax_dice_counts takes fp32 logits and int64 targets")
+    if logits.dtype != torch.float32 or target.dtype not in (torch.int64, torch.uint8):
+        raise TypeError("argmax_dice_counts takes fp32 logits and int64 (or uint8) targets")
     preds = torch.empty((N, H, W), dtype=torch.uint8, device=logits.device) if want_preds else None
     counts = torch.empty((3, 3), dtype=torch.int64, device=logits.device)
-    check(lib().unet_argmax_dice_counts(_ptr(logits), _ptr(target), _ptr(preds), counts.data_ptr(),
-                                        N, H, W, ignore_index, _stream()))
+    check(_target_twin("unet_argmax_dice_counts", target)(
+        _ptr(logits), _ptr(target), _ptr(preds), counts.data_ptr(), N, H, W, ignore_index,
+        _stream()))
     return preds, counts
 
 

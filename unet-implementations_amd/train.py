@@ -45,14 +45,18 @@ def get_loss_function():
     return SimpleLoss(weight_dice=1.0, weight_ce=1.0, ignore_index=255, dynamic_weights=True)
 
 
-def train_step(model, optimizer, loss_function, images, masks, grad_sync=None):
+def train_step(model, optimizer, loss_function, images, masks, grad_sync=None,
+               input_layout=None):
     """One optimisation step; returns the loss as a 0-dim device tensor (no host sync).
 
     `grad_sync` (optional) is called between backward and the optimizer step; the
     data-parallel wrapper passes its gradient all-reduce finaliser here.
+    `input_layout` (optional) is handed to the model's forward: with "nhwc_u8" and a
+    `SimpleLoss(target_layout="u8")` the step consumes the dataset's uint8 image and mask
+    batches as they are.
     """
     optimizer.zero_grad()
-    outputs = model(images)
+    outputs = model(images) if input_layout is None else model(images, input_layout=input_layout)
     loss = loss_function(outputs, masks)
     loss.backward()
     if grad_sync is not None:
@@ -73,6 +77,10 @@ class GraphedTrainStep:
         step = GraphedTrainStep(model, optimizer, loss_function, images, masks)
         loss = step(images, masks)        # device scalar, no host sync
 
+    `input_layout` is handed to the model's forward as in `train_step`.  The static buffers keep
+    the dtype of the batches given here (uint8 for "nhwc_u8" images and a "u8" loss: a step then
+    copies a twelfth and an eighth of the bytes), and `__call__` takes batches of that dtype.
+
     Data parallel: pass the model's `ddp.GradBucketAllReduce` as `grad_sync`.  Its bucketed
     all-reduces are issued from the backward hooks while the step is being captured, so with
     backend "nccl" (RCCL) they become nodes of the graph on RCCL's stream - forked from the
@@ -85,7 +93,8 @@ class GraphedTrainStep:
     checkpoint - and the step counter are restored afterwards.
     """
 
-    def __init__(self, model, optimizer, loss_function, images, masks, warmup=2, grad_sync=None):
+    def __init__(self, model, optimizer, loss_function, images, masks, warmup=2, grad_sync=None,
+                 input_layout=None):
         if not images.is_cuda:
             raise RuntimeError("GraphedTrainStep needs ROCm tensors (no CPU fallback exists)")
         if not isinstance(optimizer, (FusedSGD, FusedAdam)):
@@ -103,6 +112,7 @@ class GraphedTrainStep:
             finish = grad_sync.finish
         self.model, self.optimizer, self.loss_function = model, optimizer, loss_function
         self.grad_sync = grad_sync
+        self.input_layout = input_layout
         self.images = images.detach().clone()
         self.masks = masks.detach().clone()
         arena, _ = model.flat_parameters()
@@ -117,7 +127,7 @@ class GraphedTrainStep:
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
                 train_step(model, optimizer, loss_function, self.images, self.masks,
-                           grad_sync=finish)
+                           grad_sync=finish, input_layout=input_layout)
         cur.wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         # With a process group alive, its watchdog thread polls the events of earlier collectives
@@ -129,7 +139,7 @@ class GraphedTrainStep:
             torch.cuda.synchronize()      # the warm-up collectives have completed
         with torch.cuda.graph(self.graph, capture_error_mode=mode):
             self.loss = train_step(model, optimizer, loss_function, self.images, self.masks,
-                                   grad_sync=finish)
+                                   grad_sync=finish, input_layout=input_layout)
         # undo the throw-away steps (the captured step itself did not execute)
         with torch.no_grad():
             arena.copy_(keep_arena)
@@ -139,6 +149,10 @@ class GraphedTrainStep:
         if images.shape != self.images.shape or masks.shape != self.masks.shape:
             raise ValueError("GraphedTrainStep was captured for batches of shape "
                              f"{tuple(self.images.shape)} / {tuple(self.masks.shape)}")
+        if images.dtype != self.images.dtype or masks.dtype != self.masks.dtype:
+            # (copy_ would convert silently: a float image into a uint8 buffer is garbage)
+            raise ValueError("GraphedTrainStep was captured for batches of dtype "
+                             f"{self.images.dtype} / {self.masks.dtype}")
         if images.data_ptr() != self.images.data_ptr():
             self.images.copy_(images, non_blocking=True)
         if masks.data_ptr() != self.masks.data_ptr():
@@ -150,11 +164,13 @@ class GraphedTrainStep:
 
 
 @torch.no_grad()
-def validate(model, val_loader, loss_function, device, ignore_label=255):
+def validate(model, val_loader, loss_function, device, ignore_label=255, input_layout=None):
     """Counterpart of validate() (Our_UNet/src/train.py:510-589): eval-mode forward, loss, and
     per-batch Dice of the argmax predictions for background / cat / dog, averaged over batches.
     argmax and the nine integer counts come from one kernel and the per-batch Dice arithmetic
-    stays on the device, so the loop has no host sync (the reference syncs 4 times per batch)."""
+    stays on the device, so the loop has no host sync (the reference syncs 4 times per batch).
+    `input_layout` is handed to the model's forward as in `train_step`; with a loss of
+    `target_layout="u8"` the counts kernel reads the uint8 masks as well."""
     model.eval()
     val_loss = torch.zeros((), device=device)
     dice_sum = torch.zeros(3, device=device, dtype=torch.float64)
@@ -162,8 +178,12 @@ def validate(model, val_loader, loss_function, device, ignore_label=255):
     for batch in val_loader:
         images = batch["image"].to(device, non_blocking=True)
         masks = batch["mask"].to(device, non_blocking=True)
-        outputs = model(images)
+        outputs = model(images) if input_layout is None else \
+            model(images, input_layout=input_layout)
         val_loss += loss_function(outputs, masks).detach()
+        if getattr(loss_function, "target_layout", "int64") != "u8" and \
+                masks.dtype != torch.int64:
+            masks = masks.long()
         _, counts = ops.argmax_dice_counts(outputs, masks, ignore_label, want_preds=False)
         inter = counts[:, 0].double()
         union = (counts[:, 1] + counts[:, 2]).double()

@@ -521,14 +521,15 @@ class UNet(nn.Module):
         """`input_layout="nhwc"` takes the fp32 [N,H,W,3] tensor of `ops.preprocess_u8` directly;
         `"nhwc_u8"` takes the dataset's uint8 [N,H,W,3] batch itself: its normalisation
         ((v / 255) - input_mean) / input_std (Our_UNet/src/train.py:303-308) then runs inside the
-        loaders of the first convolution (fused pipeline, W % 128 == 0; other cases go through
-        `ops.preprocess_u8`)."""
+        loaders of the first convolution and of its weight gradient, in every `matmul_precision`
+        (fused pipeline, W % 128 == 0; other cases go through `ops.preprocess_u8`)."""
         u8 = None
         if input_layout == "nhwc_u8":
             if x.dtype != torch.uint8:
                 raise TypeError("input_layout='nhwc_u8' takes a uint8 [N,H,W,3] tensor")
-            fusable = self.matmul_precision == "fp32" and self.fused_pipeline and \
-                x.is_cuda and x.dim() == 4 and x.shape[2] % 128 == 0
+            # (bottleneck features in the bf16 mode run the stand-alone passes: _Walk.fused)
+            fusable = self.fused_pipeline and x.is_cuda and x.dim() == 4 and \
+                x.shape[2] % 128 == 0 and not (self.matmul_precision == "bf16" and extra is not None)
             if fusable:
                 u8 = ops.U8Image(x.contiguous(), self.input_mean, self.input_std)
             else:
@@ -925,8 +926,8 @@ class _UNetFunction(torch.autograd.Function):
         fusion = model._fusion_layer if extra is not None else None
         walk = _Walk(model, x, fusion, any(ctx.needs_input_grad))
         fused = walk.fused
-        if isinstance(x, ops.U8Image) and (not fused or walk.b16):
-            raise RuntimeError("the uint8 stem needs the fused fp32 pipeline")
+        if isinstance(x, ops.U8Image) and not fused:
+            raise RuntimeError("the uint8 stem needs the fused pipeline")
         run = walk.run_layer_fused if fused else walk.run_layer
         # (the image is a plain operand of the fused pipeline)
         cur = ops.Act(x) if fused and not isinstance(x, ops.U8Image) else x
