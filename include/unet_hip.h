@@ -490,6 +490,26 @@ int unet_stem_u8_bwd_weight_b16(const uint8_t* image_hwc, const float* mean3, co
                                 size_t workspace_bytes, int N, int H, int W, int Cout,
                                 unet_stream_t stream);
 
+/* Weight gradient of the RGB stem with the stem layer's InstanceNorm + LeakyReLU + dropout
+ * backward formed in its loader (fp32 tensors, W % 128 == 0).  g = dL/da of the stem layer, y its
+ * raw output, `partial` the per-tile reductions (S1, S2) the producer of g left (`tiles` per
+ * image, as unet_instnorm_lrelu_drop_bwd_partials takes them).  No gradient is taken with
+ * respect to the image, so the layer's dL/dz has this one consumer and is never stored: the
+ * summaries are merged, then the loader reads g and y and forms dz itself.  dw_oihw has the bits
+ * of unet_instnorm_lrelu_drop_bwd_partials followed by unet_conv_in_bwd_weight /
+ * unet_stem_u8_bwd_weight; dgamma / dbeta / dbias (each nullable) receive the layer's parameter
+ * gradients.  x: the fp32 image [N][H][W][3], or NULL with the uint8 image and its mean3 / std3
+ * (HOST pointers). */
+size_t unet_stem_in_bwd_weight_fold_workspace_bytes(int N, int H, int W, int Cout);
+int unet_stem_in_bwd_weight_fold(const float* x, const uint8_t* image_hwc, const float* mean3,
+                                 const float* std3, const float* g, const float* y,
+                                 const float* mean, const float* rstd, const float* gamma,
+                                 const float* beta, const float* mask, float slope,
+                                 const void* partial, int tiles, float* dw_oihw, float* dgamma,
+                                 float* dbeta, float* dbias, void* workspace,
+                                 size_t workspace_bytes, int N, int H, int W, int Cout,
+                                 unet_stream_t stream);
+
 /* Weight gradient with the activation applied to the input operand on load:
  * dw_oihw[Cout][Cin_total][k][k] (columns ci_offset .. +x->C) = sum_pixels act(x) (x) dy.
  * Same workspace query as unet_conv3x3_bwd_weight.  ksize 1 keeps the centre tap. */
@@ -644,6 +664,17 @@ int unet_conv_up_in_fwd_wino(const unet_act_src* low, const unet_act_src* skip, 
 int unet_conv3x3_bwd_data_bs_wino(const float* dy, const float* ud, int Cin_total, int ci_offset,
                                   float* dx, int N, int H, int W, int Cout, int Ccols,
                                   unet_bwd_stats* bs, unet_stream_t stream);
+
+/* Merge of the per-tile reductions of the InstanceNorm + LeakyReLU + dropout backward:
+ * partial[(n * tiles + t) * C + c] = (S1, S2) of tile t of image n (float pairs, as a data
+ * gradient's unet_bwd_stats epilogue leaves them) ->
+ * sums[n * C + c] = (S1, S2) and coef[n * C + c] = (S1, S2) / HW, float pairs.  The tiles are
+ * summed in double in a fixed order (deterministic), one rounding at the end.  This is the first
+ * step of unet_instnorm_lrelu_drop_bwd_partials and of the calls that form dz on the way to
+ * another result (unet_head1x1_in_bwd_fold, unet_stem_in_bwd_weight_fold). */
+int unet_instnorm_bwd_merge_partials(const void* partial, int tiles, void* coef, void* sums, int N,
+                                     int HW, int C, unet_stream_t stream);
+
 /* unet_instnorm_lrelu_drop_bwd with the reductions already summarised per tile
  * (partial[(n * tiles + t) * C + c] = (S1, S2)). */
 int unet_instnorm_lrelu_drop_bwd_partials(const float* ga, const float* y, const float* mean,
@@ -773,6 +804,21 @@ int unet_head1x1_in_bwd_bs_b16(const unet_act_src* x, float slope, const float* 
                                const float* w, uint16_t* da, float* dw, float* db,
                                void* workspace, size_t workspace_bytes, int N, int HW, int K,
                                unet_bwd_stats* bs, unet_stream_t stream);
+
+/* ... and with that layer's whole InstanceNorm + LeakyReLU + dropout backward (fp32 tensors):
+ * where unet_head1x1_in_bwd_bs would leave the reductions (bs->tiles_out > 0 on return), da is
+ * never stored.  A first launch leaves the reductions and dw / db, the summaries are merged, and
+ * a second launch of the head's kernel forms da again per lane and writes the layer's dL/dz to
+ * `dz` - the bits of unet_head1x1_in_bwd_bs followed by unet_instnorm_lrelu_drop_bwd_partials,
+ * without the two passes over da; dgamma / dbeta / dbias (each nullable) receive the layer's
+ * parameter gradients.  bs->tiles_out == 0: the call was unet_head1x1_in_bwd_bs, `dz` holds da
+ * and unet_instnorm_lrelu_drop_bwd is the caller's next step.  The workspace holds the dw / db
+ * slabs and the merged sums. */
+size_t unet_head1x1_in_bwd_fold_workspace_bytes(int N, int HW, int K);
+int unet_head1x1_in_bwd_fold(const unet_act_src* x, float slope, const float* dlogits_nchw,
+                             const float* w, float* dz, float* dw, float* db, float* dgamma,
+                             float* dbeta, float* dbias, void* workspace, size_t workspace_bytes,
+                             int N, int HW, int K, unet_bwd_stats* bs, unet_stream_t stream);
 
 /* ---- autoencoder pretraining step (recon.hip) ------------------------------------------------
  * The reference's phase 1 of transfer learning (AE_pretrained/README.md) on the same body as the

@@ -177,6 +177,14 @@ SIGNATURES = {
     "unet_head1x1_in_bwd": (_i, [_ps, _f, _p, _p, _p, _p, _p, _p, _sz, _i, _i, _i, _p]),
     "unet_head1x1_in_bwd_bs": (_i, [_ps, _f, _p, _p, _p, _p, _p, _p, _sz, _i, _i, _i, _pbs, _p]),
     "unet_head1x1_in_bwd_bs_b16": (_i, [_ps, _f, _p, _p, _p, _p, _p, _p, _sz, _i, _i, _i, _pbs, _p]),
+    "unet_stem_in_bwd_weight_fold_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "unet_stem_in_bwd_weight_fold": (_i, [_p, _p, _c.POINTER(_f), _c.POINTER(_f), _p, _p, _p, _p, _p,
+                                          _p, _p, _f, _p, _i, _p, _p, _p, _p, _p, _sz, _i, _i, _i,
+                                          _i, _p]),
+    "unet_instnorm_bwd_merge_partials": (_i, [_p, _i, _p, _p, _i, _i, _i, _p]),
+    "unet_head1x1_in_bwd_fold_workspace_bytes": (_sz, [_i, _i, _i]),
+    "unet_head1x1_in_bwd_fold": (_i, [_ps, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _i, _i, _i,
+                                      _pbs, _p]),
     "unet_recon3x3_fwd": (_i, [_ps, _i, _f, _p, _p, _p, _i, _i, _i, _i, _p]),
     "unet_recon3x3_bwd_workspace_bytes": (_sz, [_i, _i, _i]),
     "unet_recon3x3_bwd": (_i, [_ps, _i, _f, _p, _p, _p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _pbs,

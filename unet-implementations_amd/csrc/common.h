@@ -213,4 +213,69 @@ __device__ __forceinline__ void wf_merge(float& n, float& mean, float& m2, float
   n = nt;
 }
 
+// ---- InstanceNorm + LeakyReLU + dropout backward, per value ------------------------------------
+// dz = gamma rstd (gz - c1 - xhat c2),  gz = g mask (z > 0 ? 1 : slope),  for the four channels
+// 4j .. 4j+3 a lane holds.  in_bwd_apply_kernel (instnorm.hip) and the kernels that form dz on
+// the way to another result (head_bwd_kernel mode 1, the stem weight gradient's loader) all call
+// this, which is what makes them bit-identical.  Contraction is off and the roundings are
+// SPELLED OUT, per component: they are the ones the compiler's own contraction gave the apply
+// kernel (its packed instructions took components 0 and 1 fully fused, 2 half, 3 not at all),
+// kept so that every gradient keeps its bits.
+//   al = gamma * rstd,  be = in_bwd_shift(beta, mean, al): z = y al + be as in the forward.
+__device__ __forceinline__ f32x4 in_bwd_shift(const f32x4 beta, const f32x4 mean, const f32x4 al) {
+  f32x4 be;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) be[k] = __builtin_fmaf(-mean[k], al[k], beta[k]);
+  return be;
+}
+__device__ __forceinline__ f32x4 in_bwd_dz4(const f32x4 g, const f32x4 y, const f32x4 mean,
+                                            const f32x4 rstd, const f32x4 al, const f32x4 be,
+                                            const f32x4 mask, float slope, const f32x4 c1,
+                                            const f32x4 c2) {
+#pragma clang fp contract(off)
+  f32x4 o;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float xh = (y[k] - mean[k]) * rstd[k];
+    const float z = __builtin_fmaf(y[k], al[k], be[k]);
+    const float t = g[k] * mask[k], sel = z > 0.f ? 1.f : slope;
+    float in;
+    if (k < 2) in = __builtin_fmaf(-c2[k], xh, __builtin_fmaf(t, sel, -c1[k]));
+    else if (k == 2) in = __builtin_fmaf(t, sel, -c1[k]) - c2[k] * xh;
+    else in = (t * sel - c1[k]) - xh * c2[k];
+    o[k] = al[k] * in;
+  }
+  return o;
+}
+
+// Parameter gradients of an InstanceNorm layer from its per-image sums, by the `nthreads` threads
+// of ONE workgroup (N x C values to read):
+//   dgamma[c] = sum_n S2[n][c],  dbeta[c] = sum_n S1[n][c],
+//   dbias[c]  = sum over pixels of dz (the gradient of the conv bias in front of the norm)
+//             = sum_n gamma rstd (S1 - HW c1 - c2 sum(xhat)),  c1 = S1 / HW,  sum(xhat) = 0:
+// identically zero under InstanceNorm; the closed form leaves the one rounding of HW * c1
+// (the reference's autograd value is rounding noise of the same size, <= 2.4e-6 measured).
+__device__ __forceinline__ void in_bwd_param_grads(const float2* __restrict__ sums,
+                                                   const float2* __restrict__ coef,
+                                                   const float* __restrict__ gamma,
+                                                   const float* __restrict__ rstd, int N, int HW,
+                                                   int C, int tid, int nthreads,
+                                                   float* __restrict__ dgamma,
+                                                   float* __restrict__ dbeta,
+                                                   float* __restrict__ dbias) {
+#pragma clang fp contract(off)
+  for (int c = tid; c < C; c += nthreads) {
+    float dg = 0.f, db = 0.f, dbi = 0.f;
+    for (int q = 0; q < N; ++q) {
+      const float2 v = sums[(size_t)q * C + c];
+      db += v.x;
+      dg += v.y;
+      dbi += gamma[c] * rstd[(size_t)q * C + c] * (v.x - (float)HW * coef[(size_t)q * C + c].x);
+    }
+    if (dgamma) dgamma[c] = dg;
+    if (dbeta) dbeta[c] = db;
+    if (dbias) dbias[c] = dbi;
+  }
+}
+
 #endif  // __HIPCC__

@@ -1374,7 +1374,18 @@ __global__ __launch_bounds__(256) void conv_stem_wgrad_kernel(const float* __res
 constexpr int SWR_PITCH = 393;
 
 // T = unsigned char: the dataset's uint8 image, normalised on load (see unet_stem_u8_fwd)
-struct StemNormW { float mean[3], std[3]; };
+struct StemNormW {
+  float mean[3], std[3];
+  // y != nullptr (unet_stem_in_bwd_weight_fold, fp32 dy): the kernel's `dy` argument is g = dL/da
+  // of the stem layer, y its raw output, and the loader forms the layer's dL/dz from the two
+  // (in_bwd_dz4: the bits in_bwd_apply_kernel would have stored) on the way to LDS - that pass
+  // and its tensor do not exist.  coef = (c1, c2) and sums = (S1, S2) per image and channel;
+  // workgroup (0, 0) also writes the layer's parameter gradients.
+  const float* y; const float* mu; const float* rstd; const float* gamma; const float* beta;
+  const float* mask; const float2* coef; const float2* sums;
+  float* dgamma; float* dbeta; float* dbias;
+  float slope;
+};
 __device__ __forceinline__ float stem_px(const float* x, size_t i, int, const StemNormW&) {
   return x[i];
 }
@@ -1401,6 +1412,12 @@ __global__ __launch_bounds__(256) void conv_stem_wgrad_rows_kernel(
   const int a_off = (kk / 9) * SWR_PITCH + (kk % 9) + 3 * lh;
   const float a_on = li < 27 ? 1.f : 0.f;
 
+  bool fold = false;     // uniform
+  if constexpr (sizeof(TD) == 4) fold = nm.y != nullptr;
+  if (fold && blockIdx.x == 0 && blockIdx.y == 0)
+    in_bwd_param_grads(nm.sums, nm.coef, nm.gamma, nm.rstd, N, HW, Cout, tid, 256, nm.dgamma,
+                       nm.dbeta, nm.dbias);
+
   f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -1412,9 +1429,37 @@ __global__ __launch_bounds__(256) void conv_stem_wgrad_rows_kernel(
   constexpr int RV = (3 * 390 + 255) / 256;     // raw row words per thread
   float rreg[RV];
   f32x4 dreg[4];
+  // the fold: y beside g in registers; dz is formed when the registers go to LDS, so the loads
+  // stay in flight meanwhile.  The coefficient rows of the stage's image (this workgroup's 32
+  // channels) wait in LDS, rewritten by fetch() when the image changes: after the barrier that
+  // ends the previous stage's stage_lds() and before the one in front of this stage's.
+  f32x4 yreg[4];
+  __shared__ f32x4 Cf[7][8];     // mean, rstd, gamma rstd, shift, mask, c1, c2
+  int n_coef = -1;
   auto fetch = [&](long long st) __attribute__((always_inline)) {
     const long long m0 = st * SW_PIX;
     const int n = (int)(m0 / HW);
+    if (fold && n != n_coef) {     // uniform
+      if (tid < 8) {
+        const int c = co0 + tid * 4;
+        const size_t o = (size_t)n * Cout + c;
+        const f32x4 mu = *reinterpret_cast<const f32x4*>(nm.mu + o);
+        const f32x4 rs = *reinterpret_cast<const f32x4*>(nm.rstd + o);
+        const f32x4 al = *reinterpret_cast<const f32x4*>(nm.gamma + c) * rs;
+        f32x4 c1, c2;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float2 cf = nm.coef[o + k];
+          c1[k] = cf.x;
+          c2[k] = cf.y;
+        }
+        Cf[0][tid] = mu; Cf[1][tid] = rs; Cf[2][tid] = al;
+        Cf[3][tid] = in_bwd_shift(*reinterpret_cast<const f32x4*>(nm.beta + c), mu, al);
+        Cf[4][tid] = nm.mask ? *reinterpret_cast<const f32x4*>(nm.mask + o) : f32x4{1.f, 1.f, 1.f, 1.f};
+        Cf[5][tid] = c1; Cf[6][tid] = c2;
+      }
+      n_coef = n;
+    }
     const int rem = (int)(m0 - (long long)n * HW);
     const int yy = rem / W, x0 = rem - yy * W;
     // raw rows: word j of row ky = x[n][yy+ky-1][x0-1 + j/3][j%3], j < 3*130
@@ -1433,6 +1478,8 @@ __global__ __launch_bounds__(256) void conv_stem_wgrad_rows_kernel(
       const int i = tid + 256 * t;
       const int pix = i >> 3, seg = i & 7;
       dreg[t] = ld4(dy + (size_t)(m0 + pix) * Cout + co0 + seg * 4);
+      if constexpr (sizeof(TD) == 4)
+        if (fold) yreg[t] = ld4(nm.y + (size_t)(m0 + pix) * Cout + co0 + seg * 4);
     }
   };
   auto stage_lds = [&]() __attribute__((always_inline)) {
@@ -1445,11 +1492,16 @@ __global__ __launch_bounds__(256) void conv_stem_wgrad_rows_kernel(
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int i = tid + 256 * t;
-      *reinterpret_cast<f32x4*>(D + (i >> 3) * 32 + (i & 7) * 4) = dreg[t];
+      f32x4 d = dreg[t];
+      if (fold)
+        d = in_bwd_dz4(d, yreg[t], Cf[0][tid & 7], Cf[1][tid & 7], Cf[2][tid & 7], Cf[3][tid & 7],
+                       Cf[4][tid & 7], nm.slope, Cf[5][tid & 7], Cf[6][tid & 7]);
+      *reinterpret_cast<f32x4*>(D + (i >> 3) * 32 + (i & 7) * 4) = d;
     }
   };
   if (st_begin < st_end) {
     fetch(st_begin);
+    if (fold) __syncthreads();
     stage_lds();
   }
   __syncthreads();
@@ -2589,6 +2641,9 @@ struct WgradCall {
   const unsigned char* x_u8 = nullptr;
   const float* u8_mean_std = nullptr;
   const void* dy = nullptr;
+  // RGB stem only: dy is dL/da of the stem layer and the loader forms its dL/dz (the fold
+  // operands of StemNormW, taken from here)
+  const StemNormW* stem_fold = nullptr;
   // activation on load: a = lrelu(x * alpha[n][c] + beta[n][c], slope); alpha == nullptr: plain x
   const float* alpha = nullptr;
   const float* beta = nullptr;
@@ -2726,6 +2781,11 @@ int wgrad_launch_chunks(const WgradCall& c, const WgradSel& s, float* ws, int* n
 // stage never straddles image rows
 int launch_wgrad_stem(const WgradCall& c, const WgradPlan& pl, float* ws, hipStream_t stream) {
   StemNormW nm{};
+  if (c.stem_fold) {
+    UNET_REQUIRE(c.W % SW_PIX == 0 && !c.b16, "stem_in_bwd_weight_fold: needs W %% %d == 0 and an "
+                 "fp32 gradient", SW_PIX);
+    nm = *c.stem_fold;
+  }
   if (c.x_u8) {
     UNET_REQUIRE(c.W % SW_PIX == 0, "stem_u8_bwd_weight: needs W %% %d == 0", SW_PIX);
     for (int k = 0; k < 3; ++k) { nm.mean[k] = c.u8_mean_std[k]; nm.std[k] = c.u8_mean_std[3 + k]; }
@@ -3022,6 +3082,59 @@ extern "C" int unet_stem_u8_bwd_weight_b16(const uint8_t* image_hwc, const float
                "stem_u8_bwd_weight_b16: needs W %% %d == 0 (got W=%d)", SW_PIX, W);
   return stem_u8_bwd_weight_impl(image_hwc, mean3, std3, dy, true, dw_oihw, workspace,
                                  workspace_bytes, N, H, W, Cout, (hipStream_t)stream);
+}
+
+// Weight gradient of the RGB stem with the stem layer's InstanceNorm + LeakyReLU + dropout
+// backward formed in its loader (fp32 tensors, W % 128 == 0): g = dL/da of the layer, whose
+// per-tile reductions `partial` (`tiles` per image) its producer left.  The layer's dL/dz has no
+// other consumer - no gradient is taken with respect to the image - so it is never stored: the
+// summaries are merged, then the weight gradient's loader reads g and y and evaluates
+// in_bwd_dz4.  dw has the bits of unet_instnorm_lrelu_drop_bwd_partials followed by the plain
+// stem weight gradient.  x: the fp32 image, or NULL with the uint8 image and its mean3 / std3.
+extern "C" size_t unet_stem_in_bwd_weight_fold_workspace_bytes(int N, int H, int W, int Cout) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
+  return 2 * align_up((size_t)N * Cout * sizeof(float2), 256) +
+         unet_conv3x3_bwd_weight_workspace_bytes(N, H, W, 3, Cout, 1);
+}
+
+extern "C" int unet_stem_in_bwd_weight_fold(const float* x, const uint8_t* image_hwc,
+                                            const float* mean3, const float* std3, const float* g,
+                                            const float* y, const float* mean, const float* rstd,
+                                            const float* gamma, const float* beta,
+                                            const float* mask, float slope, const void* partial,
+                                            int tiles, float* dw_oihw, float* dgamma, float* dbeta,
+                                            float* dbias, void* workspace, size_t workspace_bytes,
+                                            int N, int H, int W, int Cout, unet_stream_t stream) {
+  UNET_REQUIRE((x != nullptr) != (image_hwc != nullptr) && (!image_hwc || (mean3 && std3)),
+               "stem_in_bwd_weight_fold: one image, fp32 or uint8 with mean3 / std3");
+  UNET_REQUIRE(g && y && mean && rstd && gamma && beta && partial && tiles > 0 && workspace,
+               "stem_in_bwd_weight_fold: null pointer");
+  UNET_REQUIRE(N > 0 && H > 0 && W > 0 && W % SW_PIX == 0 && Cout > 0 && Cout % 32 == 0,
+               "stem_in_bwd_weight_fold: needs W %% %d == 0 and Cout %% 32 == 0 (got W=%d Cout=%d)",
+               SW_PIX, W, Cout);
+  const size_t coef_b = align_up((size_t)N * Cout * sizeof(float2), 256);
+  if (workspace_bytes < 2 * coef_b) {
+    unet_set_error("stem_in_bwd_weight_fold: workspace too small");
+    return UNET_E_WORKSPACE;
+  }
+  char* ws = reinterpret_cast<char*>(workspace);
+  StemNormW f{};
+  f.y = y; f.mu = mean; f.rstd = rstd; f.gamma = gamma; f.beta = beta; f.mask = mask;
+  f.coef = reinterpret_cast<const float2*>(ws);
+  f.sums = reinterpret_cast<const float2*>(ws + coef_b);
+  f.dgamma = dgamma; f.dbeta = dbeta; f.dbias = dbias; f.slope = slope;
+  const int rc = unet_instnorm_bwd_merge_partials(partial, tiles, ws, ws + coef_b, N, H * W, Cout,
+                                                  stream);
+  if (rc != UNET_OK) return rc;
+  const float ms[6] = {image_hwc ? mean3[0] : 0.f, image_hwc ? mean3[1] : 0.f,
+                       image_hwc ? mean3[2] : 0.f, image_hwc ? std3[0] : 1.f,
+                       image_hwc ? std3[1] : 1.f, image_hwc ? std3[2] : 1.f};
+  WgradCall c;
+  c.x = x; c.x_u8 = image_hwc; c.u8_mean_std = ms; c.dy = g; c.stem_fold = &f;
+  c.dw = dw_oihw; c.Cin_total = 3;
+  c.workspace = ws + 2 * coef_b; c.workspace_bytes = workspace_bytes - 2 * coef_b;
+  c.N = N; c.H = H; c.W = W; c.Cx = 3; c.Cout = Cout;
+  return conv_bwd_weight_impl(c, (hipStream_t)stream);
 }
 
 // ---- conv3x3(upsample2x(a)): weight gradient w.r.t. the up-sampled operand at low resolution

@@ -103,7 +103,75 @@ struct HeadBs {
   const float* mean; const float* rstd; const float* gamma; const float* beta; const float* mask;
   float2* partial;          // nullptr: no reductions
   int tiles_per_block;
+  // apply != 0 (second launch of unet_head1x1_in_bwd_fold, fp32 tensors): da is not a result.
+  // The launch forms it again per lane, applies that layer's InstanceNorm + LeakyReLU + dropout
+  // backward with coef = (c1, c2) per image and channel and writes dz where da would go;
+  // workgroup 0 also writes the layer's parameter gradients from `sums` (N images).
+  int apply;
+  const float2* coef; const float2* sums;
+  float* dgamma; float* dbeta; float* dbias;
+  int N;
 };
+
+// The apply launch: same tiles per workgroup, same loads and the same multiply-add order for da
+// as the launch below; nothing is reduced.  Every tile is whole (the launcher checks M % HB == 0)
+// and a workgroup's tiles lie in one image.
+__device__ __forceinline__ void head_bwd_apply_body(const float* __restrict__ a,
+                                                    const float* __restrict__ dl,
+                                                    const float* __restrict__ w,
+                                                    float* __restrict__ dz, int HW, int K,
+                                                    long long tiles, float slope,
+                                                    const HeadBs& bs) {
+  const int tid = threadIdx.x;
+  const int seg = tid & 7, grp = tid >> 3;
+  if (blockIdx.x == 0)
+    in_bwd_param_grads(bs.sums, bs.coef, bs.gamma, bs.rstd, bs.N, HW, 32, tid, 256, bs.dgamma,
+                       bs.dbeta, bs.dbias);
+  f32x4 wk[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    wk[k] = k < K ? *reinterpret_cast<const f32x4*>(w + k * 32 + seg * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+  const long long t_first = (long long)blockIdx.x * bs.tiles_per_block;
+  const long long t_last = min(t_first + bs.tiles_per_block, tiles);
+  const long long n = t_first * HB / HW;
+  const size_t o = (size_t)n * 32 + seg * 4;
+  const f32x4 mu = *reinterpret_cast<const f32x4*>(bs.mean + o);
+  const f32x4 rs = *reinterpret_cast<const f32x4*>(bs.rstd + o);
+  const f32x4 al = *reinterpret_cast<const f32x4*>(bs.gamma + seg * 4) * rs;
+  const f32x4 be = in_bwd_shift(*reinterpret_cast<const f32x4*>(bs.beta + seg * 4), mu, al);
+  const f32x4 mk = bs.mask ? *reinterpret_cast<const f32x4*>(bs.mask + o) : f32x4{1.f, 1.f, 1.f, 1.f};
+  f32x4 c1, c2;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float2 cf = bs.coef[o + k];
+    c1[k] = cf.x;
+    c2[k] = cf.y;
+  }
+  for (long long t = t_first; t < t_last; ++t) {
+    const long long m0 = t * HB;
+    f32x4 yv[HB / 32];
+    float dv[HB / 32][4];
+#pragma unroll
+    for (int it = 0; it < HB / 32; ++it) {
+      const long long m = m0 + it * 32 + grp, pp = m - n * HW;
+      yv[it] = ld4(a + (size_t)m * 32 + seg * 4);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) dv[it][k] = k < K ? dl[((size_t)n * K + k) * HW + pp] : 0.f;
+    }
+#pragma unroll
+    for (int it = 0; it < HB / 32; ++it) {
+      const long long m = m0 + it * 32 + grp;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < K) {
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) v[jj] = fmaf(dv[it][k], wk[k][jj], v[jj]);
+        }
+      st4(dz + (size_t)m * 32 + seg * 4, in_bwd_dz4(v, yv[it], mu, rs, al, be, mk, slope, c1, c2));
+    }
+  }
+}
 // partial[block][K*32 + K]: dw then db
 #ifndef UNET_HEAD_BWD_OCC
 #define UNET_HEAD_BWD_OCC 1
@@ -123,6 +191,11 @@ __global__ __launch_bounds__(256, UNET_HEAD_BWD_OCC) void head_bwd_kernel(const 
   // lane keeps its own dw[k][4 channels] partial sums over the pixels it sees, merged per block
   // through LDS in fixed order.
   __shared__ float red[32][4 * 32 + 4];
+  if constexpr (sizeof(TS) == 4)
+    if (bs.apply) {   // uniform
+      head_bwd_apply_body(a, dl, w, da, HW, K, tiles, slope, bs);
+      return;
+    }
   const int tid = threadIdx.x;
   const int seg = tid & 7, grp = tid >> 3;
   f32x4 wk[4], dwacc[4];
@@ -199,7 +272,7 @@ __global__ __launch_bounds__(256, UNET_HEAD_BWD_OCC) void head_bwd_kernel(const 
           }
           dbacc[k] += dv[it][k];
         }
-      if (m < M) st4(da + (size_t)m * 32 + seg * 4, v);
+      if (da && m < M) st4(da + (size_t)m * 32 + seg * 4, v);   // (no da: the fold's first launch)
       if (with_bs) {   // uniform (rows past M carry dv = 0, so v = 0 and gz = 0)
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
@@ -754,17 +827,41 @@ extern "C" int unet_head1x1_in_fwd_b16(const unet_act_src* x, float slope, const
   return UNET_OK;
 }
 
+// Reductions of the InstanceNorm backward of the layer in front (bs): a workgroup then takes a
+// contiguous range of tiles, which must lie in one image and divide it evenly - one summary
+// "tile" of tiles_per_block * HB pixels per workgroup.  -> summaries per image, with *hb filled
+// in; 0 (*hb untouched): this shape or these operands have no such form.
+static int head_bs_plan(const float* a, const float* alpha, long long M, int HW,
+                        const unet_bwd_stats* bs, HeadBs* hb) {
+  if (!(alpha && bs->y == a && bs->mean && bs->rstd && bs->gamma && bs->beta && bs->partial &&
+        M % HB == 0))
+    return 0;
+  const long long tiles = M / HB;
+  const int blocks = head_bwd_blocks(tiles);
+  const long long tpb = ceil_div64(tiles, blocks);
+  const long long px = tpb * HB;
+  if (!(tiles % tpb == 0 && tiles / tpb == blocks && HW % px == 0 &&
+        bs->partial_bytes >= (size_t)blocks * 32 * sizeof(float2)))
+    return 0;
+  hb->mean = bs->mean; hb->rstd = bs->rstd; hb->gamma = bs->gamma; hb->beta = bs->beta;
+  hb->mask = bs->mask; hb->partial = reinterpret_cast<float2*>(bs->partial);
+  hb->tiles_per_block = (int)tpb;
+  return (int)(HW / px);
+}
+
 extern "C" size_t unet_head1x1_bwd_workspace_bytes(int N, int HW, int C, int K) {
   if (N <= 0 || HW <= 0) return 0;
   const long long tiles = ceil_div64((long long)N * HW, HB);
   return (size_t)head_bwd_blocks(tiles) * (K * 32 + K) * sizeof(float);
 }
 
+// operands of unet_head1x1_in_bwd_fold beyond those of unet_head1x1_in_bwd_bs
+struct HeadFold { float2* coef; float2* sums; float* dgamma; float* dbeta; float* dbias; };
 static int head1x1_bwd_impl(const float* a, const float* dlogits, const float* w, float* da,
                             float* dw, float* db, void* workspace, size_t workspace_bytes, int N,
                             int HW, int C, int K, const float* alpha, const float* beta,
                             float slope, unet_stream_t stream, int b16 = 0,
-                            unet_bwd_stats* bs = nullptr);
+                            unet_bwd_stats* bs = nullptr, const HeadFold* fold = nullptr);
 
 extern "C" int unet_head1x1_bwd(const float* a, const float* dlogits, const float* w, float* da,
                                 float* dw, float* db, void* workspace, size_t workspace_bytes,
@@ -817,7 +914,8 @@ extern "C" int unet_head1x1_in_bwd_b16(const unet_act_src* x, float slope, const
 static int head1x1_bwd_impl(const float* a, const float* dlogits, const float* w, float* da,
                             float* dw, float* db, void* workspace, size_t workspace_bytes, int N,
                             int HW, int C, int K, const float* alpha, const float* beta,
-                            float slope, unet_stream_t stream, int b16, unet_bwd_stats* bs) {
+                            float slope, unet_stream_t stream, int b16, unet_bwd_stats* bs,
+                            const HeadFold* fold) {
   UNET_REQUIRE(a && dlogits && w && da && workspace, "head1x1_bwd: null pointer");
   UNET_REQUIRE(C == 32 && K >= 1 && K <= 4 && N > 0 && HW > 0,
                "head1x1_bwd: needs C == 32, K <= 4 (got C=%d K=%d)", C, K);
@@ -829,24 +927,15 @@ static int head1x1_bwd_impl(const float* a, const float* dlogits, const float* w
   const long long tiles = ceil_div64(M, HB);
   const int blocks = head_bwd_blocks(tiles);
   float* partial = reinterpret_cast<float*>(workspace);
-  // reductions of the InstanceNorm backward of the layer in front (bs): a workgroup then takes a
-  // contiguous range of tiles, which must lie in one image and divide it evenly - one summary
-  // "tile" of tiles_per_block * HB pixels per workgroup
   HeadBs hb{};
-  if (bs) bs->tiles_out = 0;
-  if (bs && alpha && bs->y == a && bs->mean && bs->rstd && bs->gamma && bs->beta && bs->partial &&
-      M % HB == 0) {
-    const long long tpb = ceil_div64(tiles, blocks);
-    const long long px = tpb * HB;
-    if (tiles % tpb == 0 && tiles / tpb == blocks && HW % px == 0 &&
-        bs->partial_bytes >= (size_t)blocks * 32 * sizeof(float2)) {
-      hb.mean = bs->mean; hb.rstd = bs->rstd; hb.gamma = bs->gamma; hb.beta = bs->beta;
-      hb.mask = bs->mask; hb.partial = reinterpret_cast<float2*>(bs->partial);
-      hb.tiles_per_block = (int)tpb;
-      bs->tiles_out = (int)(HW / px);
-      UNET_REQUIRE(bs->slope == slope, "head1x1_in_bwd_bs: bs->slope differs from slope");
-    }
+  if (bs) {
+    bs->tiles_out = head_bs_plan(a, alpha, M, HW, bs, &hb);
+    UNET_REQUIRE(bs->tiles_out == 0 || bs->slope == slope,
+                 "head1x1_in_bwd_bs: bs->slope differs from slope");
   }
+  // the fold: da is never stored - this launch leaves the reductions and the dw / db slabs only
+  const bool folded = fold && bs && bs->tiles_out > 0 && !b16;
+  float* da0 = folded ? nullptr : da;
   if (b16)
     hipLaunchKernelGGL(head_bwd_kernel<__bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const __bf16*>(a), dlogits, w,
@@ -854,13 +943,61 @@ static int head1x1_bwd_impl(const float* a, const float* dlogits, const float* w
                        hb);
   else
     hipLaunchKernelGGL(head_bwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a,
-                       dlogits, w, da, partial, M, HW, K, tiles, alpha, beta, slope, hb);
+                       dlogits, w, da0, partial, M, HW, K, tiles, alpha, beta, slope, hb);
   UNET_CHECK_LAUNCH("head_bwd");
-  if (!dw && !db) return UNET_OK;     // data gradient only (Grad-CAM): no parameter gradients
-  hipLaunchKernelGGL(head_bwd_finalize_kernel, dim3(K * 32 + K), dim3(256), 0, (hipStream_t)stream,
-                     partial, dw, db, blocks, K);
-  UNET_CHECK_LAUNCH("head_bwd_finalize");
+  if (dw || db) {     // (neither: data gradient only - Grad-CAM)
+    hipLaunchKernelGGL(head_bwd_finalize_kernel, dim3(K * 32 + K), dim3(256), 0,
+                       (hipStream_t)stream, partial, dw, db, blocks, K);
+    UNET_CHECK_LAUNCH("head_bwd_finalize");
+  }
+  if (!folded) return UNET_OK;
+  // ... then the summaries are merged and a second launch forms da again, per lane, on the way
+  // to dz (written where da would have gone)
+  const int rc = unet_instnorm_bwd_merge_partials(bs->partial, bs->tiles_out, fold->coef,
+                                                  fold->sums, N, HW, 32, stream);
+  if (rc != UNET_OK) return rc;
+  hb.apply = 1;
+  hb.coef = fold->coef; hb.sums = fold->sums;
+  hb.dgamma = fold->dgamma; hb.dbeta = fold->dbeta; hb.dbias = fold->dbias;
+  hb.N = N;
+  hipLaunchKernelGGL(head_bwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a,
+                     dlogits, w, da, partial, M, HW, K, tiles, alpha, beta, slope, hb);
+  UNET_CHECK_LAUNCH("head_bwd(apply)");
   return UNET_OK;
+}
+
+// The head's backward and the InstanceNorm + LeakyReLU + dropout backward of the layer in front
+// as one call (fp32 tensors): where unet_head1x1_in_bwd_bs would leave that layer's reductions
+// (bs->tiles_out > 0 on return), da never reaches memory - `dz` receives the layer's dL/dz and
+// dgamma / dbeta / dbias (each nullable) its parameter gradients.  bs->tiles_out == 0: the call
+// did what unet_head1x1_in_bwd_bs does, `dz` holds da and unet_instnorm_lrelu_drop_bwd is the
+// caller's next step.
+extern "C" size_t unet_head1x1_in_bwd_fold_workspace_bytes(int N, int HW, int K) {
+  if (N <= 0 || HW <= 0) return 0;
+  return align_up(unet_head1x1_bwd_workspace_bytes(N, HW, 32, K), 256) +
+         2 * align_up((size_t)N * 32 * sizeof(float2), 256);
+}
+
+extern "C" int unet_head1x1_in_bwd_fold(const unet_act_src* x, float slope, const float* dlogits,
+                                        const float* w, float* dz, float* dw, float* db,
+                                        float* dgamma, float* dbeta, float* dbias,
+                                        void* workspace, size_t workspace_bytes, int N, int HW,
+                                        int K, unet_bwd_stats* bs, unet_stream_t stream) {
+  UNET_REQUIRE(x && x->x && (!x->alpha || x->beta) && bs && workspace,
+               "head1x1_in_bwd_fold: null pointer");
+  UNET_REQUIRE(N > 0 && HW > 0 && K >= 1 && K <= 4, "head1x1_in_bwd_fold: bad shape");
+  if (workspace_bytes < unet_head1x1_in_bwd_fold_workspace_bytes(N, HW, K)) {
+    unet_set_error("head1x1_in_bwd_fold: workspace too small");
+    return UNET_E_WORKSPACE;
+  }
+  char* ws = reinterpret_cast<char*>(workspace);
+  const size_t slabs = align_up(unet_head1x1_bwd_workspace_bytes(N, HW, 32, K), 256);
+  HeadFold fold{};
+  fold.coef = reinterpret_cast<float2*>(ws + slabs);
+  fold.sums = reinterpret_cast<float2*>(ws + slabs + align_up((size_t)N * 32 * sizeof(float2), 256));
+  fold.dgamma = dgamma; fold.dbeta = dbeta; fold.dbias = dbias;
+  return head1x1_bwd_impl(x->x, dlogits, w, dz, dw, db, workspace, slabs, N, HW, x->C, K, x->alpha,
+                          x->beta, slope, stream, 0, bs, &fold);
 }
 
 extern "C" size_t unet_dice_wce_loss_workspace_bytes(int N, int H, int W) {

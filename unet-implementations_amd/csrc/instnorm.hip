@@ -352,8 +352,13 @@ __global__ __launch_bounds__(kThreads) void in_bwd_reduce_kernel(
   }
 }
 
-// finalize 1: block = 32 channels x 8 lanes, grid (C/32, N): sums[n][c] = (S1, S2),
-// coef[n][c] = (S1/HW, S2/HW).
+// finalize 1: block = 32 channels x FL lanes, grid (C/32, N): sums[n][c] = (S1, S2),
+// coef[n][c] = (S1/HW, S2/HW).  Lane l merges summaries l, l+FL, ... in order.  At 32 channels
+// and 8 images the grid is 8 workgroups and a lane of the 512 x 512 layers walks 128 summaries:
+// one L2 round trip each when every add waits for its own load (19.5 us).  kFin1Batch loads are
+// issued before their adds instead - the order of the adds, and with it every bit of the
+// result, is that of the plain loop.
+constexpr int kFin1Batch = 16;
 __global__ __launch_bounds__(32 * FL) void in_bwd_finalize1_kernel(const float2* __restrict__ partial,
                                                                float2* __restrict__ coef,
                                                                float2* __restrict__ sums, int HW,
@@ -366,12 +371,25 @@ __global__ __launch_bounds__(32 * FL) void in_bwd_finalize1_kernel(const float2*
   const int cl = threadIdx.x & 31, l = threadIdx.x >> 5;
   const int c = blockIdx.x * 32 + cl, n = blockIdx.y;
   double da_ = 0.0, db_ = 0.0;
-  if (c < C)
-    for (int s = l; s < split; s += FL) {
-      const float2 v = partial[((size_t)n * split + s) * C + c];
+  if (c < C) {
+    const float2* src = partial + (size_t)n * split * C + c;
+    int s = l;
+    for (; s + (kFin1Batch - 1) * FL < split; s += kFin1Batch * FL) {
+      float2 v[kFin1Batch];
+#pragma unroll
+      for (int j = 0; j < kFin1Batch; ++j) v[j] = src[(size_t)(s + j * FL) * C];
+#pragma unroll
+      for (int j = 0; j < kFin1Batch; ++j) {
+        da_ += (double)v[j].x;
+        db_ += (double)v[j].y;
+      }
+    }
+    for (; s < split; s += FL) {
+      const float2 v = src[(size_t)s * C];
       da_ += (double)v.x;
       db_ += (double)v.y;
     }
+  }
   sa[l][cl] = da_; sb[l][cl] = db_;
   __syncthreads();
   if (l == 0 && c < C) {
@@ -400,27 +418,10 @@ __global__ __launch_bounds__(kThreads) void in_bwd_apply_kernel(
   const int tid = threadIdx.x;
   const int grp = tid / lpp, c4 = tid - grp * lpp;
   const int n = blockIdx.y, s = blockIdx.x;
-  if (sums && n == 0 && s == 0) {
-    // Parameter gradients of the layer, by one block of this launch (N x C values to read):
-    //   dgamma[c] = sum_n S2[n][c],  dbeta[c] = sum_n S1[n][c],
-    //   dbias[c]  = sum over pixels of dy (the gradient of the conv bias in front of the norm)
-    //             = sum_n gamma rstd (S1 - HW c1 - c2 sum(xhat)),  c1 = S1 / HW,  sum(xhat) = 0:
-    // identically zero under InstanceNorm; the closed form leaves the one rounding of HW * c1
-    // (the reference's autograd value is rounding noise of the same size, <= 2.4e-6 measured).
-    const int N = gridDim.y;
-    for (int c = tid; c < C; c += kThreads) {
-      float dg = 0.f, db = 0.f, dbi = 0.f;
-      for (int q = 0; q < N; ++q) {
-        const float2 v = sums[(size_t)q * C + c];
-        db += v.x;
-        dg += v.y;
-        dbi += gamma[c] * rstd[(size_t)q * C + c] * (v.x - (float)HW * coef[(size_t)q * C + c].x);
-      }
-      if (dgamma) dgamma[c] = dg;
-      if (dbeta) dbeta[c] = db;
-      if (dbias) dbias[c] = dbi;
-    }
-  }
+  // block (0, 0) also emits the layer's parameter gradients from `sums`
+  if (sums && n == 0 && s == 0)
+    in_bwd_param_grads(sums, coef, gamma, rstd, gridDim.y, HW, C, tid, kThreads, dgamma, dbeta,
+                       dbias);
   const int per = (HW + split - 1) / split;
   const int p_begin = s * per;
   const int p_end = min(p_begin + per, HW);
@@ -433,26 +434,19 @@ __global__ __launch_bounds__(kThreads) void in_bwd_apply_kernel(
     const f32x4 b = *reinterpret_cast<const f32x4*>(beta + c);
     f32x4 mk = {1.f, 1.f, 1.f, 1.f};
     if (mask) mk = *reinterpret_cast<const f32x4*>(mask + (size_t)n * C + c);
-    float c1[4], c2[4];
+    f32x4 c1, c2;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float2 cf = coef[(size_t)n * C + c + k];
       c1[k] = cf.x;
       c2[k] = cf.y;
     }
+    const f32x4 al = g * rs, be = in_bwd_shift(b, mu, al);   // z: same expression as the forward
     const size_t base = (size_t)n * HW * C + c;
     for (int pp = p_begin + grp; pp < p_end; pp += groups) {
       const f32x4 yv = ld4(y + base + (size_t)pp * C);
       const f32x4 gv = ld4(ga + base + (size_t)pp * C);
-      f32x4 o;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float xh = (yv[k] - mu[k]) * rs[k];
-        const float al = g[k] * rs[k];
-        const float z = fmaf(yv[k], al, b[k] - mu[k] * al);  // same expression as the forward
-        const float gz = gv[k] * mk[k] * (z > 0.f ? 1.f : slope);
-        o[k] = g[k] * rs[k] * (gz - c1[k] - xh * c2[k]);
-      }
+      const f32x4 o = in_bwd_dz4(gv, yv, mu, rs, al, be, mk, slope, c1, c2);
       sd += o;
       st4(dy + base + (size_t)pp * C, o);
     }
@@ -546,6 +540,20 @@ int unet_in_finalize_tiles(const void* partial, int tiles, int px_per_tile, cons
                      stream, reinterpret_cast<const float2*>(partial), gamma, beta, eps, mask, mean,
                      rstd, alpha, beta2, HW, C, tiles, (float)px_per_tile);
   UNET_CHECK_LAUNCH("in_stats_finalize(tiles)");
+  return UNET_OK;
+}
+
+// Merge of the per-tile (S1, S2) summaries a producer of dL/da left (`tiles` per image), for
+// the callers that form dz themselves as well (head_loss.hip, conv_wgrad.hip)
+extern "C" int unet_instnorm_bwd_merge_partials(const void* partial, int tiles, void* coef,
+                                                void* sums, int N, int HW, int C,
+                                                unet_stream_t stream) {
+  UNET_REQUIRE(partial && coef && sums && tiles > 0 && N > 0 && HW > 0 && C > 0,
+               "instnorm_bwd_merge_partials: bad arguments");
+  hipLaunchKernelGGL(in_bwd_finalize1_kernel, dim3(ceil_div(C, 32), N), dim3(32 * FL), 0,
+                     (hipStream_t)stream, reinterpret_cast<const float2*>(partial),
+                     reinterpret_cast<float2*>(coef), reinterpret_cast<float2*>(sums), HW, C, tiles);
+  UNET_CHECK_LAUNCH("in_bwd_finalize1");
   return UNET_OK;
 }
 

@@ -397,11 +397,14 @@ class NextNorm:
     leaves the per-tile reductions of l's InstanceNorm backward in `.partial` / `.tiles`
     (tiles == 0: that launch had no such epilogue)."""
 
-    __slots__ = ("y", "st", "gamma", "beta", "mask", "slope", "partial", "tiles")
+    __slots__ = ("y", "st", "gamma", "beta", "mask", "slope", "partial", "tiles", "applied")
 
     def __init__(self, y, st, gamma, beta, mask, slope):
         self.y, self.st, self.gamma, self.beta, self.mask, self.slope = y, st, gamma, beta, mask, slope
         self.partial, self.tiles = None, 0
+        # the producer went on to l's whole InstanceNorm backward (head1x1_in_bwd_fold): what it
+        # returned is dL/dz and l's parameter gradients are written
+        self.applied = False
 
     def c_struct(self):
         N, H, W, C = self.y.shape
@@ -610,6 +613,15 @@ def instnorm_lrelu_drop_bwd(ga, y, mean, rstd, gamma, beta, mask, slope, dgamma,
     if t0 is not None:
         _timer.end("instnorm_bwd", 0.0, launches, t0, nbytes=y.element_size() * passes * y.numel())
     return dy
+
+
+def instnorm_bwd_merge_partials(partial, tiles, N, HW, C):
+    """Per-tile reductions partial[N, tiles, C, 2] = (S1, S2) -> (coef, sums), [N, C, 2] each:
+    sums = the tiles summed (in double, fixed order), coef = sums / HW."""
+    coef, sums = _f32((N, C, 2), partial), _f32((N, C, 2), partial)
+    check(lib().unet_instnorm_bwd_merge_partials(_ptr(partial), tiles, _ptr(coef), _ptr(sums), N,
+                                                 HW, C, _stream()))
+    return coef, sums
 
 
 class _ResizeBilinear(torch.autograd.Function):
@@ -870,6 +882,41 @@ def conv_in_bwd_weight(x, slope, dy, dw_oihw, ci_offset, ksize, stride, x3=False
     return dw_oihw
 
 
+def stem_in_bwd_weight_fold_supported(x, g):
+    """Can stem_in_bwd_weight_fold take the stem's operand `x` (Act of the fp32 image, or a
+    U8Image) and the gradient g of its output?  (fp32 tensors in the raw-row kernel's widths)"""
+    xt = x.x if isinstance(x, (Act, U8Image)) else x
+    return g.dtype == torch.float32 and xt.shape[3] == 3 and xt.shape[2] % 128 == 0 and \
+        xt.dtype in (torch.float32, torch.uint8) and getattr(x, "alpha", None) is None
+
+
+def stem_in_bwd_weight_fold(x, g, y, mean, rstd, gamma, beta, mask, slope, partials, dw_oihw,
+                            dgamma, dbeta, dbias):
+    """instnorm_lrelu_drop_bwd(g, ..., partials=partials) and conv_in_bwd_weight(x, ...) of the RGB
+    stem as one call that never stores the layer's dL/dz (nothing else reads it when no gradient
+    is taken with respect to the image): the weight gradient's loader forms it from g and y."""
+    u8 = isinstance(x, U8Image)
+    if not u8 and not isinstance(x, Act):
+        x = Act(x)
+    N, H, W, _ = x.shape
+    Cout = g.shape[3]
+    if u8:
+        img = (None, _ptr(x.x), *x.c_mean_std())
+    else:
+        if x.alpha is not None:
+            raise ValueError("the RGB image is a plain operand")
+        img = (_ptr(x.x), None, None, None)
+    ws = _wgrad_ws(lib().unet_stem_in_bwd_weight_fold_workspace_bytes(N, H, W, Cout), g)
+    t0 = _begin("wgrad")
+    check(lib().unet_stem_in_bwd_weight_fold(
+        *img, _ptr(g), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(mask), slope,
+        _ptr(partials[0]), partials[1], _ptr(dw_oihw), _ptr(dgamma), _ptr(dbeta), _ptr(dbias),
+        _ptr(ws), ws.numel(), N, H, W, Cout, _stream()))
+    if t0 is not None:
+        _end_conv(t0, "conv_stem_wgrad", 2.0 * N * H * W * 27 * Cout, 3, False)
+    return dw_oihw
+
+
 def upsample2x_in_fwd(x, slope):
     x, rx = _act(x)
     N, h, w, C = x.shape
@@ -981,6 +1028,28 @@ def head1x1_in_bwd(x, slope, dlogits, w, dw, db, nxt=None):
         _timer.end("head_bwd", 0.0, 2, t0,
                    nbytes=da.element_size() * 2 * da.numel() + 4.0 * dlogits.numel())
     return da
+
+
+def head1x1_in_bwd_fold(x, slope, dlogits, w, dw, db, nxt, dgamma, dbeta, dbias):
+    """head1x1_in_bwd(..., nxt) and the InstanceNorm + LeakyReLU + dropout backward of nxt's
+    layer in one call (fp32 tensors): with `nxt.applied` set on return the result is that layer's
+    dL/dz - da was never stored - and dgamma / dbeta / dbias hold its parameter gradients;
+    otherwise (this shape has no such form) the result is da, as head1x1_in_bwd left it."""
+    x, rx = _act(x)
+    N, H, W, C = x.shape
+    K = w.shape[0]
+    dz = torch.empty_like(x.x)
+    ws = _ws(lib().unet_head1x1_in_bwd_fold_workspace_bytes(N, H * W, K), x.x)
+    t0 = _begin()
+    _call_nxt(lib().unet_head1x1_in_bwd_fold,
+              (rx, slope, _ptr(dlogits), _ptr(w), _ptr(dz), _ptr(dw), _ptr(db), _ptr(dgamma),
+               _ptr(dbeta), _ptr(dbias), _ptr(ws), ws.numel(), N, H * W, K), nxt)
+    nxt.applied = nxt.tiles > 0
+    if t0 is not None:      # folded: y + dlogits in, twice; dz out
+        _timer.end("head_bwd", 0.0, 4 if nxt.applied else 2, t0,
+                   nbytes=4.0 * ((3 if nxt.applied else 2) * dz.numel() +
+                                 (2 if nxt.applied else 1) * dlogits.numel()))
+    return dz
 
 
 # ---- bilinear 2x ---------------------------------------------------------------------

@@ -371,6 +371,11 @@ class UNet(nn.Module):
         # fp32 fused pipeline: run the stride-1 3x3 layers the Winograd F(2x2,3x3) kernel tiles
         # on it (2.25x fewer matrix-core FLOPs, a few extra fp32 roundings: csrc/conv_wino.hip)
         self.winograd = True
+        # fp32 fused pipeline: two full-resolution gradients are formed inside their consumers
+        # instead of being stored - dL/da of the last decoder layer (the head's backward goes on
+        # to that layer's dL/dz) and dL/dz of the stem (formed by the loader of its weight
+        # gradient).  Same bits either way; off = the stored forms
+        self.fullres_folds = True
         # normalisation constants of forward(..., input_layout="nhwc_u8") (ImageNet, as the
         # reference's dataset: Our_UNet/src/train.py:303-308)
         self.input_mean, self.input_std = ops.IMAGENET_MEAN, ops.IMAGENET_STD
@@ -414,6 +419,16 @@ class UNet(nn.Module):
             # g is the final gradient of the last decoder layer's output: the head's backward
             # also leaves the reductions of that layer's InstanceNorm backward (NextNorm)
             last = grad_only and rec is walk.saved[walk.stop_at]
+            if self.fullres_folds and not grad_only and walk.mode == "fp32" and \
+                    not _hooked(rec.bwd_hooks, "_backward_hooks") and \
+                    getattr(self, "_debug_capture", None) is None:
+                # nothing but that layer's InstanceNorm backward reads g: it runs inside the
+                # head's backward and g is never stored (the NextNorm then says `applied`)
+                l = rec.layer
+                return ops.head1x1_in_bwd_fold(rec.output(), walk.slope, dout, hw, dw, db,
+                                               rec.next_norm(), self._grad_view(l.norm.weight),
+                                               self._grad_view(l.norm.bias),
+                                               self._grad_view(l.conv.bias))
             return ops.head1x1_in_bwd(rec.output(), walk.slope, dout, hw, dw, db,
                                       nxt=None if last else rec.next_norm())
         return ops.head1x1_bwd(rec.a, dout, hw, dw, db)
@@ -843,15 +858,27 @@ class _Walk:
         # that layer's InstanceNorm-backward reductions
         nxt = self.saved[i - 1].next_norm() \
             if fused and need_dx and not (grad_only and i - 1 == stop) else None
-        dy = ops.instnorm_lrelu_drop_bwd(g_a, rec.y, st[0], st[1], l.norm.weight.detach(),
-                                         l.norm.bias.detach(), rec.mask, l.slope,
-                                         gv(l.norm.weight), gv(l.norm.bias), gv(l.conv.bias),
-                                         partials=(nn_.partial, nn_.tiles)
-                                         if nn_ is not None and nn_.tiles > 0 else None)
-        if dbg is not None:
-            dbg.append((l.name, "dy", dy.clone()))
         dw = gv(l.conv.weight)
         want_dw = l.conv.weight.requires_grad and not grad_only
+        partials = (nn_.partial, nn_.tiles) if nn_ is not None and nn_.tiles > 0 else None
+        if i == 0 and fused and want_dw and partials is not None and dbg is None and \
+                self.mode == "fp32" and x1 is None and low is None and l.ksize == 3 and \
+                self.model.fullres_folds and ops.stem_in_bwd_weight_fold_supported(x0, g_a):
+            # the RGB stem: no gradient goes on to the image, so its dL/dz is read by the weight
+            # gradient alone - whose loader forms it from g_a and y (never stored)
+            ops.stem_in_bwd_weight_fold(x0, g_a, rec.y, st[0], st[1], l.norm.weight.detach(),
+                                        l.norm.bias.detach(), rec.mask, l.slope, partials, dw,
+                                        gv(l.norm.weight), gv(l.norm.bias), gv(l.conv.bias))
+            return None, None
+        if nn_ is not None and nn_.applied:
+            dy = g_a       # head1x1_in_bwd_fold: the producer already went on to dL/dz
+        else:
+            dy = ops.instnorm_lrelu_drop_bwd(g_a, rec.y, st[0], st[1], l.norm.weight.detach(),
+                                             l.norm.bias.detach(), rec.mask, l.slope,
+                                             gv(l.norm.weight), gv(l.norm.bias), gv(l.conv.bias),
+                                             partials=partials)
+        if dbg is not None:
+            dbg.append((l.name, "dy", dy.clone()))
         if low is not None:
             # conv3x3(upsample2x(act(low))): both gradients of the up-sampled operand are
             # GEMMs over the LOW-resolution pixels once dy is reduced to its nine D_tap
