@@ -510,6 +510,28 @@ int unet_stem_in_bwd_weight_fold(const float* x, const uint8_t* image_hwc, const
                                  size_t workspace_bytes, int N, int H, int W, int Cout,
                                  unet_stream_t stream);
 
+/* Weight gradient of a 32 -> 32 channel 3x3 layer (stride 1) with the layer's InstanceNorm +
+ * LeakyReLU + dropout backward formed inside it (fp32 tensors), for the shapes
+ * unet_conv_in_bwd_weight_fold32_supported accepts: those unet_conv_in_bwd_weight runs on the
+ * 32-channel Winograd kernel under the calling thread's unet_set_c32_winograd switch.
+ * g = dL/da of the layer (IN / OUT), y its raw output, `partial` the per-tile reductions (S1, S2)
+ * the producer of g left (`tiles` per image).  The summaries are merged, then the weight
+ * gradient's dy side reads g and y, forms dL/dz and stores it over g in place: on return g holds
+ * dL/dz for the layer's data gradients, without the separate pass that would have written it.
+ * x (activated on load with slope_x when x->alpha is set) is the layer's operand, or the half of
+ * it whose columns ci_offset .. + 32 of dw_oihw[32][Cin_total][3][3] are written.  dw, dz and
+ * dgamma / dbeta / dbias (each nullable) have the bits of unet_instnorm_lrelu_drop_bwd_partials
+ * followed by unet_conv_in_bwd_weight. */
+int unet_conv_in_bwd_weight_fold32_supported(int N, int H, int W, int Cx, int Cout);
+size_t unet_conv_in_bwd_weight_fold32_workspace_bytes(int N, int H, int W);
+int unet_conv_in_bwd_weight_fold32(const unet_act_src* x, float slope_x, float* g, const float* y,
+                                   const float* mean, const float* rstd, const float* gamma,
+                                   const float* beta, const float* mask, float slope,
+                                   const void* partial, int tiles, float* dw_oihw, int ci_offset,
+                                   int Cin_total, float* dgamma, float* dbeta, float* dbias,
+                                   void* workspace, size_t workspace_bytes, int N, int H, int W,
+                                   unet_stream_t stream);
+
 /* Weight gradient with the activation applied to the input operand on load:
  * dw_oihw[Cout][Cin_total][k][k] (columns ci_offset .. +x->C) = sum_pixels act(x) (x) dy.
  * Same workspace query as unet_conv3x3_bwd_weight.  ksize 1 keeps the centre tap. */

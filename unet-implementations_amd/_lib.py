@@ -181,6 +181,10 @@ SIGNATURES = {
     "unet_stem_in_bwd_weight_fold": (_i, [_p, _p, _c.POINTER(_f), _c.POINTER(_f), _p, _p, _p, _p, _p,
                                           _p, _p, _f, _p, _i, _p, _p, _p, _p, _p, _sz, _i, _i, _i,
                                           _i, _p]),
+    "unet_conv_in_bwd_weight_fold32_supported": (_i, [_i, _i, _i, _i, _i]),
+    "unet_conv_in_bwd_weight_fold32_workspace_bytes": (_sz, [_i, _i, _i]),
+    "unet_conv_in_bwd_weight_fold32": (_i, [_ps, _f, _p, _p, _p, _p, _p, _p, _p, _f, _p, _i, _p, _i,
+                                            _i, _p, _p, _p, _p, _sz, _i, _i, _i, _p]),
     "unet_instnorm_bwd_merge_partials": (_i, [_p, _i, _p, _p, _i, _i, _i, _p]),
     "unet_head1x1_in_bwd_fold_workspace_bytes": (_sz, [_i, _i, _i]),
     "unet_head1x1_in_bwd_fold": (_i, [_ps, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _i, _i, _i,

@@ -51,6 +51,15 @@ struct WgradParams {
   const float* beta;   // [N][Cx]
   float slope;
   int b16;             // x and dy are bf16 tensors (mixed-precision pipeline)
+  // conv_wgrad_wino32_kernel, fy != nullptr (unet_conv_in_bwd_weight_fold32): `dy` holds
+  // g = dL/da of the layer and fy its raw output; the dy side forms the layer's dL/dz from the
+  // two (in_bwd_dz4: the bits in_bwd_apply_kernel would have stored) and stores it over g in
+  // place, its other readers' operand.  fcoef = (c1, c2), fsums = (S1, S2) per image and
+  // channel; workgroup 0 also writes the layer's parameter gradients.
+  const float* fy; const float* fmu; const float* frstd; const float* fgamma; const float* fbeta;
+  const float* fmask; const float2* fcoef; const float2* fsums;
+  float* fdgamma; float* fdbeta; float* fdbias;
+  float fslope;
 };
 
 // Epilogue shared by the weight-gradient kernels.  A wave holds nine 32x32 accumulator blocks
@@ -2176,7 +2185,20 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_wino32_kernel(const WgradPa
   const int t_ty = (tt & 3) >> 1, t_tx = 4 * (tt & 1) + (tt >> 2);
   const unsigned t_srca = lds_addr(Pb + ((2 * t_ty) * WQ_PW + 2 * t_tx) * WQ_LDA + 2 * cp);
   float* const t_dst = (xside ? Vs : Es) + tt * WQ_VP + 2 * cp;
-  f32x2v en[4];   // dy side: the next unit's 2 x 2 tile (channel pair cp)
+  // dy side, loads: lane (cp, tt) fetches the FOUR channels 4 (cp >> 1) .. + 3 of the two pixels
+  // of tile row cp & 1 of its tile (16-byte accesses); lanes cp and cp ^ 1 then swap channel
+  // halves (split_dy), which leaves each the 2 x 2 tile of its channel pair cp - the layout the
+  // transform and the E' stores have always had.  With the fold operands set the four-channel
+  // form is also what in_bwd_dz4 takes: dz is formed and stored over g before the swap.
+  const bool fold = p.fy != nullptr;   // uniform
+  // (said to be global memory: as members of a by-value struct tested against null they would
+  // be loaded through flat instructions, whose returns the LDS counter of the products sees)
+  auto ldg4 = [](const float* q) {
+    return *(const __attribute__((address_space(1))) f32x4*)q;
+  };
+  const int d_rel = ((2 * t_ty + (cp & 1)) * W + 2 * t_tx) * 32 + 4 * (cp >> 1);
+  f32x4 gn[2], yn[2];   // the next unit's values of dy (fold: of g and of y)
+  int on = 0;           // ... and their offset in dy (floats)
   auto load_unit = [&](int n, int yu, int xu) {   // patch of x (all threads) + dy tile (waves 4-7)
     const int base = ((n * H + yu - 1) * W + xu - 1) * 128;
     okm = 0;
@@ -2189,12 +2211,47 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_wino32_kernel(const WgradPa
       pr[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsx, off, 0, 0));
     }
     if (!xside) {   // uniform
-      const size_t o = (((size_t)n * H + yu + 2 * t_ty) * W + xu + 2 * t_tx) * 32 + 2 * cp;
-      const float* d = p.dy + o;
-      en[0] = *reinterpret_cast<const f32x2v*>(d);
-      en[1] = *reinterpret_cast<const f32x2v*>(d + 32);
-      en[2] = *reinterpret_cast<const f32x2v*>(d + (size_t)W * 32);
-      en[3] = *reinterpret_cast<const f32x2v*>(d + (size_t)W * 32 + 32);
+      on = ((n * H + yu) * W + xu) * 32 + d_rel;     // (< 2^29: wgrad_wino32_ok)
+      gn[0] = ld4(p.dy + on);
+      gn[1] = ld4(p.dy + on + 32);
+      if (fold) {   // uniform
+        yn[0] = ldg4(p.fy + on);
+        yn[1] = ldg4(p.fy + on + 32);
+      }
+    }
+  };
+  // the fold's coefficient rows of the image the walk is in (this lane's four channels): they
+  // change only when the walk crosses into the next image
+  f32x4 f_mu, f_rs, f_al, f_be, f_mk, f_c1, f_c2;
+  int n_fold = -1;
+  auto load_fold = [&](int n) {
+    const int c = 4 * (cp >> 1);
+    const size_t o = (size_t)n * 32 + c;
+    f_mu = ldg4(p.fmu + o);
+    f_rs = ldg4(p.frstd + o);
+    f_al = ldg4(p.fgamma + c) * f_rs;
+    f_be = in_bwd_shift(ldg4(p.fbeta + c), f_mu, f_al);
+    f_mk = p.fmask ? ldg4(p.fmask + o) : f32x4{1.f, 1.f, 1.f, 1.f};
+    const f32x4 q0 = ldg4(&p.fcoef[o].x), q1 = ldg4(&p.fcoef[o + 2].x);   // (c1, c2) pairs
+    f_c1 = f32x4{q0[0], q0[2], q1[0], q1[2]};
+    f_c2 = f32x4{q0[1], q0[3], q1[1], q1[3]};
+  };
+  // rows of pixels (v[0], v[1] of lane cp & 1 = tile row) x four channels -> e[2 row + col] of
+  // the channel pair cp: the even lane keeps the low halves and takes its neighbour's, the odd
+  // lane the high halves
+  auto from_neighbour = [](float v) {   // quad_perm [1, 0, 3, 2]: the value of lane ^ 1
+    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xf,
+                                                              0xf, true));
+  };
+  auto split_dy = [&](const f32x4 (&v)[2], f32x2v (&e)[4]) {
+    const bool odd = cp & 1;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const f32x2v got = {from_neighbour(odd ? v[c][0] : v[c][2]),
+                          from_neighbour(odd ? v[c][1] : v[c][3])};
+      const f32x2v keep = {odd ? v[c][2] : v[c][0], odd ? v[c][3] : v[c][1]};
+      e[c] = odd ? got : keep;
+      e[2 + c] = odd ? keep : got;
     }
   };
   auto load_act = [&](int n) {
@@ -2278,6 +2335,9 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_wino32_kernel(const WgradPa
 #pragma unroll
       for (int d = 0; d < 2; ++d) acc[j][c][d] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  if (fold && blockIdx.x == 0)
+    in_bwd_param_grads(p.fsums, p.fcoef, p.fgamma, p.frstd, p.N, H * W, 32, tid, 512, p.fdgamma,
+                       p.fdbeta, p.fdbias);
   if (t_first < t_end) {
     {
       int n, y0, x0;
@@ -2293,11 +2353,12 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_wino32_kernel(const WgradPa
       const bool more = nxt < t_end;
       int n, y0, x0;
       tile_pos(tile, n, y0, x0);
+      if (fold && !xside && n != n_fold) { load_fold(n); n_fold = n; }   // uniform, once per image
       for_range<0, 4>([&](auto uc) {
         constexpr int u = decltype(uc)::value;
-        f32x2v ec[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) ec[k] = en[k];   // this unit's dy tile (loaded a unit ago)
+        // this unit's dy values (loaded a unit ago)
+        f32x4 gc[2] = {gn[0], gn[1]}, yc[2] = {yn[0], yn[1]};
+        const int oc = on;
         bool have_next = true;
         int nn = n;
         if constexpr (u < 3) {
@@ -2310,8 +2371,21 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_wino32_kernel(const WgradPa
             load_unit(nn, ny, nx);
           }
         }
-        if (xside) transform_x();   // uniform
-        else transform_dy(ec);
+        if (xside) {   // uniform
+          transform_x();
+        } else {
+          if (fold) {   // uniform: dz over g, on its way out while the transform and the MFMAs run
+            float* const dz = const_cast<float*>(p.dy) + oc;
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+              gc[c] = in_bwd_dz4(gc[c], yc[c], f_mu, f_rs, f_al, f_be, f_mk, p.fslope, f_c1, f_c2);
+              st4(dz + 32 * c, gc[c]);
+            }
+          }
+          f32x2v ec[4];
+          split_dy(gc, ec);
+          transform_dy(ec);
+        }
         __syncthreads();
         {
           f32x2v fa[2], fb[2];
@@ -2644,6 +2718,9 @@ struct WgradCall {
   // RGB stem only: dy is dL/da of the stem layer and the loader forms its dL/dz (the fold
   // operands of StemNormW, taken from here)
   const StemNormW* stem_fold = nullptr;
+  // 32 -> 32 channel Winograd form only (unet_conv_in_bwd_weight_fold32): the same operands for a
+  // layer whose dL/dz has other readers - the kernel stores it over dy in place
+  const StemNormW* fold32 = nullptr;
   // activation on load: a = lrelu(x * alpha[n][c] + beta[n][c], slope); alpha == nullptr: plain x
   const float* alpha = nullptr;
   const float* beta = nullptr;
@@ -2767,6 +2844,14 @@ int wgrad_launch_chunks(const WgradCall& c, const WgradSel& s, float* ws, int* n
     p.alpha = c.alpha ? c.alpha + (size_t)nb * c.Cx : nullptr;
     p.beta = c.alpha ? c.beta + (size_t)nb * c.Cx : nullptr;
     p.slope = c.slope;
+    if (c.fold32) {
+      UNET_REQUIRE(s.form == WF_WINO32 && nc == c.N, "conv_in_bwd_weight_fold32: not a shape of "
+                   "the 32-channel Winograd weight gradient");
+      const StemNormW& f = *c.fold32;
+      p.fy = f.y; p.fmu = f.mu; p.frstd = f.rstd; p.fgamma = f.gamma; p.fbeta = f.beta;
+      p.fmask = f.mask; p.fcoef = f.coef; p.fsums = f.sums;
+      p.fdgamma = f.dgamma; p.fdbeta = f.dbeta; p.fdbias = f.dbias; p.fslope = f.slope;
+    }
     const int rc = s.form == WF_WINO32 ? launch_wgrad_wino32(p, stream)
                    : s.form == WF_WINO ? launch_wgrad_wino(p, stream)
                    : s.form == WF_TAPS ? launch_wgrad_taps_plan(p, pl, stream)
@@ -3134,6 +3219,67 @@ extern "C" int unet_stem_in_bwd_weight_fold(const float* x, const uint8_t* image
   c.dw = dw_oihw; c.Cin_total = 3;
   c.workspace = ws + 2 * coef_b; c.workspace_bytes = workspace_bytes - 2 * coef_b;
   c.N = N; c.H = H; c.W = W; c.Cx = 3; c.Cout = Cout;
+  return conv_bwd_weight_impl(c, (hipStream_t)stream);
+}
+
+// Weight gradient of a 32 -> 32 channel layer on conv_wgrad_wino32_kernel with the layer's
+// InstanceNorm + LeakyReLU + dropout backward formed on its dy side (fp32 tensors): g = dL/da of
+// the layer, whose per-tile reductions `partial` (`tiles` per image) its producer left.  The
+// summaries are merged, then waves 4-7 of the weight gradient read g and y, evaluate in_bwd_dz4
+// and store dL/dz over g IN PLACE on their way to E' - the apply launch and one pass over the
+// tensor are gone, and the data gradients that follow read dz from g.  dw (columns ci_offset ..
+// + 32 of Cin_total), dz and the parameter gradients have the bits of
+// unet_instnorm_lrelu_drop_bwd_partials followed by unet_conv_in_bwd_weight.
+extern "C" int unet_conv_in_bwd_weight_fold32_supported(int N, int H, int W, int Cx, int Cout) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cx != 32 || Cout != 32) return 0;
+  WgradCall c;
+  c.N = N; c.H = H; c.W = W; c.Cx = Cx; c.Cout = Cout;
+  return wgrad_select(c, unet_conv::c32_winograd_flag()).form == WF_WINO32 ? 1 : 0;
+}
+
+extern "C" size_t unet_conv_in_bwd_weight_fold32_workspace_bytes(int N, int H, int W) {
+  if (N <= 0 || H <= 0 || W <= 0) return 0;
+  return 2 * align_up((size_t)N * 32 * sizeof(float2), 256) +
+         unet_conv3x3_bwd_weight_workspace_bytes(N, H, W, 32, 32, 1);
+}
+
+extern "C" int unet_conv_in_bwd_weight_fold32(const unet_act_src* x, float slope_x, float* g,
+                                              const float* y, const float* mean, const float* rstd,
+                                              const float* gamma, const float* beta,
+                                              const float* mask, float slope, const void* partial,
+                                              int tiles, float* dw_oihw, int ci_offset,
+                                              int Cin_total, float* dgamma, float* dbeta,
+                                              float* dbias, void* workspace, size_t workspace_bytes,
+                                              int N, int H, int W, unet_stream_t stream) {
+  const int rc0 = check_conv_in("conv_in_bwd_weight_fold32", x, 3, 1);
+  if (rc0 != UNET_OK) return rc0;
+  UNET_REQUIRE(g && y && mean && rstd && gamma && beta && partial && tiles > 0 && workspace,
+               "conv_in_bwd_weight_fold32: null pointer");
+  UNET_REQUIRE(unet_conv_in_bwd_weight_fold32_supported(N, H, W, x->C, 32),
+               "conv_in_bwd_weight_fold32: N=%d H=%d W=%d Cx=%d is not a shape of the 32-channel "
+               "Winograd weight gradient", N, H, W, x->C);
+  UNET_REQUIRE(x->x != g && x->x != y, "conv_in_bwd_weight_fold32: g is rewritten in place and "
+               "cannot be the layer's operand");
+  const size_t coef_b = align_up((size_t)N * 32 * sizeof(float2), 256);
+  if (workspace_bytes < 2 * coef_b) {
+    unet_set_error("conv_in_bwd_weight_fold32: workspace too small");
+    return UNET_E_WORKSPACE;
+  }
+  char* ws = reinterpret_cast<char*>(workspace);
+  StemNormW f{};
+  f.y = y; f.mu = mean; f.rstd = rstd; f.gamma = gamma; f.beta = beta; f.mask = mask;
+  f.coef = reinterpret_cast<const float2*>(ws);
+  f.sums = reinterpret_cast<const float2*>(ws + coef_b);
+  f.dgamma = dgamma; f.dbeta = dbeta; f.dbias = dbias; f.slope = slope;
+  const int rc = unet_instnorm_bwd_merge_partials(partial, tiles, ws, ws + coef_b, N, H * W, 32,
+                                                  stream);
+  if (rc != UNET_OK) return rc;
+  WgradCall c;
+  set_source(c, x, slope_x);
+  c.dy = g; c.fold32 = &f;
+  c.dw = dw_oihw; c.ci_offset = ci_offset; c.Cin_total = Cin_total;
+  c.workspace = ws + 2 * coef_b; c.workspace_bytes = workspace_bytes - 2 * coef_b;
+  c.N = N; c.H = H; c.W = W; c.Cout = 32;
   return conv_bwd_weight_impl(c, (hipStream_t)stream);
 }
 

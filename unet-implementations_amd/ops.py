@@ -917,6 +917,38 @@ def stem_in_bwd_weight_fold(x, g, y, mean, rstd, gamma, beta, mask, slope, parti
     return dw_oihw
 
 
+def conv_in_bwd_weight_fold32_supported(x, g):
+    """Can conv_in_bwd_weight_fold32 take the operand `x` and the gradient g of the layer's output?
+    (fp32 tensors of a shape conv_in_bwd_weight runs on the 32-channel Winograd kernel under the
+    calling thread's c32 switch)"""
+    xt = x.x if isinstance(x, Act) else x
+    if isinstance(x, U8Image) or xt.dtype != torch.float32 or g.dtype != torch.float32 or \
+            xt.shape[:3] != g.shape[:3]:
+        return False
+    N, H, W, Cx = xt.shape
+    return bool(lib().unet_conv_in_bwd_weight_fold32_supported(N, H, W, Cx, g.shape[3]))
+
+
+def conv_in_bwd_weight_fold32(x, slope_x, g, y, mean, rstd, gamma, beta, mask, slope, partials,
+                              dw_oihw, ci_offset, dgamma, dbeta, dbias):
+    """instnorm_lrelu_drop_bwd(g, ..., partials=partials) and conv_in_bwd_weight(x, slope_x, dz,
+    dw_oihw, ci_offset, 3, 1) of a 32 -> 32 channel layer as one call: the weight gradient forms
+    the layer's dL/dz from g and y and stores it over g in place (the separate pass over the
+    tensor is gone).  Returns g, which now holds dL/dz."""
+    x, rx = _act(x)
+    N, H, W, _ = x.shape
+    assert dw_oihw.shape[0] == 32 and dw_oihw.is_contiguous() and g.is_contiguous()
+    ws = _wgrad_ws(lib().unet_conv_in_bwd_weight_fold32_workspace_bytes(N, H, W), g)
+    t0 = _begin("wgrad")
+    check(lib().unet_conv_in_bwd_weight_fold32(
+        rx, slope_x, _ptr(g), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(mask),
+        slope, _ptr(partials[0]), partials[1], _ptr(dw_oihw), ci_offset, dw_oihw.shape[1],
+        _ptr(dgamma), _ptr(dbeta), _ptr(dbias), _ptr(ws), ws.numel(), N, H, W, _stream()))
+    if t0 is not None:
+        _end_conv(t0, "conv_wgrad", 2.0 * N * H * W * 9 * 32 * 32, 3, True)
+    return g
+
+
 def upsample2x_in_fwd(x, slope):
     x, rx = _act(x)
     N, h, w, C = x.shape

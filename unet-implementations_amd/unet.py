@@ -376,6 +376,10 @@ class UNet(nn.Module):
         # to that layer's dL/dz) and dL/dz of the stem (formed by the loader of its weight
         # gradient).  Same bits either way; off = the stored forms
         self.fullres_folds = True
+        # ... and two more whose dL/dz has several readers are formed inside the 32-channel
+        # Winograd weight gradient, which stores dz over g in place (the layers' separate
+        # InstanceNorm-backward pass is gone).  Same bits either way; off = the separate pass
+        self.wgrad32_folds = True
         # normalisation constants of forward(..., input_layout="nhwc_u8") (ImageNet, as the
         # reference's dataset: Our_UNet/src/train.py:303-308)
         self.input_mean, self.input_std = ops.IMAGENET_MEAN, ops.IMAGENET_STD
@@ -870,8 +874,23 @@ class _Walk:
                                         l.norm.bias.detach(), rec.mask, l.slope, partials, dw,
                                         gv(l.norm.weight), gv(l.norm.bias), gv(l.conv.bias))
             return None, None
+        # the 32 -> 32 channel layers at full resolution: the Winograd weight gradient (of the
+        # skip half where the layer up-samples its first operand) forms dz itself and leaves it
+        # in g_a for the gradients that follow
+        xw = x1 if low is not None else x0
+        fold32 = fused and want_dw and partials is not None and dbg is None and \
+            self.mode == "fp32" and not self.x3 and l.ksize == 3 and l.stride == 1 and \
+            self.model.wgrad32_folds and not (nn_ is not None and nn_.applied) and \
+            (low is not None or x1 is None) and xw is not None and \
+            not _hooked(rec.bwd_hooks, "_backward_hooks") and \
+            ops.conv_in_bwd_weight_fold32_supported(xw, g_a)
         if nn_ is not None and nn_.applied:
             dy = g_a       # head1x1_in_bwd_fold: the producer already went on to dL/dz
+        elif fold32:
+            dy = ops.conv_in_bwd_weight_fold32(
+                xw, slope, g_a, rec.y, st[0], st[1], l.norm.weight.detach(), l.norm.bias.detach(),
+                rec.mask, l.slope, partials, dw, low.shape[3] if low is not None else 0,
+                gv(l.norm.weight), gv(l.norm.bias), gv(l.conv.bias))
         else:
             dy = ops.instnorm_lrelu_drop_bwd(g_a, rec.y, st[0], st[1], l.norm.weight.detach(),
                                              l.norm.bias.detach(), rec.mask, l.slope,
@@ -886,7 +905,8 @@ class _Walk:
             D = ops.upsample2x_bwd_taps(dy) if (want_dw or need_dx) else None
             if want_dw:
                 ops.conv3x3_up_bwd_weight(low, slope, D, dw, 0)
-                ops.conv_in_bwd_weight(x1, slope, dy, dw, C0, 3, 1, x3=self.x3)
+                if not fold32:
+                    ops.conv_in_bwd_weight(x1, slope, dy, dw, C0, 3, 1, x3=self.x3)
             g_low = ops.conv3x3_up_bwd_data(D, rec.wd, 0, C0, nxt=nxt,
                                             wd3=rec.wd3 if ops._is_b16(D) else None) \
                 if need_dx else None
@@ -895,7 +915,9 @@ class _Walk:
                                        bf16="bf16x3" if rec.wd3 is not None else False,
                                        ud=rec.ud1) if need_dx1 else None
             return g_low, dx1
-        if want_dw and fused:      # the weight gradient activates its operand on load
+        if want_dw and fused and fold32:
+            want_dw = False
+        elif want_dw and fused:      # the weight gradient activates its operand on load
             ops.conv_in_bwd_weight(x0, slope, dy, dw, 0, l.ksize, l.stride, x3=self.x3)
             if x1 is not None:
                 ops.conv_in_bwd_weight(x1, slope, dy, dw, x0.shape[3], l.ksize, l.stride,
