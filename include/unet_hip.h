@@ -373,6 +373,46 @@ int unet_eval_confusion(const float* logits_nchw, const int64_t* target, const i
 int unet_eval_maps(const float* logits_nchw, const int64_t* target, float* probs,
                    uint8_t* classes, uint8_t* errors, int B, int H, int W, unet_stream_t stream);
 
+/* ---- online batch augmentation (augment.hip; semantics defined by this project) -- */
+
+/* Floats per sample record of unet_augment_u8 (24). */
+int unet_augment_params_per_sample(void);
+
+/* image [N][H][W][3] + mask [N][H][W] (uint8, mask nullable: then mask_out is not written) ->
+ * an augmented pair of the same shape, one launch, grid (pixel tiles, N).  params [N][24] (fp32)
+ * and rng [N][4] (uint32, nullable: then all noise is off) are DEVICE arrays read by the kernel
+ * only, so a launch captured in a HIP graph follows new records on replay.  The outputs must not
+ * overlap the inputs (the kernel gathers).  Record, levels 0..255 where a value is a pixel value:
+ *    0-8   h0..h8  inverse homography, row-major: output pixel centre -> source coordinate
+ *    9     alpha (contrast gain)        10-12  beta_c per channel (brightness 255 + RGB shift)
+ *    13    gray flag (0 / 1)            14     sigma of the Gaussian noise (0 = off)
+ *    15-18 hole x0, y0, x1, y1 in output pixels, half-open; empty if x1 <= x0 or y1 <= y0
+ *    19    hole fill (image)   20  mask border fill   21  mask hole fill   22-23  reserved, 0
+ * rng[n] = seed_lo, seed_hi, pepper_thr, salt_thr.
+ * Every fp32 operation below is rounded on its own (no fused multiply-add).  Output pixel (i, j):
+ *    xc = j + 0.5, yc = i + 0.5, den = (h6 xc + h7 yc) + h8,
+ *    u = ((h0 xc + h1 yc) + h2) / den, v = ((h3 xc + h4 yc) + h5) / den.
+ * Image: fx = u - 0.5, x0 = floor(fx), ax = fx - x0 (the same in y); taps (y0,x0), (y0,x0+1),
+ * (y0+1,x0), (y0+1,x0+1), a tap outside the image contributes 0 (and a pixel none of whose taps
+ * is inside is exactly 0); top = (1-ax) p00 + ax p01, bot = (1-ax) p10 + ax p11,
+ * s = (1-ay) top + ay bot.  Mask: source (floor(v), floor(u)), the border fill outside.  A pixel
+ * with !(den > 0) is outside for both.  All range tests are made in float before any conversion.
+ * Inside the hole s_c is the hole fill and the mask the mask hole fill.  Then, in this order:
+ *    a_c = clamp(alpha s_c + beta_c, 0, 255);  gray: a_c = (0.299 a_0 + 0.587 a_1) + 0.114 a_2;
+ *    sigma > 0: a_c += sigma z_c;  q_c = clamp(rint(a_c), 0, 255);
+ *    pepper (0, 0, 0) if the pixel's word < pepper_thr, else salt (255 x 3) if salt_thr != 0 and
+ *    word >= 2^32 - salt_thr.
+ * Random words: Philox4x32-10, key (seed_lo, seed_hi), counter (pixel index lo, hi, stream, 0)
+ * with the pixel index i W + j inside the sample.  Stream 0: words w0..w3 give the normals by
+ * Box-Muller on (w0, w1) and (w2, w3): u1 = ((wa >> 8) + 1) 2^-24, u2 = (wb >> 8) 2^-24,
+ * r = sqrt(-2 ln u1), z_0 = r cos(2 pi u2), z_1 = r sin(2 pi u2) of the first pair, z_2 the
+ * cosine of the second.  Stream 1: word 0 is the salt / pepper word.
+ * UNET_E_INVALID before any launch: null image / image_out / params, a mask without mask_out,
+ * N, H or W <= 0 (or N > 65535, H or W > 32768, H W > 2^30), an output overlapping an input. */
+int unet_augment_u8(const uint8_t* image, const uint8_t* mask, uint8_t* image_out,
+                    uint8_t* mask_out, const float* params, const uint32_t* rng, int N, int H,
+                    int W, unet_stream_t stream);
+
 /* uint8 HWC image (+ uint8 mask) -> ((v/255) - mean)/std NHWC fp32 (+ int64 target with values
  * > 2 other than 255 mapped to 0): PetSegmentationDataset.__getitem__, src/train.py:300-311.
  * mean3 / std3 are HOST pointers to 3 floats. */

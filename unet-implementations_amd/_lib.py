@@ -96,6 +96,8 @@ SIGNATURES = {
     "unet_argmax_dice_counts": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "unet_eval_confusion": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "unet_eval_maps": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "unet_augment_params_per_sample": (_i, []),
+    "unet_augment_u8": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "unet_gradcam_workspace_bytes": (_sz, [_i, _i, _i]),
     "unet_gradcam_weights": (_i, [_p, _i, _p, _p, _sz, _i, _i, _i, _p]),
     "unet_gradcam_map": (_i, [_ps, _i, _f, _p, _p, _p, _sz, _i, _i, _p]),

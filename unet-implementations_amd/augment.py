@@ -1,0 +1,408 @@
+"""Online augmentation of uint8 training batches on the device (csrc/augment.hip).
+
+The reference augments offline: data_augmentation/src/augment_dataset.py runs its pipeline on the
+CPU once and stores a fixed set of augmented files, so a model sees the same pixels every epoch.
+Here the batch that is already on the device as uint8 goes through ONE kernel launch that writes
+an augmented uint8 batch of the same shape; everything downstream (`input_layout="nhwc_u8"`,
+`SimpleLoss(target_layout="u8")`, `GraphedTrainStep`) takes it as it takes the dataset's bytes.
+
+    cfg = AugmentConfig.from_yaml("augmentation_config.yaml", "cat")
+    aug = BatchAugment(cfg, seed=0)
+    images, masks = aug(images_u8, masks_u8)              # uint8 [N,H,W,3] / [N,H,W], new draws
+
+Supported transforms, and how each is realised:
+
+    HorizontalFlip, ShiftScaleRotate (about the centre), RandomResizedCrop (to the batch size),
+    Perspective (four-corner displacement, keep_size)
+        composed on the host in fp64 into ONE inverse homography per sample: the image is
+        resampled once (bilinear, zeros outside), the mask once (nearest, a border value outside)
+    CoarseDropout with one hole            the hole fields of the record
+    RandomBrightnessContrast (v * alpha + beta * 255) and RGBShift
+                                           folded into alpha / beta_c
+    ToGray                                 the gray flag
+    GaussNoise (var_limit -> sigma)        sigma
+    SaltAndPepper                          two thresholds on a per-pixel random word
+
+`OneOf` groups keep the reference's structure over the supported members: the group probability
+is drawn first, then one member by its normalised probability among the SUPPORTED members.
+
+Not supported (keys of these are ignored by `from_yaml`): elastic / grid / optical distortion,
+HueSaturationValue, CLAHE, Equalize, Gaussian and motion blur, ISO noise, shadow / sun flare /
+fog.  The semantics of what is supported are defined by this project (include/unet_hip.h,
+DESIGN 12), not recorded from the reference's augmentation library; the package ships no preset
+numbers: every probability of `AugmentConfig` defaults to 0, which is the identity.
+"""
+import dataclasses
+import math
+from typing import Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+
+PARAMS_PER_SAMPLE = 24
+# record layout (include/unet_hip.h)
+P_H, P_ALPHA, P_BETA, P_GRAY, P_SIGMA, P_HOLE, P_HOLE_FILL, P_MASK_BORDER, P_MASK_HOLE = \
+    0, 9, 10, 13, 14, 15, 19, 20, 21
+PERSPECTIVE_CLIP = 3.0      # a corner moves inward by min(|z|, 3) * scale of the image size
+
+
+def _pair(v):
+    """A limit given as one number means (-v, v), as in the reference's library."""
+    if isinstance(v, (int, float)):
+        return (-float(v), float(v))
+    a, b = v
+    return (float(a), float(b))
+
+
+@dataclasses.dataclass
+class AugmentConfig:
+    """Probabilities and limits of the supported transforms; the default is the identity."""
+    horizontal_flip_prob: float = 0.0
+    # ShiftScaleRotate about the image centre: shift in fractions of the size, scale 1 + U(limit),
+    # rotation in degrees
+    shift_scale_rotate_prob: float = 0.0
+    shift_limit: Tuple[float, float] = (0.0, 0.0)
+    scale_limit: Tuple[float, float] = (0.0, 0.0)
+    rotate_limit: Tuple[float, float] = (0.0, 0.0)
+    # RandomResizedCrop to the batch size: area fraction and (log-uniform) aspect ratio
+    crop_prob: float = 0.0
+    crop_scale: Tuple[float, float] = (1.0, 1.0)
+    crop_ratio: Tuple[float, float] = (1.0, 1.0)
+    # Perspective: each corner moves inward by min(|N(0, 1)|, 3) * s of the size, s ~ U(scale)
+    perspective_prob: float = 0.0
+    perspective_scale: Tuple[float, float] = (0.0, 0.0)
+    # CoarseDropout, one hole (sizes in pixels, inclusive)
+    dropout_prob: float = 0.0
+    dropout_height: Tuple[int, int] = (0, 0)
+    dropout_width: Tuple[int, int] = (0, 0)
+    dropout_fill: float = 0.0
+    dropout_mask_fill: float = 0.0
+    # OneOf(RandomBrightnessContrast, RGBShift)
+    color_prob: float = 0.0
+    brightness_contrast_prob: float = 0.0
+    brightness_limit: Tuple[float, float] = (0.0, 0.0)
+    contrast_limit: Tuple[float, float] = (0.0, 0.0)
+    rgb_shift_prob: float = 0.0
+    rgb_shift_limit: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+    # OneOf(ToGray)
+    gray_group_prob: float = 0.0
+    to_gray_prob: float = 0.0
+    # OneOf(GaussNoise)
+    noise_group_prob: float = 0.0
+    gauss_noise_prob: float = 0.0
+    gauss_var_limit: Tuple[float, float] = (0.0, 0.0)
+    # SaltAndPepper: shares of the pixels
+    salt_pepper_prob: float = 0.0
+    salt_p: Tuple[float, float] = (0.0, 0.0)
+    pepper_p: Tuple[float, float] = (0.0, 0.0)
+    # value of mask pixels that come from outside the image
+    mask_border_value: float = 0.0
+
+    @classmethod
+    def from_yaml(cls, path, section):
+        """The `section` ("cat" / "dog") of a file in the format of the reference's
+        data_augmentation/config/augmentation_config.yaml.  Keys of unsupported transforms are
+        ignored; a transform whose keys are absent stays off."""
+        import yaml      # lazily: only this constructor needs it
+        with open(path) as f:
+            doc = yaml.safe_load(f)
+        if section not in doc:
+            raise KeyError(f"{path} has no section '{section}' (found {sorted(doc)})")
+        s = doc[section]
+        c = cls()
+        c.horizontal_flip_prob = float(s.get("horizontal_flip_prob", 0.0))
+        c.shift_scale_rotate_prob = float(s.get("shift_scale_rotate_prob", 0.0))
+        c.shift_limit = _pair(s.get("shift_limit", 0.0))
+        c.scale_limit = _pair(s.get("scale_limit", 0.0))
+        c.rotate_limit = _pair(s.get("rotate_limit", 0.0))
+        g = s.get("random_resized_crop") or {}
+        c.crop_prob = float(g.get("prob", 0.0))
+        c.crop_scale = _pair(g.get("scale", (1.0, 1.0)))
+        c.crop_ratio = _pair(g.get("ratio", (1.0, 1.0)))
+        g = s.get("perspective") or {}
+        c.perspective_prob = float(g.get("prob", 0.0))
+        sc = g.get("scale", (0.0, 0.0))
+        c.perspective_scale = (0.0, float(sc)) if isinstance(sc, (int, float)) else _pair(sc)
+        g = s.get("coarse_dropout") or {}
+        if int(g.get("max_holes", 1)) != 1:
+            raise ValueError("CoarseDropout is supported with one hole (max_holes: 1)")
+        c.dropout_prob = float(g.get("prob", 0.0))
+        c.dropout_height = (int(g.get("min_height", 0)), int(g.get("max_height", 0)))
+        c.dropout_width = (int(g.get("min_width", 0)), int(g.get("max_width", 0)))
+        c.dropout_fill = float(g.get("fill_value", 0.0))
+        c.color_prob = float(s.get("color_transform_prob", 0.0))
+        g = s.get("brightness_contrast") or {}
+        c.brightness_contrast_prob = float(g.get("prob", 0.0))
+        c.brightness_limit = _pair(g.get("brightness_limit", 0.0))
+        c.contrast_limit = _pair(g.get("contrast_limit", 0.0))
+        g = s.get("rgb_shift") or {}
+        c.rgb_shift_prob = float(g.get("prob", 0.0))
+        c.rgb_shift_limit = tuple(float(g.get(k, 0.0))
+                                  for k in ("r_shift_limit", "g_shift_limit", "b_shift_limit"))
+        g = s.get("clahe_equalize") or {}
+        c.gray_group_prob = float(g.get("prob", 0.0))
+        c.to_gray_prob = float(g.get("to_gray_prob", 0.0))
+        c.noise_group_prob = float(s.get("noise_transform_prob", 0.0))
+        g = s.get("gauss_noise") or {}
+        c.gauss_noise_prob = float(g.get("prob", 0.0))
+        c.gauss_var_limit = _pair(g.get("var_limit", (0.0, 0.0)))
+        g = s.get("salt_pepper") or {}
+        c.salt_pepper_prob = float(g.get("prob", 0.0))
+        c.salt_p = _pair(g.get("salt_p", (0.0, 0.0)))
+        c.pepper_p = _pair(g.get("pepper_p", (0.0, 0.0)))
+        return c
+
+
+def identity_params(n):
+    """fp32 [n, 24]: the record that returns the batch unchanged."""
+    p = torch.zeros(n, PARAMS_PER_SAMPLE, dtype=torch.float32)
+    p[:, 0] = p[:, 4] = p[:, 8] = 1.0
+    p[:, P_ALPHA] = 1.0
+    return p
+
+
+def validate_params(params, H, W):
+    """Refuse a record the kernel would treat as "everything outside": every value must be
+    finite and den = h6 x + h7 y + h8 positive at the four corners of the output (it is linear in
+    (x, y), so it is then positive on every pixel)."""
+    p = params.detach().cpu().numpy() if torch.is_tensor(params) else np.asarray(params)
+    if p.ndim != 2 or p.shape[1] != PARAMS_PER_SAMPLE:
+        raise ValueError(f"params must be [n, {PARAMS_PER_SAMPLE}]")
+    if not np.isfinite(p).all():
+        raise ValueError("augmentation record holds a non-finite value")
+    p = p.astype(np.float64)
+    for x, y in ((0.0, 0.0), (W, 0.0), (0.0, H), (W, H)):
+        den = p[:, 6] * x + p[:, 7] * y + p[:, 8]
+        if not (den > 0).all():
+            raise ValueError("augmentation record has den <= 0 at an output corner "
+                             f"(sample {int(np.argmin(den))})")
+
+
+def pack_rng(rng):
+    """int32 [n, 4] holding the bits of the uint32 words the kernel reads (`sample_params` keeps
+    them as int64 in 0 .. 2^32 - 1, which every torch build can store)."""
+    a = rng.detach().cpu().numpy() if torch.is_tensor(rng) else np.asarray(rng)
+    if a.ndim != 2 or a.shape[1] != 4 or (a < 0).any() or (a > 0xFFFFFFFF).any():
+        raise ValueError("rng must be [n, 4] with values in 0 .. 2^32 - 1")
+    return torch.from_numpy(a.astype(np.uint32).view(np.int32).copy())
+
+
+def _rect_to_quad(W, H, quad):
+    """[m, 3, 3]: the homography that takes the corners (0,0), (W,0), (W,H), (0,H) of the
+    rectangle to quad [m, 4, 2], with the last entry 1."""
+    m = quad.shape[0]
+    src = np.array([[0.0, 0.0], [W, 0.0], [W, H], [0.0, H]])
+    A = np.zeros((m, 8, 8))
+    b = np.zeros((m, 8))
+    for k in range(4):
+        x, y = src[k]
+        u, v = quad[:, k, 0], quad[:, k, 1]
+        A[:, 2 * k, 0:3] = (x, y, 1.0)
+        A[:, 2 * k, 6] = -u * x
+        A[:, 2 * k, 7] = -u * y
+        A[:, 2 * k + 1, 3:6] = (x, y, 1.0)
+        A[:, 2 * k + 1, 6] = -v * x
+        A[:, 2 * k + 1, 7] = -v * y
+        b[:, 2 * k] = u
+        b[:, 2 * k + 1] = v
+    h = np.linalg.solve(A, b[..., None])[..., 0]
+    return np.concatenate([h, np.ones((m, 1))], axis=1).reshape(m, 3, 3)
+
+
+def sample_params(cfg, n, H, W, generator, which=None, return_applied=False):
+    """Draw n records: (params fp32 [n, 24], rng int64 [n, 4] with values in 0 .. 2^32 - 1), both
+    on the CPU.  `cfg` is an AugmentConfig, or a sequence of them with `which[i]` selecting the
+    configuration of sample i (the reference's cat / dog split).  `generator` is a CPU
+    torch.Generator; the same generator state gives the same records.  The records are validated
+    (`validate_params`) before they are returned.  With `return_applied` a dict of boolean [n]
+    arrays (which transform fired for which sample) comes third."""
+    cfgs = [cfg] if isinstance(cfg, AugmentConfig) else list(cfg)
+    if which is None:
+        if len(cfgs) != 1:
+            raise ValueError("several configurations need `which`")
+        sel = np.zeros(n, dtype=np.int64)
+    else:
+        sel = np.asarray(torch.as_tensor(which).cpu().numpy(), dtype=np.int64).reshape(-1)
+        if sel.shape[0] != n or (sel < 0).any() or (sel >= len(cfgs)).any():
+            raise ValueError("`which` must hold n indices into the configurations")
+
+    def f(name):        # the field per sample: [n] or [n, k]
+        return np.asarray([getattr(c, name) for c in cfgs], dtype=np.float64)[sel]
+
+    U = torch.rand(n, 40, dtype=torch.float64, generator=generator).numpy()
+    Z = torch.randn(n, 8, dtype=torch.float64, generator=generator).numpy()
+    seeds = torch.randint(0, 1 << 32, (n, 2), dtype=torch.int64, generator=generator).numpy()
+    col = iter(range(40))
+
+    def uni(lim):       # U(lim[:, 0], lim[:, 1])
+        return lim[:, 0] + (lim[:, 1] - lim[:, 0]) * U[:, next(col)]
+
+    def fires(prob):
+        return U[:, next(col)] < prob
+
+    applied = {}
+    eye = np.broadcast_to(np.eye(3), (n, 3, 3)).copy()
+    Hinv = eye.copy()       # output -> source: the inverses, multiplied in the order applied
+    cx, cy = W / 2.0, H / 2.0
+
+    flip = fires(f("horizontal_flip_prob"))
+    applied["flip"] = flip
+    F = eye.copy()
+    F[:, 0, 0], F[:, 0, 2] = -1.0, float(W)
+    Hinv = np.where(flip[:, None, None], Hinv @ F, Hinv)
+
+    ssr = fires(f("shift_scale_rotate_prob"))
+    applied["shift_scale_rotate"] = ssr
+    ang = np.radians(uni(f("rotate_limit")))
+    sc = 1.0 + uni(f("scale_limit"))
+    tx = cx + uni(f("shift_limit")) * W
+    ty = cy + uni(f("shift_limit")) * H
+    co, si = np.cos(ang) / sc, np.sin(ang) / sc
+    S = eye.copy()      # inverse of T(c + d) R(ang) sc T(-c)
+    S[:, 0, 0], S[:, 0, 1], S[:, 0, 2] = co, si, cx - (co * tx + si * ty)
+    S[:, 1, 0], S[:, 1, 1], S[:, 1, 2] = -si, co, cy - (-si * tx + co * ty)
+    Hinv = np.where(ssr[:, None, None], Hinv @ S, Hinv)
+
+    crop = fires(f("crop_prob"))
+    applied["crop"] = crop
+    area = uni(f("crop_scale"))
+    ratio = np.exp(uni(np.log(f("crop_ratio"))))
+    cw = np.minimum(np.sqrt(area * ratio), 1.0) * W     # a crop larger than the image is clipped
+    ch = np.minimum(np.sqrt(area / ratio), 1.0) * H
+    x0 = U[:, next(col)] * (W - cw)
+    y0 = U[:, next(col)] * (H - ch)
+    C = eye.copy()      # inverse of "crop (x0, y0, cw, ch), resize to (W, H)"
+    C[:, 0, 0], C[:, 0, 2], C[:, 1, 1], C[:, 1, 2] = cw / W, x0, ch / H, y0
+    Hinv = np.where(crop[:, None, None], Hinv @ C, Hinv)
+
+    persp = fires(f("perspective_prob"))
+    applied["perspective"] = persp
+    d = np.minimum(np.abs(Z), PERSPECTIVE_CLIP) * uni(f("perspective_scale"))[:, None]
+    if persp.any():
+        quad = np.empty((n, 4, 2))
+        quad[:, 0] = np.stack([d[:, 0] * W, d[:, 1] * H], 1)
+        quad[:, 1] = np.stack([W - d[:, 2] * W, d[:, 3] * H], 1)
+        quad[:, 2] = np.stack([W - d[:, 4] * W, H - d[:, 5] * H], 1)
+        quad[:, 3] = np.stack([d[:, 6] * W, H - d[:, 7] * H], 1)
+        Hinv[persp] = Hinv[persp] @ _rect_to_quad(float(W), float(H), quad[persp])
+        # den = 1 at the centre of the output
+        cen = Hinv[persp, 2, 0] * cx + Hinv[persp, 2, 1] * cy + Hinv[persp, 2, 2]
+        Hinv[persp] = Hinv[persp] / cen[:, None, None]
+
+    p = np.zeros((n, PARAMS_PER_SAMPLE), dtype=np.float64)
+    p[:, 0:9] = Hinv.reshape(n, 9)
+    p[:, P_ALPHA] = 1.0
+    p[:, P_MASK_BORDER] = f("mask_border_value")
+
+    drop = fires(f("dropout_prob"))
+    applied["dropout"] = drop
+    hh, hw = f("dropout_height"), f("dropout_width")
+    dh = np.minimum(hh[:, 0] + np.floor(U[:, next(col)] * (hh[:, 1] - hh[:, 0] + 1)), H)
+    dw = np.minimum(hw[:, 0] + np.floor(U[:, next(col)] * (hw[:, 1] - hw[:, 0] + 1)), W)
+    dy = np.floor(U[:, next(col)] * (H - dh + 1))
+    dx = np.floor(U[:, next(col)] * (W - dw + 1))
+    hole = np.stack([dx, dy, dx + dw, dy + dh], 1)
+    p[:, P_HOLE:P_HOLE + 4] = np.where(drop[:, None], hole, 0.0)
+    p[:, P_HOLE_FILL] = f("dropout_fill")
+    p[:, P_MASK_HOLE] = f("dropout_mask_fill")
+
+    # OneOf(RandomBrightnessContrast, RGBShift)
+    pb, pr = f("brightness_contrast_prob"), f("rgb_shift_prob")
+    group = fires(f("color_prob")) & (pb + pr > 0)
+    pick_b = U[:, next(col)] * (pb + pr) < pb
+    bc, rgb = group & pick_b, group & ~pick_b
+    applied["brightness_contrast"], applied["rgb_shift"] = bc, rgb
+    alpha = 1.0 + uni(f("contrast_limit"))
+    beta = uni(f("brightness_limit")) * 255.0
+    p[:, P_ALPHA] = np.where(bc, alpha, 1.0)
+    lim = f("rgb_shift_limit")
+    for c in range(3):
+        shift = (2.0 * U[:, next(col)] - 1.0) * lim[:, c]
+        p[:, P_BETA + c] = np.where(bc, beta, 0.0) + np.where(rgb, shift, 0.0)
+
+    gray = fires(f("gray_group_prob")) & (f("to_gray_prob") > 0)
+    applied["gray"] = gray
+    p[:, P_GRAY] = gray
+
+    gauss = fires(f("noise_group_prob")) & (f("gauss_noise_prob") > 0)
+    applied["gauss_noise"] = gauss
+    p[:, P_SIGMA] = np.where(gauss, np.sqrt(np.maximum(uni(f("gauss_var_limit")), 0.0)), 0.0)
+
+    sp = fires(f("salt_pepper_prob"))
+    applied["salt_pepper"] = sp
+    rng = np.zeros((n, 4), dtype=np.int64)
+    rng[:, 0:2] = seeds
+    for k, name in ((2, "pepper_p"), (3, "salt_p")):
+        share = np.clip(uni(f(name)), 0.0, 1.0)
+        thr = np.minimum(np.rint(share * 4294967296.0), 4294967295.0).astype(np.int64)
+        rng[:, k] = np.where(sp, thr, 0)
+
+    params = torch.from_numpy(p.astype(np.float32))
+    validate_params(params, H, W)
+    out = (params, torch.from_numpy(rng))
+    return out + (applied,) if return_applied else out
+
+
+class BatchAugment:
+    """Draws the records of a batch and launches `unet_augment_u8` on the current stream.
+
+        aug = BatchAugment(cfg, seed=0)                   # or BatchAugment([cat, dog], seed)
+        image, mask = aug(images_u8, masks_u8)            # which=[0, 1, ...] with two configs
+        aug(images_u8, masks_u8, out=(step.images, step.masks))   # into a GraphedTrainStep's
+                                                          # static buffers: its __call__ then
+                                                          # skips the copy (same data_ptr)
+
+    `params=(params, rng)` (CPU tensors as `sample_params` returns them; `rng` may be None: then
+    all noise is off) replaces the draw.  The records travel through a ring of two pinned host
+    buffers with non_blocking copies; an event per buffer keeps it from being rewritten while
+    its copy is in flight."""
+
+    def __init__(self, cfg, seed=0):
+        self.cfg = cfg
+        self.generator = torch.Generator()
+        self.generator.manual_seed(int(seed))
+        self._ring = None
+        self._next = 0
+
+    def _stage(self, params, rng, device):
+        n = params.shape[0]
+        if self._ring is None or self._ring[0]["n"] != n or self._ring[0]["device"] != device:
+            self._ring = [{
+                "n": n, "device": device, "event": None,
+                "hp": torch.empty((n, PARAMS_PER_SAMPLE), dtype=torch.float32, pin_memory=True),
+                "hr": torch.empty((n, 4), dtype=torch.int32, pin_memory=True),
+                "dp": torch.empty((n, PARAMS_PER_SAMPLE), dtype=torch.float32, device=device),
+                "dr": torch.empty((n, 4), dtype=torch.int32, device=device),
+            } for _ in range(2)]
+            self._next = 0
+        slot = self._ring[self._next]
+        self._next ^= 1
+        if slot["event"] is not None:
+            slot["event"].synchronize()         # the copy out of this host buffer has finished
+        slot["hp"].copy_(params)
+        slot["dp"].copy_(slot["hp"], non_blocking=True)
+        dr = None
+        if rng is not None:
+            slot["hr"].copy_(pack_rng(rng))
+            slot["dr"].copy_(slot["hr"], non_blocking=True)
+            dr = slot["dr"]
+        slot["event"] = torch.cuda.Event()
+        slot["event"].record()
+        return slot["dp"], dr
+
+    def __call__(self, images_u8, masks_u8=None, which=None, out=None, params=None):
+        if not torch.is_tensor(images_u8) or not images_u8.is_cuda:
+            raise RuntimeError("unet-implementations_amd.BatchAugment runs on MI355X only "
+                               "(no CPU fallback exists)")
+        N, H, W, _ = images_u8.shape
+        if params is None:
+            p, r = sample_params(self.cfg, N, H, W, self.generator, which=which)
+        else:
+            p, r = params if isinstance(params, (tuple, list)) else (params, None)
+            if tuple(p.shape) != (N, PARAMS_PER_SAMPLE):
+                raise ValueError(f"params must be [{N}, {PARAMS_PER_SAMPLE}]")
+            validate_params(p, H, W)
+        dp, dr = self._stage(p.to(torch.float32), r, images_u8.device)
+        return ops.augment_u8(images_u8, masks_u8, dp, dr, out=out)

@@ -1334,6 +1334,51 @@ def gradcam_heatmap(cam, ws, size):
     return out
 
 
+# ---- online batch augmentation (augment.hip) -------------------------------------------------
+def augment_u8(image, mask, params, rng=None, out=None):
+    """(image_out, mask_out): uint8 [N,H,W,3] / [N,H,W] augmented by one launch of
+    `unet_augment_u8` on the current stream.  params: fp32 [N, 24] and rng: int32 / uint32
+    [N, 4] (or None: all noise off) are DEVICE tensors the kernel reads, so a captured launch
+    follows records written into them later.  mask may be None (mask_out is then None).
+    out=(image_out, mask_out) names the tensors to write; they must not overlap the inputs."""
+    if not torch.is_tensor(image) or not image.is_cuda:
+        raise RuntimeError("unet-implementations_amd.augment_u8 runs on MI355X only "
+                           "(no CPU fallback exists)")
+    if image.dim() != 4 or image.shape[3] != 3 or image.dtype != torch.uint8 or \
+            not image.is_contiguous():
+        raise TypeError("augment_u8 takes a contiguous uint8 [N,H,W,3] image")
+    N, H, W, _ = image.shape
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (N, H, W) or
+                             not mask.is_contiguous() or mask.device != image.device):
+        raise TypeError("mask must be a contiguous uint8 [N,H,W] tensor on the image's device")
+    nrec = lib().unet_augment_params_per_sample()
+    if params.dtype != torch.float32 or tuple(params.shape) != (N, nrec) or \
+            not params.is_contiguous() or params.device != image.device:
+        raise TypeError(f"params must be a contiguous fp32 [N, {nrec}] tensor on the image's device")
+    if rng is not None and (rng.element_size() != 4 or rng.is_floating_point() or
+                            tuple(rng.shape) != (N, 4) or not rng.is_contiguous() or
+                            rng.device != image.device):
+        raise TypeError("rng must be a contiguous int32 / uint32 [N, 4] tensor on the image's "
+                        "device")
+    if out is None:
+        image_out = torch.empty_like(image)
+        mask_out = torch.empty_like(mask) if mask is not None else None
+    else:
+        image_out, mask_out = out
+        for o, like, name in ((image_out, image, "image_out"), (mask_out, mask, "mask_out")):
+            if like is None:
+                continue
+            if o is None or o.dtype != torch.uint8 or o.shape != like.shape or \
+                    not o.is_contiguous() or o.device != image.device:
+                raise TypeError(f"{name} must be a contiguous uint8 tensor of its input's shape")
+        if mask is None:
+            mask_out = None
+    check(lib().unet_augment_u8(_ptr(image), _ptr(mask), _ptr(image_out), _ptr(mask_out),
+                                _ptr(params), rng.data_ptr() if rng is not None else None,
+                                N, H, W, _stream()))
+    return image_out, mask_out
+
+
 def preprocess_u8(image_hwc_u8, mask_u8=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """uint8 [N,H,W,3] (+ uint8 [N,H,W]) on the device -> (fp32 NHWC image, int64 target)."""
     N, H, W, C = image_hwc_u8.shape

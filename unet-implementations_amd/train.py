@@ -266,8 +266,12 @@ def load_checkpoint(path, model, optimizer=None, scheduler=None, device="cuda"):
     return checkpoint["epoch"] + 1, checkpoint["best_dice"]
 
 
-def train_one_epoch(model, train_loader, optimizer, loss_function, device, scaler=None):
-    """Signature-compatible with the reference's train_one_epoch (src/train.py:592-680)."""
+def train_one_epoch(model, train_loader, optimizer, loss_function, device, scaler=None,
+                    augment=None, input_layout=None):
+    """Signature-compatible with the reference's train_one_epoch (src/train.py:592-680).
+    `augment` (optional, an `augment.BatchAugment`) takes each uint8 batch (images [N,H,W,3],
+    masks [N,H,W]; a "which" entry of the batch selects the configuration per sample) through
+    the augmentation kernel before the step; `input_layout` is handed to `train_step`."""
     if scaler is not None:
         raise NotImplementedError("fp16 GradScaler AMP is not part of the fp32 HIP path")
     model.train()
@@ -276,6 +280,9 @@ def train_one_epoch(model, train_loader, optimizer, loss_function, device, scale
     for batch in train_loader:
         images = batch["image"].to(device, non_blocking=True)
         masks = batch["mask"].to(device, non_blocking=True)
-        total += train_step(model, optimizer, loss_function, images, masks)
+        if augment is not None:
+            images, masks = augment(images, masks, which=batch.get("which"))
+        total += train_step(model, optimizer, loss_function, images, masks,
+                            input_layout=input_layout)
         n += 1
     return (total / max(n, 1)).item()
