@@ -962,6 +962,58 @@ int unet_ssim_grad(const float* pred_nchw, const void* target, int target_u8,
                    int upstream_per_image, double w_ssim, double w_mse, float* dpred_nchw, int N,
                    int C, int H, int W, unet_stream_t stream);
 
+/* ---- Perceptual (VGG16 feature) loss (perceptual.hip) -------------------------------------------
+ * PerceptualLoss (AE_pretrained/reconstruction/models/losses.py:82-168): the mean over the tapped
+ * layers of F.mse_loss between the features of a frozen, randomly initialised VGG16
+ * (models.vgg16(weights=None), :100) on the normalised output and target.  A trunk layer is
+ * relu(conv3x3(x) + b): the convolutions run on the fused pipeline's entry points with the RAW
+ * output y_l stored once and relu applied on load (unet_act_src with alpha = 1, beta = 0 and
+ * slope = 0), on the STACKED tensor of 2N images - images 0..N-1 the output, N..2N-1 the target -
+ * so one launch serves both streams; the reference's four prefix passes (:156-163) become one pass
+ * with taps.  The entry points below are everything around the convolutions.  fp32 NHWC layer
+ * tensors, C % 32 == 0, 64-bit indexing; reductions through per-workgroup partials in double and
+ * a fixed-order finalize (bit-identical from run to run); no host synchronisation. */
+
+/* PerceptualLoss._normalize (:134-136) into the stacked tensor: xn [2N][H][W][3] (plain NHWC) =
+ * (x - mean[c]) / std[c], subtraction and division each correctly rounded (the reference's two
+ * operations).  Images 0..N-1 from out_nchw [N,3,H,W]; N..2N-1 from target: the NCHW fp32 tensor
+ * (target_u8 == 0) or the dataset's uint8 NHWC image (target_u8 == 1, v / 255 rounded once to
+ * fp32 as unet_mse_loss_fwd).  mean3 / std3: 3 host floats each. */
+int unet_perceptual_prep(const float* out_nchw, const void* target, int target_u8,
+                         const float* mean3, const float* std3, float* xn, int N, int H, int W,
+                         unet_stream_t stream);
+/* nn.ReLU + nn.MaxPool2d(2, 2) of the trunk (torchvision configuration "D"): raw y [M][H][W][C]
+ * -> plain p [M][H/2][W/2][C] = max(0, max of the 2x2 window); floor semantics, an odd last row
+ * or column is ignored.  H, W >= 2. */
+int unet_relu_maxpool2x2_fwd(const float* y, float* p, int M, int H, int W, int C,
+                             unet_stream_t stream);
+/* The sums of F.mse_loss(output_features, target_features) (:162) of one tapped layer: over raw
+ * y [2N][H][W][C], sums[n] (double, n < N) = sum over the image of (relu(y[n]) - relu(y[n+N]))^2,
+ * every term two fp32 roundings, the sum in double.  The order of the sum depends on (H, W, C)
+ * only: an image pair's value is bit-identical in any batch.  The caller forms
+ * loss = (1/L) sum_l sum_n sums[l][n] / (N C_l H_l W_l)  (:162-166). */
+size_t unet_feature_mse_workspace_bytes(int N, int H, int W, int C);
+int unet_feature_mse_fwd(const float* y, double* sums, void* workspace, size_t workspace_bytes,
+                         int N, int H, int W, int C, unet_stream_t stream);
+/* autograd of one trunk layer between two convolutions, for the output half y_o [N][H][W][C]:
+ *   dz = y_o > 0 ? g_in + coef * (relu(y_o) - relu(y_t)) : 0
+ * the ReLU backward, the layer's own feature-MSE gradient (y_t = the target half, NULL at a layer
+ * that is not tapped; coef = 2 / (L N_batch C H W)) and g_in, at most one of
+ *   g  [N][H][W][C]:      the data gradient of the next convolution, or
+ *   gp [N][H/2][W/2][C]:  the gradient of the following 2x2 max-pool's output, routed to the
+ *                         window's first maximum in row-major order (PyTorch's rule); positions
+ *                         of an ignored odd row or column receive 0 from it.
+ * Both NULL: the deepest tapped layer (y_t required). */
+int unet_perceptual_relu_bwd(const float* y_o, const float* y_t, float coef, const float* g,
+                             const float* gp, float* dz, int N, int H, int W, int C,
+                             unet_stream_t stream);
+/* Data gradient of conv1_1 with the normalisation's 1/std folded in: dout_nchw [N,3,H,W] =
+ * conv3x3_transpose(dz [N][H][W][Cout], w_oihw [Cout][3][3][3])[c] / std3[c] (3 host floats), the
+ * gradient with respect to the loss's `output` argument (:150).  Cout % 32 == 0, any H, W. */
+int unet_perceptual_stem_bwd_data(const float* dz, const float* w_oihw, const float* std3,
+                                  float* dout_nchw, int N, int H, int W, int Cout,
+                                  unet_stream_t stream);
+
 /* ---- Grad-CAM (Our_UNet/utils/visualize.py:372-439) ---------------------------------------- *
  * The tail of generate_gradcam_heatmap after the backward pass, for a whole batch: A = the output
  * of the target stage, G = dL/dA, both NHWC [N][HW][C] in the layer tensors' storage type

@@ -7,7 +7,7 @@ root: `import unet_implementations_amd as ua`.
 """
 from . import _lib, ops  # noqa: F401
 from ._lib import LIB_PATH, UNetHipError, build, lib  # noqa: F401
-from .losses import MSELoss, ReconstructionLoss, SimpleLoss, SSIMLoss  # noqa: F401
+from .losses import MSELoss, PerceptualLoss, ReconstructionLoss, SimpleLoss, SSIMLoss  # noqa: F401
 from .metrics import (SegmentationMetrics, calculate_psnr, calculate_ssim,  # noqa: F401
                       compute_dice, compute_iou, compute_pixel_accuracy, evaluate_model_metrics,
                       evaluate_reconstructions)
@@ -24,6 +24,6 @@ from . import augment  # noqa: F401
 from .augment import AugmentConfig, BatchAugment  # noqa: F401
 from .evaluate import generate_gradcam_heatmap, gradcam, gradcam_batch  # noqa: F401
 
-__all__ = ["UNet", "Autoencoder", "CLIPUNet", "ConvBlock", "UpBlock", "SpatialDropout2d", "SimpleLoss", "MSELoss", "SSIMLoss", "ReconstructionLoss", "calculate_psnr", "calculate_ssim", "evaluate_reconstructions", "SegmentationMetrics", "compute_dice", "compute_iou", "compute_pixel_accuracy", "evaluate_model_metrics", "evaluate", "gradcam", "gradcam_batch", "generate_gradcam_heatmap", "FusedSGD", "FusedAdam", "ae", "augment", "AugmentConfig", "BatchAugment",
+__all__ = ["UNet", "Autoencoder", "CLIPUNet", "ConvBlock", "UpBlock", "SpatialDropout2d", "SimpleLoss", "MSELoss", "SSIMLoss", "PerceptualLoss", "ReconstructionLoss", "calculate_psnr", "calculate_ssim", "evaluate_reconstructions", "SegmentationMetrics", "compute_dice", "compute_iou", "compute_pixel_accuracy", "evaluate_model_metrics", "evaluate", "gradcam", "gradcam_batch", "generate_gradcam_heatmap", "FusedSGD", "FusedAdam", "ae", "augment", "AugmentConfig", "BatchAugment",
            "create_model", "create_optimizer", "create_lr_scheduler", "get_loss_function",
            "train_step", "GraphedTrainStep", "train_one_epoch", "save_checkpoint", "load_checkpoint", "validate", "predict_masks", "ops", "build", "lib", "UNetHipError", "LIB_PATH"]

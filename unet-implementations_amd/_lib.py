@@ -204,6 +204,12 @@ SIGNATURES = {
                            _c.c_double, _p, _sz, _i, _i, _i, _i, _p]),
     "unet_ssim_grad": (_i, [_p, _p, _i, _c.POINTER(_f), _f, _f, _p, _i, _c.c_double, _c.c_double,
                             _p, _i, _i, _i, _i, _p]),
+    "unet_perceptual_prep": (_i, [_p, _p, _i, _c.POINTER(_f), _c.POINTER(_f), _p, _i, _i, _i, _p]),
+    "unet_relu_maxpool2x2_fwd": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "unet_feature_mse_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "unet_feature_mse_fwd": (_i, [_p, _p, _p, _sz, _i, _i, _i, _i, _p]),
+    "unet_perceptual_relu_bwd": (_i, [_p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "unet_perceptual_stem_bwd_data": (_i, [_p, _p, _c.POINTER(_f), _p, _i, _i, _i, _i, _p]),
     "unet_stem_u8_fwd_b16": (_i, [_p, _c.POINTER(_f), _c.POINTER(_f), _p, _p, _p, _p, _sz,
                                   _c.POINTER(_i), _i, _i, _i, _i, _p]),
     "unet_stem_u8_bwd_weight_b16": (_i, [_p, _c.POINTER(_f), _c.POINTER(_f), _p, _p, _p, _sz, _i,

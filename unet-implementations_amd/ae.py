@@ -15,7 +15,7 @@ import torch
 
 from . import ops
 from .autoencoder import Autoencoder
-from .losses import MSELoss
+from .losses import MSELoss, PerceptualLoss, ReconstructionLoss
 from .optim import FusedAdam
 from .train import train_step
 
@@ -48,6 +48,23 @@ def create_lr_scheduler(optimizer, max_epochs):
 def get_loss_function(device=None, target_layout="nchw"):
     """nn.MSELoss() (src/train.py:420-437)."""
     return MSELoss(target_layout=target_layout)
+
+
+def get_reconstruction_loss(mse_weight=1.0, perceptual_weight=0.0, ssim_weight=0.0,
+                            perceptual_layers=None, target_layout="nchw", device=None):
+    """The loss the reference ships and documents - ReconstructionLoss(mse_weight,
+    perceptual_weight, ssim_weight) of models/losses.py:12-79, the recorded run's
+    training_config.json holding 1.0 / 0.1 / 0.1 - which its own get_loss_function never builds
+    (src/train.py:420-437 returns nn.MSELoss() although --perceptual_weight is parsed and written
+    to the config).  With perceptual_weight > 0 the random VGG16 trunk is drawn here, from torch's
+    global generator, as the reference's constructor does.  `device`: where to put the loss (its
+    trunk's weights and buffers); None leaves it on the CPU for the caller's `.to(device)`."""
+    perceptual = None
+    if perceptual_weight > 0:
+        perceptual = PerceptualLoss(layers=perceptual_layers, target_layout=target_layout)
+    loss = ReconstructionLoss(mse_weight, perceptual_weight, ssim_weight,
+                              target_layout=target_layout, perceptual=perceptual)
+    return loss if device is None else loss.to(device)
 
 
 def train_one_epoch(model, train_loader, optimizer, loss_function, device, scaler=None):

@@ -1576,3 +1576,106 @@ def ssim_grad(pred, target, upstream=None, upstream_per_image=False, target_u8=F
         _timer.end("ssim_grad", 0.0, 1, t0, nbytes=8.0 * pred.numel() + target.element_size() *
                    target.numel())
     return dpred
+
+
+# ---- perceptual (VGG16 feature) loss (perceptual.hip) -------------------------------------------
+def conv_fwd_raw(s0, slope, w, bias, wu=None):
+    """y = conv3x3(act(s0)) + bias (stride 1) on the fused layer's kernels WITHOUT the statistics
+    finalize: the launch of `conv_in_fwd`, its per-tile summaries ignored (a layer with no
+    InstanceNorm behind it: the perceptual loss's trunk).  wu: the Winograd forward form - the
+    caller checked `conv_wino_supported` and s0 carries alpha / beta."""
+    s0, r0 = _act(s0)
+    N, H, W, C0 = s0.shape
+    Cout = w.shape[1]
+    assert w.shape[0] == 9 and w.shape[2] == C0
+    wino = wu is not None
+    fn, form, tag = _sel_conv_in_fwd(False, False, wino, False, 3, C0)
+    head = (r0, None, slope, _ptr(wu), _ptr(bias)) if wino else \
+        (r0, None, slope, _ptr(w), _ptr(bias), 3, 1)
+    y, _, _, _, t0 = _conv_stats_launch(fn, head, False, s0.x, N, H, W, Cout, 1)
+    if t0 is not None:
+        if not wino and C0 != 3:
+            wino = _c32_winograd(N, H, W, C0, Cout, 1)
+        _end_conv(t0, tag, 2.0 * N * H * W * 9 * C0 * Cout, 1, wino)
+    return y
+
+
+def _mean_std3(mean, std):
+    return (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+
+
+def perceptual_prep(out, target, target_u8=False, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """The stacked, normalised NHWC tensor [2N,H,W,3] of PerceptualLoss: (x - mean) / std of the
+    output (images 0..N-1) and of the target (N..2N-1; NCHW fp32 or the uint8 NHWC image)."""
+    N, C, H, W = out.shape
+    if C != 3:
+        raise ValueError("the perceptual loss takes RGB images")
+    target = _mse_target(out, target, target_u8)
+    xn = _f32((2 * N, H, W, 3), out)
+    m, s = _mean_std3(mean, std)
+    t0 = _begin()
+    check(lib().unet_perceptual_prep(_ptr(out), _ptr(target), 1 if target_u8 else 0, m, s,
+                                     _ptr(xn), N, H, W, _stream()))
+    if t0 is not None:
+        _timer.end("perceptual_prep", 0.0, 1, t0, nbytes=4.0 * out.numel() + 4.0 * xn.numel() +
+                   target.element_size() * target.numel())
+    return xn
+
+
+def relu_maxpool2x2_fwd(y):
+    """max_pool2d(relu(y), 2) of a raw NHWC tensor (floor semantics) as a plain tensor."""
+    M, H, W, C = y.shape
+    p = _f32((M, H // 2, W // 2, C), y)
+    t0 = _begin()
+    check(lib().unet_relu_maxpool2x2_fwd(_ptr(y), _ptr(p), M, H, W, C, _stream()))
+    if t0 is not None:
+        _timer.end("relu_maxpool", 0.0, 1, t0, nbytes=4.0 * (4 * p.numel() + p.numel()))
+    return p
+
+
+def feature_mse_fwd(y, sums):
+    """sums[n] (fp64 [N]) = sum (relu(y[n]) - relu(y[n + N]))^2 over the raw stacked [2N,H,W,C]."""
+    M, H, W, C = y.shape
+    N = M // 2
+    if M != 2 * N or sums.dtype != torch.float64 or sums.numel() != N or not sums.is_contiguous():
+        raise ValueError("feature_mse_fwd takes a stacked [2N,H,W,C] tensor and fp64 sums [N]")
+    ws = _ws(lib().unet_feature_mse_workspace_bytes(N, H, W, C), y)
+    t0 = _begin()
+    check(lib().unet_feature_mse_fwd(_ptr(y), sums.data_ptr(), _ptr(ws), ws.numel(), N, H, W, C,
+                                     _stream()))
+    if t0 is not None:
+        _timer.end("feature_mse", 0.0, 2, t0, nbytes=4.0 * y.numel())
+    return sums
+
+
+def perceptual_relu_bwd(y_o, y_t=None, coef=0.0, g=None, gp=None):
+    """dz = y_o > 0 ? g_in + coef * (relu(y_o) - relu(y_t)) : 0 of one trunk layer; g_in = g (same
+    resolution), gp (the following pool's output gradient, routed to the first maximum) or none."""
+    N, H, W, C = y_o.shape
+    for t, shape in ((y_t, y_o.shape), (g, y_o.shape), (gp, (N, H // 2, W // 2, C))):
+        if t is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError("perceptual_relu_bwd: operand shape mismatch")
+    dz = torch.empty_like(y_o)
+    t0 = _begin()
+    check(lib().unet_perceptual_relu_bwd(_ptr(y_o), _ptr(y_t), coef, _ptr(g), _ptr(gp), _ptr(dz),
+                                         N, H, W, C, _stream()))
+    if t0 is not None:
+        nb = 2 + (y_t is not None) + (g is not None) + 0.25 * (gp is not None)
+        _timer.end("perceptual_relu_bwd", 0.0, 1, t0, nbytes=4.0 * nb * y_o.numel())
+    return dz
+
+
+def perceptual_stem_bwd_data(dz, w_oihw, std=IMAGENET_STD, out=None):
+    """dL/doutput (NCHW fp32 [N,3,H,W]) from dz of conv1_1: its data gradient divided by std."""
+    N, H, W, Cout = dz.shape
+    assert tuple(w_oihw.shape) == (Cout, 3, 3, 3)
+    dout = out if out is not None else _f32((N, 3, H, W), dz)
+    assert tuple(dout.shape) == (N, 3, H, W) and dout.dtype == torch.float32
+    _, s = _mean_std3(std, std)
+    t0 = _begin()
+    check(lib().unet_perceptual_stem_bwd_data(_ptr(dz), _ptr(w_oihw), s, _ptr(dout), N, H, W, Cout,
+                                              _stream()))
+    if t0 is not None:
+        _timer.end("perceptual_stem_bwd_data", 2.0 * N * H * W * 27 * Cout, 1, t0,
+                   nbytes=4.0 * (dz.numel() + dout.numel()))
+    return dout
