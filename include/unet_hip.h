@@ -1039,6 +1039,54 @@ int unet_gradcam_map(const unet_act_src* a, int a_bf16, float slope, const float
 int unet_gradcam_heatmap(const float* cam, const void* workspace, size_t workspace_bytes,
                          float* heatmap, int N, int h, int w, int H, int W, unet_stream_t stream);
 
+/* ---- CLIP ViT image tower (vit.hip) -------------------------------------------------------------
+ * ClipPatchExtractor.forward (CLIP_UNet/models/unet.py:581-613): resize to the tower's resolution,
+ * clip_model.encode_image (OpenAI CLIP's VisionTransformer, frozen), broadcast of the embedding to
+ * a 16 x 16 map.  Forward only.  The residual stream [N T, D], LayerNorm statistics, softmax and
+ * every epilogue are fp32; GEMM and attention operands are bf16 (rounded to nearest even) with
+ * fp32 accumulators.  No atomics: two runs are bit-identical.  Limits: T <= 257 tokens, D a
+ * multiple of 64 and <= 1024, head dimension 64 (ViT-B/32, B/16, L/14 at 224); anything else is
+ * UNET_E_INVALID before a launch. */
+
+/* The patch matrix of conv1 (kernel = stride = P, no bias) as a GEMM operand: patches bf16
+ * [N G^2][Kp], G = R / P, row (n, gy, gx), column k = (c P + py) P + px (the order of
+ * conv1.weight.reshape(D, -1)); columns 3 P^2 .. Kp-1 are zero (Kp % 16 == 0).  image: fp32 NCHW
+ * [N,3,H,W] taken as it is (image_u8 == 0; mean3 / std3 unused) or the dataset's uint8 NHWC
+ * [N,H,W,3] with (v / 255 - mean3[c]) / std3[c] folded in (3 host floats each).  H x W != R x R:
+ * F.interpolate(mode="bilinear", align_corners=False) of the normalised image (:595), sampled while
+ * gathering. */
+int unet_vit_patchify(const void* image, int image_u8, const float* mean3, const float* std3,
+                      void* patches, int N, int H, int W, int R, int P, int Kp,
+                      unet_stream_t stream);
+/* out [M][Nout] = a [M][K] w[Nout][K]^T, a and w bf16 with K contiguous, any M, Nout % 64 == 0,
+ * K % 16 == 0; rows >= M of `out` are not touched.  epilogue:
+ *   0  out fp32 = product (bias unused)                  the patch embedding
+ *   1  out bf16 = product + bias[Nout]                   in_proj (QKV)
+ *   2  out bf16 = QuickGELU(product + bias), x sigmoid(1.702 x)   mlp.c_fc
+ *   3  out fp32 += product + bias, in place              out_proj / mlp.c_proj into the stream */
+int unet_vit_gemm_bf16(const void* a, const void* w, const float* bias, void* out, int epilogue,
+                       int M, int Nout, int K, unet_stream_t stream);
+/* Token assembly and ln_pre: out fp32 [N T][D] = LayerNorm over D of
+ * (t == 0 ? cls[D] : patches[n (T-1) + t-1][D]) + pos[t][D]. */
+int unet_vit_tokens_ln(const float* patches, const float* cls, const float* pos,
+                       const float* gamma, const float* beta, float eps, float* out, int N, int T,
+                       int D, unet_stream_t stream);
+/* out bf16 [rows][D] = LayerNorm(x fp32 [rows][D]) * gamma + beta, biased variance of the centred
+ * row, one pass over memory. */
+int unet_vit_layernorm(const float* x, const float* gamma, const float* beta, float eps, void* out,
+                       int rows, int D, unet_stream_t stream);
+/* Multi-head self-attention of nn.MultiheadAttention's packed projection, all (image, head) pairs
+ * in one launch: qkv bf16 [N T][3 D] (q, k, v thirds; head h = columns 64h .. 64h+63 of each),
+ * out bf16 [N T][D] = softmax(q k^T / 8) v.  Scores and the row sum are fp32, the probabilities
+ * are rounded to bf16 for the second product. */
+int unet_vit_attention(const void* qkv, void* out, int N, int T, int D, int heads,
+                       unet_stream_t stream);
+/* ln_post of each image's class row of x [N T][D], @ proj [D][E] (fp32), broadcast to
+ * out fp32 NCHW [N][E][grid][grid] (:611-612: bilinear interpolation from 1 x 1 is a copy). */
+int unet_vit_head(const float* x, const float* gamma, const float* beta, float eps,
+                  const float* proj, float* out, int N, int T, int D, int E, int grid,
+                  unet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

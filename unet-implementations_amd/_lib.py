@@ -210,6 +210,13 @@ SIGNATURES = {
     "unet_feature_mse_fwd": (_i, [_p, _p, _p, _sz, _i, _i, _i, _i, _p]),
     "unet_perceptual_relu_bwd": (_i, [_p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _p]),
     "unet_perceptual_stem_bwd_data": (_i, [_p, _p, _c.POINTER(_f), _p, _i, _i, _i, _i, _p]),
+    "unet_vit_patchify": (_i, [_p, _i, _c.POINTER(_f), _c.POINTER(_f), _p, _i, _i, _i, _i, _i, _i,
+                               _p]),
+    "unet_vit_gemm_bf16": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "unet_vit_tokens_ln": (_i, [_p, _p, _p, _p, _p, _f, _p, _i, _i, _i, _p]),
+    "unet_vit_layernorm": (_i, [_p, _p, _p, _f, _p, _i, _i, _p]),
+    "unet_vit_attention": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "unet_vit_head": (_i, [_p, _p, _p, _f, _p, _p, _i, _i, _i, _i, _i, _p]),
     "unet_stem_u8_fwd_b16": (_i, [_p, _c.POINTER(_f), _c.POINTER(_f), _p, _p, _p, _p, _sz,
                                   _c.POINTER(_i), _i, _i, _i, _i, _p]),
     "unet_stem_u8_bwd_weight_b16": (_i, [_p, _c.POINTER(_f), _c.POINTER(_f), _p, _p, _p, _sz, _i,

@@ -1679,3 +1679,116 @@ def perceptual_stem_bwd_data(dz, w_oihw, std=IMAGENET_STD, out=None):
         _timer.end("perceptual_stem_bwd_data", 2.0 * N * H * W * 27 * Cout, 1, t0,
                    nbytes=4.0 * (dz.numel() + dout.numel()))
     return dout
+
+
+# ---- CLIP ViT image tower (vit.hip) ------------------------------------------------------------
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+VIT_PLAIN, VIT_BIAS, VIT_BIAS_GELU, VIT_BIAS_RESIDUAL = 0, 1, 2, 3
+
+
+def vit_k_padded(patch_size, step=16):
+    """Columns of the patch matrix: 3 P^2 rounded up to the GEMM's K step."""
+    k = 3 * patch_size * patch_size
+    return (k + step - 1) // step * step
+
+
+def vit_patchify(images, resolution, patch_size, input_layout="nchw", mean=CLIP_MEAN,
+                 std=CLIP_STD):
+    """bf16 patch matrix [N G^2, Kp] of fp32 NCHW images (taken as they are) or uint8 NHWC images
+    ("nhwc_u8": (v / 255 - mean) / std folded in), resized to resolution^2 while gathering."""
+    u8 = input_layout == "nhwc_u8"
+    if u8:
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+            raise ValueError('input_layout="nhwc_u8" takes a uint8 [N,H,W,3] batch')
+        N, H, W, _ = images.shape
+    elif input_layout == "nchw":
+        if images.dtype != torch.float32 or images.dim() != 4 or images.shape[1] != 3:
+            raise ValueError('input_layout="nchw" takes an fp32 [N,3,H,W] batch')
+        N, _, H, W = images.shape
+    else:
+        raise ValueError(f"unknown input_layout {input_layout!r}")
+    G = resolution // patch_size
+    Kp = vit_k_padded(patch_size)
+    a = _b16((N * G * G, Kp), images)
+    m, s = _mean_std3(mean, std)
+    t0 = _begin()
+    check(lib().unet_vit_patchify(_ptr(images), 1 if u8 else 0, m, s, _ptr(a), N, H, W, resolution,
+                                  patch_size, Kp, _stream()))
+    if t0 is not None:
+        _timer.end("vit_patchify", 0.0, 1, t0, nbytes=2.0 * a.numel())
+    return a
+
+
+def vit_gemm(a, w, bias=None, epilogue=VIT_PLAIN, out=None):
+    """a [M,K] @ w [Nout,K]^T (bf16 operands, fp32 accumulation) with the epilogue of
+    unet_vit_gemm_bf16; VIT_BIAS_RESIDUAL adds into `out` (the fp32 stream) in place."""
+    M, K = a.shape
+    Nout = w.shape[0]
+    if a.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or w.shape[1] != K:
+        raise ValueError("vit_gemm takes bf16 a [M,K] and w [Nout,K]")
+    if epilogue == VIT_BIAS_RESIDUAL:
+        if out is None or out.dtype != torch.float32 or out.shape[0] < M or out.shape[1] != Nout:
+            raise ValueError("the residual epilogue adds into an fp32 out [>= M, Nout]")
+    elif out is None:
+        out = _f32((M, Nout), a) if epilogue == VIT_PLAIN else _b16((M, Nout), a)
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != Nout):
+        raise ValueError("vit_gemm: bias must be fp32 [Nout]")
+    t0 = _begin()
+    check(lib().unet_vit_gemm_bf16(_ptr(a), _ptr(w), _ptr(bias), _ptr(out), epilogue, M, Nout, K,
+                                   _stream()))
+    if t0 is not None:
+        _timer.end("vit_gemm", 2.0 * M * Nout * K, 1, t0)
+    return out
+
+
+def vit_tokens_ln(patches, cls, pos, gamma, beta, N, eps=1e-5):
+    """The fp32 stream [N T, D]: ln_pre of [cls + pos[0]; patches + pos[1:]]."""
+    T, D = pos.shape
+    out = _f32((N * T, D), patches)
+    t0 = _begin()
+    check(lib().unet_vit_tokens_ln(_ptr(patches), _ptr(cls), _ptr(pos), _ptr(gamma), _ptr(beta),
+                                   eps, _ptr(out), N, T, D, _stream()))
+    if t0 is not None:
+        _timer.end("vit_ln", 0.0, 1, t0, nbytes=8.0 * out.numel())
+    return out
+
+
+def vit_layernorm(x, gamma, beta, eps=1e-5, rows=None):
+    """bf16 LayerNorm of the first `rows` rows of the fp32 x [R, D]."""
+    R, D = x.shape
+    rows = R if rows is None else rows
+    if x.dtype != torch.float32 or rows > R:
+        raise ValueError("vit_layernorm takes an fp32 [rows, D] tensor")
+    out = _b16((rows, D), x)
+    t0 = _begin()
+    check(lib().unet_vit_layernorm(_ptr(x), _ptr(gamma), _ptr(beta), eps, _ptr(out), rows, D,
+                                   _stream()))
+    if t0 is not None:
+        _timer.end("vit_ln", 0.0, 1, t0, nbytes=6.0 * out.numel())
+    return out
+
+
+def vit_attention(qkv, N, T, heads):
+    """softmax(q k^T / 8) v of the packed bf16 projection [N T, 3 D], every head in one launch."""
+    D = qkv.shape[1] // 3
+    if qkv.dtype != torch.bfloat16 or qkv.shape[0] != N * T or qkv.shape[1] != 3 * D:
+        raise ValueError("vit_attention takes the bf16 [N T, 3 D] projection")
+    out = _b16((N * T, D), qkv)
+    t0 = _begin()
+    check(lib().unet_vit_attention(_ptr(qkv), _ptr(out), N, T, D, heads, _stream()))
+    if t0 is not None:
+        _timer.end("vit_attention", 4.0 * N * heads * T * T * 64, 1, t0)
+    return out
+
+
+def vit_head(x, gamma, beta, proj, N, T, grid, eps=1e-5):
+    """ln_post(class rows) @ proj broadcast to fp32 NCHW [N, E, grid, grid]."""
+    D, E = proj.shape
+    out = _f32((N, E, grid, grid), x)
+    t0 = _begin()
+    check(lib().unet_vit_head(_ptr(x), _ptr(gamma), _ptr(beta), eps, _ptr(proj), _ptr(out), N, T,
+                              D, E, grid, _stream()))
+    if t0 is not None:
+        _timer.end("vit_head", 2.0 * N * D * E, 1, t0, nbytes=4.0 * out.numel())
+    return out
