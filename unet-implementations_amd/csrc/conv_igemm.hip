@@ -16,7 +16,7 @@
 //
 // Replaces nn.Conv2d forward / aten::convolution_backward(data) of
 // Our_UNet/models/unet.py:106-115 (reference is NCHW via oneDNN/cuDNN).
-#include "conv_params.h"
+#include "conv_host.h"
 
 namespace unet_conv {
 namespace {
@@ -941,16 +941,6 @@ static int launch_igemm_fused(IgemmParams p, hipStream_t stream, int* stats_px) 
   return launch_igemm<BM, BN, WM, WN, 32, true, KG>(p, stream);
 }
 
-// Deep layers (at most one 64x64 tile per CU): number of K groups per block (1 = no split).
-static int deep_k_groups(const IgemmParams& p) {
-  const long long M = (long long)p.N * p.Hl * p.Wl;
-  if (p.Ncols % 64 != 0 || ceil_div64(M, 64) * (p.Ncols / 64) > 256) return 1;
-  const int ks = p.ntaps * ((p.C0 + p.C1) / 32);
-  int kg = 4;
-  while (kg > 1 && (ks % kg != 0 || ks / kg < 4)) kg >>= 1;
-  return kg;
-}
-
 // plain gather-GEMM launch; with bs_px (data gradient whose output is final for a layer) the
 // BSTATS epilogue runs where every tile lies inside one image, else *bs_px = 0
 template <int BM, int BN, int WM, int WN, int KG = 1>
@@ -975,14 +965,14 @@ static int launch_igemm_deep(IgemmParams p, hipStream_t stream, int* bs_px) {
 int dispatch_igemm(const IgemmParams& p, hipStream_t stream, int* stats_px, int* bs_px) {
   const long long M = (long long)p.N * p.Hl * p.Wl;
   const int nc = p.Ncols;
-  if (patch_f32_applicable(p)) {   // conv_patch.hip; 1 = no tile shape fits this launch
+  if (patch_f32_applicable(p)) {   // conv_patch.hip
     const int rc = launch_patch_f32_auto(p, stream, stats_px, bs_px);
-    if (rc != 1) return rc;
+    if (rc != kNoTileFits) return rc;
   }
   if (stats_px) {
-    if (patch_s2_applicable(p)) {   // conv_patch.hip; 1 = too few tiles
+    if (patch_s2_applicable(p)) {   // conv_patch.hip (kNoTileFits: too few tiles)
       const int rc = launch_patch_s2_auto(p, stream, stats_px);
-      if (rc != 1) return rc;
+      if (rc != kNoTileFits) return rc;
     }
     if (nc % 128 == 0 && ceil_div64(M, 128) * (nc / 128) >= 256)
       return launch_igemm_fused<128, 128, 64, 64>(p, stream, stats_px);
@@ -1340,39 +1330,49 @@ void launch_stem_fwd_rows(const T* x, const float* wf, const float* bias, TO* y,
   }
 }
 
-void fill_fwd_taps(IgemmParams& p, int stride) {
-  p.ntaps = 9;
-  p.tapw[0] = p.tapw[1] = p.tapw[2] = 0;
-  for (int t = 0; t < 9; ++t) set_tap(p, t, t / 3 - 1, t % 3 - 1, t);
-  p.sin = stride;
-  p.sout = 1;
-  p.py = p.px = 0;
+// RGB stem forward by width: raw rows (walking strips of 8 rows where they tile) with the
+// statistics epilogue into `stats` (may be null) where W is a multiple of 128, else the generic
+// form without one.  Returns the pixels per statistics tile (0: none were written).
+template <typename TO>
+int launch_stem_fwd(const float* x, const float* wf, const float* bias, TO* y, int N, int H, int W,
+                    int Cout, float2* stats, hipStream_t stream) {
+  if (W % STEM_ROW_PIX == 0) {
+    launch_stem_fwd_rows<float, TO>(x, wf, bias, y, N, H, W, Cout, stats, StemNorm{}, stream);
+    return STEM_ROW_PIX;
+  }
+  dim3 grid((unsigned)ceil_div64((long long)N * H * W, STEM_PIX), Cout / 32);
+  hipLaunchKernelGGL(conv_stem_fwd_kernel<TO>, grid, dim3(256), 0, stream, x, wf, bias, y, N, H, W,
+                     Cout);
+  return 0;
 }
 
 }  // namespace
 }  // namespace unet_conv
 
+// ---------------------------------------------------------------------------
+// Entry points.  Every export builds its operand mode (conv_host.h ConvMode) in one line and
+// calls the shared impl; an impl validates, walks the batch chunks (for_each_chunk), builds the
+// launch descriptor of a chunk (fwd_params / dgrad_params), binds the BSTATS layer (BsBinder) and
+// tries the kernel forms in order - a form without a tile for the shape answers kNoTileFits.
+// ---------------------------------------------------------------------------
 using namespace unet_conv;
+
+// K = 32: row-fused kernel with the weights resident in LDS; wider K: the patch kernel
+static bool rf_preferred(const IgemmParams& p) {
+  return rf_applicable(p) && (p.C0 + p.C1 == 32 || !patch_f32_applicable(p) || p.Hin % 8 != 0);
+}
 
 static int conv3x3_fwd_impl(const float* x0, int C0, const float* x1, int C1, const float* wf,
                             const float* bias, float* y, int N, int H, int W, int Cout,
-                            int stride, int prec, hipStream_t stream,
-                            const uint16_t* wf3 = nullptr) {
+                            int stride, const ConvMode& m, hipStream_t stream) {
   UNET_REQUIRE(x0 && wf && y, "conv3x3_fwd: null pointer");
-  UNET_REQUIRE(prec != 3 || wf3, "conv3x3_fwd_bf16x3: the pre-split weight planes are null");
+  UNET_REQUIRE(!m.is_split() || m.w3, "conv3x3_fwd_bf16x3: the pre-split weight planes are null");
   UNET_REQUIRE(stride == 1 || stride == 2, "conv3x3_fwd: stride %d unsupported", stride);
   UNET_REQUIRE(N > 0 && H > 0 && W > 0, "conv3x3_fwd: bad shape");
   UNET_REQUIRE(Cout > 0 && Cout % 32 == 0, "conv3x3_fwd: Cout %d must be a multiple of 32", Cout);
   if (C0 == 3) {
     UNET_REQUIRE(C1 == 0 && stride == 1, "conv3x3_fwd: RGB stem is stride-1, single source");
-    const long long M = (long long)N * H * W;
-    if (W % STEM_ROW_PIX == 0) {
-      launch_stem_fwd_rows<float, float>(x0, wf, bias, y, N, H, W, Cout, nullptr, StemNorm{}, stream);
-    } else {
-      dim3 grid((unsigned)ceil_div64(M, STEM_PIX), Cout / 32);
-      hipLaunchKernelGGL(conv_stem_fwd_kernel<float>, grid, dim3(256), 0, stream, x0, wf, bias, y,
-                         N, H, W, Cout);
-    }
+    launch_stem_fwd<float>(x0, wf, bias, y, N, H, W, Cout, nullptr, stream);
     UNET_CHECK_LAUNCH("conv_stem_fwd");
     return UNET_OK;
   }
@@ -1380,92 +1380,53 @@ static int conv3x3_fwd_impl(const float* x0, int C0, const float* x1, int C1, co
                "conv3x3_fwd: channel counts (%d,%d) must be multiples of 32", C0, C1);
   UNET_REQUIRE(C1 == 0 || x1, "conv3x3_fwd: x1 is null with C1=%d", C1);
   UNET_REQUIRE((long long)9 * Cout * (C0 + C1) * 4 < (1LL << 31), "conv3x3_fwd: weights exceed 2 GiB");
-  {  // batch chunks keep every source inside the 2 GiB buffer-descriptor range
-    const int nmax = batch_chunk(N, (long long)H * W * (C0 > C1 ? C0 : C1) * 4);
-    UNET_REQUIRE(nmax >= 1, "conv3x3_fwd: one image exceeds the 2 GiB buffer-descriptor range");
-    if (nmax < N) {
-      const size_t Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-      for (int nb = 0; nb < N; nb += nmax) {
-        const int n = N - nb < nmax ? N - nb : nmax;
-        const int rc = conv3x3_fwd_impl(x0 + (size_t)nb * H * W * C0,  C0,
-                                        x1 ? x1 + (size_t)nb * H * W * C1 : nullptr, C1, wf, bias,
-                                        y + (size_t)nb * Ho * Wo * Cout, n, H, W, Cout, stride, prec,
-                                        stream, wf3);
-        if (rc != UNET_OK) return rc;
-      }
-      return UNET_OK;
-    }
-  }
-  IgemmParams p{};
-  p.src0 = x0; p.src1 = x1; p.C0 = C0; p.C1 = C1;
-  p.w = wf; p.tap_stride = Cout * (C0 + C1); p.n_off = 0; p.bias = bias;
-  p.src0_bytes = (unsigned)((long long)N * H * W * C0 * 4);
-  p.src1_bytes = (unsigned)((long long)N * H * W * C1 * 4);
-  p.w_bytes = (unsigned)((long long)9 * Cout * (C0 + C1) * 4);
-  p.out = y; p.ldo = Cout; p.accumulate = 0;
-  p.N = N; p.Hin = H; p.Win = W;
-  p.Hl = p.Hout = (H - 1) / stride + 1;
-  p.Wl = p.Wout = (W - 1) / stride + 1;
-  p.Ncols = Cout;
-  p.w3 = reinterpret_cast<const __bf16*>(wf3);
-  p.w3_plane = 9 * Cout * (C0 + C1);
-  p.w3_bytes = (unsigned)((long long)3 * p.w3_plane * 2);
-  fill_fwd_taps(p, stride);
-  if (prec == 1) return dispatch_igemm_bf16(p, stream);
-  if (prec == 3) return dispatch_igemm_split(p, stream);
-  // K = 32: row-fused kernel with the weights resident in LDS; wider K: the patch kernel
-  if (stride == 1 && rf_applicable(p) &&
-      (C0 + C1 == 32 || !patch_f32_applicable(p) || p.Hin % 8 != 0))
-    return (C0 + C1 == 32) ? launch_igemm_rf<128, 32, 32, 32, true>(p, 0, stream)
-                           : launch_igemm_rf<128, 32, 32, 32, false>(p, 0, stream);
-  return dispatch_igemm(p, stream);
+  // batch chunks keep every source inside the 2 GiB buffer-descriptor range
+  return for_each_chunk("conv3x3_fwd", N, (long long)H * W * (C0 > C1 ? C0 : C1) * 4, [&](Batch b) {
+    const IgemmParams p = fwd_params({x0, C0, nullptr, nullptr}, {x1, C1, nullptr, nullptr}, 0.f,
+                                     wf, bias, y, b, H, W, Cout, stride, 3, false, m);
+    if (m.cores == Cores::BF16) return dispatch_igemm_bf16(p, stream);
+    if (m.is_split()) return dispatch_igemm_split(p, stream);
+    if (stride == 1 && rf_preferred(p))
+      return (C0 + C1 == 32) ? launch_igemm_rf<128, 32, 32, 32, true>(p, 0, stream)
+                             : launch_igemm_rf<128, 32, 32, 32, false>(p, 0, stream);
+    return dispatch_igemm(p, stream);
+  });
 }
 
 extern "C" int unet_conv3x3_fwd(const float* x0, int C0, const float* x1, int C1, const float* wf,
                                 const float* bias, float* y, int N, int H, int W, int Cout,
                                 int stride, unet_stream_t stream) {
-  return conv3x3_fwd_impl(x0, C0, x1, C1, wf, bias, y, N, H, W, Cout, stride, 0,
+  return conv3x3_fwd_impl(x0, C0, x1, C1, wf, bias, y, N, H, W, Cout, stride, ConvMode::f32(),
                           (hipStream_t)stream);
 }
 
 extern "C" int unet_conv3x3_fwd_bf16(const float* x0, int C0, const float* x1, int C1,
                                      const float* wf, const float* bias, float* y, int N, int H,
                                      int W, int Cout, int stride, unet_stream_t stream) {
-  if (C0 == 3)   // the RGB stem is HBM-bound: it stays on the fp32 path
-    return conv3x3_fwd_impl(x0, C0, x1, C1, wf, bias, y, N, H, W, Cout, stride, 0,
-                            (hipStream_t)stream);
-  return conv3x3_fwd_impl(x0, C0, x1, C1, wf, bias, y, N, H, W, Cout, stride, 1,
-                          (hipStream_t)stream);
+  return conv3x3_fwd_impl(x0, C0, x1, C1, wf, bias, y, N, H, W, Cout, stride,
+                          ConvMode::bf16_cores().stem_on_fp32(C0), (hipStream_t)stream);
 }
 
 extern "C" int unet_conv3x3_fwd_bf16x3(const float* x0, int C0, const float* x1, int C1,
                                        const float* wf, const uint16_t* wf3, const float* bias,
                                        float* y, int N, int H, int W, int Cout, int stride,
                                        unet_stream_t stream) {
-  // the RGB stem (K = 27, HBM-bound) stays on the fp32 matrix-core path
-  return conv3x3_fwd_impl(x0, C0, x1, C1, wf, bias, y, N, H, W, Cout, stride, C0 == 3 ? 0 : 3,
-                          (hipStream_t)stream, wf3);
+  return conv3x3_fwd_impl(x0, C0, x1, C1, wf, bias, y, N, H, W, Cout, stride,
+                          ConvMode::split(wf3).stem_on_fp32(C0), (hipStream_t)stream);
 }
 
-static int conv3x3_bwd_data_impl(const float* dy, const float* wd, int Cin_total, int ci_offset,
-                                 float* dx, int N, int H, int W, int Cout, int Ccols, int stride,
-                                 int accumulate, int prec, hipStream_t stream,
-                                 const uint16_t* wd3 = nullptr, int b16 = 0,
-                                 unet_bwd_stats* bs = nullptr) {
-  // b16: dy and dx are bf16 tensors (mixed-precision pipeline; prec is then 1)
-  const long long es = b16 ? 2 : 4;
+// dy / dx are tensors of the mode's element type.  bs (may be null): dx is final for that layer.
+static int conv3x3_bwd_data_impl(const void* dy, const float* wd, int Cin_total, int ci_offset,
+                                 void* dx, int N, int H, int W, int Cout, int Ccols, int stride,
+                                 int accumulate, ConvMode m, unet_bwd_stats* bs,
+                                 hipStream_t stream) {
   if (bs) bs->tiles_out = 0;
   // split mode with reductions (fused pipeline): only the stride-1 patch shapes have a split
   // kernel with that epilogue; everything else runs the fp32 kernels
-  if (prec == 3 && bs && stride == 2) prec = 0;
-  // (b16: the stride-1 patch kernel and the gather-GEMM have the epilogue; the stride-2 patch
-  // kernel reports 0 tiles)
-  const bool use_bs = bs && (prec == 0 || prec == 3 || b16) && bs->y && bs->mean &&
-                      bs->rstd && bs->gamma &&
-                      bs->beta && bs->partial &&
-                      bs->partial_bytes >= (size_t)N * ceil_div(H * W, 64) * Ccols * sizeof(float2);
+  if (m.is_split() && bs && stride == 2) m = ConvMode::f32();
   UNET_REQUIRE(dy && wd && dx, "conv3x3_bwd_data: null pointer");
-  UNET_REQUIRE(prec != 3 || wd3, "conv3x3_bwd_data_bf16x3: the pre-split weight planes are null");
+  UNET_REQUIRE(!m.is_split() || m.w3,
+               "conv3x3_bwd_data_bf16x3: the pre-split weight planes are null");
   UNET_REQUIRE(stride == 1 || stride == 2, "conv3x3_bwd_data: stride %d unsupported", stride);
   UNET_REQUIRE(Cout > 0 && Cout % 32 == 0 && Ccols > 0 && Ccols % 32 == 0 && ci_offset >= 0 &&
                    ci_offset + Ccols <= Cin_total,
@@ -1476,134 +1437,66 @@ static int conv3x3_bwd_data_impl(const float* dy, const float* wd, int Cin_total
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
   UNET_REQUIRE((long long)9 * Cout * Cin_total * 4 < (1LL << 31),
                "conv3x3_bwd_data: weights exceed 2 GiB");
-  {  // batch chunks keep dy inside the 2 GiB buffer-descriptor range
-    const int nmax = batch_chunk(N, (long long)Ho * Wo * Cout * es);
-    UNET_REQUIRE(nmax >= 1, "conv3x3_bwd_data: one image exceeds the 2 GiB buffer-descriptor range");
-    if (nmax < N) {   // chunked batches have no single tile layout: no BSTATS epilogue
-      for (int nb = 0; nb < N; nb += nmax) {
-        const int n = N - nb < nmax ? N - nb : nmax;
-        const int rc = conv3x3_bwd_data_impl(
-            reinterpret_cast<const float*>(reinterpret_cast<const char*>(dy) +
-                                           (size_t)nb * Ho * Wo * Cout * es),
-            wd, Cin_total, ci_offset,
-            reinterpret_cast<float*>(reinterpret_cast<char*>(dx) + (size_t)nb * H * W * Ccols * es),
-            n, H, W, Cout, Ccols, stride, accumulate, prec, stream, wd3, b16);
-        if (rc != UNET_OK) return rc;
-      }
-      return UNET_OK;
+  const bool b16 = m.b16_tensors();
+  // batch chunks keep dy inside the 2 GiB buffer-descriptor range
+  const long long dy_image = (long long)Ho * Wo * Cout * (long long)m.es();
+  return for_each_chunk("conv3x3_bwd_data", N, dy_image, [&](Batch b) {
+    unet_bwd_stats* const cbs = b.whole(bs);
+    // (bf16 cores over fp32 tensors have no epilogue.  b16: the stride-1 patch kernel and the
+    // gather-GEMM have it; the stride-2 patch kernel reports 0 tiles)
+    BsBinder bsb(cbs, m.cores != Cores::BF16 || b16, N, H * W, Ccols);
+    IgemmParams p = dgrad_params(dy, wd, Cin_total, ci_offset, dx, b, H, W, Cout, Ccols, stride, 3,
+                                 accumulate, false, m);
+    bsb.bind(p);
+    if (stride == 1) {
+      if (b16) return bsb.done_px(dispatch_igemm_b16(p, stream, nullptr, bsb.report()), H * W);
+      if (m.cores == Cores::BF16) return dispatch_igemm_bf16(p, stream);
+      if (m.is_split() && !cbs) return dispatch_igemm_split(p, stream);
+      int rc = kNoTileFits;
+      if (m.is_split() && patch_split_applicable(p))   // fused pipeline, split mode (else: fp32)
+        rc = launch_patch_split_fused_auto(p, stream, nullptr, bsb.report());
+      if (rc != kNoTileFits) return bsb.done_px(rc, H * W);
+      if (c32_applicable(p))   // conv_c32.hip: 32 -> 32 channels
+        rc = launch_c32(p, 0, stream, bsb.report());
+      else if (rf_preferred(p))
+        rc = (Cout == 32) ? launch_igemm_rf<128, 32, 32, 32, true>(p, 1, stream, bsb.report())
+                          : launch_igemm_rf<128, 32, 32, 32, false>(p, 1, stream, bsb.report());
+      else
+        rc = dispatch_igemm(p, stream, nullptr, bsb.report());
+      return bsb.done_px(rc, H * W);
     }
-  }
-  IgemmParams p{};
-  p.src0 = dy; p.src1 = nullptr; p.C0 = Cout; p.C1 = 0;
-  p.w = wd; p.tap_stride = Cin_total * Cout; p.n_off = ci_offset; p.bias = nullptr;
-  p.src0_bytes = (unsigned)((long long)N * Ho * Wo * Cout * es);
-  p.src1_bytes = 0;
-  p.w_bytes = (unsigned)((long long)9 * Cout * Cin_total * 4);
-  p.out = dx; p.ldo = Ccols; p.accumulate = accumulate;
-  p.N = N; p.Hin = Ho; p.Win = Wo;
-  p.Hout = H; p.Wout = W;
-  p.Ncols = Ccols;
-  p.w3 = reinterpret_cast<const __bf16*>(wd3);
-  p.w3_plane = 9 * Cout * Cin_total;
-  p.w3_bytes = (unsigned)((long long)(b16 ? 1 : 3) * p.w3_plane * 2);
-  p.sin = 1;
-  int bs_px = 0;
-  if (use_bs) {
-    p.bs_y = bs->y; p.bs_mean = bs->mean; p.bs_rstd = bs->rstd; p.bs_gamma = bs->gamma;
-    p.bs_beta = bs->beta; p.bs_mask = bs->mask; p.slope = bs->slope;
-    p.bs_partial = reinterpret_cast<float2*>(bs->partial);
-  }
-  if (stride == 1) {
-    p.Hl = H; p.Wl = W; p.sout = 1; p.py = p.px = 0;
-    p.ntaps = 9;
-    p.tapw[0] = p.tapw[1] = p.tapw[2] = 0;
-    for (int t = 0; t < 9; ++t) set_tap(p, t, 1 - t / 3, 1 - t % 3, t);
-    if (b16) {
-      const int rc = dispatch_igemm_b16(p, stream, nullptr, use_bs ? &bs_px : nullptr);
-      if (rc == UNET_OK && use_bs && bs_px > 0) bs->tiles_out = H * W / bs_px;
-      return rc;
-    }
-    if (prec == 1) return dispatch_igemm_bf16(p, stream);
-    if (prec == 3 && !bs) return dispatch_igemm_split(p, stream);
-    int rc = 1;
-    if (prec == 3 && patch_split_applicable(p))   // fused pipeline, split mode (else: fp32 below)
-      rc = launch_patch_split_fused_auto(p, stream, nullptr, use_bs ? &bs_px : nullptr);
-    if (rc != 1) {
-    } else
-    if (c32_applicable(p))   // conv_c32.hip: 32 -> 32 channels
-      rc = launch_c32(p, 0, stream, use_bs ? &bs_px : nullptr);
-    else if (rf_applicable(p) && (Cout == 32 || !patch_f32_applicable(p) || p.Hin % 8 != 0))
-      rc = (Cout == 32) ? launch_igemm_rf<128, 32, 32, 32, true>(p, 1, stream, &bs_px)
-                        : launch_igemm_rf<128, 32, 32, 32, false>(p, 1, stream, &bs_px);
-    else
-      rc = dispatch_igemm(p, stream, nullptr, use_bs ? &bs_px : nullptr);
-    if (rc == UNET_OK && use_bs && bs_px > 0) bs->tiles_out = H * W / bs_px;
-    return rc;
-  }
-  // stride 2: dx[2a+py][2b+px] = sum over ky with (py+1-ky) even of dy[a + (py+1-ky)/2][..]
-  p.Hl = H / 2; p.Wl = W / 2; p.sout = 2;
-  {
-    // one launch for all four parity classes when there are enough tiles to fill the chip
-    const long long tiles = ceil_div64((long long)N * p.Hl * p.Wl, 128) * (Ccols / 32);
-    if (prec == 0 && !b16) {   // conv_patch.hip: the dy patch staged once per chunk
-      IgemmParams q = p;
-      if (!use_bs) q.bs_partial = nullptr;
-      int bt = 0;
-      const int rc = launch_dgrad_s2_patch_auto(q, stream, &bt);
-      if (rc != 1) {
-        if (rc == UNET_OK && use_bs && bt > 0) bs->tiles_out = bt;
-        return rc;
-      }
+    // stride 2, in one launch for all four parity classes where a form has the tiles for it:
+    if (m.cores == Cores::F32 && !b16) {   // conv_patch.hip: the dy patch staged once per chunk
+      const int rc = launch_dgrad_s2_patch_auto(p, stream, bsb.report());
+      if (rc != kNoTileFits) return bsb.done_tiles(rc, bsb.reported());
     }
     if (b16) {   // mixed-precision pipeline: one launch instead of four per class
-      IgemmParams q = p;
-      if (!use_bs) q.bs_partial = nullptr;
-      int bt = 0;
-      const int rc = launch_dgrad_s2_patch_b16_auto(q, stream, use_bs ? &bt : nullptr);
-      if (rc != 1) {
-        if (rc == UNET_OK && use_bs && bt > 0) bs->tiles_out = bt;
-        return rc;
-      }
+      const int rc = launch_dgrad_s2_patch_b16_auto(p, stream, bsb.report());
+      if (rc != kNoTileFits) return bsb.done_tiles(rc, bsb.reported());
       p.bs_partial = nullptr;   // (the per-class gather-GEMM launches below: no epilogue)
     }
-    if (prec != 1 && !b16 && tiles >= 512) {
-      p.py = p.px = 0; p.ntaps = 9;
-      if (use_bs && (p.Hl * p.Wl) % 128 == 0) p.bs_tiles = p.Hl * p.Wl / 128;
+    const long long tiles = ceil_div64((long long)b.count * p.Hl * p.Wl, 128) * (Ccols / 32);
+    if (m.cores != Cores::BF16 && !b16 && tiles >= 512) {   // enough tiles to fill the chip
+      p.ntaps = 9;
+      if (bsb.use() && (p.Hl * p.Wl) % 128 == 0) p.bs_tiles = p.Hl * p.Wl / 128;
       else p.bs_partial = nullptr;
-      const int rc = launch_dgrad_s2(p, stream);
-      if (rc == UNET_OK && p.bs_partial) bs->tiles_out = p.bs_tiles;   // 512 output pixels each
-      return rc;
+      // (reduction tiles of 512 output pixels each)
+      return bsb.done_tiles(launch_dgrad_s2(p, stream), p.bs_partial ? p.bs_tiles : 0);
     }
-  }
-  int class_tiles = 0;
-  for (int py = 0; py < 2; ++py)
-    for (int px = 0; px < 2; ++px) {
-      p.py = py; p.px = px;
-      p.tapw[0] = p.tapw[1] = p.tapw[2] = 0;
-      int nt = 0;
-      for (int ky = 0; ky < 3; ++ky) {
-        if ((py + 1 - ky) & 1) continue;
-        for (int kx = 0; kx < 3; ++kx) {
-          if ((px + 1 - kx) & 1) continue;
-          set_tap(p, nt, (py + 1 - ky) / 2, (px + 1 - kx) / 2, ky * 3 + kx);
-          ++nt;
-        }
-      }
-      p.ntaps = nt;
-      int bpx = 0;
-      p.bs_tile0 = (py * 2 + px) * (class_tiles > 0 ? class_tiles : 0);
-      int rc = b16 ? dispatch_igemm_b16(p, stream, nullptr)
-                   : prec == 1 ? dispatch_igemm_bf16(p, stream)
-                   : (prec == 3 ? dispatch_igemm_split(p, stream)
-                                : dispatch_igemm(p, stream, nullptr, use_bs ? &bpx : nullptr));
+    for (int cls = 0; cls < 4; ++cls) {
+      set_s2_class_taps(p, cls >> 1, cls & 1);
+      bsb.begin_class(p, cls);
+      // per-class launches of one stride-2 gradient pass bs_tile0 themselves
+      const int rc = b16 ? dispatch_igemm_b16(p, stream, nullptr)
+                     : m.cores == Cores::BF16 ? dispatch_igemm_bf16(p, stream)
+                     : m.is_split() ? dispatch_igemm_split(p, stream)
+                                    : dispatch_igemm(p, stream, nullptr, bsb.report());
       if (rc != UNET_OK) return rc;
-      if (use_bs) {
-        if (bpx == 0) { p.bs_partial = nullptr; class_tiles = -1; }   // no epilogue: give up on it
-        else if (class_tiles == 0) class_tiles = p.Hl * p.Wl / bpx;
-      }
+      bsb.end_class(p, p.Hl * p.Wl);
     }
-  if (use_bs && class_tiles > 0 && p.bs_partial) bs->tiles_out = 4 * class_tiles;
-  return UNET_OK;
+    bsb.done_classes(p);
+    return UNET_OK;
+  });
 }
 
 extern "C" int unet_conv3x3_bwd_data(const float* dy, const float* wd, int Cin_total,
@@ -1611,7 +1504,7 @@ extern "C" int unet_conv3x3_bwd_data(const float* dy, const float* wd, int Cin_t
                                      int Ccols, int stride, int accumulate,
                                      unet_stream_t stream) {
   return conv3x3_bwd_data_impl(dy, wd, Cin_total, ci_offset, dx, N, H, W, Cout, Ccols, stride,
-                               accumulate, 0, (hipStream_t)stream);
+                               accumulate, ConvMode::f32(), nullptr, (hipStream_t)stream);
 }
 
 extern "C" int unet_conv3x3_bwd_data_bf16(const float* dy, const float* wd, int Cin_total,
@@ -1619,7 +1512,7 @@ extern "C" int unet_conv3x3_bwd_data_bf16(const float* dy, const float* wd, int 
                                           int Ccols, int stride, int accumulate,
                                           unet_stream_t stream) {
   return conv3x3_bwd_data_impl(dy, wd, Cin_total, ci_offset, dx, N, H, W, Cout, Ccols, stride,
-                               accumulate, 1, (hipStream_t)stream);
+                               accumulate, ConvMode::bf16_cores(), nullptr, (hipStream_t)stream);
 }
 
 extern "C" int unet_conv3x3_bwd_data_bs(const float* dy, const float* wd, int Cin_total,
@@ -1627,7 +1520,7 @@ extern "C" int unet_conv3x3_bwd_data_bs(const float* dy, const float* wd, int Ci
                                         int Ccols, int stride, int accumulate, unet_bwd_stats* bs,
                                         unet_stream_t stream) {
   return conv3x3_bwd_data_impl(dy, wd, Cin_total, ci_offset, dx, N, H, W, Cout, Ccols, stride,
-                               accumulate, 0, (hipStream_t)stream, nullptr, 0, bs);
+                               accumulate, ConvMode::f32(), bs, (hipStream_t)stream);
 }
 
 // Mixed-precision pipeline with the BSTATS epilogue: dy, dx and bs->y are bf16 tensors
@@ -1635,9 +1528,8 @@ extern "C" int unet_conv3x3_bwd_data_bs_b16(const uint16_t* dy, const float* wd,
                                             int ci_offset, uint16_t* dx, int N, int H, int W,
                                             int Cout, int Ccols, int stride, int accumulate,
                                             unet_bwd_stats* bs, unet_stream_t stream) {
-  return conv3x3_bwd_data_impl(reinterpret_cast<const float*>(dy), wd, Cin_total, ci_offset,
-                               reinterpret_cast<float*>(dx), N, H, W, Cout, Ccols, stride,
-                               accumulate, 1, (hipStream_t)stream, nullptr, 1, bs);
+  return conv3x3_bwd_data_impl(dy, wd, Cin_total, ci_offset, dx, N, H, W, Cout, Ccols, stride,
+                               accumulate, ConvMode::b16(nullptr), bs, (hipStream_t)stream);
 }
 
 // ... with the weights also pre-rounded to bf16 (wdb = [9][Cin_total][Cout] bf16: plane 0 of
@@ -1647,9 +1539,8 @@ extern "C" int unet_conv3x3_bwd_data_bs_b16_wb(const uint16_t* dy, const float* 
                                                uint16_t* dx, int N, int H, int W, int Cout,
                                                int Ccols, int stride, int accumulate,
                                                unet_bwd_stats* bs, unet_stream_t stream) {
-  return conv3x3_bwd_data_impl(reinterpret_cast<const float*>(dy), wd, Cin_total, ci_offset,
-                               reinterpret_cast<float*>(dx), N, H, W, Cout, Ccols, stride,
-                               accumulate, 1, (hipStream_t)stream, wdb, 1, bs);
+  return conv3x3_bwd_data_impl(dy, wd, Cin_total, ci_offset, dx, N, H, W, Cout, Ccols, stride,
+                               accumulate, ConvMode::b16(wdb), bs, (hipStream_t)stream);
 }
 
 // Split-bf16 mode of the fused pipeline (wd3 = pre-split planes, data-gradient layout); bs may
@@ -1660,7 +1551,7 @@ extern "C" int unet_conv3x3_bwd_data_bs_bf16x3(const float* dy, const float* wd,
                                                int stride, int accumulate, unet_bwd_stats* bs,
                                                unet_stream_t stream) {
   return conv3x3_bwd_data_impl(dy, wd, Cin_total, ci_offset, dx, N, H, W, Cout, Ccols, stride,
-                               accumulate, 3, (hipStream_t)stream, wd3, 0, bs);
+                               accumulate, ConvMode::split(wd3), bs, (hipStream_t)stream);
 }
 
 // dy and dx are bf16 tensors, bf16 matrix cores (mixed-precision pipeline)
@@ -1668,9 +1559,8 @@ extern "C" int unet_conv3x3_bwd_data_b16(const uint16_t* dy, const float* wd, in
                                          int ci_offset, uint16_t* dx, int N, int H, int W, int Cout,
                                          int Ccols, int stride, int accumulate,
                                          unet_stream_t stream) {
-  return conv3x3_bwd_data_impl(reinterpret_cast<const float*>(dy), wd, Cin_total, ci_offset,
-                               reinterpret_cast<float*>(dx), N, H, W, Cout, Ccols, stride,
-                               accumulate, 1, (hipStream_t)stream, nullptr, 1);
+  return conv3x3_bwd_data_impl(dy, wd, Cin_total, ci_offset, dx, N, H, W, Cout, Ccols, stride,
+                               accumulate, ConvMode::b16(nullptr), nullptr, (hipStream_t)stream);
 }
 
 extern "C" int unet_conv3x3_bwd_data_bf16x3(const float* dy, const float* wd,
@@ -1678,7 +1568,7 @@ extern "C" int unet_conv3x3_bwd_data_bf16x3(const float* dy, const float* wd,
                                             float* dx, int N, int H, int W, int Cout, int Ccols,
                                             int stride, int accumulate, unet_stream_t stream) {
   return conv3x3_bwd_data_impl(dy, wd, Cin_total, ci_offset, dx, N, H, W, Cout, Ccols, stride,
-                               accumulate, 3, (hipStream_t)stream, wd3);
+                               accumulate, ConvMode::split(wd3), nullptr, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1693,32 +1583,11 @@ extern "C" int unet_conv1x1_fwd(const float* x0, int C0, const float* x1, int C1
   UNET_REQUIRE(N > 0 && H > 0 && W > 0 && Cout > 0 && Cout % 32 == 0 && C0 > 0 && C0 % 32 == 0 &&
                    C1 >= 0 && C1 % 32 == 0 && (C1 == 0 || x1),
                "conv1x1_fwd: channel counts (%d,%d)->%d must be multiples of 32", C0, C1, Cout);
-  {
-    const int nmax = batch_chunk(N, (long long)H * W * (C0 > C1 ? C0 : C1) * 4);
-    UNET_REQUIRE(nmax >= 1, "conv1x1_fwd: one image exceeds the 2 GiB buffer-descriptor range");
-    if (nmax < N) {
-      for (int nb = 0; nb < N; nb += nmax) {
-        const int n = N - nb < nmax ? N - nb : nmax;
-        const int rc = unet_conv1x1_fwd(x0 + (size_t)nb * H * W * C0, C0,
-                                        x1 ? x1 + (size_t)nb * H * W * C1 : nullptr, C1, w, bias,
-                                        y + (size_t)nb * H * W * Cout, n, H, W, Cout, stream);
-        if (rc != UNET_OK) return rc;
-      }
-      return UNET_OK;
-    }
-  }
-  IgemmParams p{};
-  p.src0 = x0; p.src1 = x1; p.C0 = C0; p.C1 = C1;
-  p.w = w; p.tap_stride = Cout * (C0 + C1); p.n_off = 0; p.bias = bias;
-  p.src0_bytes = (unsigned)((long long)N * H * W * C0 * 4);
-  p.src1_bytes = (unsigned)((long long)N * H * W * C1 * 4);
-  p.w_bytes = (unsigned)((long long)Cout * (C0 + C1) * 4);
-  p.out = y; p.ldo = Cout; p.accumulate = 0;
-  p.N = N; p.Hin = p.Hl = p.Hout = H; p.Win = p.Wl = p.Wout = W;
-  p.Ncols = Cout; p.sin = 1; p.sout = 1; p.py = p.px = 0;
-  p.ntaps = 1; p.tapw[0] = p.tapw[1] = p.tapw[2] = 0;
-  set_tap(p, 0, 0, 0, 0);
-  return dispatch_igemm(p, (hipStream_t)stream);
+  return for_each_chunk("conv1x1_fwd", N, (long long)H * W * (C0 > C1 ? C0 : C1) * 4, [&](Batch b) {
+    return dispatch_igemm(fwd_params({x0, C0, nullptr, nullptr}, {x1, C1, nullptr, nullptr}, 0.f, w,
+                                     bias, y, b, H, W, Cout, 1, 1, false, ConvMode::f32()),
+                          (hipStream_t)stream);
+  });
 }
 
 extern "C" int unet_conv1x1_bwd_data(const float* dy, const float* wT, int Cin_total,
@@ -1727,32 +1596,11 @@ extern "C" int unet_conv1x1_bwd_data(const float* dy, const float* wT, int Cin_t
   UNET_REQUIRE(dy && wT && dx, "conv1x1_bwd_data: null pointer");
   UNET_REQUIRE(Cout > 0 && Cout % 32 == 0 && Ccols > 0 && Ccols % 32 == 0 && ci_offset >= 0 &&
                    ci_offset + Ccols <= Cin_total, "conv1x1_bwd_data: bad channel slice");
-  {
-    const int nmax = batch_chunk(N, (long long)H * W * Cout * 4);
-    UNET_REQUIRE(nmax >= 1, "conv1x1_bwd_data: one image exceeds the 2 GiB buffer-descriptor range");
-    if (nmax < N) {
-      for (int nb = 0; nb < N; nb += nmax) {
-        const int n = N - nb < nmax ? N - nb : nmax;
-        const int rc = unet_conv1x1_bwd_data(dy + (size_t)nb * H * W * Cout, wT, Cin_total,
-                                             ci_offset, dx + (size_t)nb * H * W * Ccols, n, H, W,
-                                             Cout, Ccols, accumulate, stream);
-        if (rc != UNET_OK) return rc;
-      }
-      return UNET_OK;
-    }
-  }
-  IgemmParams p{};
-  p.src0 = dy; p.src1 = nullptr; p.C0 = Cout; p.C1 = 0;
-  p.w = wT; p.tap_stride = Cin_total * Cout; p.n_off = ci_offset; p.bias = nullptr;
-  p.src0_bytes = (unsigned)((long long)N * H * W * Cout * 4);
-  p.src1_bytes = 0;
-  p.w_bytes = (unsigned)((long long)Cout * Cin_total * 4);
-  p.out = dx; p.ldo = Ccols; p.accumulate = accumulate;
-  p.N = N; p.Hin = p.Hl = p.Hout = H; p.Win = p.Wl = p.Wout = W;
-  p.Ncols = Ccols; p.sin = 1; p.sout = 1; p.py = p.px = 0;
-  p.ntaps = 1; p.tapw[0] = p.tapw[1] = p.tapw[2] = 0;
-  set_tap(p, 0, 0, 0, 0);
-  return dispatch_igemm(p, (hipStream_t)stream);
+  return for_each_chunk("conv1x1_bwd_data", N, (long long)H * W * Cout * 4, [&](Batch b) {
+    return dispatch_igemm(dgrad_params(dy, wT, Cin_total, ci_offset, dx, b, H, W, Cout, Ccols, 1, 1,
+                                       accumulate, false, ConvMode::f32()),
+                          (hipStream_t)stream);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1777,16 +1625,14 @@ extern "C" size_t unet_conv_in_fwd_workspace_bytes(int N, int H, int W, int Cout
   return a > b ? a : b;
 }
 
-// b16: the layer tensors (sources other than the RGB image, and y) are bf16 in HBM and the
-// contraction runs on the bf16 matrix cores (mixed-precision pipeline); else fp32 / fp32 MFMA.
-// w3 != nullptr: the split-bf16 mode - shapes the split patch kernel tiles run there (fp32
-// tensors, three-term operands, fp32-class accuracy), everything else on the fp32 kernels.
+// The layer tensors (sources other than the fp32 RGB image, and y) are of the mode's element
+// type; b16: the contraction runs on the bf16 matrix cores (mixed-precision pipeline).  Split
+// mode: shapes the split patch kernel tiles run there (fp32 tensors, three-term operands,
+// fp32-class accuracy), everything else on the fp32 kernels.
 static int conv_in_fwd_impl(const unet_act_src* s0, const unet_act_src* s1, float slope,
-                            const float* w, const float* bias, int ksize, int stride, float* y,
+                            const float* w, const float* bias, int ksize, int stride, void* y,
                             void* workspace, size_t workspace_bytes, int* stats_px_out, int N,
-                            int H, int W, int Cout, hipStream_t stream, int b16,
-                            const uint16_t* w3 = nullptr) {
-  const size_t es = b16 ? 2 : 4;   // bytes per activation element
+                            int H, int W, int Cout, const ConvMode& m, hipStream_t stream) {
   UNET_REQUIRE(s0 && s0->x && w && y && workspace && stats_px_out, "conv_in_fwd: null pointer");
   UNET_REQUIRE(ksize == 3 || ksize == 1, "conv_in_fwd: kernel size %d unsupported", ksize);
   UNET_REQUIRE(stride == 1 || (stride == 2 && ksize == 3), "conv_in_fwd: stride %d unsupported",
@@ -1794,115 +1640,53 @@ static int conv_in_fwd_impl(const unet_act_src* s0, const unet_act_src* s1, floa
   UNET_REQUIRE(N > 0 && H > 0 && W > 0, "conv_in_fwd: bad shape");
   UNET_REQUIRE(Cout > 0 && Cout % 32 == 0, "conv_in_fwd: Cout %d must be a multiple of 32", Cout);
   const int C0 = s0->C, C1 = s1 ? s1->C : 0;
-  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
   if (workspace_bytes < unet_conv_in_fwd_workspace_bytes(N, H, W, Cout, stride)) {
     unet_set_error("conv_in_fwd: workspace too small");
     return UNET_E_WORKSPACE;
   }
-  int stats_px = 0;
+  const bool b16 = m.b16_tensors();
+  float2* const stats = reinterpret_cast<float2*>(workspace);
   if (C0 == 3) {   // RGB stem: the image is a plain operand
     UNET_REQUIRE(C1 == 0 && stride == 1 && ksize == 3 && !s0->alpha,
                  "conv_in_fwd: the RGB stem is a plain stride-1 3x3 single source");
-    const long long M = (long long)N * H * W;
-    __bf16* yh = reinterpret_cast<__bf16*>(y);
-    if (W % STEM_ROW_PIX == 0) {
-      if (b16)
-        launch_stem_fwd_rows<float, __bf16>(s0->x, w, bias, yh, N, H, W, Cout,
-                                            reinterpret_cast<float2*>(workspace), StemNorm{}, stream);
-      else
-        launch_stem_fwd_rows<float, float>(s0->x, w, bias, y, N, H, W, Cout,
-                                           reinterpret_cast<float2*>(workspace), StemNorm{}, stream);
-      stats_px = STEM_ROW_PIX;
-    } else {
-      dim3 grid((unsigned)ceil_div64(M, STEM_PIX), Cout / 32);
-      if (b16)
-        hipLaunchKernelGGL(conv_stem_fwd_kernel<__bf16>, grid, dim3(256), 0, stream, s0->x, w, bias,
-                           yh, N, H, W, Cout);
-      else
-        hipLaunchKernelGGL(conv_stem_fwd_kernel<float>, grid, dim3(256), 0, stream, s0->x, w, bias,
-                           y, N, H, W, Cout);
-    }
+    *stats_px_out = b16 ? launch_stem_fwd(s0->x, w, bias, static_cast<__bf16*>(y), N, H, W, Cout,
+                                          stats, stream)
+                        : launch_stem_fwd(s0->x, w, bias, static_cast<float*>(y), N, H, W, Cout,
+                                          stats, stream);
     UNET_CHECK_LAUNCH("conv_stem_fwd");
-  } else {
-    UNET_REQUIRE(C0 > 0 && C0 % 32 == 0 && C1 >= 0 && C1 % 32 == 0,
-                 "conv_in_fwd: channel counts (%d,%d) must be multiples of 32", C0, C1);
-    UNET_REQUIRE(C1 == 0 || s1->x, "conv_in_fwd: second source is null with C1=%d", C1);
-    UNET_REQUIRE((!s0->alpha || s0->beta) && (!s1 || !s1->alpha || s1->beta),
-                 "conv_in_fwd: alpha without beta");
-    const int Cin = C0 + C1;
-    const int taps = ksize * ksize;
-    UNET_REQUIRE((long long)taps * Cout * Cin * 4 < (1LL << 31), "conv_in_fwd: weights exceed 2 GiB");
-    // batch chunks keep each source inside the 2 GiB buffer-descriptor range
-    const int nmax = batch_chunk(N, (long long)H * W * (C0 > C1 ? C0 : C1) * (long long)es);
-    UNET_REQUIRE(nmax >= 1, "conv_in_fwd: one image exceeds the 2 GiB buffer-descriptor range");
-    const bool chunked = nmax < N;
-    for (int nb = 0; nb < N; nb += nmax) {
-      const int n = (N - nb) < nmax ? (N - nb) : nmax;
-      IgemmParams p{};
-      p.src0 = reinterpret_cast<const float*>(reinterpret_cast<const char*>(s0->x) +
-                                              (size_t)nb * H * W * C0 * es);
-      p.src1 = s1 ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(s1->x) +
-                                                   (size_t)nb * H * W * C1 * es)
-                  : nullptr;
-      p.C0 = C0; p.C1 = C1;
-      p.act0_alpha = s0->alpha ? s0->alpha + (size_t)nb * C0 : nullptr;
-      p.act0_beta = s0->alpha ? s0->beta + (size_t)nb * C0 : nullptr;
-      p.act1_alpha = (s1 && s1->alpha) ? s1->alpha + (size_t)nb * C1 : nullptr;
-      p.act1_beta = (s1 && s1->alpha) ? s1->beta + (size_t)nb * C1 : nullptr;
-      p.slope = slope;
-      p.w = w; p.tap_stride = Cout * Cin; p.n_off = 0; p.bias = bias;
-      p.src0_bytes = (unsigned)((long long)n * H * W * C0 * (long long)es);
-      p.src1_bytes = (unsigned)((long long)n * H * W * C1 * (long long)es);
-      p.w_bytes = (unsigned)((long long)taps * Cout * Cin * 4);
-      p.out = reinterpret_cast<float*>(reinterpret_cast<char*>(y) +
-                                       (size_t)nb * Ho * Wo * Cout * es);
-      p.ldo = Cout; p.accumulate = 0;
-      p.N = n; p.Hin = H; p.Win = W;
-      p.Hl = p.Hout = Ho; p.Wl = p.Wout = Wo;
-      p.Ncols = Cout;
-      // the statistics epilogue needs one tile layout for the whole batch: chunked calls use
-      // the stand-alone statistics pass instead
-      p.stats = chunked ? nullptr : reinterpret_cast<float2*>(workspace);
-      int px = 0;
-      int rc;
-      if (ksize == 1) {
-        p.sin = 1; p.sout = 1; p.py = p.px = 0;
-        p.ntaps = 1; p.tapw[0] = p.tapw[1] = p.tapw[2] = 0;
-        set_tap(p, 0, 0, 0, 0);
-        rc = b16 ? dispatch_igemm_b16(p, stream, &px) : dispatch_igemm(p, stream, &px);
-      } else if (b16) {
-        fill_fwd_taps(p, stride);
-        if (w3) {   // plane 0 of the pre-split weights = the bf16-rounded weights (patch kernel)
-          p.w3 = reinterpret_cast<const __bf16*>(w3);
-          p.w3_plane = 9 * Cout * Cin;
-          p.w3_bytes = (unsigned)((long long)p.w3_plane * 2);
-        }
-        rc = dispatch_igemm_b16(p, stream, &px);
-      } else {
-        fill_fwd_taps(p, stride);
-        rc = 1;
-        if (w3 && stride == 1 && patch_split_applicable(p)) {   // split-bf16 patch kernel
-          p.w3 = reinterpret_cast<const __bf16*>(w3);
-          p.w3_plane = 9 * Cout * Cin;
-          p.w3_bytes = (unsigned)((long long)3 * p.w3_plane * 2);
-          rc = launch_patch_split_fused_auto(p, stream, &px, nullptr);
-        }
-        if (rc != 1) {
-        } else
-        // K = 32: row-fused kernel with the weights resident in LDS; wider K: the patch kernel
-        if (stride == 1 && c32_applicable(p))   // conv_c32.hip: 32 -> 32 channels
-          rc = launch_c32(p, 1, stream, &px);
-        else if (stride == 1 && rf_applicable(p) &&
-            (Cin == 32 || !patch_f32_applicable(p) || p.Hin % 8 != 0))
-          rc = (Cin == 32) ? launch_igemm_rf<128, 32, 32, 32, true, true>(p, 0, stream, &px)
-                           : launch_igemm_rf<128, 32, 32, 32, false, true>(p, 0, stream, &px);
-        else
-          rc = dispatch_igemm(p, stream, &px);
-      }
-      if (rc != UNET_OK) return rc;
-      stats_px = px;
-    }
+    return UNET_OK;
   }
+  UNET_REQUIRE(C0 > 0 && C0 % 32 == 0 && C1 >= 0 && C1 % 32 == 0,
+               "conv_in_fwd: channel counts (%d,%d) must be multiples of 32", C0, C1);
+  UNET_REQUIRE(C1 == 0 || s1->x, "conv_in_fwd: second source is null with C1=%d", C1);
+  UNET_REQUIRE((!s0->alpha || s0->beta) && (!s1 || !s1->alpha || s1->beta),
+               "conv_in_fwd: alpha without beta");
+  const int Cin = C0 + C1;
+  UNET_REQUIRE((long long)ksize * ksize * Cout * Cin * 4 < (1LL << 31),
+               "conv_in_fwd: weights exceed 2 GiB");
+  int stats_px = 0;
+  // batch chunks keep each source inside the 2 GiB buffer-descriptor range
+  const int rc = for_each_chunk(
+      "conv_in_fwd", N, (long long)H * W * (C0 > C1 ? C0 : C1) * (long long)m.es(), [&](Batch b) {
+        IgemmParams p = fwd_params(conv_src(s0), conv_src(s1), slope, w, bias, y, b, H, W, Cout,
+                                   stride, ksize, false, m);
+        // (chunked calls use the stand-alone statistics pass instead)
+        p.stats = b.whole(stats);
+        int rc = kNoTileFits;
+        if (b16) return dispatch_igemm_b16(p, stream, &stats_px);
+        if (ksize == 1) return dispatch_igemm(p, stream, &stats_px);
+        // the split-bf16 patch kernel, where it has a tile for the shape
+        if (m.is_split() && m.w3 && stride == 1 && patch_split_applicable(p))
+          rc = launch_patch_split_fused_auto(p, stream, &stats_px, nullptr);
+        if (rc != kNoTileFits) return rc;
+        if (stride == 1 && c32_applicable(p))   // conv_c32.hip: 32 -> 32 channels
+          return launch_c32(p, 1, stream, &stats_px);
+        if (stride == 1 && rf_preferred(p))
+          return Cin == 32 ? launch_igemm_rf<128, 32, 32, 32, true, true>(p, 0, stream, &stats_px)
+                           : launch_igemm_rf<128, 32, 32, 32, false, true>(p, 0, stream, &stats_px);
+        return dispatch_igemm(p, stream, &stats_px);
+      });
+  if (rc != UNET_OK) return rc;
   *stats_px_out = stats_px;
   return UNET_OK;
 }
@@ -1912,7 +1696,7 @@ extern "C" int unet_conv_in_fwd(const unet_act_src* s0, const unet_act_src* s1, 
                                 void* workspace, size_t workspace_bytes, int* stats_px_out, int N,
                                 int H, int W, int Cout, unet_stream_t stream) {
   return conv_in_fwd_impl(s0, s1, slope, w, bias, ksize, stride, y, workspace, workspace_bytes,
-                          stats_px_out, N, H, W, Cout, (hipStream_t)stream, 0);
+                          stats_px_out, N, H, W, Cout, ConvMode::f32(), (hipStream_t)stream);
 }
 
 // Split-bf16 mode of the fused pipeline: fp32 tensors; w3 = the pre-split weight planes of
@@ -1924,7 +1708,7 @@ extern "C" int unet_conv_in_fwd_bf16x3(const unet_act_src* s0, const unet_act_sr
                                        int W, int Cout, unet_stream_t stream) {
   UNET_REQUIRE(w3 || ksize != 3, "conv_in_fwd_bf16x3: the pre-split weight planes are null");
   return conv_in_fwd_impl(s0, s1, slope, w, bias, ksize, stride, y, workspace, workspace_bytes,
-                          stats_px_out, N, H, W, Cout, (hipStream_t)stream, 0, w3);
+                          stats_px_out, N, H, W, Cout, ConvMode::split(w3), (hipStream_t)stream);
 }
 
 // Mixed-precision pipeline (BASELINE config 4): the sources (except the fp32 RGB image) and y
@@ -1935,9 +1719,8 @@ extern "C" int unet_conv_in_fwd_b16(const unet_act_src* s0, const unet_act_src* 
                                     uint16_t* y, void* workspace, size_t workspace_bytes,
                                     int* stats_px_out, int N, int H, int W, int Cout,
                                     unet_stream_t stream) {
-  return conv_in_fwd_impl(s0, s1, slope, w, bias, ksize, stride, reinterpret_cast<float*>(y),
-                          workspace, workspace_bytes, stats_px_out, N, H, W, Cout,
-                          (hipStream_t)stream, 1);
+  return conv_in_fwd_impl(s0, s1, slope, w, bias, ksize, stride, y, workspace, workspace_bytes,
+                          stats_px_out, N, H, W, Cout, ConvMode::b16(nullptr), (hipStream_t)stream);
 }
 
 // The same with the weights also given pre-rounded to bf16 (wb = [9][Cout][Cin] bf16: plane 0 of
@@ -1949,43 +1732,16 @@ extern "C" int unet_conv_in_fwd_b16_wb(const unet_act_src* s0, const unet_act_sr
                                        const float* bias, int ksize, int stride, uint16_t* y,
                                        void* workspace, size_t workspace_bytes, int* stats_px_out,
                                        int N, int H, int W, int Cout, unet_stream_t stream) {
-  return conv_in_fwd_impl(s0, s1, slope, w, bias, ksize, stride, reinterpret_cast<float*>(y),
-                          workspace, workspace_bytes, stats_px_out, N, H, W, Cout,
-                          (hipStream_t)stream, 1, ksize == 3 ? wb : nullptr);
+  return conv_in_fwd_impl(s0, s1, slope, w, bias, ksize, stride, y, workspace, workspace_bytes,
+                          stats_px_out, N, H, W, Cout, ConvMode::b16(ksize == 3 ? wb : nullptr),
+                          (hipStream_t)stream);
 }
 
-static int conv_in_stats_finalize_impl(const float* y, void* workspace, size_t workspace_bytes,
+static int conv_in_stats_finalize_impl(const void* y, void* workspace, size_t workspace_bytes,
                                        int stats_px, const float* gamma, const float* beta,
                                        float eps, const float* mask, float* mean, float* rstd,
                                        float* alpha_out, float* beta_out, int N, int HoWo, int Cout,
-                                       unet_stream_t stream, int b16);
-
-extern "C" int unet_conv_in_stats_finalize(const float* y, void* workspace, size_t workspace_bytes,
-                                           int stats_px, const float* gamma, const float* beta,
-                                           float eps, const float* mask, float* mean, float* rstd,
-                                           float* alpha_out, float* beta_out, int N, int HoWo,
-                                           int Cout, unet_stream_t stream) {
-  return conv_in_stats_finalize_impl(y, workspace, workspace_bytes, stats_px, gamma, beta, eps,
-                                     mask, mean, rstd, alpha_out, beta_out, N, HoWo, Cout, stream,
-                                     0);
-}
-
-extern "C" int unet_conv_in_stats_finalize_b16(const uint16_t* y, void* workspace,
-                                               size_t workspace_bytes, int stats_px,
-                                               const float* gamma, const float* beta, float eps,
-                                               const float* mask, float* mean, float* rstd,
-                                               float* alpha_out, float* beta_out, int N, int HoWo,
-                                               int Cout, unet_stream_t stream) {
-  return conv_in_stats_finalize_impl(reinterpret_cast<const float*>(y), workspace, workspace_bytes,
-                                     stats_px, gamma, beta, eps, mask, mean, rstd, alpha_out,
-                                     beta_out, N, HoWo, Cout, stream, 1);
-}
-
-static int conv_in_stats_finalize_impl(const float* y, void* workspace, size_t workspace_bytes,
-                                       int stats_px, const float* gamma, const float* beta,
-                                       float eps, const float* mask, float* mean, float* rstd,
-                                       float* alpha_out, float* beta_out, int N, int HoWo, int Cout,
-                                       unet_stream_t stream, int b16) {
+                                       unet_stream_t stream, Elem elem) {
   UNET_REQUIRE(y && workspace && mean && rstd, "conv_in_stats_finalize: null pointer");
   UNET_REQUIRE(stats_px >= 0 && (stats_px == 0 || HoWo % stats_px == 0),
                "conv_in_stats_finalize: %d-pixel tiles do not cover %d pixels", stats_px, HoWo);
@@ -1995,8 +1751,31 @@ static int conv_in_stats_finalize_impl(const float* y, void* workspace, size_t w
                                   (hipStream_t)stream,
                                   reinterpret_cast<char*>(workspace) +
                                       stats_partial_bytes(N, HoWo, Cout));
-  return unet_in_stats_masked(y, gamma, beta, eps, mask, mean, rstd, alpha_out, beta_out, workspace,
-                              workspace_bytes, N, HoWo, Cout, (hipStream_t)stream, b16);
+  // (unet_in_stats_masked reads y by its element flag)
+  return unet_in_stats_masked(static_cast<const float*>(y), gamma, beta, eps, mask, mean, rstd,
+                              alpha_out, beta_out, workspace, workspace_bytes, N, HoWo, Cout,
+                              (hipStream_t)stream, elem == Elem::BF16);
+}
+
+extern "C" int unet_conv_in_stats_finalize(const float* y, void* workspace, size_t workspace_bytes,
+                                           int stats_px, const float* gamma, const float* beta,
+                                           float eps, const float* mask, float* mean, float* rstd,
+                                           float* alpha_out, float* beta_out, int N, int HoWo,
+                                           int Cout, unet_stream_t stream) {
+  return conv_in_stats_finalize_impl(y, workspace, workspace_bytes, stats_px, gamma, beta, eps,
+                                     mask, mean, rstd, alpha_out, beta_out, N, HoWo, Cout, stream,
+                                     Elem::F32);
+}
+
+extern "C" int unet_conv_in_stats_finalize_b16(const uint16_t* y, void* workspace,
+                                               size_t workspace_bytes, int stats_px,
+                                               const float* gamma, const float* beta, float eps,
+                                               const float* mask, float* mean, float* rstd,
+                                               float* alpha_out, float* beta_out, int N, int HoWo,
+                                               int Cout, unet_stream_t stream) {
+  return conv_in_stats_finalize_impl(y, workspace, workspace_bytes, stats_px, gamma, beta, eps,
+                                     mask, mean, rstd, alpha_out, beta_out, N, HoWo, Cout, stream,
+                                     Elem::BF16);
 }
 
 // ---------------------------------------------------------------------------
@@ -2006,33 +1785,52 @@ static int conv_in_stats_finalize_impl(const float* y, void* workspace, size_t w
 // resolution pixels with K = 9*Cout, i.e. a quarter of the FLOPs of the 3x3 data gradient on the
 // up-sampled grid, and it lands directly on the low-resolution tensor (no upsample2x_bwd pass).
 // ---------------------------------------------------------------------------
-static int conv3x3_up_bwd_data_impl(const float* D, const float* wd, int Cin_total, int ci_offset,
-                                    float* g, int N, int h, int w, int Cout, int Ccols,
-                                    int accumulate, unet_stream_t stream, int b16,
-                                    unet_bwd_stats* bs = nullptr, const uint16_t* wdb = nullptr);
+static int conv3x3_up_bwd_data_impl(const void* D, const float* wd, int Cin_total, int ci_offset,
+                                    void* g, int N, int h, int w, int Cout, int Ccols,
+                                    int accumulate, const ConvMode& m, unet_bwd_stats* bs,
+                                    hipStream_t stream) {
+  if (bs) bs->tiles_out = 0;
+  UNET_REQUIRE(D && wd && g, "conv3x3_up_bwd_data: null pointer");
+  UNET_REQUIRE(Cout > 0 && Cout % 32 == 0 && Ccols > 0 && Ccols % 32 == 0 && ci_offset >= 0 &&
+                   ci_offset + Ccols <= Cin_total && N > 0 && h > 0 && w > 0,
+               "conv3x3_up_bwd_data: bad shape Cout=%d Ccols=%d slice %d of %d", Cout, Ccols,
+               ci_offset, Cin_total);
+  UNET_REQUIRE((long long)9 * Cout * Cin_total * 4 < (1LL << 31),
+               "conv3x3_up_bwd_data: weights exceed 2 GiB");
+  const long long D_image = (long long)h * w * 9 * Cout * (long long)m.es();
+  return for_each_chunk("conv3x3_up_bwd_data", N, D_image, [&](Batch b) {
+    BsBinder bsb(b.whole(bs), true, N, h * w, Ccols);
+    // (the pre-rounded weights select the plain-GEMM form of conv_lowp.hip)
+    IgemmParams p = dgrad_params(D, wd, Cin_total, ci_offset, g, b, h, w, Cout, Ccols, 1, 3,
+                                 accumulate, true, m);
+    bsb.bind(p);
+    const int rc = m.b16_tensors() ? dispatch_igemm_b16(p, stream, nullptr, bsb.report())
+                                   : dispatch_igemm(p, stream, nullptr, bsb.report());
+    return bsb.done_px(rc, h * w);
+  });
+}
 
 extern "C" int unet_conv3x3_up_bwd_data_bs(const float* D, const float* wd, int Cin_total,
                                            int ci_offset, float* g, int N, int h, int w, int Cout,
                                            int Ccols, int accumulate, unet_bwd_stats* bs,
                                            unet_stream_t stream) {
   return conv3x3_up_bwd_data_impl(D, wd, Cin_total, ci_offset, g, N, h, w, Cout, Ccols, accumulate,
-                                  stream, 0, bs);
+                                  ConvMode::f32(), bs, (hipStream_t)stream);
 }
 
 extern "C" int unet_conv3x3_up_bwd_data(const float* D, const float* wd, int Cin_total,
                                         int ci_offset, float* g, int N, int h, int w, int Cout,
                                         int Ccols, int accumulate, unet_stream_t stream) {
   return conv3x3_up_bwd_data_impl(D, wd, Cin_total, ci_offset, g, N, h, w, Cout, Ccols, accumulate,
-                                  stream, 0);
+                                  ConvMode::f32(), nullptr, (hipStream_t)stream);
 }
 
 extern "C" int unet_conv3x3_up_bwd_data_b16(const uint16_t* D, const float* wd, int Cin_total,
                                             int ci_offset, uint16_t* g, int N, int h, int w,
                                             int Cout, int Ccols, int accumulate,
                                             unet_stream_t stream) {
-  return conv3x3_up_bwd_data_impl(reinterpret_cast<const float*>(D), wd, Cin_total, ci_offset,
-                                  reinterpret_cast<float*>(g), N, h, w, Cout, Ccols, accumulate,
-                                  stream, 1);
+  return conv3x3_up_bwd_data_impl(D, wd, Cin_total, ci_offset, g, N, h, w, Cout, Ccols, accumulate,
+                                  ConvMode::b16(nullptr), nullptr, (hipStream_t)stream);
 }
 
 // wdb = the data-gradient weights pre-rounded to bf16 ([9][Cin_total][Cout], plane 0 of the
@@ -2042,9 +1840,8 @@ extern "C" int unet_conv3x3_up_bwd_data_bs_b16_wb(const uint16_t* D, const float
                                                   int ci_offset, uint16_t* g, int N, int h, int w,
                                                   int Cout, int Ccols, int accumulate,
                                                   unet_bwd_stats* bs, unet_stream_t stream) {
-  return conv3x3_up_bwd_data_impl(reinterpret_cast<const float*>(D), wd, Cin_total, ci_offset,
-                                  reinterpret_cast<float*>(g), N, h, w, Cout, Ccols, accumulate,
-                                  stream, 1, bs, wdb);
+  return conv3x3_up_bwd_data_impl(D, wd, Cin_total, ci_offset, g, N, h, w, Cout, Ccols, accumulate,
+                                  ConvMode::b16(wdb), bs, (hipStream_t)stream);
 }
 
 // the same with the BSTATS epilogue: g is final for the layer described by bs (bs->y bf16)
@@ -2052,133 +1849,8 @@ extern "C" int unet_conv3x3_up_bwd_data_bs_b16(const uint16_t* D, const float* w
                                                int ci_offset, uint16_t* g, int N, int h, int w,
                                                int Cout, int Ccols, int accumulate,
                                                unet_bwd_stats* bs, unet_stream_t stream) {
-  return conv3x3_up_bwd_data_impl(reinterpret_cast<const float*>(D), wd, Cin_total, ci_offset,
-                                  reinterpret_cast<float*>(g), N, h, w, Cout, Ccols, accumulate,
-                                  stream, 1, bs);
-}
-
-static int conv3x3_up_bwd_data_impl(const float* D, const float* wd, int Cin_total, int ci_offset,
-                                    float* g, int N, int h, int w, int Cout, int Ccols,
-                                    int accumulate, unet_stream_t stream, int b16,
-                                    unet_bwd_stats* bs, const uint16_t* wdb) {
-  const long long es = b16 ? 2 : 4;
-  if (bs) bs->tiles_out = 0;
-  const bool use_bs = bs && bs->y && bs->mean && bs->rstd && bs->gamma && bs->beta &&
-                      bs->partial &&
-                      bs->partial_bytes >= (size_t)N * ceil_div(h * w, 64) * Ccols * sizeof(float2);
-  UNET_REQUIRE(D && wd && g, "conv3x3_up_bwd_data: null pointer");
-  UNET_REQUIRE(Cout > 0 && Cout % 32 == 0 && Ccols > 0 && Ccols % 32 == 0 && ci_offset >= 0 &&
-                   ci_offset + Ccols <= Cin_total && N > 0 && h > 0 && w > 0,
-               "conv3x3_up_bwd_data: bad shape Cout=%d Ccols=%d slice %d of %d", Cout, Ccols,
-               ci_offset, Cin_total);
-  UNET_REQUIRE((long long)9 * Cout * Cin_total * 4 < (1LL << 31),
-               "conv3x3_up_bwd_data: weights exceed 2 GiB");
-  {
-    const int nmax = batch_chunk(N, (long long)h * w * 9 * Cout * es);
-    UNET_REQUIRE(nmax >= 1, "conv3x3_up_bwd_data: one image exceeds the 2 GiB buffer-descriptor range");
-    if (nmax < N) {
-      for (int nb = 0; nb < N; nb += nmax) {
-        const int n = N - nb < nmax ? N - nb : nmax;
-        const int rc = conv3x3_up_bwd_data_impl(
-            reinterpret_cast<const float*>(reinterpret_cast<const char*>(D) +
-                                           (size_t)nb * h * w * 9 * Cout * es),
-            wd, Cin_total, ci_offset,
-            reinterpret_cast<float*>(reinterpret_cast<char*>(g) + (size_t)nb * h * w * Ccols * es),
-            n, h, w, Cout, Ccols, accumulate, stream, b16, nullptr, wdb);
-        if (rc != UNET_OK) return rc;
-      }
-      return UNET_OK;
-    }
-  }
-  IgemmParams p{};
-  p.src0 = D; p.src1 = nullptr; p.C0 = Cout; p.C1 = 0;
-  if (b16 && wdb) {   // the weights pre-rounded to bf16: the plain-GEMM form (conv_lowp.hip)
-    p.w3 = reinterpret_cast<const __bf16*>(wdb);
-    p.w3_plane = 9 * Cout * Cin_total;
-    p.w3_bytes = (unsigned)((long long)p.w3_plane * 2);
-  }
-  p.src0_pitch = 9 * Cout; p.tap_cstride = Cout;
-  p.w = wd; p.tap_stride = Cin_total * Cout; p.n_off = ci_offset; p.bias = nullptr;
-  p.src0_bytes = (unsigned)((long long)N * h * w * 9 * Cout * es);
-  p.src1_bytes = 0;
-  p.w_bytes = (unsigned)((long long)9 * Cout * Cin_total * 4);
-  p.out = g; p.ldo = Ccols; p.accumulate = accumulate;
-  p.N = N; p.Hin = p.Hl = p.Hout = h; p.Win = p.Wl = p.Wout = w;
-  p.Ncols = Ccols; p.sin = 1; p.sout = 1; p.py = p.px = 0;
-  p.ntaps = 9; p.tapw[0] = p.tapw[1] = p.tapw[2] = 0;
-  for (int t = 0; t < 9; ++t) set_tap(p, t, 0, 0, t);
-  int bs_px = 0;
-  if (use_bs) {
-    p.bs_y = bs->y; p.bs_mean = bs->mean; p.bs_rstd = bs->rstd; p.bs_gamma = bs->gamma;
-    p.bs_beta = bs->beta; p.bs_mask = bs->mask; p.slope = bs->slope;
-    p.bs_partial = reinterpret_cast<float2*>(bs->partial);
-  }
-  const int rc = b16 ? dispatch_igemm_b16(p, (hipStream_t)stream, nullptr, use_bs ? &bs_px : nullptr)
-                     : dispatch_igemm(p, (hipStream_t)stream, nullptr, use_bs ? &bs_px : nullptr);
-  if (rc == UNET_OK && use_bs && bs_px > 0) bs->tiles_out = h * w / bs_px;
-  return rc;
-}
-
-// unet_conv_up_in_fwd on bf16 tensors (mixed-precision pipeline): low [N][H/2][W/2][C0] and
-// skip [N][H][W][C1] are bf16 and activated on load, y [N][H][W][Cout] is bf16; wf fp32 packed
-// weights, w3 (may be null) their bf16-rounded plane.  1 from _supported = a tile shape exists.
-extern "C" int unet_conv_up_in_fwd_b16_supported(int N, int H, int W, int C0, int C1, int Cout) {
-  if (N <= 0 || H <= 0 || W <= 0 || H % 4 || W % 32 || C0 < 32 || C0 % 32 || C1 < 0 || C1 % 32 ||
-      Cout % 32)
-    return 0;
-  const long long M = (long long)N * H * W, mt = M / 128;
-  if ((long long)H * W * (C0 > 4 * C1 ? C0 / 4 : C1) * 2 * N >= (1LL << 31)) return 0;
-  if (Cout % 64 == 0 && mt * (Cout / 64) >= 256) return 1;
-  if (Cout == 32 && H % 8 == 0 && M / 256 >= 256) return 1;
-  return 0;
-}
-
-extern "C" int unet_conv_up_in_fwd_b16(const unet_act_src* low, const unet_act_src* skip,
-                                       float slope, const float* wf, const uint16_t* w3,
-                                       const float* bias, uint16_t* y, void* workspace,
-                                       size_t workspace_bytes, int* stats_px_out, int N, int H,
-                                       int W, int Cout, unet_stream_t stream) {
-  UNET_REQUIRE(low && low->x && wf && w3 && y && workspace && stats_px_out,
-               "conv_up_in_fwd_b16: null pointer (w3, the bf16 weight plane of unet_pack_w_batched, "
-               "is required here)");
-  const int C0 = low->C, C1 = skip ? skip->C : 0;
-  UNET_REQUIRE(C1 == 0 || skip->x, "conv_up_in_fwd_b16: skip source is null");
-  UNET_REQUIRE(low->alpha && low->beta && (!skip || (skip->alpha && skip->beta)),
-               "conv_up_in_fwd_b16: the loader takes activated sources (alpha / beta set)");
-  UNET_REQUIRE(H % 2 == 0 && W % 2 == 0 && unet_conv_up_in_fwd_b16_supported(N, H, W, C0, C1, Cout),
-               "conv_up_in_fwd_b16: shape N=%d %dx%d (%d+%d)->%d has no fused-upsample tile (query "
-               "unet_conv_up_in_fwd_b16_supported and fall back to unet_upsample2x_in_fwd_b16)",
-               N, H, W, C0, C1, Cout);
-  if (workspace_bytes < unet_conv_in_fwd_workspace_bytes(N, H, W, Cout, 1)) {
-    unet_set_error("conv_up_in_fwd_b16: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
-  IgemmParams p{};
-  p.src0 = low->x; p.src1 = skip ? skip->x : nullptr; p.C0 = C0; p.C1 = C1;
-  p.act0_alpha = low->alpha; p.act0_beta = low->beta;
-  p.act1_alpha = skip ? skip->alpha : nullptr;
-  p.act1_beta = skip ? skip->beta : nullptr;
-  p.slope = slope;
-  p.w = wf; p.tap_stride = Cout * (C0 + C1); p.n_off = 0; p.bias = bias;
-  if (w3) {
-    p.w3 = reinterpret_cast<const __bf16*>(w3);
-    p.w3_plane = 9 * Cout * (C0 + C1);
-    p.w3_bytes = (unsigned)((long long)p.w3_plane * 2);
-  }
-  p.src0_bytes = (unsigned)((long long)N * (H / 2) * (W / 2) * C0 * 2);
-  p.src1_bytes = (unsigned)((long long)N * H * W * C1 * 2);
-  p.w_bytes = (unsigned)((long long)9 * Cout * (C0 + C1) * 4);
-  p.out = reinterpret_cast<float*>(y); p.ldo = Cout; p.accumulate = 0;
-  p.N = N; p.Hin = H; p.Win = W; p.Hl = p.Hout = H; p.Wl = p.Wout = W;
-  p.Ncols = Cout;
-  p.stats = reinterpret_cast<float2*>(workspace);
-  fill_fwd_taps(p, 1);
-  int px = 0;
-  const int rc = launch_patch_b16_up_auto(p, (hipStream_t)stream, &px);
-  UNET_REQUIRE(rc != 1, "conv_up_in_fwd_b16: no tile fits");
-  if (rc != UNET_OK) return rc;
-  *stats_px_out = px;
-  return UNET_OK;
+  return conv3x3_up_bwd_data_impl(D, wd, Cin_total, ci_offset, g, N, h, w, Cout, Ccols, accumulate,
+                                  ConvMode::b16(nullptr), bs, (hipStream_t)stream);
 }
 
 // RGB stem straight from the dataset's uint8 HWC image: normalisation fused into the loader
@@ -2231,6 +1903,8 @@ extern "C" int unet_stem_u8_fwd_b16(const uint8_t* image_hwc, const float* mean3
 // the patch loader (conv_patch.hip conv_patch_up_kernel): UpBlock.forward without the up-sampled
 // tensor and without the concatenation (Our_UNet/models/unet.py:215-231).  low->x is
 // [N][H/2][W/2][C0], skip->x [N][H][W][C1]; workspace / *stats_px_out as unet_conv_in_fwd.
+// On bf16 tensors (mixed-precision pipeline): low and skip are bf16 and must be activated on
+// load, y is bf16; w3 = the bf16-rounded plane of the packed weights, required.
 // ---------------------------------------------------------------------------
 extern "C" int unet_conv_up_in_fwd_supported(int N, int H, int W, int C0, int C1, int Cout) {
   if (N <= 0 || H <= 0 || W <= 0 || H % 4 || W % 32 || C0 < 32 || C0 % 32 || C1 < 0 || C1 % 32 ||
@@ -2246,6 +1920,18 @@ extern "C" int unet_conv_up_in_fwd_supported(int N, int H, int W, int C0, int C1
   return 0;
 }
 
+// 1 from _supported = a tile shape exists
+extern "C" int unet_conv_up_in_fwd_b16_supported(int N, int H, int W, int C0, int C1, int Cout) {
+  if (N <= 0 || H <= 0 || W <= 0 || H % 4 || W % 32 || C0 < 32 || C0 % 32 || C1 < 0 || C1 % 32 ||
+      Cout % 32)
+    return 0;
+  const long long M = (long long)N * H * W, mt = M / 128;
+  if ((long long)H * W * (C0 > 4 * C1 ? C0 / 4 : C1) * 2 * N >= (1LL << 31)) return 0;
+  if (Cout % 64 == 0 && mt * (Cout / 64) >= 256) return 1;
+  if (Cout == 32 && H % 8 == 0 && M / 256 >= 256) return 1;
+  return 0;
+}
+
 // 1 when unet_conv_up_in_fwd runs this shape (both sources activated on load) on the Winograd
 // kernel of csrc/conv_c32.hip (conv_wino_up32_kernel): 16/36 of the direct matrix FLOPs
 extern "C" int unet_conv_up_c32_is_winograd(int N, int H, int W, int C0, int C1, int Cout) {
@@ -2256,43 +1942,65 @@ extern "C" int unet_conv_up_c32_is_winograd(int N, int H, int W, int C0, int C1,
   return f == 2 || (long long)N * (H / 8) * (W / 32) >= 256;
 }
 
+// The two exports differ in the element type, in what they require of the sources and in the
+// wording of their errors (`who`, `twin` = "" / "_b16").
+static int conv_up_in_fwd_impl(const char* who, const char* twin, const unet_act_src* low,
+                               const unet_act_src* skip, float slope, const float* wf,
+                               const float* bias, void* y, void* workspace,
+                               size_t workspace_bytes, int* stats_px_out, int N, int H, int W,
+                               int Cout, const ConvMode& m, hipStream_t stream) {
+  const bool b16 = m.b16_tensors();
+  if (b16)
+    UNET_REQUIRE(low && low->x && wf && m.w3 && y && workspace && stats_px_out,
+                 "%s: null pointer (w3, the bf16 weight plane of unet_pack_w_batched, "
+                 "is required here)", who);
+  else
+    UNET_REQUIRE(low && low->x && wf && y && workspace && stats_px_out, "%s: null pointer", who);
+  const int C0 = low->C, C1 = skip ? skip->C : 0;
+  UNET_REQUIRE(C1 == 0 || skip->x, "%s: skip source is null", who);
+  if (b16)
+    UNET_REQUIRE(low->alpha && low->beta && (!skip || (skip->alpha && skip->beta)),
+                 "%s: the loader takes activated sources (alpha / beta set)", who);
+  else
+    UNET_REQUIRE((!low->alpha || low->beta) && (!skip || !skip->alpha || skip->beta),
+                 "%s: alpha without beta", who);
+  UNET_REQUIRE(H % 2 == 0 && W % 2 == 0 &&
+                   (b16 ? unet_conv_up_in_fwd_b16_supported(N, H, W, C0, C1, Cout)
+                        : unet_conv_up_in_fwd_supported(N, H, W, C0, C1, Cout)),
+               "%s: shape N=%d %dx%d (%d+%d)->%d has no fused-upsample tile (query "
+               "unet_conv_up_in_fwd%s_supported and fall back to unet_upsample2x_in_fwd%s)",
+               who, N, H, W, C0, C1, Cout, twin, twin);
+  if (workspace_bytes < unet_conv_in_fwd_workspace_bytes(N, H, W, Cout, 1)) {
+    unet_set_error("%s: workspace too small", who);
+    return UNET_E_WORKSPACE;
+  }
+  IgemmParams p = fwd_params(conv_src(low), conv_src(skip), slope, wf, bias, y, Batch{0, N, false},
+                             H, W, Cout, 1, 3, true, m);
+  p.stats = reinterpret_cast<float2*>(workspace);
+  int px = 0;
+  const int rc = b16 ? launch_patch_b16_up_auto(p, stream, &px)
+                     : launch_patch_up_auto(p, stream, &px);
+  UNET_REQUIRE(rc != kNoTileFits, "%s: no tile fits", who);
+  if (rc != UNET_OK) return rc;
+  *stats_px_out = px;
+  return UNET_OK;
+}
+
 extern "C" int unet_conv_up_in_fwd(const unet_act_src* low, const unet_act_src* skip, float slope,
                                    const float* wf, const float* bias, float* y, void* workspace,
                                    size_t workspace_bytes, int* stats_px_out, int N, int H, int W,
                                    int Cout, unet_stream_t stream) {
-  UNET_REQUIRE(low && low->x && wf && y && workspace && stats_px_out,
-               "conv_up_in_fwd: null pointer");
-  const int C0 = low->C, C1 = skip ? skip->C : 0;
-  UNET_REQUIRE(C1 == 0 || skip->x, "conv_up_in_fwd: skip source is null");
-  UNET_REQUIRE((!low->alpha || low->beta) && (!skip || !skip->alpha || skip->beta),
-               "conv_up_in_fwd: alpha without beta");
-  UNET_REQUIRE(H % 2 == 0 && W % 2 == 0 && unet_conv_up_in_fwd_supported(N, H, W, C0, C1, Cout),
-               "conv_up_in_fwd: shape N=%d %dx%d (%d+%d)->%d has no fused-upsample tile (query "
-               "unet_conv_up_in_fwd_supported and fall back to unet_upsample2x_in_fwd)",
-               N, H, W, C0, C1, Cout);
-  if (workspace_bytes < unet_conv_in_fwd_workspace_bytes(N, H, W, Cout, 1)) {
-    unet_set_error("conv_up_in_fwd: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
-  IgemmParams p{};
-  p.src0 = low->x; p.src1 = skip ? skip->x : nullptr; p.C0 = C0; p.C1 = C1;
-  p.act0_alpha = low->alpha; p.act0_beta = low->alpha ? low->beta : nullptr;
-  p.act1_alpha = skip ? skip->alpha : nullptr;
-  p.act1_beta = (skip && skip->alpha) ? skip->beta : nullptr;
-  p.slope = slope;
-  p.w = wf; p.tap_stride = Cout * (C0 + C1); p.n_off = 0; p.bias = bias;
-  p.src0_bytes = (unsigned)((long long)N * (H / 2) * (W / 2) * C0 * 4);
-  p.src1_bytes = (unsigned)((long long)N * H * W * C1 * 4);
-  p.w_bytes = (unsigned)((long long)9 * Cout * (C0 + C1) * 4);
-  p.out = y; p.ldo = Cout; p.accumulate = 0;
-  p.N = N; p.Hin = H; p.Win = W; p.Hl = p.Hout = H; p.Wl = p.Wout = W;
-  p.Ncols = Cout;
-  p.stats = reinterpret_cast<float2*>(workspace);
-  fill_fwd_taps(p, 1);
-  int px = 0;
-  const int rc = launch_patch_up_auto(p, (hipStream_t)stream, &px);
-  UNET_REQUIRE(rc != 1, "conv_up_in_fwd: no tile fits");
-  if (rc != UNET_OK) return rc;
-  *stats_px_out = px;
-  return UNET_OK;
+  return conv_up_in_fwd_impl("conv_up_in_fwd", "", low, skip, slope, wf, bias, y, workspace,
+                             workspace_bytes, stats_px_out, N, H, W, Cout, ConvMode::f32(),
+                             (hipStream_t)stream);
+}
+
+extern "C" int unet_conv_up_in_fwd_b16(const unet_act_src* low, const unet_act_src* skip,
+                                       float slope, const float* wf, const uint16_t* w3,
+                                       const float* bias, uint16_t* y, void* workspace,
+                                       size_t workspace_bytes, int* stats_px_out, int N, int H,
+                                       int W, int Cout, unet_stream_t stream) {
+  return conv_up_in_fwd_impl("conv_up_in_fwd_b16", "_b16", low, skip, slope, wf, bias, y, workspace,
+                             workspace_bytes, stats_px_out, N, H, W, Cout, ConvMode::b16(w3),
+                             (hipStream_t)stream);
 }

@@ -752,16 +752,6 @@ int launch_igemm_b16(IgemmParams p, hipStream_t stream, int* stats_px, int* bs_p
   return UNET_OK;
 }
 
-// Deep layers (at most one 64x64 tile per CU): number of K groups per block (1 = no split)
-static int deep_k_groups_b16(const IgemmParams& p) {
-  const long long M = (long long)p.N * p.Hl * p.Wl;
-  if (p.Ncols % 64 != 0 || ceil_div64(M, 64) * (p.Ncols / 64) > 256) return 1;
-  const int ks = p.ntaps * ((p.C0 + p.C1) / 32);
-  int kg = 4;
-  while (kg > 1 && (ks % kg != 0 || ks / kg < 4)) kg >>= 1;
-  return kg;
-}
-
 template <int BM, int BN, int WM, int WN>
 int launch_igemm_split(const IgemmParams& p, hipStream_t stream) {
   constexpr size_t lds = 2 * 3 * (size_t)(BM + BN) * 24 * sizeof(__bf16);
@@ -795,12 +785,12 @@ int dispatch_igemm_b16(const IgemmParams& p, hipStream_t stream, int* stats_px, 
   {   // stride-1 3x3 that tiles as 4 x 32 pixels: the patch-staged kernel (conv_patch.hip);
       // only it has the BSTATS epilogue (bs_px), the gather-GEMM forms report 0 tiles
     const int rc = launch_patch_b16_auto(p, stream, stats_px, bs_px);
-    if (rc != 1) return rc;
+    if (rc != kNoTileFits) return rc;
     if (bs_px) *bs_px = 0;
   }
   if (stats_px && !bs_px) {   // the stride-2 fused forward: its own patch form (conv_patch.hip)
     const int rc = launch_patch_s2_b16_auto(p, stream, stats_px);
-    if (rc != 1) return rc;
+    if (rc != kNoTileFits) return rc;
   }
   // "channel taps" on contiguous rows with the bf16 weight plane: the plain-GEMM (DENSE) form.
   // 64 x 64 tiles throughout - four workgroups per CU (37 KB of LDS, 94 registers): the K loop
@@ -826,7 +816,7 @@ int dispatch_igemm_b16(const IgemmParams& p, hipStream_t stream, int* stats_px, 
       (p.ntaps * ((p.C0 + p.C1) / 64)) % 4 == 0 && p.ntaps * ((p.C0 + p.C1) / 64) >= 8)
     return launch_igemm_b16<64, 64, 32, 32, 4, 1>(p, stream, stats_px, bs_px);
   if (nc % 64 == 0 && M <= 128 * 256) {
-    const int kg = deep_k_groups_b16(p);
+    const int kg = deep_k_groups(p);
     return kg == 4   ? launch_igemm_b16<64, 64, 32, 32, 4>(p, stream, stats_px, bs_px)
            : kg == 2 ? launch_igemm_b16<64, 64, 32, 32, 2>(p, stream, stats_px, bs_px)
                      : launch_igemm_b16<64, 64, 32, 32>(p, stream, stats_px, bs_px);

@@ -77,6 +77,21 @@ inline int batch_chunk(int N, long long per_image_bytes) {
   return (int)(n < N ? n : N);
 }
 
+// "No tile shape fits this launch: try the next form" - what the launch_*_auto functions answer
+// besides UNET_OK / UNET_E_*.  Distinct from every UNET_* code (those are <= 0); it stays
+// between the dispatchers and never leaves an export.
+constexpr int kNoTileFits = 1;
+
+// Deep layers (at most one 64x64 tile per CU): number of K groups per block (1 = no split).
+inline int deep_k_groups(const IgemmParams& p) {
+  const long long M = (long long)p.N * p.Hl * p.Wl;
+  if (p.Ncols % 64 != 0 || ceil_div64(M, 64) * (p.Ncols / 64) > 256) return 1;
+  const int ks = p.ntaps * ((p.C0 + p.C1) / 32);
+  int kg = 4;
+  while (kg > 1 && (ks % kg != 0 || ks / kg < 4)) kg >>= 1;
+  return kg;
+}
+
 inline void set_tap(IgemmParams& p, int t, int oy, int ox, int wt) {
   const unsigned e = (unsigned)(oy + 1) | ((unsigned)(ox + 1) << 2) | ((unsigned)wt << 4);
   p.tapw[t >> 2] |= e << ((t & 3) * 8);
@@ -243,7 +258,7 @@ __device__ __forceinline__ bool block_col_stats(float2* red, int wave_m, int col
 
 // ---- dispatchers implemented in the other translation units -------------------------------
 bool patch_f32_applicable(const IgemmParams& p);              // conv_patch.hip
-int launch_patch_f32_auto(const IgemmParams& p, hipStream_t stream,    // returns 1 if no tile fits
+int launch_patch_f32_auto(const IgemmParams& p, hipStream_t stream,    // kNoTileFits if none
                           int* stats_px = nullptr, int* bs_px = nullptr);
 int launch_patch_up_auto(const IgemmParams& p, hipStream_t stream, int* stats_px);
 int& c32_winograd_flag();                                      // unet_set_c32_winograd, conv_c32.hip

@@ -2227,7 +2227,8 @@ int launch_dgrad_s2_patch_b16(const IgemmParams& p, hipStream_t stream) {
 int launch_dgrad_s2_patch_b16_auto(const IgemmParams& p0, hipStream_t stream, int* bs_tiles_out) {
   IgemmParams p = p0;
   if (bs_tiles_out) *bs_tiles_out = 0;
-  if (p.Wl % 32 != 0 || p.C0 % 32 != 0 || p.Hout != 2 * p.Hl || p.Wout != 2 * p.Wl) return 1;
+  if (p.Wl % 32 != 0 || p.C0 % 32 != 0 || p.Hout != 2 * p.Hl || p.Wout != 2 * p.Wl)
+    return kNoTileFits;
   const long long pos = (long long)p.N * p.Hl * p.Wl;
   const int nc = p.Ncols;
   p.bs_tile0 = 0;
@@ -2242,16 +2243,17 @@ int launch_dgrad_s2_patch_b16_auto(const IgemmParams& p0, hipStream_t stream, in
     if (bs_tiles_out) *bs_tiles_out = p.bs_partial ? p.bs_tiles : 0;
     return launch_dgrad_s2_patch_b16<32, 64, 32, 8>(p, stream);
   }
-  return 1;
+  return kNoTileFits;
 }
 
 // Stride-2 data gradient on the patch-staged kernel: p describes the dy grid (Hl x Wl, K = C0,
-// fp32) and dx = (2 Hl) x (2 Wl) x Ncols.  Returns 1 when the shape does not tile or too few
-// tiles would run (the caller keeps its gather-GEMM forms).  With p.bs_partial set the BSTATS
+// fp32) and dx = (2 Hl) x (2 Wl) x Ncols.  Returns kNoTileFits when the shape does not tile or too
+// few tiles would run (the caller keeps its gather-GEMM forms).  With p.bs_partial set the BSTATS
 // epilogue runs and *bs_tiles_out receives the reduction tiles per image.
 int launch_dgrad_s2_patch_auto(const IgemmParams& p0, hipStream_t stream, int* bs_tiles_out) {
   IgemmParams p = p0;
-  if (p.Wl % 32 != 0 || p.C0 % 32 != 0 || p.Hout != 2 * p.Hl || p.Wout != 2 * p.Wl) return 1;
+  if (p.Wl % 32 != 0 || p.C0 % 32 != 0 || p.Hout != 2 * p.Hl || p.Wout != 2 * p.Wl)
+    return kNoTileFits;
   const long long pos = (long long)p.N * p.Hl * p.Wl;
   const int nc = p.Ncols;
   p.bs_tile0 = 0;
@@ -2265,7 +2267,7 @@ int launch_dgrad_s2_patch_auto(const IgemmParams& p0, hipStream_t stream, int* b
     if (bs_tiles_out) *bs_tiles_out = p.bs_partial ? p.bs_tiles : 0;
     return launch_dgrad_s2_patch<32, 64, 32, 8>(p, stream);
   }
-  return 1;
+  return kNoTileFits;
 }
 
 // stride-2 3x3 forward whose OUTPUT tiles as 4 x 32 pixels, 16-channel chunks, standard taps
@@ -2295,14 +2297,14 @@ int launch_patch_b16_up_t(const IgemmParams& p, hipStream_t stream) {
 }
 
 // y = conv3x3(cat(upsample2x(act(low)), act(skip))) on bf16 tensors: p.src0 = low
-// [N][Hin/2][Win/2][C0], p.src1 = skip [N][Hin][Win][C1], both activated on load.  Returns 1 when
+// [N][Hin/2][Win/2][C0], p.src1 = skip [N][Hin][Win][C1], both activated on load.  kNoTileFits when
 // no tile shape fits (the caller materialises the up-sampled tensor).
 int launch_patch_b16_up_auto(const IgemmParams& p0, hipStream_t stream, int* stats_px) {
   IgemmParams p = p0;
   if (p.Hin % 4 || p.Win % 32 || p.C0 % 32 || p.C1 % 32 || p.C0 < 32 || !p.act0_alpha ||
       (p.C1 && !p.act1_alpha) || !p.w3 || p.accumulate || (p.ldo & 7) ||
       (reinterpret_cast<uintptr_t>(p.out) & 15))
-    return 1;
+    return kNoTileFits;
   const long long M = (long long)p.N * p.Hin * p.Win, mt = M / 128;
   const int nc = p.Ncols;
   p.bs_partial = nullptr;
@@ -2318,7 +2320,7 @@ int launch_patch_b16_up_auto(const IgemmParams& p0, hipStream_t stream, int* sta
     *stats_px = p.stats ? 256 : 0; p.stats_tiles = p.Hin * p.Win / 256;
     return launch_patch_b16_up_t<32, 64, 32, 8>(p, stream);
   }
-  return 1;
+  return kNoTileFits;
 }
 
 template <int BN, int WM, int WN, int TH, bool ACT, bool STATS, bool BSTATS = false>
@@ -2345,10 +2347,10 @@ int launch_patch_b16_t(const IgemmParams& p, hipStream_t stream) {
 
 // Mixed-precision pipeline (bf16 tensors): stride-1 3x3 whose image tiles as 4 x 32 pixels.
 // stats_px != nullptr = fused forward (activation on load + statistics), else data gradient.
-// Returns 1 when the shape does not qualify (the caller keeps the bf16 gather-GEMM).
+// Returns kNoTileFits when the shape does not qualify (the caller keeps the bf16 gather-GEMM).
 int launch_patch_b16_auto(const IgemmParams& p0, hipStream_t stream, int* stats_px, int* bs_px) {
   if (bs_px) *bs_px = 0;
-  if (!patch_f32_applicable(p0) || p0.src0_pitch) return 1;
+  if (!patch_f32_applicable(p0) || p0.src0_pitch) return kNoTileFits;
   IgemmParams p = p0;
   const long long M = (long long)p.N * p.Hl * p.Wl;
   const int nc = p.Ncols;
@@ -2376,7 +2378,7 @@ int launch_patch_b16_auto(const IgemmParams& p0, hipStream_t stream, int* stats_
       *bs_px = 256; p.bs_tiles = p.Hin * p.Win / 256;
       return launch_patch_b16_t<32, 64, 32, 8, false, false, true>(p, stream);
     }
-    return 1;
+    return kNoTileFits;
   }
   p.bs_partial = nullptr;
   if (th8) {
@@ -2399,12 +2401,12 @@ int launch_patch_b16_auto(const IgemmParams& p0, hipStream_t stream, int* stats_
     *stats_px = p.stats ? 256 : 0; p.stats_tiles = p.Hin * p.Win / 256;
     return launch_patch_b16_t<32, 64, 32, 8, true, true>(p, stream);
   }
-  return 1;
+  return kNoTileFits;
 }
 
-// Fused-layer stride-2 forward on the patch-staged kernel; returns 1 when no tile shape fills
+// Fused-layer stride-2 forward on the patch-staged kernel; kNoTileFits when no tile shape fills
 // the chip (the caller falls back to the gather-GEMM).  *stats_px = pixels per statistics tile.
-// Stride-2 fused forward on bf16 tensors (round 4): conv_patch_b16_kernel<.., SD = 2>.  Returns 1
+// Stride-2 fused forward on bf16 tensors (round 4): conv_patch_b16_kernel<.., SD = 2>.  kNoTileFits
 // when the shape does not tile or fill the chip (the caller keeps the bf16 gather-GEMM).
 template <int BN, int WM, int WN, int TH>
 int launch_patch_b16_s2_t(const IgemmParams& p, hipStream_t stream) {
@@ -2421,7 +2423,7 @@ int launch_patch_s2_b16_auto(const IgemmParams& p0, hipStream_t stream, int* sta
   IgemmParams p = p0;
   if (!p.w3 || !patch_s2_applicable(p) || p.C0 % 32 || p.C1 % 32 || (p.ldo & 7) ||
       (reinterpret_cast<uintptr_t>(p.out) & 15))
-    return 1;
+    return kNoTileFits;
   const long long mt = (long long)p.N * p.Hl * p.Wl / 128;
   const int nc = p.Ncols;
   if (nc % 64 == 0 && mt * (nc / 64) >= 512) {
@@ -2430,7 +2432,7 @@ int launch_patch_s2_b16_auto(const IgemmParams& p0, hipStream_t stream, int* sta
     p.bs_partial = nullptr;
     return launch_patch_b16_s2_t<64, 64, 32, 4>(p, stream);
   }
-  return 1;
+  return kNoTileFits;
 }
 
 int launch_patch_s2_auto(const IgemmParams& p0, hipStream_t stream, int* stats_px) {
@@ -2442,7 +2444,7 @@ int launch_patch_s2_auto(const IgemmParams& p0, hipStream_t stream, int* stats_p
   if (nc % 128 == 0 && mt * (nc / 128) >= 512) return launch_patch_s2<128, 64, 64, 4>(p, stream);
   if (nc % 64 == 0 && mt * (nc / 64) >= 512) return launch_patch_s2<64, 64, 32, 4>(p, stream);
   *stats_px = 0;
-  return 1;
+  return kNoTileFits;
 }
 
 // stride-1 3x3 over an image that tiles as 4 x 32 pixels, 16-channel chunks
@@ -2460,7 +2462,7 @@ bool patch_f32_applicable(const IgemmParams& p) {
 }
 
 // fp32: measured on the net's layers +5..19 % over the gather-GEMM at 64 and 128 columns, +8 %
-// at 32 columns when K > 32 (K = 32 stays on the row-fused kernel).  Returns 1 when no tile
+// at 32 columns when K > 32 (K = 32 stays on the row-fused kernel).  kNoTileFits when no tile
 // shape fits (too few tiles): the caller falls back to the gather-GEMM.
 // stats_px != nullptr selects the fused-layer instantiation (activation on load, statistics
 // epilogue into p.stats) and receives the number of pixels per statistics tile.
@@ -2486,7 +2488,7 @@ int launch_patch_f32_auto(const IgemmParams& p0, hipStream_t stream, int* stats_
       *bs_px = 256; p.bs_tiles = p.Hin * p.Win / 256;
       return launch_patch_f32<32, 64, 32, 8, false, false, true>(p, stream);
     }
-    return 1;
+    return kNoTileFits;
   }
   if (nc % 128 == 0 && mt * (nc / 128) >= 512) {
     if (!fused) return launch_patch_f32<128, 64, 64, 4>(p, stream);
@@ -2503,18 +2505,19 @@ int launch_patch_f32_auto(const IgemmParams& p0, hipStream_t stream, int* stats_
     *stats_px = p.stats ? 256 : 0; p.stats_tiles = p.Hin * p.Win / 256;
     return launch_patch_f32<32, 64, 32, 8, true, true>(p, stream);
   }
-  return 1;
+  return kNoTileFits;
 }
 
 // conv3x3(cat(upsample2x(act(src0 at half resolution)), act(src1))): the up-sampling in the
-// loader.  Same tile choice as launch_patch_f32_auto; returns 1 when no tile fits (the caller
+// loader.  Same tile choice as launch_patch_f32_auto; kNoTileFits when no tile fits (the caller
 // then materialises the up-sampled operand).
 int launch_patch_up_auto(const IgemmParams& p0, hipStream_t stream, int* stats_px) {
   IgemmParams p = p0;
   const long long M = (long long)p.N * p.Hl * p.Wl;
   const int nc = p.Ncols;
   const long long mt = M / 128;
-  if (p.Hin % 4 != 0 || p.Win % 32 != 0 || p.C0 % 32 != 0 || p.C1 % 32 != 0 || p.C0 < 32) return 1;
+  if (p.Hin % 4 != 0 || p.Win % 32 != 0 || p.C0 % 32 != 0 || p.C1 % 32 != 0 || p.C0 < 32)
+    return kNoTileFits;
   if (nc % 128 == 0 && mt * (nc / 128) >= 512) {
     *stats_px = p.stats ? 128 : 0; p.stats_tiles = p.Hin * p.Win / 128;
     return launch_patch_up<128, 64, 64, 4>(p, stream);
@@ -2531,12 +2534,12 @@ int launch_patch_up_auto(const IgemmParams& p0, hipStream_t stream, int* stats_p
     *stats_px = p.stats ? 256 : 0; p.stats_tiles = p.Hin * p.Win / 256;
     return launch_patch_up<32, 64, 32, 8>(p, stream);
   }
-  return 1;
+  return kNoTileFits;
 }
 
 // The split mode of the fused layer pipeline: stats_px != nullptr = fused forward (activation
 // on load, statistics epilogue), bs_px != nullptr = data gradient with the BSTATS epilogue.
-// Returns 1 when no tile shape fills the chip (the caller runs the fp32 fused kernel instead).
+// kNoTileFits when no tile shape fills the chip (the caller runs the fp32 fused kernel instead).
 int launch_patch_split_fused_auto(const IgemmParams& p0, hipStream_t stream, int* stats_px,
                                   int* bs_px) {
   IgemmParams p = p0;
@@ -2550,7 +2553,7 @@ int launch_patch_split_fused_auto(const IgemmParams& p0, hipStream_t stream, int
   else if (nc % 64 == 0 && tall && (M / 256) * (nc / 64) >= 512) { cls = 2; px = 256; }
   else if (nc % 64 == 0 && (M / 128) * (nc / 64) >= 256) { cls = 3; px = 128; }
   else if (nc == 32 && tall && (M / 256) >= 512) { cls = 4; px = 256; }
-  if (!cls) return 1;
+  if (!cls) return kNoTileFits;
   if (fwd) {
     *stats_px = p.stats ? px : 0;
     p.stats_tiles = p.Hin * p.Win / px;
