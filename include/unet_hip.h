@@ -413,6 +413,66 @@ int unet_augment_u8(const uint8_t* image, const uint8_t* mask, uint8_t* image_ou
                     uint8_t* mask_out, const float* params, const uint32_t* rng, int N, int H,
                     int W, unet_stream_t stream);
 
+/* ---- elastic, grid and optical distortion: a per-pixel warp in front of the homography ------ */
+
+/* Floats per sample record `warp` of unet_augment_warp_u8 / unet_elastic_field (64). */
+int unet_augment_warp_params_per_sample(void);
+
+/* unet_augment_u8 behind a warp stage (normative text).  The warp acts in the OUTPUT
+ * frame, before the homography: output pixel (i, j) with centre xc = j + 0.5, yc = i + 0.5 goes
+ * through the stage below to (xw, yw), and from there on everything of the unet_augment_u8 comment
+ * holds with (xw, yw) in place of (xc, yc) in den, u and v.  The hole test stays on the integer
+ * output pixel (i, j), the random counters on the output pixel index i W + j, and the mask is
+ * sampled at (floor(v), floor(u)) of the same warped coordinates.  Every fp32 operation is rounded
+ * on its own, in the order the parentheses give; range tests are made in float before any
+ * conversion; !(den > 0) is outside.
+ * warp [N][64] (fp32, DEVICE, read by the kernels only): value 0 is the mode, 1.. the mode's
+ * numbers, every value a mode does not name is 0:
+ *   mode 0, none:    (xw, yw) = (xc, yc): the bytes of unet_augment_u8 on the same params / rng.
+ *                    Any mode value other than 1, 2, 3 is treated as 0.
+ *   mode 1, elastic: 1-6 a0..a5, 7 alpha (pixels), 8 R (radius, 0..16), 9-25 g[0..16] (taps of the
+ *                    Gaussian, g[t] = 0 for t > R).
+ *                      xw = (((a0 xc) + (a1 yc)) + a2) + dx(i, j)
+ *                      yw = (((a3 xc) + (a4 yc)) + a5) + dy(i, j)
+ *                    (dx, dy) = field[n][i][j][0..1] as unet_elastic_field wrote it; 0 with a
+ *                    null field.  alpha, R and g are read by unet_elastic_field only.
+ *   mode 2, grid:    1 Kx, 2 invcell_x, 3 Ky, 4 invcell_y, 8-15 ax_k, 16-23 bx_k, 24-31 ay_k,
+ *                    32-39 by_k (k < K; 1 <= K <= 8).  Per axis, independently:
+ *                      k = min((int)floor(xc invcell_x), Kx - 1),  xw = (ax_k xc) + bx_k
+ *                    and the same in y with yc.  (On the device the cell index is clamped to
+ *                    0..7 in float first, so a record never indexes past its 64 floats.)
+ *   mode 3, optical: 1 cx, 2 cy, 3 k, 4 iw = 1/W, 5 ih = 1/H (rounded to fp32 by the host).
+ *                      ex = xc - cx, ey = yc - cy, xn = ex iw, yn = ey ih,
+ *                      r2 = (xn xn) + (yn yn),  f = (1 + (k r2)) + ((k r2) r2),
+ *                      xw = cx + (ex f),  yw = cy + (ey f).
+ * field [N][H][W][2] (fp32, nullable, 8-byte aligned) is read for the samples of mode 1 only.
+ * UNET_E_INVALID before any launch: as unet_augment_u8, and a null warp, a misaligned field, an
+ * output overlapping warp or field. */
+int unet_augment_warp_u8(const uint8_t* image, const uint8_t* mask, uint8_t* image_out,
+                         uint8_t* mask_out, const float* params, const uint32_t* rng,
+                         const float* warp, const float* field, int N, int H, int W,
+                         unet_stream_t stream);
+
+/* The displacement field of the elastic samples: field[n][i][j][0..1] = (dx, dy) in pixels
+ * (fp32), written for the samples whose warp record has mode 1 ONLY - the workgroups of every
+ * other sample return at once and leave their slice of `field` untouched, so the launch is the
+ * same for every batch and a captured one follows new records.  Grid (32 x 32 tiles, N), 48 KB LDS.
+ *   noise      n_c(i, j) = (2 u) - 1, u = (word_c >> 8) 2^-24, c = 0 (x), 1 (y): words 0 and 1 of
+ *              Philox4x32-10 STREAM 2, key (seed_lo, seed_hi) of rng[n], counter (pixel index lo,
+ *              hi, 2, 0) with the pixel index i W + j.  At a position outside the image the noise
+ *              is exactly 0.  With rng == NULL all noise is 0 and so is the field.
+ *   smoothing  separable Gaussian of radius R, one-sided taps g[0..R] from the record (the host
+ *              computes them in fp64 - exp(-t^2 / (2 sigma^2)), normalised so that g[0] + 2 sum
+ *              g[1..R] = 1 - and rounds them to fp32; the device evaluates no exp);
+ *              R = min(ceil(3 sigma), 16).
+ *   row pass   r_c(i, j) = sum over t = -R..R, ascending, from 0.f, of g[|t|] n_c(i, j + t): each
+ *              product and each sum rounded on its own; rows outside the image give 0.
+ *   column     d_c(i, j) = alpha * (the same sum over r_c(i + t, j)).
+ * UNET_E_INVALID before any launch: null field / warp, a bad shape (as unet_augment_u8), a field
+ * that is not 8-byte aligned or overlaps warp / rng. */
+int unet_elastic_field(float* field, const float* warp, const uint32_t* rng, int N, int H, int W,
+                       unet_stream_t stream);
+
 /* uint8 HWC image (+ uint8 mask) -> ((v/255) - mean)/std NHWC fp32 (+ int64 target with values
  * > 2 other than 255 mapped to 0): PetSegmentationDataset.__getitem__, src/train.py:300-311.
  * mean3 / std3 are HOST pointers to 3 floats. */

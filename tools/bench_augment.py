@@ -129,7 +129,7 @@ def bench_feed(batches, dev, args):
         if form == "copy":
             return
         p, r = ua.augment.sample_params(aug.cfg, n, hw, hw, aug.generator)
-        dp, dr = aug._stage(p, r, dev)
+        dp, dr, _ = aug._stage(p, r, dev)
         if form == "copy+records+kernel":
             ua.ops.augment_u8(x, m, dp, dr, out=out)
 

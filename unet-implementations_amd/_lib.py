@@ -98,6 +98,9 @@ SIGNATURES = {
     "unet_eval_maps": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "unet_augment_params_per_sample": (_i, []),
     "unet_augment_u8": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "unet_augment_warp_params_per_sample": (_i, []),
+    "unet_augment_warp_u8": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "unet_elastic_field": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "unet_gradcam_workspace_bytes": (_sz, [_i, _i, _i]),
     "unet_gradcam_weights": (_i, [_p, _i, _p, _p, _sz, _i, _i, _i, _p]),
     "unet_gradcam_map": (_i, [_ps, _i, _f, _p, _p, _p, _sz, _i, _i, _p]),

@@ -22,15 +22,23 @@ Supported transforms, and how each is realised:
     ToGray                                 the gray flag
     GaussNoise (var_limit -> sigma)        sigma
     SaltAndPepper                          two thresholds on a per-pixel random word
+    OneOf(ElasticTransform, GridDistortion, OpticalDistortion)
+        a second record of 64 floats per sample (`sample_warp`) that warps the OUTPUT frame in
+        front of the homography, still one resampling pass: the elastic member's smoothed random
+        displacement field is written by a kernel of its own (`unet_elastic_field`), the grid
+        member is a monotone piecewise-linear map per axis, the optical member a radial
+        polynomial.  Only a `BatchAugment` whose configuration has `distort_group_prob > 0`
+        draws these records and launches the two kernels; `from_yaml(..., distortion=True)`
+        reads the group from the reference's file.
 
 `OneOf` groups keep the reference's structure over the supported members: the group probability
 is drawn first, then one member by its normalised probability among the SUPPORTED members.
 
-Not supported (keys of these are ignored by `from_yaml`): elastic / grid / optical distortion,
-HueSaturationValue, CLAHE, Equalize, Gaussian and motion blur, ISO noise, shadow / sun flare /
-fog.  The semantics of what is supported are defined by this project (include/unet_hip.h,
-DESIGN 12), not recorded from the reference's augmentation library; the package ships no preset
-numbers: every probability of `AugmentConfig` defaults to 0, which is the identity.
+Not supported (keys of these are ignored by `from_yaml`): HueSaturationValue, CLAHE, Equalize,
+Gaussian and motion blur, ISO noise, shadow / sun flare / fog.  The semantics of what is
+supported are defined by this project (include/unet_hip.h), not recorded from the
+reference's augmentation library; the package ships no preset numbers: every probability of
+`AugmentConfig` defaults to 0, which is the identity.
 """
 import dataclasses
 import math
@@ -42,6 +50,14 @@ import torch
 from . import ops
 
 PARAMS_PER_SAMPLE = 24
+WARP_PER_SAMPLE = 64
+# warp record layout (include/unet_hip.h): value 0 is the mode, the rest belongs to the mode
+WARP_NONE, WARP_ELASTIC, WARP_GRID, WARP_OPTICAL = 0, 1, 2, 3
+W_AFFINE, W_ALPHA, W_RADIUS, W_TAPS = 1, 7, 8, 9                   # elastic
+W_KX, W_INVCELL_X, W_KY, W_INVCELL_Y, W_AX, W_BX, W_AY, W_BY = 1, 2, 3, 4, 8, 16, 24, 32    # grid
+W_CX, W_CY, W_K, W_INV_W, W_INV_H = 1, 2, 3, 4, 5                   # optical
+MAX_RADIUS = 16
+MAX_GRID_STEPS = 8
 # record layout (include/unet_hip.h)
 P_H, P_ALPHA, P_BETA, P_GRAY, P_SIGMA, P_HOLE, P_HOLE_FILL, P_MASK_BORDER, P_MASK_HOLE = \
     0, 9, 10, 13, 14, 15, 19, 20, 21
@@ -99,12 +115,32 @@ class AugmentConfig:
     pepper_p: Tuple[float, float] = (0.0, 0.0)
     # value of mask pixels that come from outside the image
     mask_border_value: float = 0.0
+    # OneOf(ElasticTransform, GridDistortion, OpticalDistortion): the warp record
+    distort_group_prob: float = 0.0
+    # displacement alpha * (uniform noise smoothed by a Gaussian of sigma), in pixels, on top of an
+    # affine part that moves three anchor points by U(-alpha_affine, alpha_affine) pixels
+    elastic_prob: float = 0.0
+    elastic_alpha: float = 0.0
+    elastic_sigma: float = 0.0
+    elastic_alpha_affine: float = 0.0
+    # num_steps cells per axis (1..8), each of weight 1 + U(-distort_limit, distort_limit) (< 1)
+    grid_distortion_prob: float = 0.0
+    grid_num_steps: int = 0
+    grid_distort_limit: float = 0.0
+    # f = 1 + k r^2 + k r^4, k ~ U(-distort_limit, distort_limit), about a centre shifted by
+    # U(-shift_limit, shift_limit) of the size
+    optical_distortion_prob: float = 0.0
+    optical_distort_limit: float = 0.0
+    optical_shift_limit: float = 0.0
 
     @classmethod
-    def from_yaml(cls, path, section):
+    def from_yaml(cls, path, section, distortion=False):
         """The `section` ("cat" / "dog") of a file in the format of the reference's
         data_augmentation/config/augmentation_config.yaml.  Keys of unsupported transforms are
-        ignored; a transform whose keys are absent stays off."""
+        ignored; a transform whose keys are absent stays off.  The elastic / grid / optical
+        group (`elastic_transform_prob`, `elastic`, `grid_distortion`, `optical_distortion`) is
+        read with `distortion=True` only: it costs a second record and a second kernel per
+        batch, so a caller asks for it."""
         import yaml      # lazily: only this constructor needs it
         with open(path) as f:
             doc = yaml.safe_load(f)
@@ -152,6 +188,21 @@ class AugmentConfig:
         c.salt_pepper_prob = float(g.get("prob", 0.0))
         c.salt_p = _pair(g.get("salt_p", (0.0, 0.0)))
         c.pepper_p = _pair(g.get("pepper_p", (0.0, 0.0)))
+        if distortion:
+            c.distort_group_prob = float(s.get("elastic_transform_prob", 0.0))
+            g = s.get("elastic") or {}
+            c.elastic_prob = float(g.get("prob", 0.0))
+            c.elastic_alpha = float(g.get("alpha", 0.0))
+            c.elastic_sigma = float(g.get("sigma", 0.0))
+            c.elastic_alpha_affine = float(g.get("alpha_affine", 0.0))
+            g = s.get("grid_distortion") or {}
+            c.grid_distortion_prob = float(g.get("prob", 0.0))
+            c.grid_num_steps = int(g.get("num_steps", 0))
+            c.grid_distort_limit = float(g.get("distort_limit", 0.0))
+            g = s.get("optical_distortion") or {}
+            c.optical_distortion_prob = float(g.get("prob", 0.0))
+            c.optical_distort_limit = float(g.get("distort_limit", 0.0))
+            c.optical_shift_limit = float(g.get("shift_limit", 0.0))
         return c
 
 
@@ -211,13 +262,8 @@ def _rect_to_quad(W, H, quad):
     return np.concatenate([h, np.ones((m, 1))], axis=1).reshape(m, 3, 3)
 
 
-def sample_params(cfg, n, H, W, generator, which=None, return_applied=False):
-    """Draw n records: (params fp32 [n, 24], rng int64 [n, 4] with values in 0 .. 2^32 - 1), both
-    on the CPU.  `cfg` is an AugmentConfig, or a sequence of them with `which[i]` selecting the
-    configuration of sample i (the reference's cat / dog split).  `generator` is a CPU
-    torch.Generator; the same generator state gives the same records.  The records are validated
-    (`validate_params`) before they are returned.  With `return_applied` a dict of boolean [n]
-    arrays (which transform fired for which sample) comes third."""
+def _select(cfg, n, which):
+    """(configurations, index of sample i's configuration [n])"""
     cfgs = [cfg] if isinstance(cfg, AugmentConfig) else list(cfg)
     if which is None:
         if len(cfgs) != 1:
@@ -227,6 +273,17 @@ def sample_params(cfg, n, H, W, generator, which=None, return_applied=False):
         sel = np.asarray(torch.as_tensor(which).cpu().numpy(), dtype=np.int64).reshape(-1)
         if sel.shape[0] != n or (sel < 0).any() or (sel >= len(cfgs)).any():
             raise ValueError("`which` must hold n indices into the configurations")
+    return cfgs, sel
+
+
+def sample_params(cfg, n, H, W, generator, which=None, return_applied=False):
+    """Draw n records: (params fp32 [n, 24], rng int64 [n, 4] with values in 0 .. 2^32 - 1), both
+    on the CPU.  `cfg` is an AugmentConfig, or a sequence of them with `which[i]` selecting the
+    configuration of sample i (the reference's cat / dog split).  `generator` is a CPU
+    torch.Generator; the same generator state gives the same records.  The records are validated
+    (`validate_params`) before they are returned.  With `return_applied` a dict of boolean [n]
+    arrays (which transform fired for which sample) comes third."""
+    cfgs, sel = _select(cfg, n, which)
 
     def f(name):        # the field per sample: [n] or [n, k]
         return np.asarray([getattr(c, name) for c in cfgs], dtype=np.float64)[sel]
@@ -345,6 +402,173 @@ def sample_params(cfg, n, H, W, generator, which=None, return_applied=False):
     return out + (applied,) if return_applied else out
 
 
+# ---- the warp record: elastic / grid / optical distortion --------------------------------------
+def identity_warp(n):
+    """fp32 [n, 64]: the warp record that leaves the pixel centres where they are (mode 0)."""
+    return torch.zeros(n, WARP_PER_SAMPLE, dtype=torch.float32)
+
+
+def gaussian_taps(sigma):
+    """(R, g fp64 [17]): radius R = min(ceil(3 sigma), 16) and the one-sided taps g[0..R] of the
+    Gaussian, normalised so that the full kernel g[0] + 2 sum g[1..R] is 1; g[t] = 0 past R."""
+    sigma = float(sigma)
+    R = min(int(math.ceil(3.0 * sigma)), MAX_RADIUS) if sigma > 0 else 0
+    g = np.zeros(MAX_RADIUS + 1)
+    t = np.arange(R + 1, dtype=np.float64)
+    g[:R + 1] = np.exp(-t * t / (2.0 * sigma * sigma)) if R > 0 else 1.0
+    g /= g[0] + 2.0 * g[1:].sum()
+    return R, g
+
+
+def _warp_reach(w, H, W):
+    """fp64 [n]: the farthest a record can move a pixel centre of the output rectangle, in pixels
+    (max norm): alpha plus the affine part's corner motion for an elastic record, 0 for a grid
+    record (it maps [0, W] x [0, H] onto itself), the corner value of |f - 1| * extent for an
+    optical one (both factors grow with the distance to the centre)."""
+    mode = w[:, 0]
+    corners = np.array([[0.0, 0.0], [W, 0.0], [0.0, H], [W, H]])
+    reach = np.zeros(w.shape[0])
+    for x, y in corners:
+        ax = np.abs(w[:, 1] * x + w[:, 2] * y + w[:, 3] - x)
+        ay = np.abs(w[:, 4] * x + w[:, 5] * y + w[:, 6] - y)
+        elastic = np.maximum(ax, ay) + np.abs(w[:, W_ALPHA])
+        ex, ey = x - w[:, W_CX], y - w[:, W_CY]
+        r2 = (ex * w[:, W_INV_W]) ** 2 + (ey * w[:, W_INV_H]) ** 2
+        f1 = np.abs(w[:, W_K] * r2 + w[:, W_K] * r2 * r2)
+        optical = f1 * np.maximum(np.abs(ex), np.abs(ey))
+        reach = np.maximum(reach, np.where(mode == WARP_ELASTIC, elastic,
+                                           np.where(mode == WARP_OPTICAL, optical, 0.0)))
+    return reach
+
+
+def validate_warp(warp, params, H, W):
+    """Refuse a warp record the kernels are not specified for, or one that can carry a pixel to
+    where `params` has den <= 0: every value finite, the mode one of 0..3, an elastic record with
+    alpha >= 0 and an integer radius in 0..16, a grid record with integer K in 1..8 per axis and
+    increasing maps (a_k > 0), and den = h6 x + h7 y + h8 of `params` positive at the corners of
+    the output rectangle GROWN by the record's largest possible displacement."""
+    w = warp.detach().cpu().numpy() if torch.is_tensor(warp) else np.asarray(warp)
+    p = params.detach().cpu().numpy() if torch.is_tensor(params) else np.asarray(params)
+    if w.ndim != 2 or w.shape[1] != WARP_PER_SAMPLE:
+        raise ValueError(f"warp must be [n, {WARP_PER_SAMPLE}]")
+    if p.ndim != 2 or p.shape != (w.shape[0], PARAMS_PER_SAMPLE):
+        raise ValueError(f"params must be [{w.shape[0]}, {PARAMS_PER_SAMPLE}]")
+    if not np.isfinite(w).all():
+        raise ValueError("warp record holds a non-finite value")
+    w, p = w.astype(np.float64), p.astype(np.float64)
+    mode = w[:, 0]
+    if not np.isin(mode, (WARP_NONE, WARP_ELASTIC, WARP_GRID, WARP_OPTICAL)).all():
+        raise ValueError("warp record has a mode outside 0..3")
+    e = mode == WARP_ELASTIC
+    rad = w[e, W_RADIUS]
+    if (w[e, W_ALPHA] < 0).any() or (rad != np.rint(rad)).any() or (rad < 0).any() or \
+            (rad > MAX_RADIUS).any():
+        raise ValueError(f"elastic warp record needs alpha >= 0 and a radius in 0..{MAX_RADIUS}")
+    for i in np.nonzero(mode == WARP_GRID)[0]:
+        for k_at, a_at in ((W_KX, W_AX), (W_KY, W_AY)):
+            K = w[i, k_at]
+            if K != np.rint(K) or K < 1 or K > MAX_GRID_STEPS:
+                raise ValueError(f"grid warp record needs 1 <= K <= {MAX_GRID_STEPS} "
+                                 f"(sample {i}: {K})")
+            if not (w[i, a_at:a_at + int(K)] > 0).all():
+                raise ValueError(f"grid warp record is not increasing (sample {i})")
+    reach = _warp_reach(w, H, W)
+    for x, y in ((-reach, -reach), (W + reach, -reach), (-reach, H + reach),
+                 (W + reach, H + reach)):
+        den = p[:, 6] * x + p[:, 7] * y + p[:, 8]
+        if not (den > 0).all():
+            raise ValueError("warp record reaches den <= 0: the output rectangle grown by its "
+                             f"largest displacement (sample {int(np.argmin(den))})")
+
+
+def sample_warp(cfg, n, H, W, generator, which=None, return_applied=False):
+    """Draw n warp records (fp32 [n, 64], on the CPU) of the group OneOf(ElasticTransform,
+    GridDistortion, OpticalDistortion): the group probability is drawn first, then one member by
+    its probability normalised over the three, as for the colour group.  `cfg`, `which` and
+    `generator` as for `sample_params`; the draws come from a block of uniforms of their own, so
+    `sample_params` is unaffected by whether this is called.  The records are NOT validated
+    against a `params` here (`validate_warp`; `BatchAugment` does it).  With `return_applied` a
+    dict of boolean [n] arrays comes second."""
+    cfgs, sel = _select(cfg, n, which)
+
+    def f(name):
+        return np.asarray([getattr(c, name) for c in cfgs], dtype=np.float64)[sel]
+
+    for c in cfgs:
+        if c.distort_group_prob > 0 and c.grid_distortion_prob > 0:
+            if not 1 <= int(c.grid_num_steps) <= MAX_GRID_STEPS or \
+                    int(c.grid_num_steps) != c.grid_num_steps:
+                raise ValueError(f"grid_num_steps must be 1..{MAX_GRID_STEPS}")
+            if not 0 <= c.grid_distort_limit < 1:
+                raise ValueError("grid_distort_limit must be in [0, 1): a cell of weight <= 0 "
+                                 "would not be monotone")
+        if min(c.elastic_alpha, c.elastic_sigma, c.elastic_alpha_affine,
+               c.optical_distort_limit, c.optical_shift_limit) < 0:
+            raise ValueError("the limits of the distortion group must not be negative")
+
+    U = torch.rand(n, 32, dtype=torch.float64, generator=generator).numpy()
+    S = 2.0 * U - 1.0                                   # U(-1, 1)
+    pe, pg, po = f("elastic_prob"), f("grid_distortion_prob"), f("optical_distortion_prob")
+    tot = pe + pg + po
+    group = (U[:, 0] < f("distort_group_prob")) & (tot > 0)
+    pick = U[:, 1] * tot
+    elastic = group & (pick < pe)
+    grid = group & ~elastic & (pick < pe + pg)
+    optical = group & ~elastic & ~grid
+    applied = {"elastic": elastic, "grid_distortion": grid, "optical_distortion": optical}
+    w = np.zeros((n, WARP_PER_SAMPLE), dtype=np.float64)
+    w[:, 0] = np.where(elastic, WARP_ELASTIC, np.where(grid, WARP_GRID,
+                                                       np.where(optical, WARP_OPTICAL, WARP_NONE)))
+
+    # elastic: three anchors of the image, each moved by U(-alpha_affine, alpha_affine) pixels;
+    # the record holds the INVERSE (moved anchors -> anchors: output -> source), solved in fp64
+    if elastic.any():
+        cx, cy, q = W / 2.0, H / 2.0, min(H, W) / 3.0
+        src = np.array([[cx + q, cy + q], [cx + q, cy - q], [cx - q, cy - q]])
+        dst = src[None] + S[:, 2:8].reshape(n, 3, 2) * f("elastic_alpha_affine")[:, None, None]
+        dst = np.where(elastic[:, None, None], dst, src[None])
+        M = np.concatenate([dst, np.ones((n, 3, 1))], axis=2)       # rows (x', y', 1)
+        A = np.linalg.solve(M, np.broadcast_to(src, (n, 3, 2)))     # [n, 3, 2]: columns -> x, y
+        w[:, W_AFFINE:W_AFFINE + 3] = np.where(elastic[:, None], A[:, :, 0], 0.0)
+        w[:, W_AFFINE + 3:W_AFFINE + 6] = np.where(elastic[:, None], A[:, :, 1], 0.0)
+        w[:, W_ALPHA] = np.where(elastic, f("elastic_alpha"), 0.0)
+        for i in np.nonzero(elastic)[0]:
+            R, g = gaussian_taps(cfgs[sel[i]].elastic_sigma)
+            w[i, W_RADIUS] = R
+            w[i, W_TAPS:W_TAPS + MAX_RADIUS + 1] = g
+
+    # grid: per axis K cells of equal width in the output, cell k of weight s_k; knots
+    # Y_k = size * cumsum(s) / sum(s) against X_k = size * k / K, so the map fixes 0 and the size
+    if grid.any():
+        K = np.where(grid, f("grid_num_steps"), 1.0)
+        cell = np.arange(MAX_GRID_STEPS)[None, :]
+        live = cell < K[:, None]
+        for size, cols, k_at, inv_at, a_at, b_at in (
+                (float(W), slice(8, 16), W_KX, W_INVCELL_X, W_AX, W_BX),
+                (float(H), slice(16, 24), W_KY, W_INVCELL_Y, W_AY, W_BY)):
+            s = np.where(live, 1.0 + S[:, cols] * f("grid_distort_limit")[:, None], 0.0)
+            Y1 = size * (np.cumsum(s, axis=1) / s.sum(axis=1, keepdims=True))
+            Y0 = np.concatenate([np.zeros((n, 1)), Y1[:, :-1]], axis=1)
+            X1, X0 = size * ((cell + 1.0) / K[:, None]), size * (cell / K[:, None])
+            a = np.where(live, (Y1 - Y0) / (X1 - X0), 0.0)
+            b = np.where(live, Y0 - a * X0, 0.0)
+            g2 = grid[:, None]
+            w[:, a_at:a_at + MAX_GRID_STEPS] = np.where(g2, a, w[:, a_at:a_at + MAX_GRID_STEPS])
+            w[:, b_at:b_at + MAX_GRID_STEPS] = np.where(g2, b, w[:, b_at:b_at + MAX_GRID_STEPS])
+            w[:, k_at] = np.where(grid, K, w[:, k_at])
+            w[:, inv_at] = np.where(grid, K / size, w[:, inv_at])
+
+    # optical: f = 1 + k r^2 + k r^4 about a shifted centre, r in units of the image size
+    w[:, W_CX] = np.where(optical, W / 2.0 + S[:, 25] * f("optical_shift_limit") * W, w[:, W_CX])
+    w[:, W_CY] = np.where(optical, H / 2.0 + S[:, 26] * f("optical_shift_limit") * H, w[:, W_CY])
+    w[:, W_K] = np.where(optical, S[:, 24] * f("optical_distort_limit"), w[:, W_K])
+    w[:, W_INV_W] = np.where(optical, 1.0 / W, w[:, W_INV_W])
+    w[:, W_INV_H] = np.where(optical, 1.0 / H, w[:, W_INV_H])
+
+    warp = torch.from_numpy(w.astype(np.float32))
+    return (warp, applied) if return_applied else warp
+
+
 class BatchAugment:
     """Draws the records of a batch and launches `unet_augment_u8` on the current stream.
 
@@ -357,18 +581,30 @@ class BatchAugment:
     `params=(params, rng)` (CPU tensors as `sample_params` returns them; `rng` may be None: then
     all noise is off) replaces the draw.  The records travel through a ring of two pinned host
     buffers with non_blocking copies; an event per buffer keeps it from being rewritten while
-    its copy is in flight."""
+    its copy is in flight.
+
+    When a configuration has `distort_group_prob > 0` (or `params=(params, rng, warp)` names warp
+    records), a warp record per sample is drawn after `sample_params` (`sample_warp`), validated
+    against the drawn params, staged through the same ring, and two launches follow:
+    `unet_elastic_field` into a field buffer kept per batch shape, then `unet_augment_warp_u8`.
+    Otherwise nothing of this happens: the same draws, the same single launch."""
 
     def __init__(self, cfg, seed=0):
         self.cfg = cfg
         self.generator = torch.Generator()
         self.generator.manual_seed(int(seed))
+        cfgs = [cfg] if isinstance(cfg, AugmentConfig) else list(cfg)
+        self.distortion = any(c.distort_group_prob > 0 for c in cfgs)
         self._ring = None
         self._next = 0
+        self._field = {}
 
-    def _stage(self, params, rng, device):
+    def _stage(self, params, rng, device, warp=None):
+        """-> (params, rng or None, warp or None) on the device"""
         n = params.shape[0]
-        if self._ring is None or self._ring[0]["n"] != n or self._ring[0]["device"] != device:
+        head = self._ring[0] if self._ring is not None else None
+        if head is None or head["n"] != n or head["device"] != device or \
+                (warp is not None and "hw" not in head):
             self._ring = [{
                 "n": n, "device": device, "event": None,
                 "hp": torch.empty((n, PARAMS_PER_SAMPLE), dtype=torch.float32, pin_memory=True),
@@ -376,6 +612,12 @@ class BatchAugment:
                 "dp": torch.empty((n, PARAMS_PER_SAMPLE), dtype=torch.float32, device=device),
                 "dr": torch.empty((n, 4), dtype=torch.int32, device=device),
             } for _ in range(2)]
+            if warp is not None:
+                for slot in self._ring:
+                    slot["hw"] = torch.empty((n, WARP_PER_SAMPLE), dtype=torch.float32,
+                                             pin_memory=True)
+                    slot["dw"] = torch.empty((n, WARP_PER_SAMPLE), dtype=torch.float32,
+                                             device=device)
             self._next = 0
         slot = self._ring[self._next]
         self._next ^= 1
@@ -383,26 +625,49 @@ class BatchAugment:
             slot["event"].synchronize()         # the copy out of this host buffer has finished
         slot["hp"].copy_(params)
         slot["dp"].copy_(slot["hp"], non_blocking=True)
-        dr = None
+        dr = dw = None
         if rng is not None:
             slot["hr"].copy_(pack_rng(rng))
             slot["dr"].copy_(slot["hr"], non_blocking=True)
             dr = slot["dr"]
+        if warp is not None:
+            slot["hw"].copy_(warp)
+            slot["dw"].copy_(slot["hw"], non_blocking=True)
+            dw = slot["dw"]
         slot["event"] = torch.cuda.Event()
         slot["event"].record()
-        return slot["dp"], dr
+        return slot["dp"], dr, dw
+
+    def _field_buffer(self, N, H, W, device):
+        key = (N, H, W, device)
+        if key not in self._field:
+            self._field[key] = torch.zeros((N, H, W, 2), dtype=torch.float32, device=device)
+        return self._field[key]
 
     def __call__(self, images_u8, masks_u8=None, which=None, out=None, params=None):
         if not torch.is_tensor(images_u8) or not images_u8.is_cuda:
             raise RuntimeError("unet-implementations_amd.BatchAugment runs on MI355X only "
                                "(no CPU fallback exists)")
         N, H, W, _ = images_u8.shape
+        w = None
         if params is None:
             p, r = sample_params(self.cfg, N, H, W, self.generator, which=which)
+            if self.distortion:
+                w = sample_warp(self.cfg, N, H, W, self.generator, which=which)
         else:
-            p, r = params if isinstance(params, (tuple, list)) else (params, None)
+            p, r, w = (tuple(params) + (None, None))[:3] if isinstance(params, (tuple, list)) \
+                else (params, None, None)
             if tuple(p.shape) != (N, PARAMS_PER_SAMPLE):
                 raise ValueError(f"params must be [{N}, {PARAMS_PER_SAMPLE}]")
             validate_params(p, H, W)
-        dp, dr = self._stage(p.to(torch.float32), r, images_u8.device)
-        return ops.augment_u8(images_u8, masks_u8, dp, dr, out=out)
+        if w is None:
+            dp, dr, _ = self._stage(p.to(torch.float32), r, images_u8.device)
+            return ops.augment_u8(images_u8, masks_u8, dp, dr, out=out)
+        if tuple(w.shape) != (N, WARP_PER_SAMPLE):
+            raise ValueError(f"warp must be [{N}, {WARP_PER_SAMPLE}]")
+        validate_warp(w, p, H, W)
+        dp, dr, dw = self._stage(p.to(torch.float32), r, images_u8.device,
+                                 warp=w.to(torch.float32))
+        field = self._field_buffer(N, H, W, images_u8.device)
+        ops.elastic_field(dw, dr, (H, W), out=field)
+        return ops.augment_warp_u8(images_u8, masks_u8, dp, dr, dw, field, out=out)

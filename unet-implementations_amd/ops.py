@@ -1335,18 +1335,14 @@ def gradcam_heatmap(cam, ws, size):
 
 
 # ---- online batch augmentation (augment.hip) -------------------------------------------------
-def augment_u8(image, mask, params, rng=None, out=None):
-    """(image_out, mask_out): uint8 [N,H,W,3] / [N,H,W] augmented by one launch of
-    `unet_augment_u8` on the current stream.  params: fp32 [N, 24] and rng: int32 / uint32
-    [N, 4] (or None: all noise off) are DEVICE tensors the kernel reads, so a captured launch
-    follows records written into them later.  mask may be None (mask_out is then None).
-    out=(image_out, mask_out) names the tensors to write; they must not overlap the inputs."""
+def _augment_args(what, image, mask, params, rng, out):
+    """The argument checks `augment_u8` and `augment_warp_u8` share -> (image_out, mask_out)."""
     if not torch.is_tensor(image) or not image.is_cuda:
-        raise RuntimeError("unet-implementations_amd.augment_u8 runs on MI355X only "
+        raise RuntimeError(f"unet-implementations_amd.{what} runs on MI355X only "
                            "(no CPU fallback exists)")
     if image.dim() != 4 or image.shape[3] != 3 or image.dtype != torch.uint8 or \
             not image.is_contiguous():
-        raise TypeError("augment_u8 takes a contiguous uint8 [N,H,W,3] image")
+        raise TypeError(f"{what} takes a contiguous uint8 [N,H,W,3] image")
     N, H, W, _ = image.shape
     if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (N, H, W) or
                              not mask.is_contiguous() or mask.device != image.device):
@@ -1355,11 +1351,7 @@ def augment_u8(image, mask, params, rng=None, out=None):
     if params.dtype != torch.float32 or tuple(params.shape) != (N, nrec) or \
             not params.is_contiguous() or params.device != image.device:
         raise TypeError(f"params must be a contiguous fp32 [N, {nrec}] tensor on the image's device")
-    if rng is not None and (rng.element_size() != 4 or rng.is_floating_point() or
-                            tuple(rng.shape) != (N, 4) or not rng.is_contiguous() or
-                            rng.device != image.device):
-        raise TypeError("rng must be a contiguous int32 / uint32 [N, 4] tensor on the image's "
-                        "device")
+    _check_rng(rng, N, image.device)
     if out is None:
         image_out = torch.empty_like(image)
         mask_out = torch.empty_like(mask) if mask is not None else None
@@ -1373,9 +1365,74 @@ def augment_u8(image, mask, params, rng=None, out=None):
                 raise TypeError(f"{name} must be a contiguous uint8 tensor of its input's shape")
         if mask is None:
             mask_out = None
+    return image_out, mask_out
+
+
+def _check_rng(rng, N, device):
+    if rng is not None and (rng.element_size() != 4 or rng.is_floating_point() or
+                            tuple(rng.shape) != (N, 4) or not rng.is_contiguous() or
+                            rng.device != device):
+        raise TypeError("rng must be a contiguous int32 / uint32 [N, 4] tensor on the image's "
+                        "device")
+
+
+def _check_warp(warp, N, device):
+    nrec = lib().unet_augment_warp_params_per_sample()
+    if not torch.is_tensor(warp) or warp.dtype != torch.float32 or \
+            tuple(warp.shape) != (N, nrec) or not warp.is_contiguous() or warp.device != device:
+        raise TypeError(f"warp must be a contiguous fp32 [N, {nrec}] tensor on the image's device")
+
+
+def augment_u8(image, mask, params, rng=None, out=None):
+    """(image_out, mask_out): uint8 [N,H,W,3] / [N,H,W] augmented by one launch of
+    `unet_augment_u8` on the current stream.  params: fp32 [N, 24] and rng: int32 / uint32
+    [N, 4] (or None: all noise off) are DEVICE tensors the kernel reads, so a captured launch
+    follows records written into them later.  mask may be None (mask_out is then None).
+    out=(image_out, mask_out) names the tensors to write; they must not overlap the inputs."""
+    image_out, mask_out = _augment_args("augment_u8", image, mask, params, rng, out)
+    N, H, W, _ = image.shape
     check(lib().unet_augment_u8(_ptr(image), _ptr(mask), _ptr(image_out), _ptr(mask_out),
                                 _ptr(params), rng.data_ptr() if rng is not None else None,
                                 N, H, W, _stream()))
+    return image_out, mask_out
+
+
+def elastic_field(warp, rng, size, out=None):
+    """fp32 [N, H, W, 2]: the displacement field (dx, dy in pixels) of the samples whose warp
+    record (fp32 [N, 64], DEVICE) says "elastic", by one launch of `unet_elastic_field`; the
+    slices of all other samples are NOT written (a fresh tensor starts as zeros).  rng as for
+    `augment_u8` (None: the field is 0).  size = (H, W); out names the tensor to write."""
+    if not torch.is_tensor(warp) or not warp.is_cuda:
+        raise RuntimeError("unet-implementations_amd.elastic_field runs on MI355X only "
+                           "(no CPU fallback exists)")
+    N, H, W = warp.shape[0], int(size[0]), int(size[1])
+    _check_warp(warp, N, warp.device)
+    _check_rng(rng, N, warp.device)
+    if out is None:
+        out = torch.zeros((N, H, W, 2), dtype=torch.float32, device=warp.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (N, H, W, 2) or \
+            not out.is_contiguous() or out.device != warp.device:
+        raise TypeError("out must be a contiguous fp32 [N, H, W, 2] tensor on warp's device")
+    check(lib().unet_elastic_field(_ptr(out), _ptr(warp),
+                                   rng.data_ptr() if rng is not None else None, N, H, W,
+                                   _stream()))
+    return out
+
+
+def augment_warp_u8(image, mask, params, rng, warp, field=None, out=None):
+    """`augment_u8` behind the per-pixel warp of `unet_augment_warp_u8`: warp is the fp32 [N, 64]
+    DEVICE record of elastic / grid / optical distortion, field the fp32 [N, H, W, 2] tensor
+    `elastic_field` wrote (None: elastic samples get a zero displacement)."""
+    image_out, mask_out = _augment_args("augment_warp_u8", image, mask, params, rng, out)
+    N, H, W, _ = image.shape
+    _check_warp(warp, N, image.device)
+    if field is not None and (field.dtype != torch.float32 or
+                              tuple(field.shape) != (N, H, W, 2) or not field.is_contiguous() or
+                              field.device != image.device):
+        raise TypeError("field must be a contiguous fp32 [N, H, W, 2] tensor on the image's device")
+    check(lib().unet_augment_warp_u8(_ptr(image), _ptr(mask), _ptr(image_out), _ptr(mask_out),
+                                     _ptr(params), rng.data_ptr() if rng is not None else None,
+                                     _ptr(warp), _ptr(field), N, H, W, _stream()))
     return image_out, mask_out
 
 

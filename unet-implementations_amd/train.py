@@ -271,7 +271,8 @@ def train_one_epoch(model, train_loader, optimizer, loss_function, device, scale
     """Signature-compatible with the reference's train_one_epoch (src/train.py:592-680).
     `augment` (optional, an `augment.BatchAugment`) takes each uint8 batch (images [N,H,W,3],
     masks [N,H,W]; a "which" entry of the batch selects the configuration per sample) through
-    the augmentation kernel before the step; `input_layout` is handed to `train_step`."""
+    the augmentation kernel (with a distortion configuration: the displacement-field kernel and
+    the warp gather) before the step; `input_layout` is handed to `train_step`."""
     if scaler is not None:
         raise NotImplementedError("fp16 GradScaler AMP is not part of the fp32 HIP path")
     model.train()
