@@ -473,6 +473,87 @@ int unet_augment_warp_u8(const uint8_t* image, const uint8_t* mask, uint8_t* ima
 int unet_elastic_field(float* field, const float* warp, const uint32_t* rng, int N, int H, int W,
                        unet_stream_t stream);
 
+/* ---- HSV shift, equalize / CLAHE and blur: a second stage behind the gather ------ */
+
+/* Floats per sample record `post` of unet_augment_post_u8 (64). */
+int unet_augment_post_params_per_sample(void);
+
+/* Bytes of the workspace unet_augment_post_u8 needs for N samples: counts [N][3][256] uint32, then
+ * LUTs [N][64][256] bytes.  0 for N <= 0. */
+size_t unet_augment_post_workspace_bytes(int N);
+
+/* image [N][H][W][3] (uint8) -> image_out of the same shape (normative text).  post
+ * [N][64] (fp32) and rng [N][4] (uint32, nullable: then there is no salt / pepper) are DEVICE arrays
+ * read by the kernels only, and the launch sequence (one memset of the counts, the histogram kernel,
+ * the apply kernel) is the same for every batch, so a captured sequence follows new records on
+ * replay.  image_out must not overlap image, post, rng or workspace.  Record; every value a mode
+ * does not name is 0:
+ *    0      HSV on: exactly 1; any other value is off
+ *    1-3    dh, ds, dv: hue in half-degrees (h in [0, 180)), saturation and value in levels 0..255
+ *    4      histogram op: 1 equalize, 2 CLAHE; any other value is none
+ *    5      CLAHE clip_limit          6, 7   CLAHE tile grid ty, tx (integers in 1..8)
+ *    8      blur: 1 separable, 2 dense; any other value is none
+ *    9      radius R: clamped IN FLOAT to 1..4 (separable) or 1..3 (dense), then truncated
+ *    10-14  one-sided separable taps g[0..4]
+ *    15-63  dense weights w, row-major over (2R+1)^2 <= 49: index 15 + (dy+R)(2R+1) + (dx+R)
+ * rng[n] = seed_lo, seed_hi, pepper_thr, salt_thr as for unet_augment_u8.
+ * Every fp32 operation is rounded on its own (no fused multiply-add), in the order the parentheses
+ * give; fmin / fmax return the other operand for a NaN; byte(x) = clamp(rint(x), 0, 255); all range
+ * tests are made in float before any conversion to an index.  Per sample, in this order:
+ *    input byte p_c -> HSV -> byte -> histogram op -> byte -> blur -> byte -> salt / pepper.
+ * HSV (skipped entirely unless value 0 is 1), with r, g, b = (float)p_0..2:
+ *    V = max(r, g, b), m = min(r, g, b), d = V - m, S = (V == 0) ? 0 : (255 d) / V;
+ *    h = 0 if d == 0, else by the channel that is the maximum (ties: r, then g):
+ *      r: 30 ((g - b) / d)     g: 60 + (30 ((b - r) / d))     b: 120 + (30 ((r - g) / d));
+ *    h < 0: h = h + 180.
+ *    h' = h + dh, h' = h' - (180 floor(h' / 180)), h' = fmin(fmax(h', 0), 180 - 2^-16) (the largest
+ *    float below 180);  S' = fmin(fmax(S + ds, 0), 255);  V' = fmin(fmax(V + dv, 0), 255).
+ *    c = (V' S') / 255, hp = h' / 30, k = fmin(fmax(floor(hp), 0), 5), f = hp - k,
+ *    P = V' - c, Q = V' - (c f), T = V' - (c (1 - f));  (r, g, b)' by k = 0..5:
+ *      (V',T,P) (Q,V',P) (P,V',T) (P,Q,V') (T,P,V') (V',P,Q);   q_c = byte(that).
+ * Equalize (op 1), per channel over the whole sample of the q_c: hist the 256-bin histogram, i0 the
+ *    first non-empty bin, total = H W.  hist[i0] == total: the channel is unchanged.  Otherwise
+ *    scale = 255.f / (float)(total - hist[i0]), lut[i] = 0 for i <= i0, and for i > i0 with
+ *    sum = hist[i0+1] + .. + hist[i]:  lut[i] = min(255, (int)rint((float)sum scale)).
+ * CLAHE (op 2) on luma Y = (int)byte(((0.299 q_0) + (0.587 q_1)) + (0.114 q_2)).  The grid (ty, tx)
+ *    must be two integers in 1..8 with H % ty == 0 and W % tx == 0; a record where it is not is
+ *    treated as "no histogram op".  Tiles are th = H / ty by tw = W / tx, area = th tw.  Per tile,
+ *    in integers: hist of Y;  t = fmax(floor((clip_limit (float)area) / 256.f), 1),
+ *    climit = (t >= (float)area) ? area : (int)t;  excess = sum max(hist_i - climit, 0),
+ *    hist_i = min(hist_i, climit);  batch = excess / 256, resid = excess - 256 batch,
+ *    hist_i += batch;  if resid > 0: step = max(256 / resid, 1) and hist_i += 1 for the i with
+ *    i % step == 0 and i / step < resid;  cdf the inclusive sum,
+ *    L_i = min(255, (int)rint((float)cdf_i (255.f / (float)area))).
+ *    Pixel (i, j): fx = ((float)j (1.f / (float)tw)) - 0.5, x1 = floor(fx), ax = fx - x1,
+ *    x2 = x1 + 1, then x1 and x2 clamped to 0 .. tx - 1; the same in y with i, th, ty.
+ *    top = ((1 - ax) L[y1][x1][Y]) + (ax L[y1][x2][Y]), bot the same with y2,
+ *    s = ((1 - ay) top) + (ay bot), Y' = (int)byte(s), out_c = clamp(q_c + (Y' - Y), 0, 255).
+ * Blur over the bytes B after the histogram op.  Borders reflect without repeating the edge
+ *    (x < 0: -x; x > W - 1: 2 (W - 1) - x), the result then clamped to 0 .. W - 1; rows likewise.
+ *    Separable (1): row(i, j) = sum over t = -R..R, ascending, from 0.f, of g[|t|] (float)B(i, j+t),
+ *    each product and each sum rounded on its own, kept in fp32;  out = byte(the same sum over
+ *    t of g[|t|] row(i+t, j)).  Dense (2): out = byte(sum over dy = -R..R, then dx = -R..R, both
+ *    ascending, from 0.f, of w[dy][dx] (float)B(i+dy, j+dx)).
+ * Salt / pepper last, with the rule and the Philox stream-1 word of the output pixel index i W + j
+ * of unet_augment_u8.  A sample with nothing on is copied.
+ * workspace: unet_augment_post_workspace_bytes(N) bytes, 16-byte aligned, scratch of this call.
+ * UNET_E_INVALID before any launch: null image / image_out / post, a bad shape (as
+ * unet_augment_u8), a null, too small or misaligned workspace, image_out overlapping an input or
+ * the workspace, the workspace overlapping an input. */
+int unet_augment_post_u8(const uint8_t* image, uint8_t* image_out, const float* post,
+                         const uint32_t* rng, void* workspace, size_t workspace_bytes, int N, int H,
+                         int W, unet_stream_t stream);
+
+/* The two halves of unet_augment_post_u8, for a caller that measures or overlaps them: the
+ * histogram half (the memset of the counts and the histogram kernel) fills the workspace the apply
+ * half reads; hist followed by apply on one stream, with the same arguments, is
+ * unet_augment_post_u8.  The same refusals. */
+int unet_augment_post_hist(const uint8_t* image, const float* post, void* workspace,
+                           size_t workspace_bytes, int N, int H, int W, unet_stream_t stream);
+int unet_augment_post_apply(const uint8_t* image, uint8_t* image_out, const float* post,
+                            const uint32_t* rng, void* workspace, size_t workspace_bytes, int N,
+                            int H, int W, unet_stream_t stream);
+
 /* uint8 HWC image (+ uint8 mask) -> ((v/255) - mean)/std NHWC fp32 (+ int64 target with values
  * > 2 other than 255 mapped to 0): PetSegmentationDataset.__getitem__, src/train.py:300-311.
  * mean3 / std3 are HOST pointers to 3 floats. */

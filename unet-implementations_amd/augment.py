@@ -31,14 +31,24 @@ Supported transforms, and how each is realised:
         draws these records and launches the two kernels; `from_yaml(..., distortion=True)`
         reads the group from the reference's file.
 
-`OneOf` groups keep the reference's structure over the supported members: the group probability
-is drawn first, then one member by its normalised probability among the SUPPORTED members.
+    HueSaturationValue, OneOf(CLAHE, Equalize), OneOf(GaussianBlur, MotionBlur)
+        a third record of 64 floats per sample (`sample_post`) and a SECOND STAGE of two kernels
+        over the image the gather wrote (`unet_augment_post_u8`, csrc/augment_post.hip): a
+        histogram kernel (per-sample counts for Equalize, per-tile LUTs for CLAHE on luma) and a
+        tiled kernel that applies the HSV shift, the LUTs, the blur (separable Gaussian taps or
+        the dense weights of a rasterised motion line, both from the record) and, last, salt /
+        pepper, which moves there from the gather.  Only a `BatchAugment` whose configuration
+        has one of these members on draws the record and launches the stage;
+        `from_yaml(..., photometric=True)` reads them from the reference's file.
 
-Not supported (keys of these are ignored by `from_yaml`): HueSaturationValue, CLAHE, Equalize,
-Gaussian and motion blur, ISO noise, shadow / sun flare / fog.  The semantics of what is
-supported are defined by this project (include/unet_hip.h), not recorded from the
-reference's augmentation library; the package ships no preset numbers: every probability of
-`AugmentConfig` defaults to 0, which is the identity.
+`OneOf` groups keep the reference's structure over the supported members: the group probability
+is drawn first, then one member by its normalised probability among the SUPPORTED members (with
+the second stage on, the new members count: `sample_post`).
+
+Not supported (keys of these are ignored by `from_yaml`): ISO noise, shadow / sun flare / fog.
+The semantics of what is supported are defined by this project (include/unet_hip.h, DESIGN 12,
+12b, 12c), not recorded from the reference's augmentation library; the package ships no preset
+numbers: every probability of `AugmentConfig` defaults to 0, which is the identity.
 """
 import dataclasses
 import math
@@ -61,6 +71,14 @@ MAX_GRID_STEPS = 8
 # record layout (include/unet_hip.h)
 P_H, P_ALPHA, P_BETA, P_GRAY, P_SIGMA, P_HOLE, P_HOLE_FILL, P_MASK_BORDER, P_MASK_HOLE = \
     0, 9, 10, 13, 14, 15, 19, 20, 21
+# post record layout (include/unet_hip.h): the second stage
+POST_PER_SAMPLE = 64
+Q_HSV, Q_DH, Q_DS, Q_DV, Q_HIST, Q_CLIP, Q_TY, Q_TX, Q_BLUR, Q_RADIUS, Q_TAPS, Q_DENSE = \
+    0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 15
+HIST_NONE, HIST_EQUALIZE, HIST_CLAHE = 0, 1, 2
+BLUR_NONE, BLUR_SEPARABLE, BLUR_DENSE = 0, 1, 2
+MAX_BLUR_RADIUS = {BLUR_SEPARABLE: 4, BLUR_DENSE: 3}
+MAX_TILE_GRID = 8
 PERSPECTIVE_CLIP = 3.0      # a corner moves inward by min(|z|, 3) * scale of the image size
 
 
@@ -70,6 +88,14 @@ def _pair(v):
         return (-float(v), float(v))
     a, b = v
     return (float(a), float(b))
+
+
+def _blur_limit(v):
+    """A kernel-size limit given as one number means (3, v), as in the reference's library."""
+    if isinstance(v, (int, float)):
+        return (3, int(v))
+    a, b = v
+    return (int(a), int(b))
 
 
 @dataclasses.dataclass
@@ -132,15 +158,37 @@ class AugmentConfig:
     optical_distortion_prob: float = 0.0
     optical_distort_limit: float = 0.0
     optical_shift_limit: float = 0.0
+    # the members of the three photometric groups that need the second stage (`sample_post`):
+    # HueSaturationValue in the colour group: shifts U(-limit, limit), hue in half-degrees
+    # (h in [0, 180)), saturation and value in levels
+    hsv_prob: float = 0.0
+    hue_shift_limit: float = 0.0
+    sat_shift_limit: float = 0.0
+    val_shift_limit: float = 0.0
+    # CLAHE (clip limit U(1, clahe_clip_limit), tile grid (rows, columns), each 1..8 and dividing
+    # the batch shape) and Equalize in the gray group
+    clahe_prob: float = 0.0
+    clahe_clip_limit: float = 1.0
+    clahe_tile_grid: Tuple[int, int] = (8, 8)
+    equalize_prob: float = 0.0
+    # GaussianBlur (kernel size uniform over the odd values in [max(3, lo), hi], hi <= 9) and
+    # MotionBlur (odd sizes in [max(3, lo), hi], hi <= 7) in the noise group
+    gaussian_blur_prob: float = 0.0
+    gaussian_blur_limit: Tuple[int, int] = (3, 3)
+    motion_blur_prob: float = 0.0
+    motion_blur_limit: Tuple[int, int] = (3, 3)
 
     @classmethod
-    def from_yaml(cls, path, section, distortion=False):
+    def from_yaml(cls, path, section, distortion=False, photometric=False):
         """The `section` ("cat" / "dog") of a file in the format of the reference's
         data_augmentation/config/augmentation_config.yaml.  Keys of unsupported transforms are
         ignored; a transform whose keys are absent stays off.  The elastic / grid / optical
         group (`elastic_transform_prob`, `elastic`, `grid_distortion`, `optical_distortion`) is
         read with `distortion=True` only: it costs a second record and a second kernel per
-        batch, so a caller asks for it."""
+        batch, so a caller asks for it.  Likewise `photometric=True` reads the members that
+        need the second stage (`hsv`; `clahe_prob`, `clahe_clip_limit`, `clahe_tile_grid_size`
+        and `equalize_prob` of `clahe_equalize`; `gaussian_blur`; `motion_blur`), which then
+        share their groups' probabilities with the old members (`sample_post`)."""
         import yaml      # lazily: only this constructor needs it
         with open(path) as f:
             doc = yaml.safe_load(f)
@@ -203,6 +251,23 @@ class AugmentConfig:
             c.optical_distortion_prob = float(g.get("prob", 0.0))
             c.optical_distort_limit = float(g.get("distort_limit", 0.0))
             c.optical_shift_limit = float(g.get("shift_limit", 0.0))
+        if photometric:
+            g = s.get("hsv") or {}
+            c.hsv_prob = float(g.get("prob", 0.0))
+            c.hue_shift_limit = float(g.get("hue_shift_limit", 0.0))
+            c.sat_shift_limit = float(g.get("sat_shift_limit", 0.0))
+            c.val_shift_limit = float(g.get("val_shift_limit", 0.0))
+            g = s.get("clahe_equalize") or {}
+            c.clahe_prob = float(g.get("clahe_prob", 0.0))
+            c.clahe_clip_limit = float(g.get("clahe_clip_limit", 1.0))
+            c.clahe_tile_grid = tuple(int(v) for v in g.get("clahe_tile_grid_size", (8, 8)))
+            c.equalize_prob = float(g.get("equalize_prob", 0.0))
+            g = s.get("gaussian_blur") or {}
+            c.gaussian_blur_prob = float(g.get("prob", 0.0))
+            c.gaussian_blur_limit = _blur_limit(g.get("blur_limit", 3))
+            g = s.get("motion_blur") or {}
+            c.motion_blur_prob = float(g.get("prob", 0.0))
+            c.motion_blur_limit = _blur_limit(g.get("blur_limit", 3))
         return c
 
 
@@ -276,13 +341,16 @@ def _select(cfg, n, which):
     return cfgs, sel
 
 
-def sample_params(cfg, n, H, W, generator, which=None, return_applied=False):
+def sample_params(cfg, n, H, W, generator, which=None, return_applied=False,
+                  return_groups=False):
     """Draw n records: (params fp32 [n, 24], rng int64 [n, 4] with values in 0 .. 2^32 - 1), both
     on the CPU.  `cfg` is an AugmentConfig, or a sequence of them with `which[i]` selecting the
     configuration of sample i (the reference's cat / dog split).  `generator` is a CPU
     torch.Generator; the same generator state gives the same records.  The records are validated
     (`validate_params`) before they are returned.  With `return_applied` a dict of boolean [n]
-    arrays (which transform fired for which sample) comes third."""
+    arrays (which transform fired for which sample) comes third; with `return_groups` a dict of the
+    raw draws of the three photometric groups ("color", "gray", "noise": the group probability
+    fired, whatever its members' probabilities) comes last, for `sample_post`."""
     cfgs, sel = _select(cfg, n, which)
 
     def f(name):        # the field per sample: [n] or [n, k]
@@ -367,7 +435,8 @@ def sample_params(cfg, n, H, W, generator, which=None, return_applied=False):
 
     # OneOf(RandomBrightnessContrast, RGBShift)
     pb, pr = f("brightness_contrast_prob"), f("rgb_shift_prob")
-    group = fires(f("color_prob")) & (pb + pr > 0)
+    color_draw = fires(f("color_prob"))
+    group = color_draw & (pb + pr > 0)
     pick_b = U[:, next(col)] * (pb + pr) < pb
     bc, rgb = group & pick_b, group & ~pick_b
     applied["brightness_contrast"], applied["rgb_shift"] = bc, rgb
@@ -379,11 +448,13 @@ def sample_params(cfg, n, H, W, generator, which=None, return_applied=False):
         shift = (2.0 * U[:, next(col)] - 1.0) * lim[:, c]
         p[:, P_BETA + c] = np.where(bc, beta, 0.0) + np.where(rgb, shift, 0.0)
 
-    gray = fires(f("gray_group_prob")) & (f("to_gray_prob") > 0)
+    gray_draw = fires(f("gray_group_prob"))
+    gray = gray_draw & (f("to_gray_prob") > 0)
     applied["gray"] = gray
     p[:, P_GRAY] = gray
 
-    gauss = fires(f("noise_group_prob")) & (f("gauss_noise_prob") > 0)
+    noise_draw = fires(f("noise_group_prob"))
+    gauss = noise_draw & (f("gauss_noise_prob") > 0)
     applied["gauss_noise"] = gauss
     p[:, P_SIGMA] = np.where(gauss, np.sqrt(np.maximum(uni(f("gauss_var_limit")), 0.0)), 0.0)
 
@@ -399,7 +470,11 @@ def sample_params(cfg, n, H, W, generator, which=None, return_applied=False):
     params = torch.from_numpy(p.astype(np.float32))
     validate_params(params, H, W)
     out = (params, torch.from_numpy(rng))
-    return out + (applied,) if return_applied else out
+    if return_applied:
+        out += (applied,)
+    if return_groups:
+        out += ({"color": color_draw, "gray": gray_draw, "noise": noise_draw},)
+    return out
 
 
 # ---- the warp record: elastic / grid / optical distortion --------------------------------------
@@ -408,11 +483,15 @@ def identity_warp(n):
     return torch.zeros(n, WARP_PER_SAMPLE, dtype=torch.float32)
 
 
-def gaussian_taps(sigma):
+def gaussian_taps(sigma, radius=None):
     """(R, g fp64 [17]): radius R = min(ceil(3 sigma), 16) and the one-sided taps g[0..R] of the
-    Gaussian, normalised so that the full kernel g[0] + 2 sum g[1..R] is 1; g[t] = 0 past R."""
+    Gaussian, normalised so that the full kernel g[0] + 2 sum g[1..R] is 1; g[t] = 0 past R.
+    `radius` names R instead (the blur's kernel size fixes it: R = (k - 1) / 2)."""
     sigma = float(sigma)
-    R = min(int(math.ceil(3.0 * sigma)), MAX_RADIUS) if sigma > 0 else 0
+    if radius is not None:
+        R = int(radius)
+    else:
+        R = min(int(math.ceil(3.0 * sigma)), MAX_RADIUS) if sigma > 0 else 0
     g = np.zeros(MAX_RADIUS + 1)
     t = np.arange(R + 1, dtype=np.float64)
     g[:R + 1] = np.exp(-t * t / (2.0 * sigma * sigma)) if R > 0 else 1.0
@@ -569,6 +648,170 @@ def sample_warp(cfg, n, H, W, generator, which=None, return_applied=False):
     return (warp, applied) if return_applied else warp
 
 
+# ---- the post record: HSV shift, equalize / CLAHE, Gaussian / motion blur ----------------------
+def identity_post(n):
+    """fp32 [n, 64]: the post record that copies the image (everything off)."""
+    return torch.zeros(n, POST_PER_SAMPLE, dtype=torch.float32)
+
+
+def validate_post(post, H, W):
+    """Refuse a post record the kernels are not specified for: every value finite, the HSV flag 0
+    or 1, the histogram op and the blur mode in 0..2, a CLAHE record with clip_limit > 0 and an
+    integer tile grid in 1..8 per axis that divides (H, W), a blur record with an integer radius
+    in 1..4 (separable) or 1..3 (dense) below min(H, W) and taps / weights that are not negative
+    and whose full sum is 1 within 1e-6."""
+    q = post.detach().cpu().numpy() if torch.is_tensor(post) else np.asarray(post)
+    if q.ndim != 2 or q.shape[1] != POST_PER_SAMPLE:
+        raise ValueError(f"post must be [n, {POST_PER_SAMPLE}]")
+    if not np.isfinite(q).all():
+        raise ValueError("post record holds a non-finite value")
+    q = q.astype(np.float64)
+    if not np.isin(q[:, Q_HSV], (0, 1)).all():
+        raise ValueError("post record has an HSV flag other than 0 / 1")
+    if not np.isin(q[:, Q_HIST], (HIST_NONE, HIST_EQUALIZE, HIST_CLAHE)).all():
+        raise ValueError("post record has a histogram op outside 0..2")
+    if not np.isin(q[:, Q_BLUR], (BLUR_NONE, BLUR_SEPARABLE, BLUR_DENSE)).all():
+        raise ValueError("post record has a blur mode outside 0..2")
+    for i in np.nonzero(q[:, Q_HIST] == HIST_CLAHE)[0]:
+        for t, size in ((q[i, Q_TY], H), (q[i, Q_TX], W)):
+            if t != np.rint(t) or t < 1 or t > MAX_TILE_GRID or size % int(t) != 0:
+                raise ValueError(f"CLAHE tile grid must be integers in 1..{MAX_TILE_GRID} that "
+                                 f"divide the shape (sample {i}: {t} on {size})")
+        if not q[i, Q_CLIP] > 0:
+            raise ValueError(f"CLAHE clip_limit must be positive (sample {i})")
+    for i in np.nonzero(q[:, Q_BLUR] != BLUR_NONE)[0]:
+        mode, R = int(q[i, Q_BLUR]), q[i, Q_RADIUS]
+        if R != np.rint(R) or R < 1 or R > MAX_BLUR_RADIUS[mode]:
+            raise ValueError(f"blur radius must be an integer in 1..{MAX_BLUR_RADIUS[mode]} "
+                             f"(sample {i}: {R})")
+        R = int(R)
+        if R >= min(H, W):
+            raise ValueError(f"blur radius {R} reaches across the image ({H} x {W})")
+        if mode == BLUR_SEPARABLE:
+            g = q[i, Q_TAPS:Q_TAPS + R + 1]
+            total = g[0] + 2.0 * g[1:].sum()
+        else:
+            g = q[i, Q_DENSE:Q_DENSE + (2 * R + 1) ** 2]
+            total = g.sum()
+        if (g < 0).any():
+            raise ValueError(f"blur weights must not be negative (sample {i})")
+        if abs(total - 1.0) > 1e-6:
+            raise ValueError(f"blur weights must sum to 1 (sample {i}: {total})")
+
+
+def motion_line(k, a, b):
+    """[k, k] fp64 weights of a motion-blur kernel: the line from cell a = (x, y) to cell b of the
+    k x k grid, rasterised by the DDA rule: with n = max(|dx|, |dy|) (>= 1, the cells differ) the
+    line has the n + 1 cells (x0 + floor(s dx / n + 0.5), y0 + floor(s dy / n + 0.5)), s = 0..n -
+    one cell per step along the longer axis, so they are distinct - each of weight 1 / (n + 1).
+    Row index is y (dy of the kernel), column index x."""
+    (x0, y0), (x1, y1) = a, b
+    dx, dy = x1 - x0, y1 - y0
+    n = max(abs(dx), abs(dy))
+    if n < 1:
+        raise ValueError("a motion line needs two distinct cells")
+    w = np.zeros((k, k))
+    for s in range(n + 1):
+        w[y0 + int(math.floor(s * dy / n + 0.5)), x0 + int(math.floor(s * dx / n + 0.5))] = 1.0
+    return w / w.sum()
+
+
+def _odd_sizes(limit, top, what):
+    lo, hi = int(limit[0]), int(limit[1])
+    ks = [k for k in range(max(3, lo), hi + 1) if k % 2 == 1]
+    if hi > top or not ks:
+        raise ValueError(f"{what} must hold an odd kernel size in 3..{top} and end at most there")
+    return ks
+
+
+def sample_post(cfg, n, H, W, generator, params, rng, groups, which=None, return_applied=False):
+    """Draw n post records for a batch whose (params, rng) `sample_params` drew with
+    `return_groups=True` -> (params, rng, post fp32 [n, 64]), on the CPU; params and rng are new
+    tensors.  Each of the three photometric groups keeps the reference's OneOf structure over ALL
+    members supported now: where the group's probability fired (`groups`), the sample goes to a
+    new member with the new members' share of the group's probability mass -
+        colour: HueSaturationValue against RandomBrightnessContrast + RGBShift,
+        gray:   CLAHE + Equalize against ToGray,
+        noise:  GaussianBlur + MotionBlur against GaussNoise -
+    and the old member's fields in `params` are reset (alpha = 1 and beta = 0; gray 0; sigma 0), so
+    the two never both act on a sample; otherwise the old member stands as `sample_params` drew
+    it.  rng is returned as it came (salt / pepper stays where it is).  The draws come from a
+    block of uniforms of their own.  With `return_applied` a dict of boolean [n] arrays comes
+    last."""
+    cfgs, sel = _select(cfg, n, which)
+
+    def f(name):
+        return np.asarray([getattr(c, name) for c in cfgs], dtype=np.float64)[sel]
+
+    sizes = []
+    for c in cfgs:
+        sizes.append((
+            _odd_sizes(c.gaussian_blur_limit, 9, "gaussian_blur_limit")
+            if c.gaussian_blur_prob > 0 else [3],
+            _odd_sizes(c.motion_blur_limit, 7, "motion_blur_limit")
+            if c.motion_blur_prob > 0 else [3]))
+        if min(c.hue_shift_limit, c.sat_shift_limit, c.val_shift_limit) < 0:
+            raise ValueError("the HSV shift limits must not be negative")
+        if c.clahe_prob > 0 and not c.clahe_clip_limit >= 1:
+            raise ValueError("clahe_clip_limit must be at least 1 (the clip limit is drawn from "
+                             "U(1, clahe_clip_limit))")
+
+    U = torch.rand(n, 16, dtype=torch.float64, generator=generator).numpy()
+    p = params.detach().cpu().numpy().astype(np.float64).copy()
+    q = np.zeros((n, POST_PER_SAMPLE), dtype=np.float64)
+
+    def take(group, old, new, u):       # the group fired and the pick falls on a new member
+        tot = old + new
+        return np.asarray(group, dtype=bool) & (tot > 0) & (u * tot < new)
+
+    ph = f("hsv_prob")
+    hsv = take(groups["color"], f("brightness_contrast_prob") + f("rgb_shift_prob"), ph, U[:, 0])
+    p[hsv, P_ALPHA] = 1.0
+    p[hsv, P_BETA:P_BETA + 3] = 0.0
+    q[:, Q_HSV] = hsv
+    for k, name in ((Q_DH, "hue_shift_limit"), (Q_DS, "sat_shift_limit"),
+                    (Q_DV, "val_shift_limit")):
+        q[:, k] = np.where(hsv, (2.0 * U[:, k] - 1.0) * f(name), 0.0)
+
+    pc, pe = f("clahe_prob"), f("equalize_prob")
+    hist = take(groups["gray"], f("to_gray_prob"), pc + pe, U[:, 4])
+    clahe = hist & (U[:, 5] * (pc + pe) < pc)
+    equalize = hist & ~clahe
+    p[hist, P_GRAY] = 0.0
+    q[:, Q_HIST] = np.where(clahe, HIST_CLAHE, np.where(equalize, HIST_EQUALIZE, HIST_NONE))
+    q[:, Q_CLIP] = np.where(clahe, 1.0 + (f("clahe_clip_limit") - 1.0) * U[:, 6], 0.0)
+    grid = f("clahe_tile_grid")
+    q[:, Q_TY] = np.where(clahe, grid[:, 0], 0.0)
+    q[:, Q_TX] = np.where(clahe, grid[:, 1], 0.0)
+
+    pg, pm = f("gaussian_blur_prob"), f("motion_blur_prob")
+    blur = take(groups["noise"], f("gauss_noise_prob"), pg + pm, U[:, 7])
+    gaussian = blur & (U[:, 8] * (pg + pm) < pg)
+    motion = blur & ~gaussian
+    p[blur, P_SIGMA] = 0.0
+    for i in np.nonzero(gaussian)[0]:
+        ks = sizes[sel[i]][0]
+        k = ks[min(int(U[i, 9] * len(ks)), len(ks) - 1)]
+        R, g = gaussian_taps(0.3 * ((k - 1) * 0.5 - 1.0) + 0.8, radius=(k - 1) // 2)
+        q[i, Q_BLUR], q[i, Q_RADIUS] = BLUR_SEPARABLE, R
+        q[i, Q_TAPS:Q_TAPS + R + 1] = g[:R + 1]
+    for i in np.nonzero(motion)[0]:
+        ks = sizes[sel[i]][1]
+        k = ks[min(int(U[i, 9] * len(ks)), len(ks) - 1)]
+        a = min(int(U[i, 10] * k * k), k * k - 1)
+        b = min(int(U[i, 11] * (k * k - 1)), k * k - 2)
+        b += b >= a                                     # two distinct cells
+        w = motion_line(k, (a % k, a // k), (b % k, b // k))
+        q[i, Q_BLUR], q[i, Q_RADIUS] = BLUR_DENSE, (k - 1) // 2
+        q[i, Q_DENSE:Q_DENSE + k * k] = w.reshape(-1)
+
+    out = (torch.from_numpy(p.astype(np.float32)), rng, torch.from_numpy(q.astype(np.float32)))
+    if return_applied:
+        out += ({"hsv": hsv, "clahe": clahe, "equalize": equalize, "gaussian_blur": gaussian,
+                 "motion_blur": motion},)
+    return out
+
+
 class BatchAugment:
     """Draws the records of a batch and launches `unet_augment_u8` on the current stream.
 
@@ -587,7 +830,15 @@ class BatchAugment:
     records), a warp record per sample is drawn after `sample_params` (`sample_warp`), validated
     against the drawn params, staged through the same ring, and two launches follow:
     `unet_elastic_field` into a field buffer kept per batch shape, then `unet_augment_warp_u8`.
-    Otherwise nothing of this happens: the same draws, the same single launch."""
+    Otherwise nothing of this happens: the same draws, the same single launch.
+
+    When a configuration has one of `hsv_prob`, `clahe_prob`, `equalize_prob`,
+    `gaussian_blur_prob`, `motion_blur_prob` on (or `params=(params, rng, warp or None, post)`
+    names post records), `sample_post` is drawn after `sample_params` (and `sample_warp`), the
+    records are validated (`validate_post`) and staged through the same ring, the gather runs
+    with ZERO salt / pepper thresholds into an intermediate image kept per batch shape, and
+    `unet_augment_post_u8` writes the output, applying salt / pepper last with the same word and
+    rule.  Otherwise nothing of this happens either."""
 
     def __init__(self, cfg, seed=0):
         self.cfg = cfg
@@ -595,16 +846,20 @@ class BatchAugment:
         self.generator.manual_seed(int(seed))
         cfgs = [cfg] if isinstance(cfg, AugmentConfig) else list(cfg)
         self.distortion = any(c.distort_group_prob > 0 for c in cfgs)
+        self.photometric = any(max(c.hsv_prob, c.clahe_prob, c.equalize_prob,
+                                   c.gaussian_blur_prob, c.motion_blur_prob) > 0 for c in cfgs)
         self._ring = None
         self._next = 0
         self._field = {}
+        self._post = {}
 
-    def _stage(self, params, rng, device, warp=None):
-        """-> (params, rng or None, warp or None) on the device"""
+    def _stage(self, params, rng, device, warp=None, post=None):
+        """-> (params, rng or None, warp or None, post or None, rng with zero salt / pepper
+        thresholds or None: for the gather in front of the post stage) on the device"""
         n = params.shape[0]
         head = self._ring[0] if self._ring is not None else None
         if head is None or head["n"] != n or head["device"] != device or \
-                (warp is not None and "hw" not in head):
+                (warp is not None and "hw" not in head) or (post is not None and "hq" not in head):
             self._ring = [{
                 "n": n, "device": device, "event": None,
                 "hp": torch.empty((n, PARAMS_PER_SAMPLE), dtype=torch.float32, pin_memory=True),
@@ -618,6 +873,14 @@ class BatchAugment:
                                              pin_memory=True)
                     slot["dw"] = torch.empty((n, WARP_PER_SAMPLE), dtype=torch.float32,
                                              device=device)
+            if post is not None:
+                for slot in self._ring:
+                    slot["hq"] = torch.empty((n, POST_PER_SAMPLE), dtype=torch.float32,
+                                             pin_memory=True)
+                    slot["dq"] = torch.empty((n, POST_PER_SAMPLE), dtype=torch.float32,
+                                             device=device)
+                    slot["hr0"] = torch.empty((n, 4), dtype=torch.int32, pin_memory=True)
+                    slot["dr0"] = torch.empty((n, 4), dtype=torch.int32, device=device)
             self._next = 0
         slot = self._ring[self._next]
         self._next ^= 1
@@ -625,7 +888,7 @@ class BatchAugment:
             slot["event"].synchronize()         # the copy out of this host buffer has finished
         slot["hp"].copy_(params)
         slot["dp"].copy_(slot["hp"], non_blocking=True)
-        dr = dw = None
+        dr = dw = dq = dr0 = None
         if rng is not None:
             slot["hr"].copy_(pack_rng(rng))
             slot["dr"].copy_(slot["hr"], non_blocking=True)
@@ -634,9 +897,18 @@ class BatchAugment:
             slot["hw"].copy_(warp)
             slot["dw"].copy_(slot["hw"], non_blocking=True)
             dw = slot["dw"]
+        if post is not None:
+            slot["hq"].copy_(post)
+            slot["dq"].copy_(slot["hq"], non_blocking=True)
+            dq = slot["dq"]
+            if rng is not None:
+                slot["hr0"].copy_(slot["hr"])
+                slot["hr0"][:, 2:] = 0
+                slot["dr0"].copy_(slot["hr0"], non_blocking=True)
+                dr0 = slot["dr0"]
         slot["event"] = torch.cuda.Event()
         slot["event"].record()
-        return slot["dp"], dr, dw
+        return slot["dp"], dr, dw, dq, dr0
 
     def _field_buffer(self, N, H, W, device):
         key = (N, H, W, device)
@@ -644,30 +916,71 @@ class BatchAugment:
             self._field[key] = torch.zeros((N, H, W, 2), dtype=torch.float32, device=device)
         return self._field[key]
 
+    def _post_buffers(self, N, H, W, device):
+        """(the intermediate image between the gather and the post stage, the post workspace),
+        kept per batch shape"""
+        key = (N, H, W, device)
+        if key not in self._post:
+            need = ops.lib().unet_augment_post_workspace_bytes(N)
+            self._post[key] = (torch.empty((N, H, W, 3), dtype=torch.uint8, device=device),
+                               torch.empty(need, dtype=torch.uint8, device=device))
+        return self._post[key]
+
     def __call__(self, images_u8, masks_u8=None, which=None, out=None, params=None):
         if not torch.is_tensor(images_u8) or not images_u8.is_cuda:
             raise RuntimeError("unet-implementations_amd.BatchAugment runs on MI355X only "
                                "(no CPU fallback exists)")
         N, H, W, _ = images_u8.shape
-        w = None
+        w = q = None
         if params is None:
-            p, r = sample_params(self.cfg, N, H, W, self.generator, which=which)
+            if self.photometric:
+                p, r, groups = sample_params(self.cfg, N, H, W, self.generator, which=which,
+                                             return_groups=True)
+            else:
+                p, r = sample_params(self.cfg, N, H, W, self.generator, which=which)
             if self.distortion:
                 w = sample_warp(self.cfg, N, H, W, self.generator, which=which)
+            if self.photometric:
+                p, r, q = sample_post(self.cfg, N, H, W, self.generator, p, r, groups,
+                                      which=which)
         else:
-            p, r, w = (tuple(params) + (None, None))[:3] if isinstance(params, (tuple, list)) \
-                else (params, None, None)
+            p, r, w, q = (tuple(params) + (None, None, None))[:4] \
+                if isinstance(params, (tuple, list)) else (params, None, None, None)
             if tuple(p.shape) != (N, PARAMS_PER_SAMPLE):
                 raise ValueError(f"params must be [{N}, {PARAMS_PER_SAMPLE}]")
             validate_params(p, H, W)
-        if w is None:
-            dp, dr, _ = self._stage(p.to(torch.float32), r, images_u8.device)
+        if w is None and q is None:
+            dp, dr, _, _, _ = self._stage(p.to(torch.float32), r, images_u8.device)
             return ops.augment_u8(images_u8, masks_u8, dp, dr, out=out)
-        if tuple(w.shape) != (N, WARP_PER_SAMPLE):
-            raise ValueError(f"warp must be [{N}, {WARP_PER_SAMPLE}]")
-        validate_warp(w, p, H, W)
-        dp, dr, dw = self._stage(p.to(torch.float32), r, images_u8.device,
-                                 warp=w.to(torch.float32))
-        field = self._field_buffer(N, H, W, images_u8.device)
-        ops.elastic_field(dw, dr, (H, W), out=field)
-        return ops.augment_warp_u8(images_u8, masks_u8, dp, dr, dw, field, out=out)
+        if w is not None:
+            if tuple(w.shape) != (N, WARP_PER_SAMPLE):
+                raise ValueError(f"warp must be [{N}, {WARP_PER_SAMPLE}]")
+            validate_warp(w, p, H, W)
+            w = w.to(torch.float32)
+        if q is not None:
+            if tuple(q.shape) != (N, POST_PER_SAMPLE):
+                raise ValueError(f"post must be [{N}, {POST_PER_SAMPLE}]")
+            validate_post(q, H, W)
+            q = q.to(torch.float32)
+        dp, dr, dw, dq, dr0 = self._stage(p.to(torch.float32), r, images_u8.device, warp=w,
+                                          post=q)
+        image_out, mask_out = out if out is not None else (None, None)
+        if q is not None:
+            # the gather writes an intermediate image with salt / pepper off; the post stage
+            # applies it last, with the same word and rule
+            gather_rng, (mid, workspace) = dr0, self._post_buffers(N, H, W, images_u8.device)
+            if masks_u8 is not None and mask_out is None:
+                mask_out = torch.empty_like(masks_u8)
+            gather_out = (mid, mask_out)
+        else:
+            gather_rng, gather_out = dr, out
+        if w is None:
+            res = ops.augment_u8(images_u8, masks_u8, dp, gather_rng, out=gather_out)
+        else:
+            field = self._field_buffer(N, H, W, images_u8.device)
+            ops.elastic_field(dw, dr, (H, W), out=field)
+            res = ops.augment_warp_u8(images_u8, masks_u8, dp, gather_rng, dw, field,
+                                      out=gather_out)
+        if q is None:
+            return res
+        return ops.augment_post_u8(mid, dq, dr, out=image_out, workspace=workspace), res[1]

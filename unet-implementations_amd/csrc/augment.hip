@@ -27,7 +27,7 @@
 // The kernel gathers (four 3-byte taps per output pixel): inputs and outputs must not overlap.
 // 8 x 512 x 512 moves 17 MB; the call is bound by launch and gather latency, not by bandwidth,
 // and is written plainly.
-#include "common.h"
+#include "augment_common.h"
 
 // no fused multiply-adds anywhere below: hipcc contracts device code by default
 #pragma clang fp contract(off)
@@ -38,25 +38,6 @@ constexpr int AUG_PARAMS = 24;
 constexpr int AUG_WARP = 64;                   // floats per warp record (layout: unet_hip.h)
 constexpr int AUG_MAX_R = 16;                  // largest radius of the Gaussian of the field
 constexpr int AUG_MAX_K = 8;                   // most cells per axis of the grid distortion
-constexpr int AUG_MAX_DIM = 32768;             // (float)H, (float)W exact; indices fit int
-constexpr long long AUG_MAX_PIXELS = 1ll << 30;
-
-// Philox4x32-10 (Salmon et al., SC'11): counter c[4], key k[2] -> four random words.
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
-                                              unsigned k0, unsigned k1, unsigned (&out)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 // Box-Muller on one pair of words: u1 = ((a >> 8) + 1) 2^-24 in (0, 1], u2 = (b >> 8) 2^-24 in
 // [0, 1) (both exact in fp32), r = sqrt(-2 ln u1), z = r cos(2 pi u2) and r sin(2 pi u2).
@@ -345,21 +326,6 @@ __global__ __launch_bounds__(256) void elastic_field_kernel(
     float* o = field + (((size_t)n * H + i) * W + j) * 2;
     *reinterpret_cast<float2*>(o) = make_float2((alpha * s0), (alpha * s1));
   }
-}
-
-bool aug_aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-bool aug_aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-
-// [a, a + an) and [b, b + bn) share a byte
-bool aug_overlap(const void* a, size_t an, const void* b, size_t bn) {
-  if (!a || !b) return false;
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y + bn && y < x + an;
-}
-
-bool aug_shape_ok(int N, int H, int W) {
-  return N > 0 && N <= 65535 && H > 0 && W > 0 && H <= AUG_MAX_DIM && W <= AUG_MAX_DIM &&
-         (long long)H * W <= AUG_MAX_PIXELS;
 }
 
 // the checks and the launch of both gather entry points; `warped` is unet_augment_warp_u8

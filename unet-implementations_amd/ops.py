@@ -1436,6 +1436,43 @@ def augment_warp_u8(image, mask, params, rng, warp, field=None, out=None):
     return image_out, mask_out
 
 
+def augment_post_u8(image, post, rng=None, out=None, workspace=None):
+    """uint8 [N,H,W,3]: `image` behind the second augmentation stage of `unet_augment_post_u8`
+    (HSV shift, equalize / CLAHE, Gaussian / motion blur, salt / pepper) on the current stream.
+    post: fp32 [N, 64] and rng: int32 / uint32 [N, 4] (or None: no salt / pepper) are DEVICE
+    tensors the kernels read.  out names the tensor to write (it must not overlap image);
+    workspace is a uint8 tensor of at least `unet_augment_post_workspace_bytes(N)` bytes that a
+    caller may keep between calls (None: one is allocated)."""
+    if not torch.is_tensor(image) or not image.is_cuda:
+        raise RuntimeError("unet-implementations_amd.augment_post_u8 runs on MI355X only "
+                           "(no CPU fallback exists)")
+    if image.dim() != 4 or image.shape[3] != 3 or image.dtype != torch.uint8 or \
+            not image.is_contiguous():
+        raise TypeError("augment_post_u8 takes a contiguous uint8 [N,H,W,3] image")
+    N, H, W, _ = image.shape
+    nrec = lib().unet_augment_post_params_per_sample()
+    if not torch.is_tensor(post) or post.dtype != torch.float32 or \
+            tuple(post.shape) != (N, nrec) or not post.is_contiguous() or \
+            post.device != image.device:
+        raise TypeError(f"post must be a contiguous fp32 [N, {nrec}] tensor on the image's device")
+    _check_rng(rng, N, image.device)
+    if out is None:
+        out = torch.empty_like(image)
+    elif out.dtype != torch.uint8 or out.shape != image.shape or not out.is_contiguous() or \
+            out.device != image.device:
+        raise TypeError("out must be a contiguous uint8 tensor of the image's shape")
+    need = lib().unet_augment_post_workspace_bytes(N)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=image.device)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or \
+            workspace.device != image.device:
+        raise TypeError("workspace must be a contiguous uint8 tensor on the image's device")
+    check(lib().unet_augment_post_u8(_ptr(image), _ptr(out), _ptr(post),
+                                     rng.data_ptr() if rng is not None else None,
+                                     _ptr(workspace), workspace.numel(), N, H, W, _stream()))
+    return out
+
+
 def preprocess_u8(image_hwc_u8, mask_u8=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """uint8 [N,H,W,3] (+ uint8 [N,H,W]) on the device -> (fp32 NHWC image, int64 target)."""
     N, H, W, C = image_hwc_u8.shape

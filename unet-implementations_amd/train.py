@@ -272,7 +272,8 @@ def train_one_epoch(model, train_loader, optimizer, loss_function, device, scale
     `augment` (optional, an `augment.BatchAugment`) takes each uint8 batch (images [N,H,W,3],
     masks [N,H,W]; a "which" entry of the batch selects the configuration per sample) through
     the augmentation kernel (with a distortion configuration: the displacement-field kernel and
-    the warp gather) before the step; `input_layout` is handed to `train_step`."""
+    the warp gather; with a photometric one: the histogram and apply kernels behind the gather)
+    before the step; `input_layout` is handed to `train_step`."""
     if scaler is not None:
         raise NotImplementedError("fp16 GradScaler AMP is not part of the fp32 HIP path")
     model.train()
