@@ -554,6 +554,100 @@ int unet_augment_post_apply(const uint8_t* image, uint8_t* image_out, const floa
                             const uint32_t* rng, void* workspace, size_t workspace_bytes, int N,
                             int H, int W, unet_stream_t stream);
 
+/* ---- ISO noise, shadow, sun flare and fog: a third stage (augment_light.hip) ------- */
+
+/* Floats per sample record `light` of unet_augment_light_u8 (272). */
+int unet_augment_light_params_per_sample(void);
+
+/* Bytes of the workspace unet_augment_light_u8 needs for N samples: sums [N][2] uint64.  0 for
+ * N <= 0. */
+size_t unet_augment_light_workspace_bytes(int N);
+
+/* image [N][H][W][3] (uint8) -> image_out of the same shape (normative text).  light
+ * [N][272] (fp32) and rng [N][4] (uint32, nullable: then ISO noise is off) are DEVICE arrays read
+ * by the kernels only, and the launch sequence (one memset of the sums, the statistics kernel, the
+ * apply kernel) is the same for every batch, so a captured sequence follows new records on replay.
+ * image_out must not overlap image, light, rng or workspace.  Record; every value a mode does not
+ * name is 0; x runs along W, y along H, in output pixels:
+ *    0      ISO noise on: exactly 1; any other value is off
+ *    1      sigma_h, the standard deviation of the hue noise in degrees      2   intensity
+ *    3      mode: 1 shadow, 2 sun flare, 3 fog; any other value is none
+ *    4      count: polygons (shadow), secondary circles (flare), points (fog).  Clamped IN FLOAT to
+ *           0..2, 0..10 or 0..128 (a NaN is 0), then truncated; 0 polygons leave the sample as it is
+ *    shadow 16 + 10 p + 2 v, + 1: vertex v = 0..4 of polygon p as (x, y)
+ *    flare  5, 6 the source centre (x, y);  7 Rs;  8 T, clamped in float to 2..40 (a NaN is 2), then
+ *           truncated;  16 + 7 c ..: circle c as cx, cy, r, a, colour_0..2
+ *    fog    5 the common radius;  6 a = alpha_coef fog_coef;  7 the box size k, clamped in float to
+ *           1..9 (a NaN is 1), then truncated (1: no box);  16 + 2 p, + 1: point p as (x, y)
+ * A radius r is used as fmax(r, 0) (a NaN is 0) and only in arithmetic.  rng[n] = seed_lo, seed_hi
+ * (the two thresholds are not read).
+ * Every fp32 operation is rounded on its own (no fused multiply-add), in the order the parentheses
+ * give; fmin / fmax return the other operand for a NaN; byte(x) = clamp(rint(x), 0, 255); all range
+ * tests are made in float before any conversion to an index or a loop bound.  Per sample:
+ *    input byte p_c -> ISO noise -> byte -> one of { shadow | sun flare | fog } -> byte.
+ * HLS is carried in fp64, each operation rounded on its own, and a channel that comes out of it is
+ * rounded to fp32 before byte: S and the hue's fraction are quotients, and only so does the way back
+ * return exactly the value that went in (a shadowed pixel with s <= 255 is exactly byte(p / 2)).
+ * HLS of a pixel, r, g, b = (double)p_0..2:  V = max, m = min, s = V + m, d = V - m;  L = s / 510;
+ *    S = 0 if d == 0, else d / s for s <= 255, else d / (510 - s);  H = 0 if d == 0, else by the
+ *    channel that is the maximum (ties: r, then g):  r: 60 ((g - b) / d)   g: 120 + (60 ((b - r) / d))
+ *    b: 240 + (60 ((r - g) / d));  H < 0: H = H + 360.
+ * Back from (H, L, S), in levels:  l2 = 510 L;  c = l2 S if l2 <= 255, else (510 - l2) S;
+ *    hp = H / 60, k = fmin(fmax(floor(hp), 0), 5), f = hp - k;  x = c (1 - f) for odd k, c f for even;
+ *    lo = 0.5 (l2 - c), hi = lo + c, mid = lo + x;  (r, g, b) by k = 0..5:
+ *      (hi,mid,lo) (mid,hi,lo) (lo,hi,mid) (lo,mid,hi) (mid,lo,hi) (hi,lo,mid);
+ *    q_c = byte((float)that).
+ * ISO noise (value 0 is 1 and rng is not null).  S1 = sum of s and S2 = sum of s^2 over the
+ *    sample's input pixels, exact integers.  In fp64, each operation rounded on its own:  n = H W,
+ *    mean = S1 / n, var = fmax((S2 / n) - (mean mean), 0), sd = sqrt(var) / 510,
+ *    lambda = (float)fmin(fmax((intensity 255) sd, 0), 64).  The table, in fp32:  t_0 = 1,
+ *    t_k = (t_{k-1} lambda) / k and t_k = 0 where that is below FLT_MIN;  c_k = c_{k-1} + t_k from
+ *    c_0 = t_0, k = 1..255;  T = c_255.  Pixel with index i W + j: words w0..w3 of Philox4x32-10
+ *    STREAM 3, key (seed_lo, seed_hi), counter (pixel index lo, hi, 3, 0).  z = the first Box-Muller
+ *    normal of (w0, w1) as unet_augment_u8 forms it;  u = (w2 >> 8) 2^-24;  kp = the number of
+ *    c_j <= (u T), at most 255.  In fp64, with sigma_h, z and kp converted:
+ *    H' = H + (sigma_h z), H' = H' - (360 floor(H' / 360)),
+ *    H' = fmin(fmax(H', 0), 360 - 2^-44) (the largest double below 360);
+ *    L' = fmin(L + ((kp / 255) (1 - L)), 1);  back from (H', L', S).
+ * Shadow: pixel (i, j) has the centre xc = j + 0.5, yc = i + 0.5.  Edge e of a polygon runs from
+ *    vertex e = (x1, y1) to vertex (e + 1) mod 5 = (x2, y2); it is crossed where
+ *    (y1 <= yc) != (y2 <= yc) (half-open in y, so a centre level with a vertex is decided once) and
+ *    xc < x1 + (((yc - y1) / (y2 - y1)) (x2 - x1)).  A centre with an odd number of crossed edges is
+ *    inside the polygon.  m = the number of polygons the centre is inside: m == 0 keeps the bytes;
+ *    else back from (H, 0.5 L, S) for m == 1 and from (H, 0.25 L, S) for m == 2.
+ * Circles (flare, fog): pixel (i, j) is inside (cx, cy, r) where
+ *    (((float)j - cx)^2 + ((float)i - cy)^2) <= (fmax(r, 0) fmax(r, 0)), each square and the sum
+ *    rounded; a NaN makes it outside.
+ * Sun flare, per channel: ov = o = the byte.  Circle c = 0..count-1 in order: inside: ov = colour_c;
+ *    then o = byte((a ov) + ((1 - a) o)).  Then i = 0..T-1:  r_i = 1 + (((Rs - 1) (float)i) /
+ *    (float)(T - 1)); inside (source centre, r_i): ov = 255;  q = (float)(T - 1 - i) / (float)(T - 1),
+ *    a_i = (q q) q;  o = byte((a_i ov) + ((1 - a_i) o)).
+ * Fog, per channel: for point p = 0..count-1 in order, inside (point, radius):
+ *    o = byte((a 255) + ((1 - a) o)).  Then for k >= 2 the k x k box mean over the fogged bytes B:
+ *    offsets -(k / 2) .. k - 1 - (k / 2) per axis (integer division), borders reflect without
+ *    repeating the edge (x < 0: -x; x > W - 1: 2 (W - 1) - x), the result then clamped to
+ *    0 .. W - 1, rows likewise;  out = byte((sum over dy, then dx, both ascending, from 0.f, of
+ *    (float)B(i + dy, j + dx)) / (float)(k k)).  A halo pixel's B is the value of the whole chain
+ *    at that pixel, ISO noise included (its words depend on the pixel index only).
+ * A sample with nothing on is copied.
+ * workspace: unet_augment_light_workspace_bytes(N) bytes, 16-byte aligned, scratch of this call.
+ * UNET_E_INVALID before any launch: null image / image_out / light, a bad shape (as
+ * unet_augment_u8), a null, too small or misaligned workspace, image_out overlapping an input or
+ * the workspace, the workspace overlapping an input. */
+int unet_augment_light_u8(const uint8_t* image, uint8_t* image_out, const float* light,
+                          const uint32_t* rng, void* workspace, size_t workspace_bytes, int N,
+                          int H, int W, unet_stream_t stream);
+
+/* The two halves of unet_augment_light_u8, for a caller that measures or overlaps them: the
+ * statistics half (the memset of the sums and the statistics kernel) fills the workspace the apply
+ * half reads; stats followed by apply on one stream, with the same arguments, is
+ * unet_augment_light_u8.  The same refusals. */
+int unet_augment_light_stats(const uint8_t* image, const float* light, void* workspace,
+                             size_t workspace_bytes, int N, int H, int W, unet_stream_t stream);
+int unet_augment_light_apply(const uint8_t* image, uint8_t* image_out, const float* light,
+                             const uint32_t* rng, void* workspace, size_t workspace_bytes, int N,
+                             int H, int W, unet_stream_t stream);
+
 /* uint8 HWC image (+ uint8 mask) -> ((v/255) - mean)/std NHWC fp32 (+ int64 target with values
  * > 2 other than 255 mapped to 0): PetSegmentationDataset.__getitem__, src/train.py:300-311.
  * mean3 / std3 are HOST pointers to 3 floats. */

@@ -106,6 +106,11 @@ SIGNATURES = {
     "unet_augment_post_u8": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _i, _p]),
     "unet_augment_post_hist": (_i, [_p, _p, _p, _sz, _i, _i, _i, _p]),
     "unet_augment_post_apply": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _i, _p]),
+    "unet_augment_light_params_per_sample": (_i, []),
+    "unet_augment_light_workspace_bytes": (_sz, [_i]),
+    "unet_augment_light_u8": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _i, _p]),
+    "unet_augment_light_stats": (_i, [_p, _p, _p, _sz, _i, _i, _i, _p]),
+    "unet_augment_light_apply": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _i, _p]),
     "unet_gradcam_workspace_bytes": (_sz, [_i, _i, _i]),
     "unet_gradcam_weights": (_i, [_p, _i, _p, _p, _sz, _i, _i, _i, _p]),
     "unet_gradcam_map": (_i, [_ps, _i, _f, _p, _p, _p, _sz, _i, _i, _p]),

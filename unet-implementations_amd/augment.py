@@ -41,13 +41,25 @@ Supported transforms, and how each is realised:
         has one of these members on draws the record and launches the stage;
         `from_yaml(..., photometric=True)` reads them from the reference's file.
 
+    ISONoise, OneOf(RandomShadow, RandomSunFlare, RandomFog)
+        a fourth record of 272 floats per sample (`sample_light`) and a THIRD STAGE of two kernels
+        (`unet_augment_light_u8`, csrc/augment_light.hip) over the image the gather or the second
+        stage wrote: a statistics kernel (exact integer sums of the lightness, for the Poisson
+        rate of ISO noise) and a tiled kernel that applies ISO noise (hue by a normal, lightness
+        by a Poisson draw, in float HLS), then the shadow polygons, the flare's circles or the
+        fog's points through byte-rounded blends, the fog's box mean from a staged tile.  Only a
+        `BatchAugment` whose configuration has `iso_noise_prob > 0` or `lighting_group_prob > 0`
+        draws the record and launches the stage; `from_yaml(..., lighting=True)` reads them from
+        the reference's file.
+
 `OneOf` groups keep the reference's structure over the supported members: the group probability
 is drawn first, then one member by its normalised probability among the SUPPORTED members (with
 the second stage on, the new members count: `sample_post`).
 
-Not supported (keys of these are ignored by `from_yaml`): ISO noise, shadow / sun flare / fog.
+With `from_yaml(path, section, distortion=True, photometric=True, lighting=True)` every key of
+the reference's file is read.
 The semantics of what is supported are defined by this project (include/unet_hip.h, DESIGN 12,
-12b, 12c), not recorded from the reference's augmentation library; the package ships no preset
+12b, 12c, 12d), not recorded from the reference's augmentation library; the package ships no preset
 numbers: every probability of `AugmentConfig` defaults to 0, which is the identity.
 """
 import dataclasses
@@ -79,6 +91,13 @@ HIST_NONE, HIST_EQUALIZE, HIST_CLAHE = 0, 1, 2
 BLUR_NONE, BLUR_SEPARABLE, BLUR_DENSE = 0, 1, 2
 MAX_BLUR_RADIUS = {BLUR_SEPARABLE: 4, BLUR_DENSE: 3}
 MAX_TILE_GRID = 8
+# light record layout (include/unet_hip.h): the third stage
+LIGHT_PER_SAMPLE = 272
+L_ISO, L_SIGMA_H, L_INTENSITY, L_MODE, L_COUNT, L_BODY = 0, 1, 2, 3, 4, 16
+L_SRC_X, L_SRC_Y, L_SRC_RADIUS, L_STEPS = 5, 6, 7, 8               # sun flare
+L_FOG_RADIUS, L_FOG_ALPHA, L_FOG_BOX = 5, 6, 7                     # fog
+LIGHT_NONE, LIGHT_SHADOW, LIGHT_FLARE, LIGHT_FOG = 0, 1, 2, 3
+MAX_POLYGONS, MAX_FLARE_CIRCLES, MAX_FOG_POINTS, MAX_FLARE_STEPS, MAX_FOG_BOX = 2, 10, 128, 40, 9
 PERSPECTIVE_CLIP = 3.0      # a corner moves inward by min(|z|, 3) * scale of the image size
 
 
@@ -177,9 +196,23 @@ class AugmentConfig:
     gaussian_blur_limit: Tuple[int, int] = (3, 3)
     motion_blur_prob: float = 0.0
     motion_blur_limit: Tuple[int, int] = (3, 3)
+    # the third stage (`sample_light`).  ISONoise: colour shift and intensity drawn from their
+    # ranges; the hue noise has sigma = color_shift * 360 * intensity degrees, the Poisson rate
+    # of the lightness noise is intensity * 255 * std(L) of the sample
+    iso_noise_prob: float = 0.0
+    iso_color_shift: Tuple[float, float] = (0.0, 0.0)
+    iso_intensity: Tuple[float, float] = (0.0, 0.0)
+    # OneOf(RandomShadow, RandomSunFlare, RandomFog)
+    lighting_group_prob: float = 0.0
+    shadow_prob: float = 0.0
+    sunflare_prob: float = 0.0
+    sunflare_src_radius: int = 400      # 20..400; the source is drawn in src_radius // 10 steps
+    fog_prob: float = 0.0
+    fog_coef: Tuple[float, float] = (0.0, 0.0)
+    fog_alpha_coef: float = 0.0
 
     @classmethod
-    def from_yaml(cls, path, section, distortion=False, photometric=False):
+    def from_yaml(cls, path, section, distortion=False, photometric=False, lighting=False):
         """The `section` ("cat" / "dog") of a file in the format of the reference's
         data_augmentation/config/augmentation_config.yaml.  Keys of unsupported transforms are
         ignored; a transform whose keys are absent stays off.  The elastic / grid / optical
@@ -188,7 +221,11 @@ class AugmentConfig:
         batch, so a caller asks for it.  Likewise `photometric=True` reads the members that
         need the second stage (`hsv`; `clahe_prob`, `clahe_clip_limit`, `clahe_tile_grid_size`
         and `equalize_prob` of `clahe_equalize`; `gaussian_blur`; `motion_blur`), which then
-        share their groups' probabilities with the old members (`sample_post`)."""
+        share their groups' probabilities with the old members (`sample_post`), and
+        `lighting=True` the third stage (`iso_noise`; `lighting_transform_prob`, `shadow`,
+        `sunflare`, `fog`).  With all three every key of the reference's file is read
+        (`random_resized_crop.size` is read and not used: the crop is resized to the batch's
+        own shape)."""
         import yaml      # lazily: only this constructor needs it
         with open(path) as f:
             doc = yaml.safe_load(f)
@@ -205,6 +242,7 @@ class AugmentConfig:
         c.crop_prob = float(g.get("prob", 0.0))
         c.crop_scale = _pair(g.get("scale", (1.0, 1.0)))
         c.crop_ratio = _pair(g.get("ratio", (1.0, 1.0)))
+        g.get("size")       # the crop is resized to the shape of the batch, whatever this says
         g = s.get("perspective") or {}
         c.perspective_prob = float(g.get("prob", 0.0))
         sc = g.get("scale", (0.0, 0.0))
@@ -268,6 +306,18 @@ class AugmentConfig:
             g = s.get("motion_blur") or {}
             c.motion_blur_prob = float(g.get("prob", 0.0))
             c.motion_blur_limit = _blur_limit(g.get("blur_limit", 3))
+        if lighting:
+            g = s.get("iso_noise") or {}
+            c.iso_noise_prob = float(g.get("prob", 0.0))
+            c.iso_color_shift = tuple(float(v) for v in g.get("color_shift", (0.0, 0.0)))
+            c.iso_intensity = tuple(float(v) for v in g.get("intensity", (0.0, 0.0)))
+            c.lighting_group_prob = float(s.get("lighting_transform_prob", 0.0))
+            c.shadow_prob = float((s.get("shadow") or {}).get("prob", 0.0))
+            c.sunflare_prob = float((s.get("sunflare") or {}).get("prob", 0.0))
+            g = s.get("fog") or {}
+            c.fog_prob = float(g.get("prob", 0.0))
+            c.fog_coef = (float(g.get("fog_coef_lower", 0.0)), float(g.get("fog_coef_upper", 0.0)))
+            c.fog_alpha_coef = float(g.get("alpha_coef", 0.0))
         return c
 
 
@@ -812,6 +862,203 @@ def sample_post(cfg, n, H, W, generator, params, rng, groups, which=None, return
     return out
 
 
+# ---- the light record: ISO noise, shadow / sun flare / fog --------------------------------------
+def identity_light(n):
+    """fp32 [n, 272]: the light record that copies the image (everything off)."""
+    return torch.zeros(n, LIGHT_PER_SAMPLE, dtype=torch.float32)
+
+
+def validate_light(light, H, W):
+    """Refuse a light record the kernels are not specified for: every value finite, the ISO flag
+    0 or 1 with sigma_h >= 0 and 0 <= intensity <= 1, the mode in 0..3, an integer count in 1..2
+    (shadow), 0..10 (flare) or 0..128 (fog), integer flare steps T in 2..40 and an integer fog box
+    k in 1..9 with k - 1 - k // 2 < min(H, W), radii that are not negative (the source's at least
+    1), blend weights a in [0, 1] and flare colours in 0..255."""
+    q = light.detach().cpu().numpy() if torch.is_tensor(light) else np.asarray(light)
+    if q.ndim != 2 or q.shape[1] != LIGHT_PER_SAMPLE:
+        raise ValueError(f"light must be [n, {LIGHT_PER_SAMPLE}]")
+    if not np.isfinite(q).all():
+        raise ValueError("light record holds a non-finite value")
+    q = q.astype(np.float64)
+    if not np.isin(q[:, L_ISO], (0, 1)).all():
+        raise ValueError("light record has an ISO flag other than 0 / 1")
+    iso = q[:, L_ISO] == 1
+    if (q[iso, L_SIGMA_H] < 0).any() or (q[iso, L_INTENSITY] < 0).any() or \
+            (q[iso, L_INTENSITY] > 1).any():
+        raise ValueError("ISO noise needs sigma_h >= 0 and an intensity in [0, 1]")
+    if not np.isin(q[:, L_MODE], (LIGHT_NONE, LIGHT_SHADOW, LIGHT_FLARE, LIGHT_FOG)).all():
+        raise ValueError("light record has a mode outside 0..3")
+
+    def whole(v, lo, hi, what, i):
+        if v != np.rint(v) or v < lo or v > hi:
+            raise ValueError(f"{what} must be an integer in {lo}..{hi} (sample {i}: {v})")
+        return int(v)
+
+    for i in np.nonzero(q[:, L_MODE] != LIGHT_NONE)[0]:
+        mode = int(q[i, L_MODE])
+        if mode == LIGHT_SHADOW:
+            whole(q[i, L_COUNT], 1, MAX_POLYGONS, "the shadow's polygon count", i)
+        elif mode == LIGHT_FLARE:
+            n = whole(q[i, L_COUNT], 0, MAX_FLARE_CIRCLES, "the flare's circle count", i)
+            whole(q[i, L_STEPS], 2, MAX_FLARE_STEPS, "the flare's step count T", i)
+            if q[i, L_SRC_RADIUS] < 1:
+                raise ValueError(f"the flare's source radius must be at least 1 (sample {i})")
+            c = q[i, L_BODY:L_BODY + 7 * n].reshape(n, 7)
+            if (c[:, 2] < 0).any():
+                raise ValueError(f"a flare circle has a negative radius (sample {i})")
+            if (c[:, 3] < 0).any() or (c[:, 3] > 1).any():
+                raise ValueError(f"a flare circle's a must be in [0, 1] (sample {i})")
+            if (c[:, 4:] < 0).any() or (c[:, 4:] > 255).any():
+                raise ValueError(f"a flare circle's colour must be in 0..255 (sample {i})")
+        else:
+            whole(q[i, L_COUNT], 0, MAX_FOG_POINTS, "the fog's point count", i)
+            k = whole(q[i, L_FOG_BOX], 1, MAX_FOG_BOX, "the fog's box size k", i)
+            if k - 1 - k // 2 >= min(H, W):
+                raise ValueError(f"the fog's box {k} reaches across the image ({H} x {W})")
+            if q[i, L_FOG_RADIUS] < 0:
+                raise ValueError(f"the fog's radius must not be negative (sample {i})")
+            if not 0 <= q[i, L_FOG_ALPHA] <= 1:
+                raise ValueError(f"the fog's a must be in [0, 1] (sample {i})")
+
+
+def fog_points(hw, H, W, uniforms):
+    """The reference library's haze-point loop: rings that grow outward from the centre, ring
+    `index` holding (hw // 10) * index points, each at a uniform integer position of the ring's
+    rectangle, moved by hw // 2.  `uniforms` yields the U[0, 1) numbers it consumes (two per
+    point).  -> float64 [P, 2] as (x, y)"""
+    pts = []
+    midx, midy, index = W // 2 - 2 * hw, H // 2 - hw, 1
+    while midx > -hw or midy > -hw:
+        for _ in range(hw // 10 * index):
+            x = midx + math.floor(next(uniforms) * (W - midx - hw - midx + 1))
+            y = midy + math.floor(next(uniforms) * (H - midy - hw - midy + 1))
+            pts.append((x + hw // 2, y + hw // 2))
+        midy -= 3 * hw * H // (H + W)
+        midx -= 3 * hw * W // (H + W)
+        index += 1
+    return np.asarray(pts, dtype=np.float64).reshape(-1, 2)
+
+
+def fog_point_count(hw, H, W):
+    """the number of points `fog_points` draws (it does not depend on the uniforms)"""
+    n, midx, midy, index = 0, W // 2 - 2 * hw, H // 2 - hw, 1
+    while midx > -hw or midy > -hw:
+        n += hw // 10 * index
+        midy -= 3 * hw * H // (H + W)
+        midx -= 3 * hw * W // (H + W)
+        index += 1
+    return n
+
+
+LIGHT_UNIFORMS = 5 + 2 * MAX_FOG_POINTS + 3     # the widest member (fog) behind the five heads
+
+
+def sample_light(cfg, n, H, W, generator, which=None, return_applied=False):
+    """Draw n light records (fp32 [n, 272], on the CPU): ISONoise on its own probability, then the
+    group OneOf(RandomShadow, RandomSunFlare, RandomFog): the group probability first, then one
+    member by its probability normalised over the three.  `cfg`, `which` and `generator` as for
+    `sample_params`; the draws come from a block of uniforms of their own, drawn AFTER those of
+    `sample_params`, `sample_warp` and `sample_post`, which are unaffected by whether this is
+    called.  The draw rules are those of the reference's library:
+        ISO     colour shift and intensity uniform over their ranges; sigma_h = shift 360 intensity
+        shadow  1 or 2 polygons of five vertices at uniform integer positions of the image
+        flare   centre uniform, angle 2 pi U, 6..10 circles at random points (every 10 pixels) of
+                the line through the centre, radius an integer in 1..max(H // 100 - 2, 2),
+                a ~ U(0.05, 0.2), channels integers in 205..255; T = src_radius // 10
+        fog     coef uniform, hw = int((W // 3) coef), the haze-point loop (`fog_points`), radius
+                hw // 2, a = alpha_coef coef, box k = hw // 10 (below 2: no box)
+    A draw that exceeds a cap of the record (128 fog points, a box of 9) raises.  The records are
+    validated (`validate_light`).  With `return_applied` a dict of boolean [n] arrays comes
+    second."""
+    cfgs, sel = _select(cfg, n, which)
+
+    def f(name):
+        return np.asarray([getattr(c, name) for c in cfgs], dtype=np.float64)[sel]
+
+    for c in cfgs:
+        if c.iso_noise_prob > 0:
+            if not 0 <= min(c.iso_intensity) <= max(c.iso_intensity) <= 1:
+                raise ValueError("iso_intensity must lie in [0, 1]")
+            if min(c.iso_color_shift) < 0:
+                raise ValueError("iso_color_shift must not be negative")
+        if c.lighting_group_prob > 0 and c.sunflare_prob > 0:
+            if int(c.sunflare_src_radius) != c.sunflare_src_radius or \
+                    not 20 <= c.sunflare_src_radius <= 400:
+                raise ValueError("sunflare_src_radius must be an integer in 20..400")
+        if c.lighting_group_prob > 0 and c.fog_prob > 0:
+            if not 0 <= min(c.fog_coef) <= max(c.fog_coef) <= 1 or not 0 <= c.fog_alpha_coef <= 1:
+                raise ValueError("fog_coef and fog_alpha_coef must lie in [0, 1]")
+
+    U = torch.rand(n, LIGHT_UNIFORMS, dtype=torch.float64, generator=generator).numpy()
+    q = np.zeros((n, LIGHT_PER_SAMPLE), dtype=np.float64)
+
+    iso = U[:, 0] < f("iso_noise_prob")
+    cs, it = f("iso_color_shift"), f("iso_intensity")
+    shift = cs[:, 0] + (cs[:, 1] - cs[:, 0]) * U[:, 1]
+    intensity = it[:, 0] + (it[:, 1] - it[:, 0]) * U[:, 2]
+    q[:, L_ISO] = iso
+    q[:, L_SIGMA_H] = np.where(iso, shift * 360.0 * intensity, 0.0)
+    q[:, L_INTENSITY] = np.where(iso, intensity, 0.0)
+
+    ps, pf, pg = f("shadow_prob"), f("sunflare_prob"), f("fog_prob")
+    tot = ps + pf + pg
+    group = (U[:, 3] < f("lighting_group_prob")) & (tot > 0)
+    pick = U[:, 4] * tot
+    shadow = group & (pick < ps)
+    flare = group & ~shadow & (pick < ps + pf)
+    fog = group & ~shadow & ~flare
+    q[:, L_MODE] = np.where(shadow, LIGHT_SHADOW, np.where(flare, LIGHT_FLARE,
+                                                           np.where(fog, LIGHT_FOG, LIGHT_NONE)))
+
+    def whole(u, lo, hi):       # a uniform integer in lo..hi, both included
+        return lo + min(int(u * (hi - lo + 1)), hi - lo)
+
+    for i in np.nonzero(shadow)[0]:
+        u = iter(U[i, 5:])
+        count = whole(next(u), 1, MAX_POLYGONS)
+        q[i, L_COUNT] = count
+        for v in range(5 * count):
+            q[i, L_BODY + 2 * v] = whole(next(u), 0, W)
+            q[i, L_BODY + 2 * v + 1] = whole(next(u), 0, H)
+    for i in np.nonzero(flare)[0]:
+        u = iter(U[i, 5:])
+        rs = int(cfgs[sel[i]].sunflare_src_radius)
+        cx, cy = int(next(u) * W), int(next(u) * H)
+        ang = 2.0 * math.pi * next(u)
+        count = whole(next(u), 6, MAX_FLARE_CIRCLES)
+        q[i, L_COUNT], q[i, L_SRC_X], q[i, L_SRC_Y] = count, cx, cy
+        q[i, L_SRC_RADIUS], q[i, L_STEPS] = rs, rs // 10
+        ts = range(-cx, W - cx, 10)                     # the points of the line, every 10 pixels
+        for c in range(count):
+            a = 0.05 + 0.15 * next(u)
+            t = ts[whole(next(u), 0, len(ts) - 1)]
+            rad = whole(next(u), 1, max(H // 100 - 2, 2))
+            colour = [whole(next(u), 205, 255) for _ in range(3)]
+            q[i, L_BODY + 7 * c:L_BODY + 7 * c + 7] = [
+                int(cx + t * math.cos(ang)), int(cy + t * math.sin(ang)), rad, a] + colour
+    for i in np.nonzero(fog)[0]:
+        u = iter(U[i, 5:])
+        lim = cfgs[sel[i]].fog_coef
+        coef = lim[0] + (lim[1] - lim[0]) * next(u)
+        hw = max(1, int((W // 3) * coef))
+        count = fog_point_count(hw, H, W)
+        if count > MAX_FOG_POINTS or hw // 10 > MAX_FOG_BOX:
+            raise ValueError(f"a fog of coefficient {coef:.3f} on {H} x {W} draws {count} points "
+                             f"and a box of {hw // 10}: the record holds {MAX_FOG_POINTS} points "
+                             f"and a box of at most {MAX_FOG_BOX}")
+        pts = fog_points(hw, H, W, u)
+        q[i, L_COUNT], q[i, L_FOG_RADIUS] = count, hw // 2
+        q[i, L_FOG_ALPHA] = cfgs[sel[i]].fog_alpha_coef * coef
+        q[i, L_FOG_BOX] = max(hw // 10, 1)
+        q[i, L_BODY:L_BODY + 2 * count] = pts.reshape(-1)
+
+    light = torch.from_numpy(q.astype(np.float32))
+    validate_light(light, H, W)
+    if return_applied:
+        return light, {"iso_noise": iso, "shadow": shadow, "sunflare": flare, "fog": fog}
+    return light
+
+
 class BatchAugment:
     """Draws the records of a batch and launches `unet_augment_u8` on the current stream.
 
@@ -838,7 +1085,15 @@ class BatchAugment:
     records are validated (`validate_post`) and staged through the same ring, the gather runs
     with ZERO salt / pepper thresholds into an intermediate image kept per batch shape, and
     `unet_augment_post_u8` writes the output, applying salt / pepper last with the same word and
-    rule.  Otherwise nothing of this happens either."""
+    rule.  Otherwise nothing of this happens either.
+
+    When a configuration has `iso_noise_prob > 0` or `lighting_group_prob > 0` (or
+    `params=(params, rng, warp or None, post or None, light)` names light records),
+    `sample_light` is drawn last, the records are validated (`validate_light`) and staged through
+    the same ring, whichever stage wrote the output before writes a second intermediate image
+    kept per batch shape, and `unet_augment_light_u8` writes the output.  Salt / pepper stays
+    where it is (in the post stage when there is one, else in the gather), in front of ISO
+    noise as in the reference.  Otherwise nothing of this happens either."""
 
     def __init__(self, cfg, seed=0):
         self.cfg = cfg
@@ -848,18 +1103,23 @@ class BatchAugment:
         self.distortion = any(c.distort_group_prob > 0 for c in cfgs)
         self.photometric = any(max(c.hsv_prob, c.clahe_prob, c.equalize_prob,
                                    c.gaussian_blur_prob, c.motion_blur_prob) > 0 for c in cfgs)
+        self.lighting = any(max(c.iso_noise_prob, c.lighting_group_prob) > 0 for c in cfgs)
         self._ring = None
         self._next = 0
         self._field = {}
         self._post = {}
+        self._light = {}
 
-    def _stage(self, params, rng, device, warp=None, post=None):
+    def _stage(self, params, rng, device, warp=None, post=None, light=None):
         """-> (params, rng or None, warp or None, post or None, rng with zero salt / pepper
-        thresholds or None: for the gather in front of the post stage) on the device"""
+        thresholds or None: for the gather in front of the post stage) on the device; with
+        `light` its device copy comes sixth"""
         n = params.shape[0]
         head = self._ring[0] if self._ring is not None else None
         if head is None or head["n"] != n or head["device"] != device or \
-                (warp is not None and "hw" not in head) or (post is not None and "hq" not in head):
+                (warp is not None and "hw" not in head) or \
+                (post is not None and "hq" not in head) or \
+                (light is not None and "hl" not in head):
             self._ring = [{
                 "n": n, "device": device, "event": None,
                 "hp": torch.empty((n, PARAMS_PER_SAMPLE), dtype=torch.float32, pin_memory=True),
@@ -881,6 +1141,12 @@ class BatchAugment:
                                              device=device)
                     slot["hr0"] = torch.empty((n, 4), dtype=torch.int32, pin_memory=True)
                     slot["dr0"] = torch.empty((n, 4), dtype=torch.int32, device=device)
+            if light is not None:
+                for slot in self._ring:
+                    slot["hl"] = torch.empty((n, LIGHT_PER_SAMPLE), dtype=torch.float32,
+                                             pin_memory=True)
+                    slot["dl"] = torch.empty((n, LIGHT_PER_SAMPLE), dtype=torch.float32,
+                                             device=device)
             self._next = 0
         slot = self._ring[self._next]
         self._next ^= 1
@@ -906,8 +1172,13 @@ class BatchAugment:
                 slot["hr0"][:, 2:] = 0
                 slot["dr0"].copy_(slot["hr0"], non_blocking=True)
                 dr0 = slot["dr0"]
+        if light is not None:
+            slot["hl"].copy_(light)
+            slot["dl"].copy_(slot["hl"], non_blocking=True)
         slot["event"] = torch.cuda.Event()
         slot["event"].record()
+        if light is not None:
+            return slot["dp"], dr, dw, dq, dr0, slot["dl"]
         return slot["dp"], dr, dw, dq, dr0
 
     def _field_buffer(self, N, H, W, device):
@@ -926,12 +1197,22 @@ class BatchAugment:
                                torch.empty(need, dtype=torch.uint8, device=device))
         return self._post[key]
 
+    def _light_buffers(self, N, H, W, device):
+        """(the intermediate image in front of the light stage, the light workspace), kept per
+        batch shape"""
+        key = (N, H, W, device)
+        if key not in self._light:
+            need = ops.lib().unet_augment_light_workspace_bytes(N)
+            self._light[key] = (torch.empty((N, H, W, 3), dtype=torch.uint8, device=device),
+                                torch.empty(max(need, 16), dtype=torch.uint8, device=device))
+        return self._light[key]
+
     def __call__(self, images_u8, masks_u8=None, which=None, out=None, params=None):
         if not torch.is_tensor(images_u8) or not images_u8.is_cuda:
             raise RuntimeError("unet-implementations_amd.BatchAugment runs on MI355X only "
                                "(no CPU fallback exists)")
         N, H, W, _ = images_u8.shape
-        w = q = None
+        w = q = lt = None
         if params is None:
             if self.photometric:
                 p, r, groups = sample_params(self.cfg, N, H, W, self.generator, which=which,
@@ -943,13 +1224,15 @@ class BatchAugment:
             if self.photometric:
                 p, r, q = sample_post(self.cfg, N, H, W, self.generator, p, r, groups,
                                       which=which)
+            if self.lighting:
+                lt = sample_light(self.cfg, N, H, W, self.generator, which=which)
         else:
-            p, r, w, q = (tuple(params) + (None, None, None))[:4] \
-                if isinstance(params, (tuple, list)) else (params, None, None, None)
+            p, r, w, q, lt = (tuple(params) + (None, None, None, None))[:5] \
+                if isinstance(params, (tuple, list)) else (params, None, None, None, None)
             if tuple(p.shape) != (N, PARAMS_PER_SAMPLE):
                 raise ValueError(f"params must be [{N}, {PARAMS_PER_SAMPLE}]")
             validate_params(p, H, W)
-        if w is None and q is None:
+        if w is None and q is None and lt is None:
             dp, dr, _, _, _ = self._stage(p.to(torch.float32), r, images_u8.device)
             return ops.augment_u8(images_u8, masks_u8, dp, dr, out=out)
         if w is not None:
@@ -962,10 +1245,32 @@ class BatchAugment:
                 raise ValueError(f"post must be [{N}, {POST_PER_SAMPLE}]")
             validate_post(q, H, W)
             q = q.to(torch.float32)
-        dp, dr, dw, dq, dr0 = self._stage(p.to(torch.float32), r, images_u8.device, warp=w,
-                                          post=q)
+        if lt is None:
+            staged = self._stage(p.to(torch.float32), r, images_u8.device, warp=w, post=q)
+            return self._launch(images_u8, masks_u8, staged, out)
+        if tuple(lt.shape) != (N, LIGHT_PER_SAMPLE):
+            raise ValueError(f"light must be [{N}, {LIGHT_PER_SAMPLE}]")
+        validate_light(lt, H, W)
+        staged = self._stage(p.to(torch.float32), r, images_u8.device, warp=w, post=q,
+                             light=lt.to(torch.float32))
+        # whichever stage wrote the output before writes a second intermediate image; the light
+        # stage writes the output.  The mask is none of its business.
         image_out, mask_out = out if out is not None else (None, None)
-        if q is not None:
+        mid, workspace = self._light_buffers(N, H, W, images_u8.device)
+        if masks_u8 is not None and mask_out is None:
+            mask_out = torch.empty_like(masks_u8)
+        res = self._launch(images_u8, masks_u8, staged[:5], (mid, mask_out))
+        return ops.augment_light_u8(mid, staged[5], staged[1], out=image_out,
+                                    workspace=workspace), res[1]
+
+    def _launch(self, images_u8, masks_u8, staged, out):
+        """the gather (behind the field kernel with a warp record) and the post stage"""
+        dp, dr, dw, dq, dr0 = staged
+        N, H, W, _ = images_u8.shape
+        if dw is None and dq is None:
+            return ops.augment_u8(images_u8, masks_u8, dp, dr, out=out)
+        image_out, mask_out = out if out is not None else (None, None)
+        if dq is not None:
             # the gather writes an intermediate image with salt / pepper off; the post stage
             # applies it last, with the same word and rule
             gather_rng, (mid, workspace) = dr0, self._post_buffers(N, H, W, images_u8.device)
@@ -974,13 +1279,13 @@ class BatchAugment:
             gather_out = (mid, mask_out)
         else:
             gather_rng, gather_out = dr, out
-        if w is None:
+        if dw is None:
             res = ops.augment_u8(images_u8, masks_u8, dp, gather_rng, out=gather_out)
         else:
             field = self._field_buffer(N, H, W, images_u8.device)
             ops.elastic_field(dw, dr, (H, W), out=field)
             res = ops.augment_warp_u8(images_u8, masks_u8, dp, gather_rng, dw, field,
                                       out=gather_out)
-        if q is None:
+        if dq is None:
             return res
         return ops.augment_post_u8(mid, dq, dr, out=image_out, workspace=workspace), res[1]

@@ -1,4 +1,4 @@
-// augment_common.h — what augment.hip and augment_post.hip share: the shape limits, the host-side
+// augment_common.h — what augment.hip, augment_post.hip and augment_light.hip share: the shape limits, the host-side
 // argument checks and Philox4x32-10.
 #pragma once
 #include "common.h"

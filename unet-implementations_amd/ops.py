@@ -1473,6 +1473,71 @@ def augment_post_u8(image, post, rng=None, out=None, workspace=None):
     return out
 
 
+def _light_args(name, image, light, rng, out, workspace, need_out):
+    """The argument checks of `augment_light_u8` and its two halves -> (out, workspace)."""
+    if not torch.is_tensor(image) or not image.is_cuda:
+        raise RuntimeError(f"unet-implementations_amd.{name} runs on MI355X only "
+                           "(no CPU fallback exists)")
+    if image.dim() != 4 or image.shape[3] != 3 or image.dtype != torch.uint8 or \
+            not image.is_contiguous():
+        raise TypeError(f"{name} takes a contiguous uint8 [N,H,W,3] image")
+    N = image.shape[0]
+    nrec = lib().unet_augment_light_params_per_sample()
+    if not torch.is_tensor(light) or light.dtype != torch.float32 or \
+            tuple(light.shape) != (N, nrec) or not light.is_contiguous() or \
+            light.device != image.device:
+        raise TypeError(f"light must be a contiguous fp32 [N, {nrec}] tensor on the image's device")
+    _check_rng(rng, N, image.device)
+    if need_out:
+        if out is None:
+            out = torch.empty_like(image)
+        elif out.dtype != torch.uint8 or out.shape != image.shape or not out.is_contiguous() or \
+                out.device != image.device:
+            raise TypeError("out must be a contiguous uint8 tensor of the image's shape")
+    if workspace is None:
+        workspace = torch.empty(lib().unet_augment_light_workspace_bytes(N), dtype=torch.uint8,
+                                device=image.device)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or \
+            workspace.device != image.device:
+        raise TypeError("workspace must be a contiguous uint8 tensor on the image's device")
+    return out, workspace
+
+
+def augment_light_u8(image, light, rng=None, out=None, workspace=None):
+    """uint8 [N,H,W,3]: `image` behind the third augmentation stage of `unet_augment_light_u8`
+    (ISO noise, then one of shadow / sun flare / fog) on the current stream.  light: fp32
+    [N, 272] and rng: int32 / uint32 [N, 4] (or None: no ISO noise) are DEVICE tensors the kernels
+    read.  out names the tensor to write (it must not overlap image); workspace is a uint8 tensor
+    of at least `unet_augment_light_workspace_bytes(N)` bytes that a caller may keep between calls
+    (None: one is allocated)."""
+    out, workspace = _light_args("augment_light_u8", image, light, rng, out, workspace, True)
+    N, H, W, _ = image.shape
+    check(lib().unet_augment_light_u8(_ptr(image), _ptr(out), _ptr(light),
+                                      rng.data_ptr() if rng is not None else None,
+                                      _ptr(workspace), workspace.numel(), N, H, W, _stream()))
+    return out
+
+
+def augment_light_stats(image, light, workspace):
+    """The statistics half of `augment_light_u8` (the memset of the sums and the statistics
+    kernel) into `workspace`, which `augment_light_apply` reads."""
+    _, workspace = _light_args("augment_light_stats", image, light, None, None, workspace, False)
+    N, H, W, _ = image.shape
+    check(lib().unet_augment_light_stats(_ptr(image), _ptr(light), _ptr(workspace),
+                                         workspace.numel(), N, H, W, _stream()))
+    return workspace
+
+
+def augment_light_apply(image, light, rng, workspace, out=None):
+    """The apply half of `augment_light_u8`, on a workspace `augment_light_stats` filled."""
+    out, workspace = _light_args("augment_light_apply", image, light, rng, out, workspace, True)
+    N, H, W, _ = image.shape
+    check(lib().unet_augment_light_apply(_ptr(image), _ptr(out), _ptr(light),
+                                         rng.data_ptr() if rng is not None else None,
+                                         _ptr(workspace), workspace.numel(), N, H, W, _stream()))
+    return out
+
+
 def preprocess_u8(image_hwc_u8, mask_u8=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """uint8 [N,H,W,3] (+ uint8 [N,H,W]) on the device -> (fp32 NHWC image, int64 target)."""
     N, H, W, C = image_hwc_u8.shape
