@@ -373,6 +373,60 @@ int unet_eval_confusion(const float* logits_nchw, const int64_t* target, const i
 int unet_eval_maps(const float* logits_nchw, const int64_t* target, float* probs,
                    uint8_t* classes, uint8_t* errors, int B, int H, int W, unet_stream_t stream);
 
+/* ---- evaluation pictures (render.hip) -------------------------------------------------------
+ * The tiles of the reference's figure functions as uint8 RGB, on the device; titles, legends and
+ * colour bars are not drawn. */
+
+/* panel ids of unet_render_seg_panels */
+#define UNET_RENDER_IMAGE 0  /* the input image as bytes */
+#define UNET_RENDER_GT 1     /* colorize_mask(mask): 1 red, 2 green, anything else black */
+#define UNET_RENDER_PRED 2   /* colorize_mask(argmax), first maximum wins */
+#define UNET_RENDER_ERROR 3  /* create_error_visualization: (image + category colour) >> 1 */
+#define UNET_RENDER_CONF0 4  /* confidence overlay of class 0 .. 2: (image + jet[idx(p)]) >> 1 */
+#define UNET_RENDER_CONF1 5
+#define UNET_RENDER_CONF2 6
+#define UNET_RENDER_TARGET 7 /* (image + c) >> 1, c = (103,0,12) where mask == target_class, else
+                                (255,245,240): the two ends of matplotlib's Reds */
+#define UNET_RENDER_HEAT 8   /* Grad-CAM overlay: (image + jet[idx(heat)]) >> 1 */
+
+/* out[B][H][P][W][3] (uint8) = the P requested panels of every image side by side - the same
+ * memory as the picture [B * H][P * W][3] of the whole batch.  One launch.
+ *   image   image_is_u8 == 0: fp32 [B][3][H][W] normalised with the ImageNet mean / std; a byte is
+ *           trunc(clip(double(x) * std + mean, 0, 1) * 255), each operation rounded to double
+ *           in that order (Our_UNet/utils/visualize.py:60-62, :277).  image_is_u8 != 0: uint8
+ *           [B][H][W][3], the bytes themselves.
+ *   logits  fp32 [B][3][H][W]; NULL allowed when no panel needs it (pred, error, conf0..2 do).
+ *   mask    int64 [B][H][W], or uint8 with mask_is_u8 != 0; NULL allowed when no panel needs it
+ *           (gt, error, target do).  In the error panel 255 reads as background.
+ *   heat    fp32 [B][H][W]; NULL allowed without the heat panel.
+ *   jet     uint8 [256][3], the colour table of the overlays; idx(v) = min((int)(v * 256), 255)
+ *           of v clipped to [0, 1], NaN reading as 0 (matplotlib's rule).  The confidence p is
+ *           the fp32 softmax of unet_eval_maps.
+ *   panels  the ordered list, 4 bits per panel from bit 0: id + 1; the first zero nibble ends it;
+ *           1 to 9 panels, an id may repeat.
+ * All blends are the truncating half-sum per byte.  UNET_E_INVALID before the launch: a null
+ * image / jet / out, a bad shape (B in 1..65535, H * W <= 2^30), an empty, too long or unknown
+ * panel list, a panel whose operand is NULL. */
+int unet_render_seg_panels(const void* image, int image_is_u8, const float* logits_nchw,
+                           const void* mask, int mask_is_u8, const float* heat, const uint8_t* jet,
+                           int target_class, uint64_t panels, uint8_t* out, int B, int H, int W,
+                           unet_stream_t stream);
+
+/* out[B][H][3][W][3] (uint8) = original | reconstruction | error map: create_comparison_image on
+ * denormalize_image without mean / std (AE_pretrained/reconstruction/utils/visualize.py:16-95).
+ *   original  fp32 [B][3][H][W] in [0, 1] - a byte is trunc(clamp(x, 0, 1) * 255) with an fp32
+ *             multiply - or, with original_is_u8 != 0, uint8 [B][H][W][3].
+ *   recon     fp32 [B][3][H][W], converted the same way.
+ *   error map d = |original byte - reconstruction byte| per channel; m = the maximum of d over the
+ *             whole image, PER IMAGE; e = trunc(d / m * 255), the division and then the product
+ *             each rounded to fp32 (all zero if m = 0);
+ *             gray = (4899 e_R + 9617 e_G + 1868 e_B + 8192) >> 14; colour = jet[gray], RGB.
+ *   maxima    uint32 [B] scratch: cleared on the stream, then holds m.
+ * Two launches (the integer maximum, then the picture). */
+int unet_render_recon_panels(const void* original, int original_is_u8, const float* recon_nchw,
+                             const uint8_t* jet, uint32_t* maxima, uint8_t* out, int B, int H,
+                             int W, unet_stream_t stream);
+
 /* ---- online batch augmentation (augment.hip; semantics defined by this project) -- */
 
 /* Floats per sample record of unet_augment_u8 (24). */

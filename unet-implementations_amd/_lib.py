@@ -96,6 +96,8 @@ SIGNATURES = {
     "unet_argmax_dice_counts": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "unet_eval_confusion": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "unet_eval_maps": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "unet_render_seg_panels": (_i, [_p, _i, _p, _p, _i, _p, _p, _i, _c.c_uint64, _p, _i, _i, _i, _p]),
+    "unet_render_recon_panels": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _p]),
     "unet_augment_params_per_sample": (_i, []),
     "unet_augment_u8": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "unet_augment_warp_params_per_sample": (_i, []),

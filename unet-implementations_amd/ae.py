@@ -121,11 +121,22 @@ def evaluate_reconstruction_quality(model, test_loader, device, output_dir=None,
     """src/evaluate.py:268-377: eval mode, per-image MSE, PSNR and SSIM (calculate_psnr /
     calculate_ssim) summed over the test set and divided by the number of images.  One fused
     forward per batch gives all three; the sums stay on the device and are read once at the end.
-    Returns {"mse", "psnr", "ssim", "num_samples"}.  The reference's comparison images need cv2:
-    `visualize_samples > 0` is not supported, and nothing is written to `output_dir`."""
-    if visualize_samples > 0:
+    Returns {"mse", "psnr", "ssim", "num_samples"}.
+
+    With `visualize_samples > 0` and an `output_dir`, the first `visualize_samples` images each
+    leave `visualizations/comparison_{i}_{name}` there (src/evaluate.py:333-368): original |
+    reconstruction | error map, rendered on the device (`ops.render_recon_panels`, DESIGN.md
+    section 9b) and written as PNG.  `name` is the batch's `filename` entry, or `sample_{i}.png`;
+    `.png` is appended to a name with another extension.  The metrics are those of a
+    `visualize_samples=0` run.  Without an `output_dir`, `visualize_samples > 0` raises."""
+    if visualize_samples > 0 and output_dir is None:
         raise NotImplementedError("reconstruction visualisations are not part of the HIP path "
                                   "(use visualize_samples=0)")
+    vis_dir, written = None, 0
+    if visualize_samples > 0:
+        from .render import write_png
+        vis_dir = os.path.join(str(output_dir), "visualizations")
+        os.makedirs(vis_dir, exist_ok=True)
     model.eval()
     sums = torch.zeros(3, device=device, dtype=torch.float64)
     num_samples = 0
@@ -133,6 +144,18 @@ def evaluate_reconstruction_quality(model, test_loader, device, output_dir=None,
         images = batch["image"].to(device, non_blocking=True)
         targets = batch["target"].to(device, non_blocking=True)
         recon = model(images).contiguous().float()
+        if written < visualize_samples:
+            k = min(images.shape[0], visualize_samples - written)
+            names = batch.get("filename") if hasattr(batch, "get") else None
+            panels = ops.render_recon_panels(images[:k], recon[:k])
+            for j in range(k):
+                name = str(names[j]) if names is not None else f"sample_{written}.png"
+                if not name.lower().endswith(".png"):
+                    name += ".png"
+                H, P, W, _ = panels[j].shape
+                write_png(os.path.join(vis_dir, f"comparison_{written}_{name}"),
+                          panels[j].view(H, P * W, 3))
+                written += 1
         u8 = targets.dtype == torch.uint8
         if not u8 and targets.dtype != torch.float32:
             targets = targets.float()

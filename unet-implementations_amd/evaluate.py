@@ -12,8 +12,11 @@ a batch in one launch and the loop has no host sync until the results are read.
 tensors (`unet_eval_maps`).  `gradcam` / `gradcam_batch` / `generate_gradcam_heatmap` are the
 tensors behind `visualize_gradcam` (utils/visualize.py:372-516): a gradient-only backward that
 stops at the target stage and three small kernels (`unet_gradcam_*`), for a whole batch.
-Plotting itself (matplotlib) is not part of this package.
+The pictures themselves - the tiles of those figures as uint8 RGB - are `ua.render`
+(`unet_render_seg_panels`); matplotlib is not part of this package.
 """
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -36,17 +39,40 @@ def load_model(model_path, device):
     return model
 
 
-def evaluate_model(model, test_loader, device, visualize_samples=0):
+def evaluate_model(model, test_loader, device, visualize_samples=0, output_dir=None):
     """The dictionary of src/evaluate.py:239-268 (pixel accuracy, mean IoU, per-class dice / iou /
     precision / recall, `mean_foreground_dice`), every image counted at its original size, plus
     `"confusion_matrix"`: int64 [3, 3] numpy, target class x predicted class, what the reference's
-    plot_confusion_matrix counts from the resized maps it keeps.  The reference's plots need
-    matplotlib: `visualize_samples > 0` is not supported (see confidence_maps / error_maps)."""
-    if visualize_samples > 0:
+    plot_confusion_matrix counts from the resized maps it keeps.
+
+    With `visualize_samples > 0` and an `output_dir`, the first `visualize_samples` batches each
+    leave `predictions_batch{i}.png`, `confidence_batch{i}.png` and `errors_batch{i}.png` there:
+    the tiles of the three figures the reference shows per sample batch (src/evaluate.py:214-223),
+    one row per image, rendered on the device from the logits of the metrics pass (`ua.render`,
+    DESIGN.md section 9b) - the returned numbers are those of a `visualize_samples=0` run.
+    Nothing is shown on a screen, so without an `output_dir` there is nowhere to put a picture and
+    `visualize_samples > 0` raises."""
+    if visualize_samples > 0 and output_dir is None:
         raise NotImplementedError("plots are not part of the HIP path (use visualize_samples=0; "
                                   "confidence_maps / error_maps / gradcam return the plotted "
                                   "tensors)")
-    metrics = accumulate_test_metrics(model, test_loader, device)
+    on_batch = None
+    if visualize_samples > 0:
+        from . import render
+        os.makedirs(str(output_dir), exist_ok=True)
+
+        def on_batch(i, images, masks, logits):
+            if i >= visualize_samples:
+                return
+            if masks.dtype not in (torch.int64, torch.uint8):
+                masks = masks.long()
+            logits = logits.detach().float()
+            for stem, panels in (("predictions", render.PREDICTION_PANELS),
+                                 ("confidence", render.CONFIDENCE_PANELS),
+                                 ("errors", render.ERROR_PANELS)):
+                render.write_png(os.path.join(str(output_dir), f"{stem}_batch{i}.png"),
+                                 render.figure(images, logits, masks, panels))
+    metrics = accumulate_test_metrics(model, test_loader, device, on_batch=on_batch)
     results = {"pixel_accuracy": metrics.compute_pixel_accuracy(),
                "mean_iou": metrics.compute_mean_iou()}
     for cls, name in enumerate(("background", "cat", "dog")):

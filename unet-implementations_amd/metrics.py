@@ -221,16 +221,21 @@ def compute_pixel_accuracy(pred, target, ignore_index=255):
 
 
 @torch.no_grad()
-def accumulate_test_metrics(model, data_loader, device, ignore_index=255):
+def accumulate_test_metrics(model, data_loader, device, ignore_index=255, on_batch=None):
     """The loop of evaluate_model / evaluate_model_metrics: eval-mode forward, then one launch per
     batch for argmax, both nearest resizes to `original_dims` and all counting.  Nothing is read
-    on the host until the returned SegmentationMetrics is asked for a value."""
+    on the host until the returned SegmentationMetrics is asked for a value.
+    on_batch(i, images, masks, logits), if given, sees every batch's device tensors after they
+    were counted (evaluate_model renders its pictures from them: no second forward)."""
     model.eval()
     metrics = SegmentationMetrics(num_classes=3, ignore_index=ignore_index)
-    for batch in data_loader:
+    for i, batch in enumerate(data_loader):
         images = batch["image"].to(device, non_blocking=True)
         masks = batch["mask"].to(device, non_blocking=True)
-        metrics.update_from_logits(model(images), masks, batch["original_dims"])
+        logits = model(images)
+        metrics.update_from_logits(logits, masks, batch["original_dims"])
+        if on_batch is not None:
+            on_batch(i, images, masks, logits)
     return metrics
 
 

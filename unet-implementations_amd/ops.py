@@ -1284,6 +1284,120 @@ def eval_maps(logits, target=None, want_probs=True, want_classes=True, want_erro
     return probs, classes, errors
 
 
+# ---- evaluation pictures (render.hip) --------------------------------------------------------
+RENDER_PANELS = ("image", "gt", "pred", "error", "conf0", "conf1", "conf2", "target", "heat")
+_RENDER_NEEDS_MASK = ("gt", "error", "target")
+_RENDER_NEEDS_LOGITS = ("pred", "error", "conf0", "conf1", "conf2")
+_jet_tables = {}
+
+
+def _jet_table(device):
+    """The jet colour table uint8 [256, 3] on `device` (uploaded once per device)."""
+    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    table = _jet_tables.get(key)
+    if table is None:
+        from .render import jet_lut
+        table = _jet_tables[key] = torch.from_numpy(jet_lut()).to(device)
+    return table
+
+
+def _render_image(name, what, image):
+    """(contiguous image, is_u8, B, H, W): fp32 [B,3,H,W] or uint8 [B,H,W,3] on the device."""
+    if not torch.is_tensor(image) or image.dim() != 4 or not (
+            (image.dtype == torch.uint8 and image.shape[3] == 3) or
+            (image.dtype == torch.float32 and image.shape[1] == 3)):
+        raise TypeError(f"{name}: {what} must be fp32 [B,3,H,W] or uint8 [B,H,W,3]")
+    if not image.is_cuda:
+        raise RuntimeError(f"unet-implementations_amd.{name} runs on MI355X only "
+                           "(no CPU fallback exists)")
+    if image.dtype == torch.uint8:
+        B, H, W, _ = image.shape
+        return image.contiguous(), 1, B, H, W
+    B, _, H, W = image.shape
+    return image.contiguous(), 0, B, H, W
+
+
+def _render_out(name, out, shape, like):
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=like.device)
+    if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != shape or \
+            not out.is_contiguous() or out.device != like.device:
+        raise TypeError(f"{name}: out must be a contiguous uint8 {list(shape)} tensor on the "
+                        "image's device")
+    return out
+
+
+def render_seg_panels(image, logits, mask=None, heat=None, panels=("image", "gt", "pred"),
+                      target_class=1, out=None):
+    """uint8 [B, H, P, W, 3] on the device: the requested panels of every image side by side, one
+    launch of `unet_render_seg_panels` (`.view(B * H, P * W, 3)` is the picture of the batch).
+    image: fp32 [B,3,H,W] normalised with the ImageNet mean / std, or the uint8 [B,H,W,3] bytes
+    (taken from the dtype).  logits: fp32 [B,3,H,W], or None when no panel needs them.  mask:
+    int64 or uint8 [B,H,W]; heat: fp32 [B,H,W].  panels: 1 to 9 names of RENDER_PANELS, in order."""
+    name = "render_seg_panels"
+    panels = tuple(panels)
+    if not 1 <= len(panels) <= 9:
+        raise ValueError(f"{name}: 1 to 9 panels")
+    for p in panels:
+        if p not in RENDER_PANELS:
+            raise ValueError(f"{name}: unknown panel {p!r} (one of {', '.join(RENDER_PANELS)})")
+    if mask is None and any(p in _RENDER_NEEDS_MASK for p in panels):
+        raise TypeError(f"{name}: the panels gt, error and target need the mask")
+    if logits is None and any(p in _RENDER_NEEDS_LOGITS for p in panels):
+        raise TypeError(f"{name}: the panels pred, error and conf0..2 need the logits")
+    if heat is None and "heat" in panels:
+        raise TypeError(f"{name}: the heat panel needs the heat map")
+    image, image_u8, B, H, W = _render_image(name, "image", image)
+    if logits is not None:
+        logits, _ = _eval_operands(name, logits, None)
+        if tuple(logits.shape) != (B, 3, H, W) or logits.device != image.device:
+            raise ValueError(f"{name}: logits must be [B, 3, H, W] of the image's size and device")
+    mask_u8 = 0
+    if mask is not None:
+        if not torch.is_tensor(mask) or mask.dtype not in (torch.int64, torch.uint8):
+            raise TypeError(f"{name} takes int64 or uint8 masks")
+        if tuple(mask.shape) != (B, H, W) or mask.device != image.device:
+            raise ValueError(f"{name}: mask must be [B, H, W] of the image's size and device")
+        mask, mask_u8 = mask.contiguous(), int(mask.dtype == torch.uint8)
+    if heat is not None:
+        if not torch.is_tensor(heat) or heat.dtype != torch.float32:
+            raise TypeError(f"{name} takes an fp32 heat map")
+        if tuple(heat.shape) != (B, H, W) or heat.device != image.device:
+            raise ValueError(f"{name}: heat must be [B, H, W] of the image's size and device")
+        heat = heat.contiguous()
+    out = _render_out(name, out, (B, H, len(panels), W, 3), image)
+    word = 0
+    for k, p in enumerate(panels):
+        word |= (RENDER_PANELS.index(p) + 1) << (4 * k)
+    check(lib().unet_render_seg_panels(_ptr(image), image_u8, _ptr(logits), _ptr(mask), mask_u8,
+                                       _ptr(heat), _ptr(_jet_table(image.device)),
+                                       int(target_class), word, _ptr(out), B, H, W, _stream()))
+    return out
+
+
+def render_recon_panels(original, recon, out=None):
+    """uint8 [B, H, 3, W, 3] on the device: original | reconstruction | error map per image
+    (create_comparison_image of the autoencoder's visualize.py), `unet_render_recon_panels`.
+    original: fp32 [B,3,H,W] in [0, 1] or the uint8 [B,H,W,3] bytes; recon: fp32 [B,3,H,W].  The
+    error map is scaled by each image's own maximum difference."""
+    name = "render_recon_panels"
+    original, original_u8, B, H, W = _render_image(name, "original", original)
+    if not torch.is_tensor(recon) or not recon.is_cuda:
+        raise RuntimeError(f"unet-implementations_amd.{name} runs on MI355X only "
+                           "(no CPU fallback exists)")
+    if recon.dtype != torch.float32:
+        raise TypeError(f"{name} takes an fp32 reconstruction")
+    if tuple(recon.shape) != (B, 3, H, W) or recon.device != original.device:
+        raise ValueError(f"{name}: recon must be [B, 3, H, W] of the original's size and device")
+    recon = recon.contiguous()
+    out = _render_out(name, out, (B, H, 3, W, 3), original)
+    maxima = torch.empty(B, dtype=torch.int32, device=original.device)
+    check(lib().unet_render_recon_panels(_ptr(original), original_u8, _ptr(recon),
+                                         _ptr(_jet_table(original.device)), maxima.data_ptr(),
+                                         _ptr(out), B, H, W, _stream()))
+    return out
+
+
 # ---- Grad-CAM (gradcam.hip) ------------------------------------------------------------------
 def gradcam_workspace(N, HW, C, like):
     """The workspace the three Grad-CAM calls of one heatmap share."""
