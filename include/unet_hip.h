@@ -1376,6 +1376,57 @@ int unet_vit_head(const float* x, const float* gamma, const float* beta, float e
                   const float* proj, float* out, int N, int T, int D, int E, int grid,
                   unet_stream_t stream);
 
+/* ---- from decoded samples to a network-size batch (letterbox.hip) ---------------------
+ * What the reference does with OpenCV on the host before a sample reaches the network: the
+ * aspect-preserving resize into a centred square (data_augmentation/src/preprocess_dataset.py:
+ * 307-355, preprocess_training_labels.py:109-167, CLIP_UNet/scripts/create_clip_resized_images.py:
+ * 104-152), the dataset's plain stretch (src/train.py __getitem__), the re-encoding of the trimap
+ * bytes (preprocess_test_val_labels.py:201-331) and the class-pixel scan of src/train.py main.
+ *
+ * A ragged batch is ONE device byte arena holding B samples of different sizes (images HWC uint8,
+ * masks HW uint8, at any byte offset) and a device table of one record per sample, never read on the
+ * host: table[b][UNET_LETTERBOX_FIELDS] (int64)
+ *     0 image byte offset    1 mask byte offset (< 0: the sample has no mask)
+ *     2 h    3 w             source size
+ *     4 out_h    5 out_w     size the sample is resized to
+ *     6 pad_y    7 pad_x     where the resized sample sits in its S_h x S_w tile
+ * arena_bytes bounds every read: a record whose image (mask) does not lie inside the arena is
+ * treated as a record with bad sizes. */
+#define UNET_LETTERBOX_FIELDS 8
+
+/* image_out[B][S_h][S_w][3] and (mask_out != NULL) mask_out[B][S_h][S_w], uint8: every sample
+ * resized to out_h x out_w - the image with OpenCV's INTER_LINEAR, the mask with INTER_NEAREST -
+ * and written at (pad_y, pad_x) of its tile; every other byte of the tile is 0 (no memset: the
+ * kernel writes whole rows).  One launch, grid (row bands, B).  A stretch is out = S, pad = 0.
+ * lut (nullable) [B][256] uint8 is applied to the mask bytes read (not to the padding).
+ * Per axis (src -> dst), all in the precision named:
+ *   scale = 1.0 / ((double)dst / (double)src)
+ *   linear   f = (float)((d + 0.5) * scale - 0.5) (double, two roundings), s = floor(f), f -= s;
+ *            s < 0: s = 0, f = 0;  s >= src - 1: s = src - 1, f = 0;
+ *            taps s and min(s + 1, src - 1), weights (rint((1.f - f) * 2048.f), rint(f * 2048.f));
+ *            R = S[s] a0 + S[s1] a1 along x for the two rows, then
+ *            out = (((b0 (R0 >> 4)) >> 16) + ((b1 (R1 >> 4)) >> 16) + 2) >> 2
+ *   area     h == 2 out_h and w == 2 out_w: out = (a + b + c + d + 2) >> 2 over the 2 x 2 block
+ *            instead (OpenCV's INTER_LINEAR takes its fast area path there)
+ *   nearest  s = min((int)floor(d * scale), src - 1), the product in double.
+ * A record with h or w outside 1..16384, out outside 1..S, a negative pad or pad + out > S gives
+ * that sample an all-zero tile (image and mask); a sample without a mask gets a zero mask tile.
+ * UNET_E_INVALID before the launch: null arena / table / image_out, a lut without mask_out,
+ * B outside 1..65535, S_h or S_w outside 1..4096. */
+int unet_letterbox_u8(const uint8_t* arena, size_t arena_bytes, const int64_t* table, int B,
+                      int S_h, int S_w, uint8_t* image_out, uint8_t* mask_out, const uint8_t* lut,
+                      unet_stream_t stream);
+
+/* hist[B][256] (uint64, device; zeroed here) = how often every byte value occurs in each sample's
+ * mask at its original size: the set of values present (what the label table of the trimap
+ * re-encoding needs) and the class pixel counts (the static class weights).  Fields 4..7 of the
+ * records are not read; a contiguous [B][H][W] batch is the table with equal sizes.  A record
+ * with h or w outside 1..16384, no mask, or a mask outside the arena gives zero counts.  Integer
+ * adds only: the result does not depend on the order of the workgroups.
+ * UNET_E_INVALID before the launch: null arena / table / hist, B outside 1..65535. */
+int unet_byte_histogram_u8(const uint8_t* arena, size_t arena_bytes, const int64_t* table, int B,
+                           uint64_t* hist, unet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

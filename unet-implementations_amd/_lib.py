@@ -98,6 +98,8 @@ SIGNATURES = {
     "unet_eval_maps": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "unet_render_seg_panels": (_i, [_p, _i, _p, _p, _i, _p, _p, _i, _c.c_uint64, _p, _i, _i, _i, _p]),
     "unet_render_recon_panels": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "unet_letterbox_u8": (_i, [_p, _sz, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "unet_byte_histogram_u8": (_i, [_p, _sz, _p, _i, _p, _p]),
     "unet_augment_params_per_sample": (_i, []),
     "unet_augment_u8": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "unet_augment_warp_params_per_sample": (_i, []),

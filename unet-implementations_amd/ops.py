@@ -1284,6 +1284,76 @@ def eval_maps(logits, target=None, want_probs=True, want_classes=True, want_erro
     return probs, classes, errors
 
 
+# ---- ragged uint8 batches to network size (letterbox.hip) ------------------------------------
+LETTERBOX_FIELDS = 8    # UNET_LETTERBOX_FIELDS: image offset, mask offset, h, w, out_h, out_w,
+#                         pad_y, pad_x
+
+
+def _ragged_operands(name, arena, table):
+    if not torch.is_tensor(arena) or not arena.is_cuda:
+        raise RuntimeError(f"unet-implementations_amd.{name} runs on MI355X only "
+                           "(no CPU fallback exists)")
+    if arena.dtype != torch.uint8 or arena.dim() != 1:
+        raise TypeError(f"{name}: the arena is a flat uint8 tensor")
+    if not torch.is_tensor(table) or table.dtype != torch.int64 or table.dim() != 2 or \
+            table.shape[1] != LETTERBOX_FIELDS or table.shape[0] < 1:
+        raise TypeError(f"{name}: the table is int64 [B, {LETTERBOX_FIELDS}]")
+    if table.device != arena.device:
+        raise ValueError(f"{name}: the table lives on the arena's device (it is never read on "
+                         "the host)")
+    return arena.contiguous(), table.contiguous()
+
+
+def letterbox_u8(arena, table, size, want_mask=True, lut=None, out=None):
+    """(images uint8 [B, S_h, S_w, 3], masks uint8 [B, S_h, S_w] or None): every sample of a
+    ragged batch resized and placed in its tile in one launch (`unet_letterbox_u8`; cv2.resize's
+    fixed-point INTER_LINEAR for the image, INTER_NEAREST for the mask, zero padding).
+    arena: flat uint8 device tensor holding the samples; table: int64 [B, 8] device tensor of
+    (image offset, mask offset or -1, h, w, out_h, out_w, pad_y, pad_x) - `dataprep` builds both.
+    size: S or (S_h, S_w).  lut: uint8 [B, 256], applied to the mask bytes.  out: (images, masks)
+    to write into."""
+    arena, table = _ragged_operands("letterbox_u8", arena, table)
+    S_h, S_w = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    B = table.shape[0]
+    if lut is not None:
+        if not want_mask:
+            raise ValueError("letterbox_u8: a lut needs the mask output")
+        if lut.dtype != torch.uint8 or tuple(lut.shape) != (B, 256) or lut.device != arena.device:
+            raise TypeError("letterbox_u8: lut is uint8 [B, 256] on the arena's device")
+        lut = lut.contiguous()
+    images, masks = out if out is not None else (None, None)
+    if images is None:
+        images = torch.empty((B, max(S_h, 0), max(S_w, 0), 3), dtype=torch.uint8,
+                             device=arena.device)
+    if want_mask and masks is None:
+        masks = torch.empty((B, max(S_h, 0), max(S_w, 0)), dtype=torch.uint8, device=arena.device)
+    if tuple(images.shape) != (B, S_h, S_w, 3) or images.dtype != torch.uint8 or \
+            (want_mask and (tuple(masks.shape) != (B, S_h, S_w) or masks.dtype != torch.uint8)):
+        raise ValueError("letterbox_u8: out must be uint8 [B, S_h, S_w, 3] and [B, S_h, S_w]")
+    check(lib().unet_letterbox_u8(_ptr(arena), arena.numel(), _ptr(table), B, S_h, S_w,
+                                  _ptr(images), _ptr(masks) if want_mask else None, _ptr(lut),
+                                  _stream()))
+    return images, (masks if want_mask else None)
+
+
+def byte_histogram_u8(arena, table=None):
+    """int64 [B, 256]: how often every byte value occurs in each sample's mask at its original
+    size (`unet_byte_histogram_u8`, one launch).  arena / table as for `letterbox_u8`; with
+    table=None, `arena` is a contiguous uint8 [B, H, W] mask batch."""
+    if table is None:
+        if not torch.is_tensor(arena) or arena.dim() != 3 or arena.dtype != torch.uint8:
+            raise TypeError("byte_histogram_u8: without a table, a uint8 [B, H, W] mask batch")
+        B, H, W = arena.shape
+        rows = [[-1, b * H * W, H, W, 0, 0, 0, 0] for b in range(B)]
+        table = torch.tensor(rows, dtype=torch.int64).to(arena.device, non_blocking=True)
+        arena = arena.contiguous().view(-1)
+    arena, table = _ragged_operands("byte_histogram_u8", arena, table)
+    hist = torch.empty((table.shape[0], 256), dtype=torch.int64, device=arena.device)
+    check(lib().unet_byte_histogram_u8(_ptr(arena), arena.numel(), _ptr(table), table.shape[0],
+                                       hist.data_ptr(), _stream()))
+    return hist
+
+
 # ---- evaluation pictures (render.hip) --------------------------------------------------------
 RENDER_PANELS = ("image", "gt", "pred", "error", "conf0", "conf1", "conf2", "target", "heat")
 _RENDER_NEEDS_MASK = ("gt", "error", "target")
