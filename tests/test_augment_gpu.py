@@ -420,3 +420,21 @@ def test_train_one_epoch_with_augment(ua):
                            ua.SimpleLoss(target_layout="u8"), DEV, augment=both,
                            input_layout="nhwc_u8")
     assert math.isfinite(v) and v not in (res[0], res[1])
+
+
+def test_bench_tool_feeds_a_batch_through_the_staged_record():
+    """part 3 of tools/bench_augment.py (copies, plus drawing and staging the records, plus the
+    kernel) runs in a child process: the one caller of `BatchAugment._stage` outside the package"""
+    import json
+    import subprocess
+    import sys
+    proc = subprocess.run(
+        [sys.executable, os.path.join(ROOT, "tools", "bench_augment.py"), "--parts", "feed",
+         "--batch", "2", "--hw", "64", "--warmup", "1", "--rounds", "1", "--steps", "2"],
+        capture_output=True, text=True, timeout=300)
+    assert proc.returncode == 0, proc.stdout + proc.stderr
+    res = json.loads(proc.stdout.strip().splitlines()[-1])
+    assert "kernel" not in res and not res["step_ms"]
+    assert sorted(res["feed_us"]) == ["copy", "copy+records", "copy+records+kernel"]
+    for form, v in res["feed_us"].items():
+        assert math.isfinite(v["median_us"]) and v["median_us"] > 0, form

@@ -347,7 +347,7 @@ def test_batch_augment_without_distortion_is_unchanged(ua):
         want = ua.ops.augment_u8(x, m, p.to(DEV), dev_rng(ua, r))
         got = aug(x, m)
         assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
-    assert not aug._field and "hw" not in aug._ring[0]
+    assert not aug._scratch and "warp" not in aug._ring["slots"][0]["host"]
 
 
 def test_distortion_through_out_and_train_one_epoch(ua):

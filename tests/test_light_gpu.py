@@ -387,7 +387,7 @@ def test_batch_augment_without_a_lighting_configuration_is_unchanged(ua):
         want = ua.ops.augment_u8(x, m, p.to(DEV), dev_rng(ua, r))
         got = aug(x, m)
         assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
-    assert not aug._light and not aug._post and not aug._field and "hl" not in aug._ring[0]
+    assert not aug._scratch and "light" not in aug._ring["slots"][0]["host"]
     # with the post stage and without lighting: the bytes of gather + post from the same seed
     cfg = _e2e_config(ua, False, photometric=True)
     aug = ua.BatchAugment(cfg, seed=4)
@@ -400,7 +400,8 @@ def test_batch_augment_without_a_lighting_configuration_is_unchanged(ua):
     want = ua.ops.augment_post_u8(mid, q.to(DEV), dev_rng(ua, r))
     got = aug(x, m)
     assert torch.equal(got[0], want) and torch.equal(got[1], mw)
-    assert not aug._light and "hl" not in aug._ring[0]
+    assert not any(key[0] == "light" for key in aug._scratch)
+    assert "light" not in aug._ring["slots"][0]["host"]
 
 
 def test_lighting_through_out_and_train_one_epoch(ua):
@@ -431,3 +432,67 @@ def test_lighting_through_out_and_train_one_epoch(ua):
                                       ua.SimpleLoss(target_layout="u8"), DEV, augment=augment,
                                       input_layout="nhwc_u8"))
     assert all(np.isfinite(v) for v in res) and res[0] != res[1]
+
+
+# ----------------------------------------------------- the chain of stages, record by record
+@pytest.fixture(scope="module")
+def chain_records(ua):
+    """(params, rng, warp, post, light) of one draw with every stage on; never modified"""
+    N, H, W = E2E
+    cfg = ua.augment.AugmentConfig(**{
+        **vars(_e2e_config(ua, True, photometric=True)), "distort_group_prob": 1.0,
+        "elastic_prob": 0.5, "elastic_alpha": 3.0, "elastic_sigma": 2.0,
+        "elastic_alpha_affine": 2.0, "grid_distortion_prob": 0.5, "grid_num_steps": 5,
+        "grid_distort_limit": 0.3})
+    for seed in range(20):          # a draw with one elastic and one grid sample
+        gen = torch.Generator().manual_seed(seed)
+        p, r, groups = ua.augment.sample_params(cfg, N, H, W, gen, return_groups=True)
+        w = ua.augment.sample_warp(cfg, N, H, W, gen)
+        if sorted(w[:, 0].tolist()) == [ua.augment.WARP_ELASTIC, ua.augment.WARP_GRID]:
+            break
+    p, r, q = ua.augment.sample_post(cfg, N, H, W, gen, p, r, groups)
+    lt = ua.augment.sample_light(cfg, N, H, W, gen)
+    assert sorted(w[:, 0].tolist()) == [ua.augment.WARP_ELASTIC, ua.augment.WARP_GRID]
+    assert (q[:, ua.augment.Q_BLUR] > 0).all() and (lt[:, 3] > 0).all() and (r[:, 2:] > 0).any()
+    return p, r, w, q, lt
+
+
+@pytest.mark.parametrize("light", [False, True], ids=["", "light"])
+@pytest.mark.parametrize("post", [False, True], ids=["", "post"])
+@pytest.mark.parametrize("warp", [False, True], ids=["gather", "warp"])
+def test_batch_augment_is_the_explicit_chain_of_stages(ua, chain_records, warp, post, light):
+    """every on / off combination of the three optional records through params=: the bytes of
+    the chain of `ops.*` calls written out here, with and without `out=`; the last stage writes
+    the caller's tensor, and no scratch of a stage that is off is allocated"""
+    N, H, W = E2E
+    x, m = _e2e_batch()
+    p, r, w, q, lt = chain_records
+    w, q, lt = w if warp else None, q if post else None, lt if light else None
+    # the chain: gather or warp gather (salt / pepper off in front of a post stage), post, light
+    dp, dr = p.to(DEV), dev_rng(ua, r)
+    r0 = r.clone()
+    r0[:, 2:] = 0
+    gather_rng = dev_rng(ua, r0) if post else dr
+    if warp:
+        field = ua.ops.elastic_field(w.to(DEV), dr, (H, W))
+        want, want_mask = ua.ops.augment_warp_u8(x, m, dp, gather_rng, w.to(DEV), field)
+    else:
+        want, want_mask = ua.ops.augment_u8(x, m, dp, gather_rng)
+    if post:
+        want = ua.ops.augment_post_u8(want, q.to(DEV), dr)
+    if light:
+        want = ua.ops.augment_light_u8(want, lt.to(DEV), dr)
+
+    aug = ua.BatchAugment(ua.augment.AugmentConfig(), seed=0)
+    got, got_mask = aug(x, m, params=(p, r, w, q, lt))
+    assert torch.equal(got, want) and torch.equal(got_mask, want_mask)
+    out = (torch.full_like(x, 7), torch.full_like(m, 7))
+    got, got_mask = aug(x, m, params=(p, r, w, q, lt), out=out)
+    assert got.data_ptr() == out[0].data_ptr() and got_mask.data_ptr() == out[1].data_ptr()
+    assert torch.equal(out[0], want) and torch.equal(out[1], want_mask)
+    ran = {k for k, on in (("field", warp), ("post", post), ("light", light)) if on}
+    assert {key[0] for key in aug._scratch} == ran
+    assert len(aug._scratch) == len(ran)
+    staged = {k for k, on in (("warp", warp), ("post", post), ("gather_rng", post),
+                              ("light", light)) if on}
+    assert set(aug._ring["slots"][0]["host"]) == {"params", "rng"} | staged

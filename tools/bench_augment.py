@@ -16,9 +16,11 @@
      alternated in one process, eager and as `GraphedTrainStep` replays (the augmented replay
      writes through `out=(step.images, step.masks)`); a timed step ends in a device synchronise.
 
-Prints a table and one JSON line; `--out FILE` also writes the JSON there.
+Prints a table and one JSON line; `--out FILE` also writes the JSON there.  `--parts` selects
+what runs: `kernel` (1 and 2), `feed` (3), `steps` (4).
 
     python tools/bench_augment.py [--batch 8] [--hw 512] [--calls 100] [--steps 20] [--rounds 5]
+                                  [--parts kernel,feed,steps]
 """
 import argparse
 import json
@@ -129,9 +131,9 @@ def bench_feed(batches, dev, args):
         if form == "copy":
             return
         p, r = ua.augment.sample_params(aug.cfg, n, hw, hw, aug.generator)
-        dp, dr, _ = aug._stage(p, r, dev)
+        staged = aug._stage(p, r, dev)
         if form == "copy+records+kernel":
-            ua.ops.augment_u8(x, m, dp, dr, out=out)
+            ua.ops.augment_u8(x, m, staged.params, staged.rng, out=out)
 
     forms = ("copy", "copy+records", "copy+records+kernel")
     ms = {f: [] for f in forms}
@@ -216,8 +218,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--modes", default="fp32,bf16")
+    ap.add_argument("--parts", default="kernel,feed,steps",
+                    help="which parts run: kernel (1 and 2), feed (3), steps (4)")
     ap.add_argument("--out", default=None, help="also write the JSON result to this file")
     args = ap.parse_args()
+    parts = args.parts.split(",")
+    if not parts or set(parts) - {"kernel", "feed", "steps"}:
+        raise SystemExit("bench_augment: --parts takes kernel, feed, steps")
     if not torch.cuda.is_available():
         raise SystemExit("bench_augment: no ROCm device (there is nothing to measure on a CPU)")
     dev = torch.device("cuda", 0)
@@ -227,20 +234,24 @@ def main():
            "calls": args.calls, "steps": args.steps, "rounds": args.rounds, "warmup": args.warmup}
     print(f"# {res['device']}  batch {n} x {hw}^2")
     x, m = (t.to(dev) for t in batches[0])
-    res["kernel"] = bench_kernel(x, m, dev, args)
-    print(f"{'call':20s} {'median us':>10s} {'min':>8s} {'max':>8s}   "
-          f"({res['kernel']['bytes_moved'] / 1e6:.1f} MB moved)")
-    for k, v in res["kernel"].items():
-        if isinstance(v, dict):
+    if "kernel" in parts:
+        res["kernel"] = bench_kernel(x, m, dev, args)
+        print(f"{'call':20s} {'median us':>10s} {'min':>8s} {'max':>8s}   "
+              f"({res['kernel']['bytes_moved'] / 1e6:.1f} MB moved)")
+        for k, v in res["kernel"].items():
+            if isinstance(v, dict):
+                print(f"{k:20s} {v['median_us']:10.1f} {v['min_us']:8.1f} {v['max_us']:8.1f}",
+                      flush=True)
+    if "feed" in parts:
+        res["feed_us"] = bench_feed(batches, dev, args)
+        print(f"{'feeding one batch':20s} {'median us':>10s} {'min':>8s} {'max':>8s}")
+        for k, v in res["feed_us"].items():
             print(f"{k:20s} {v['median_us']:10.1f} {v['min_us']:8.1f} {v['max_us']:8.1f}",
                   flush=True)
-    res["feed_us"] = bench_feed(batches, dev, args)
-    print(f"{'feeding one batch':20s} {'median us':>10s} {'min':>8s} {'max':>8s}")
-    for k, v in res["feed_us"].items():
-        print(f"{k:20s} {v['median_us']:10.1f} {v['min_us']:8.1f} {v['max_us']:8.1f}", flush=True)
     res["step_ms"] = {}
-    print(f"{'mode':6s} {'step':6s} {'input':10s} {'median ms':>10s} {'min':>8s} {'max':>8s}")
-    for mode in args.modes.split(","):
+    if "steps" in parts:
+        print(f"{'mode':6s} {'step':6s} {'input':10s} {'median ms':>10s} {'min':>8s} {'max':>8s}")
+    for mode in args.modes.split(",") if "steps" in parts else ():
         for graphed in (False, True):
             r = bench_steps(mode, graphed, batches, dev, args)
             kind = "graph" if graphed else "eager"

@@ -62,7 +62,9 @@ The semantics of what is supported are defined by this project (include/unet_hip
 12b, 12c, 12d), not recorded from the reference's augmentation library; the package ships no preset
 numbers: every probability of `AugmentConfig` defaults to 0, which is the identity.
 """
+import collections
 import dataclasses
+import itertools
 import math
 from typing import Tuple
 
@@ -333,12 +335,7 @@ def validate_params(params, H, W):
     """Refuse a record the kernel would treat as "everything outside": every value must be
     finite and den = h6 x + h7 y + h8 positive at the four corners of the output (it is linear in
     (x, y), so it is then positive on every pixel)."""
-    p = params.detach().cpu().numpy() if torch.is_tensor(params) else np.asarray(params)
-    if p.ndim != 2 or p.shape[1] != PARAMS_PER_SAMPLE:
-        raise ValueError(f"params must be [n, {PARAMS_PER_SAMPLE}]")
-    if not np.isfinite(p).all():
-        raise ValueError("augmentation record holds a non-finite value")
-    p = p.astype(np.float64)
+    p = _record_array(params, "params", PARAMS_PER_SAMPLE, "augmentation record")
     for x, y in ((0.0, 0.0), (W, 0.0), (0.0, H), (W, H)):
         den = p[:, 6] * x + p[:, 7] * y + p[:, 8]
         if not (den > 0).all():
@@ -377,8 +374,9 @@ def _rect_to_quad(W, H, quad):
     return np.concatenate([h, np.ones((m, 1))], axis=1).reshape(m, 3, 3)
 
 
-def _select(cfg, n, which):
-    """(configurations, index of sample i's configuration [n])"""
+def _fields(cfg, n, which):
+    """`cfg` and `which` of a sampler, resolved once -> (f, cfgs, sel): f(name) is the field `name`
+    per sample (fp64 [n] or [n, k]), cfgs the configurations, sel [n] the index of sample i's."""
     cfgs = [cfg] if isinstance(cfg, AugmentConfig) else list(cfg)
     if which is None:
         if len(cfgs) != 1:
@@ -388,7 +386,35 @@ def _select(cfg, n, which):
         sel = np.asarray(torch.as_tensor(which).cpu().numpy(), dtype=np.int64).reshape(-1)
         if sel.shape[0] != n or (sel < 0).any() or (sel >= len(cfgs)).any():
             raise ValueError("`which` must hold n indices into the configurations")
-    return cfgs, sel
+
+    def f(name):
+        return np.asarray([getattr(c, name) for c in cfgs], dtype=np.float64)[sel]
+    return f, cfgs, sel
+
+
+def _one_of(group, u, probs):
+    """OneOf: where the group's draw `group` fired, one member by its probability (`probs`, an
+    fp64 [n] array per member) normalised over the members, picked by the uniform `u`.  Yields a
+    boolean [n] mask per member, each computed when it is asked for: u * total is held against
+    the running sums, accumulated left to right; the last member takes what is left."""
+    sums = list(itertools.accumulate(probs))
+    left = np.asarray(group, dtype=bool) & (sums[-1] > 0)
+    pick = u * sums[-1]
+    for s in sums[:-1]:
+        mask = left & (pick < s)
+        yield mask
+        left = left & ~mask
+    yield left
+
+
+def _record_array(record, kind, width, what):
+    """The head of every `validate_*`: the record as fp64 [n, width], finite."""
+    a = record.detach().cpu().numpy() if torch.is_tensor(record) else np.asarray(record)
+    if a.ndim != 2 or a.shape[1] != width:
+        raise ValueError(f"{kind} must be [n, {width}]")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{what} holds a non-finite value")
+    return a.astype(np.float64)
 
 
 def sample_params(cfg, n, H, W, generator, which=None, return_applied=False,
@@ -401,11 +427,7 @@ def sample_params(cfg, n, H, W, generator, which=None, return_applied=False,
     arrays (which transform fired for which sample) comes third; with `return_groups` a dict of the
     raw draws of the three photometric groups ("color", "gray", "noise": the group probability
     fired, whatever its members' probabilities) comes last, for `sample_post`."""
-    cfgs, sel = _select(cfg, n, which)
-
-    def f(name):        # the field per sample: [n] or [n, k]
-        return np.asarray([getattr(c, name) for c in cfgs], dtype=np.float64)[sel]
-
+    f, _, _ = _fields(cfg, n, which)
     U = torch.rand(n, 40, dtype=torch.float64, generator=generator).numpy()
     Z = torch.randn(n, 8, dtype=torch.float64, generator=generator).numpy()
     seeds = torch.randint(0, 1 << 32, (n, 2), dtype=torch.int64, generator=generator).numpy()
@@ -484,11 +506,9 @@ def sample_params(cfg, n, H, W, generator, which=None, return_applied=False,
     p[:, P_MASK_HOLE] = f("dropout_mask_fill")
 
     # OneOf(RandomBrightnessContrast, RGBShift)
-    pb, pr = f("brightness_contrast_prob"), f("rgb_shift_prob")
     color_draw = fires(f("color_prob"))
-    group = color_draw & (pb + pr > 0)
-    pick_b = U[:, next(col)] * (pb + pr) < pb
-    bc, rgb = group & pick_b, group & ~pick_b
+    bc, rgb = _one_of(color_draw, U[:, next(col)],
+                      (f("brightness_contrast_prob"), f("rgb_shift_prob")))
     applied["brightness_contrast"], applied["rgb_shift"] = bc, rgb
     alpha = 1.0 + uni(f("contrast_limit"))
     beta = uni(f("brightness_limit")) * 255.0
@@ -576,15 +596,11 @@ def validate_warp(warp, params, H, W):
     alpha >= 0 and an integer radius in 0..16, a grid record with integer K in 1..8 per axis and
     increasing maps (a_k > 0), and den = h6 x + h7 y + h8 of `params` positive at the corners of
     the output rectangle GROWN by the record's largest possible displacement."""
-    w = warp.detach().cpu().numpy() if torch.is_tensor(warp) else np.asarray(warp)
+    w = _record_array(warp, "warp", WARP_PER_SAMPLE, "warp record")
     p = params.detach().cpu().numpy() if torch.is_tensor(params) else np.asarray(params)
-    if w.ndim != 2 or w.shape[1] != WARP_PER_SAMPLE:
-        raise ValueError(f"warp must be [n, {WARP_PER_SAMPLE}]")
     if p.ndim != 2 or p.shape != (w.shape[0], PARAMS_PER_SAMPLE):
         raise ValueError(f"params must be [{w.shape[0]}, {PARAMS_PER_SAMPLE}]")
-    if not np.isfinite(w).all():
-        raise ValueError("warp record holds a non-finite value")
-    w, p = w.astype(np.float64), p.astype(np.float64)
+    p = p.astype(np.float64)
     mode = w[:, 0]
     if not np.isin(mode, (WARP_NONE, WARP_ELASTIC, WARP_GRID, WARP_OPTICAL)).all():
         raise ValueError("warp record has a mode outside 0..3")
@@ -618,11 +634,7 @@ def sample_warp(cfg, n, H, W, generator, which=None, return_applied=False):
     `sample_params` is unaffected by whether this is called.  The records are NOT validated
     against a `params` here (`validate_warp`; `BatchAugment` does it).  With `return_applied` a
     dict of boolean [n] arrays comes second."""
-    cfgs, sel = _select(cfg, n, which)
-
-    def f(name):
-        return np.asarray([getattr(c, name) for c in cfgs], dtype=np.float64)[sel]
-
+    f, cfgs, sel = _fields(cfg, n, which)
     for c in cfgs:
         if c.distort_group_prob > 0 and c.grid_distortion_prob > 0:
             if not 1 <= int(c.grid_num_steps) <= MAX_GRID_STEPS or \
@@ -637,13 +649,9 @@ def sample_warp(cfg, n, H, W, generator, which=None, return_applied=False):
 
     U = torch.rand(n, 32, dtype=torch.float64, generator=generator).numpy()
     S = 2.0 * U - 1.0                                   # U(-1, 1)
-    pe, pg, po = f("elastic_prob"), f("grid_distortion_prob"), f("optical_distortion_prob")
-    tot = pe + pg + po
-    group = (U[:, 0] < f("distort_group_prob")) & (tot > 0)
-    pick = U[:, 1] * tot
-    elastic = group & (pick < pe)
-    grid = group & ~elastic & (pick < pe + pg)
-    optical = group & ~elastic & ~grid
+    elastic, grid, optical = _one_of(
+        U[:, 0] < f("distort_group_prob"), U[:, 1],
+        (f("elastic_prob"), f("grid_distortion_prob"), f("optical_distortion_prob")))
     applied = {"elastic": elastic, "grid_distortion": grid, "optical_distortion": optical}
     w = np.zeros((n, WARP_PER_SAMPLE), dtype=np.float64)
     w[:, 0] = np.where(elastic, WARP_ELASTIC, np.where(grid, WARP_GRID,
@@ -710,12 +718,7 @@ def validate_post(post, H, W):
     integer tile grid in 1..8 per axis that divides (H, W), a blur record with an integer radius
     in 1..4 (separable) or 1..3 (dense) below min(H, W) and taps / weights that are not negative
     and whose full sum is 1 within 1e-6."""
-    q = post.detach().cpu().numpy() if torch.is_tensor(post) else np.asarray(post)
-    if q.ndim != 2 or q.shape[1] != POST_PER_SAMPLE:
-        raise ValueError(f"post must be [n, {POST_PER_SAMPLE}]")
-    if not np.isfinite(q).all():
-        raise ValueError("post record holds a non-finite value")
-    q = q.astype(np.float64)
+    q = _record_array(post, "post", POST_PER_SAMPLE, "post record")
     if not np.isin(q[:, Q_HSV], (0, 1)).all():
         raise ValueError("post record has an HSV flag other than 0 / 1")
     if not np.isin(q[:, Q_HIST], (HIST_NONE, HIST_EQUALIZE, HIST_CLAHE)).all():
@@ -788,11 +791,7 @@ def sample_post(cfg, n, H, W, generator, params, rng, groups, which=None, return
     it.  rng is returned as it came (salt / pepper stays where it is).  The draws come from a
     block of uniforms of their own.  With `return_applied` a dict of boolean [n] arrays comes
     last."""
-    cfgs, sel = _select(cfg, n, which)
-
-    def f(name):
-        return np.asarray([getattr(c, name) for c in cfgs], dtype=np.float64)[sel]
-
+    f, cfgs, sel = _fields(cfg, n, which)
     sizes = []
     for c in cfgs:
         sizes.append((
@@ -807,15 +806,12 @@ def sample_post(cfg, n, H, W, generator, params, rng, groups, which=None, return
                              "U(1, clahe_clip_limit))")
 
     U = torch.rand(n, 16, dtype=torch.float64, generator=generator).numpy()
-    p = params.detach().cpu().numpy().astype(np.float64).copy()
+    p = params.detach().cpu().numpy().astype(np.float64)      # a copy: params is not written
     q = np.zeros((n, POST_PER_SAMPLE), dtype=np.float64)
 
-    def take(group, old, new, u):       # the group fired and the pick falls on a new member
-        tot = old + new
-        return np.asarray(group, dtype=bool) & (tot > 0) & (u * tot < new)
-
-    ph = f("hsv_prob")
-    hsv = take(groups["color"], f("brightness_contrast_prob") + f("rgb_shift_prob"), ph, U[:, 0])
+    # per group: the new members against the old ones, then one of the new members
+    hsv = next(_one_of(groups["color"], U[:, 0],
+                       (f("hsv_prob"), f("brightness_contrast_prob") + f("rgb_shift_prob"))))
     p[hsv, P_ALPHA] = 1.0
     p[hsv, P_BETA:P_BETA + 3] = 0.0
     q[:, Q_HSV] = hsv
@@ -824,9 +820,8 @@ def sample_post(cfg, n, H, W, generator, params, rng, groups, which=None, return
         q[:, k] = np.where(hsv, (2.0 * U[:, k] - 1.0) * f(name), 0.0)
 
     pc, pe = f("clahe_prob"), f("equalize_prob")
-    hist = take(groups["gray"], f("to_gray_prob"), pc + pe, U[:, 4])
-    clahe = hist & (U[:, 5] * (pc + pe) < pc)
-    equalize = hist & ~clahe
+    hist = next(_one_of(groups["gray"], U[:, 4], (pc + pe, f("to_gray_prob"))))
+    clahe, equalize = _one_of(hist, U[:, 5], (pc, pe))
     p[hist, P_GRAY] = 0.0
     q[:, Q_HIST] = np.where(clahe, HIST_CLAHE, np.where(equalize, HIST_EQUALIZE, HIST_NONE))
     q[:, Q_CLIP] = np.where(clahe, 1.0 + (f("clahe_clip_limit") - 1.0) * U[:, 6], 0.0)
@@ -835,9 +830,8 @@ def sample_post(cfg, n, H, W, generator, params, rng, groups, which=None, return
     q[:, Q_TX] = np.where(clahe, grid[:, 1], 0.0)
 
     pg, pm = f("gaussian_blur_prob"), f("motion_blur_prob")
-    blur = take(groups["noise"], f("gauss_noise_prob"), pg + pm, U[:, 7])
-    gaussian = blur & (U[:, 8] * (pg + pm) < pg)
-    motion = blur & ~gaussian
+    blur = next(_one_of(groups["noise"], U[:, 7], (pg + pm, f("gauss_noise_prob"))))
+    gaussian, motion = _one_of(blur, U[:, 8], (pg, pm))
     p[blur, P_SIGMA] = 0.0
     for i in np.nonzero(gaussian)[0]:
         ks = sizes[sel[i]][0]
@@ -874,12 +868,7 @@ def validate_light(light, H, W):
     (shadow), 0..10 (flare) or 0..128 (fog), integer flare steps T in 2..40 and an integer fog box
     k in 1..9 with k - 1 - k // 2 < min(H, W), radii that are not negative (the source's at least
     1), blend weights a in [0, 1] and flare colours in 0..255."""
-    q = light.detach().cpu().numpy() if torch.is_tensor(light) else np.asarray(light)
-    if q.ndim != 2 or q.shape[1] != LIGHT_PER_SAMPLE:
-        raise ValueError(f"light must be [n, {LIGHT_PER_SAMPLE}]")
-    if not np.isfinite(q).all():
-        raise ValueError("light record holds a non-finite value")
-    q = q.astype(np.float64)
+    q = _record_array(light, "light", LIGHT_PER_SAMPLE, "light record")
     if not np.isin(q[:, L_ISO], (0, 1)).all():
         raise ValueError("light record has an ISO flag other than 0 / 1")
     iso = q[:, L_ISO] == 1
@@ -970,11 +959,7 @@ def sample_light(cfg, n, H, W, generator, which=None, return_applied=False):
     A draw that exceeds a cap of the record (128 fog points, a box of 9) raises.  The records are
     validated (`validate_light`).  With `return_applied` a dict of boolean [n] arrays comes
     second."""
-    cfgs, sel = _select(cfg, n, which)
-
-    def f(name):
-        return np.asarray([getattr(c, name) for c in cfgs], dtype=np.float64)[sel]
-
+    f, cfgs, sel = _fields(cfg, n, which)
     for c in cfgs:
         if c.iso_noise_prob > 0:
             if not 0 <= min(c.iso_intensity) <= max(c.iso_intensity) <= 1:
@@ -1000,13 +985,8 @@ def sample_light(cfg, n, H, W, generator, which=None, return_applied=False):
     q[:, L_SIGMA_H] = np.where(iso, shift * 360.0 * intensity, 0.0)
     q[:, L_INTENSITY] = np.where(iso, intensity, 0.0)
 
-    ps, pf, pg = f("shadow_prob"), f("sunflare_prob"), f("fog_prob")
-    tot = ps + pf + pg
-    group = (U[:, 3] < f("lighting_group_prob")) & (tot > 0)
-    pick = U[:, 4] * tot
-    shadow = group & (pick < ps)
-    flare = group & ~shadow & (pick < ps + pf)
-    fog = group & ~shadow & ~flare
+    shadow, flare, fog = _one_of(U[:, 3] < f("lighting_group_prob"), U[:, 4],
+                                 (f("shadow_prob"), f("sunflare_prob"), f("fog_prob")))
     q[:, L_MODE] = np.where(shadow, LIGHT_SHADOW, np.where(flare, LIGHT_FLARE,
                                                            np.where(fog, LIGHT_FOG, LIGHT_NONE)))
 
@@ -1059,6 +1039,25 @@ def sample_light(cfg, n, H, W, generator, which=None, return_applied=False):
     return light
 
 
+# The record kinds a batch travels with, in the order they are copied to the device: the width and
+# dtype of a row, and the record whose presence puts the kind into a ring slot (rng buffers exist
+# with params whether a call names an rng or not; `gather_rng`, rng with zero salt / pepper
+# thresholds, rides with post).
+Record = collections.namedtuple("Record", "width dtype owner")
+RECORDS = {
+    "params": Record(PARAMS_PER_SAMPLE, torch.float32, "params"),
+    "rng": Record(4, torch.int32, "params"),
+    "warp": Record(WARP_PER_SAMPLE, torch.float32, "warp"),
+    "post": Record(POST_PER_SAMPLE, torch.float32, "post"),
+    "gather_rng": Record(4, torch.int32, "post"),
+    "light": Record(LIGHT_PER_SAMPLE, torch.float32, "light"),
+}
+Staged = collections.namedtuple("Staged", "params rng warp post light gather_rng")
+VALIDATE = {"warp": lambda rec, params, H, W: validate_warp(rec, params, H, W),
+            "post": lambda rec, params, H, W: validate_post(rec, H, W),
+            "light": lambda rec, params, H, W: validate_light(rec, H, W)}
+
+
 class BatchAugment:
     """Draws the records of a batch and launches `unet_augment_u8` on the current stream.
 
@@ -1104,108 +1103,58 @@ class BatchAugment:
         self.photometric = any(max(c.hsv_prob, c.clahe_prob, c.equalize_prob,
                                    c.gaussian_blur_prob, c.motion_blur_prob) > 0 for c in cfgs)
         self.lighting = any(max(c.iso_noise_prob, c.lighting_group_prob) > 0 for c in cfgs)
-        self._ring = None
-        self._next = 0
-        self._field = {}
-        self._post = {}
-        self._light = {}
+        self._ring = None       # {"n", "device", "kinds", "next", "slots": two of them}
+        self._scratch = {}      # (kind, N, H, W, device): "field", "post", "light"
 
     def _stage(self, params, rng, device, warp=None, post=None, light=None):
-        """-> (params, rng or None, warp or None, post or None, rng with zero salt / pepper
-        thresholds or None: for the gather in front of the post stage) on the device; with
-        `light` its device copy comes sixth"""
+        """-> Staged: the device copy of every record given (None for one that is not).
+        `gather_rng` is rng with zero salt / pepper thresholds, for the gather in front of the
+        post stage."""
         n = params.shape[0]
-        head = self._ring[0] if self._ring is not None else None
-        if head is None or head["n"] != n or head["device"] != device or \
-                (warp is not None and "hw" not in head) or \
-                (post is not None and "hq" not in head) or \
-                (light is not None and "hl" not in head):
-            self._ring = [{
-                "n": n, "device": device, "event": None,
-                "hp": torch.empty((n, PARAMS_PER_SAMPLE), dtype=torch.float32, pin_memory=True),
-                "hr": torch.empty((n, 4), dtype=torch.int32, pin_memory=True),
-                "dp": torch.empty((n, PARAMS_PER_SAMPLE), dtype=torch.float32, device=device),
-                "dr": torch.empty((n, 4), dtype=torch.int32, device=device),
-            } for _ in range(2)]
-            if warp is not None:
-                for slot in self._ring:
-                    slot["hw"] = torch.empty((n, WARP_PER_SAMPLE), dtype=torch.float32,
-                                             pin_memory=True)
-                    slot["dw"] = torch.empty((n, WARP_PER_SAMPLE), dtype=torch.float32,
-                                             device=device)
-            if post is not None:
-                for slot in self._ring:
-                    slot["hq"] = torch.empty((n, POST_PER_SAMPLE), dtype=torch.float32,
-                                             pin_memory=True)
-                    slot["dq"] = torch.empty((n, POST_PER_SAMPLE), dtype=torch.float32,
-                                             device=device)
-                    slot["hr0"] = torch.empty((n, 4), dtype=torch.int32, pin_memory=True)
-                    slot["dr0"] = torch.empty((n, 4), dtype=torch.int32, device=device)
-            if light is not None:
-                for slot in self._ring:
-                    slot["hl"] = torch.empty((n, LIGHT_PER_SAMPLE), dtype=torch.float32,
-                                             pin_memory=True)
-                    slot["dl"] = torch.empty((n, LIGHT_PER_SAMPLE), dtype=torch.float32,
-                                             device=device)
-            self._next = 0
-        slot = self._ring[self._next]
-        self._next ^= 1
+        host = {"params": params, "rng": pack_rng(rng) if rng is not None else None,
+                "warp": warp, "post": post, "gather_rng": None, "light": light}     # as RECORDS
+        if post is not None and rng is not None:
+            host["gather_rng"] = host["rng"].clone()
+            host["gather_rng"][:, 2:] = 0
+        ring = self._ring
+        if ring is None or ring["n"] != n or ring["device"] != device or \
+                any(rec is not None and k not in ring["kinds"] for k, rec in host.items()):
+            kinds = {k for k, rec in RECORDS.items() if host[rec.owner] is not None}
+            ring = self._ring = {
+                "n": n, "device": device, "kinds": kinds, "next": 0,
+                "slots": [{"event": None,
+                           "host": {k: torch.empty((n, RECORDS[k].width), dtype=RECORDS[k].dtype,
+                                                   pin_memory=True) for k in kinds},
+                           "device": {k: torch.empty((n, RECORDS[k].width),
+                                                     dtype=RECORDS[k].dtype, device=device)
+                                      for k in kinds}} for _ in range(2)]}
+        slot = ring["slots"][ring["next"]]
+        ring["next"] ^= 1
         if slot["event"] is not None:
             slot["event"].synchronize()         # the copy out of this host buffer has finished
-        slot["hp"].copy_(params)
-        slot["dp"].copy_(slot["hp"], non_blocking=True)
-        dr = dw = dq = dr0 = None
-        if rng is not None:
-            slot["hr"].copy_(pack_rng(rng))
-            slot["dr"].copy_(slot["hr"], non_blocking=True)
-            dr = slot["dr"]
-        if warp is not None:
-            slot["hw"].copy_(warp)
-            slot["dw"].copy_(slot["hw"], non_blocking=True)
-            dw = slot["dw"]
-        if post is not None:
-            slot["hq"].copy_(post)
-            slot["dq"].copy_(slot["hq"], non_blocking=True)
-            dq = slot["dq"]
-            if rng is not None:
-                slot["hr0"].copy_(slot["hr"])
-                slot["hr0"][:, 2:] = 0
-                slot["dr0"].copy_(slot["hr0"], non_blocking=True)
-                dr0 = slot["dr0"]
-        if light is not None:
-            slot["hl"].copy_(light)
-            slot["dl"].copy_(slot["hl"], non_blocking=True)
+        staged = dict.fromkeys(RECORDS)
+        for k, rec in host.items():
+            if rec is not None:
+                slot["host"][k].copy_(rec)
+                staged[k] = slot["device"][k].copy_(slot["host"][k], non_blocking=True)
         slot["event"] = torch.cuda.Event()
         slot["event"].record()
-        if light is not None:
-            return slot["dp"], dr, dw, dq, dr0, slot["dl"]
-        return slot["dp"], dr, dw, dq, dr0
+        return Staged(**staged)
 
-    def _field_buffer(self, N, H, W, device):
-        key = (N, H, W, device)
-        if key not in self._field:
-            self._field[key] = torch.zeros((N, H, W, 2), dtype=torch.float32, device=device)
-        return self._field[key]
-
-    def _post_buffers(self, N, H, W, device):
-        """(the intermediate image between the gather and the post stage, the post workspace),
-        kept per batch shape"""
-        key = (N, H, W, device)
-        if key not in self._post:
-            need = ops.lib().unet_augment_post_workspace_bytes(N)
-            self._post[key] = (torch.empty((N, H, W, 3), dtype=torch.uint8, device=device),
-                               torch.empty(need, dtype=torch.uint8, device=device))
-        return self._post[key]
-
-    def _light_buffers(self, N, H, W, device):
-        """(the intermediate image in front of the light stage, the light workspace), kept per
-        batch shape"""
-        key = (N, H, W, device)
-        if key not in self._light:
-            need = ops.lib().unet_augment_light_workspace_bytes(N)
-            self._light[key] = (torch.empty((N, H, W, 3), dtype=torch.uint8, device=device),
-                                torch.empty(max(need, 16), dtype=torch.uint8, device=device))
-        return self._light[key]
+    def _scratch_for(self, kind, N, H, W, device):
+        """The scratch tensors of a stage, kept per batch shape: the displacement field ("field"),
+        or (the intermediate image the stage reads, its workspace) ("post", "light")."""
+        key = (kind, N, H, W, device)
+        if key not in self._scratch:
+            if kind == "field":     # zeros: the field kernel does not write non-elastic samples
+                self._scratch[key] = torch.zeros((N, H, W, 2), dtype=torch.float32,
+                                                 device=device)
+            else:
+                need = ops.lib().unet_augment_post_workspace_bytes(N) if kind == "post" else \
+                    max(ops.lib().unet_augment_light_workspace_bytes(N), 16)
+                self._scratch[key] = (torch.empty((N, H, W, 3), dtype=torch.uint8, device=device),
+                                      torch.empty(need, dtype=torch.uint8, device=device))
+        return self._scratch[key]
 
     def __call__(self, images_u8, masks_u8=None, which=None, out=None, params=None):
         if not torch.is_tensor(images_u8) or not images_u8.is_cuda:
@@ -1232,60 +1181,40 @@ class BatchAugment:
             if tuple(p.shape) != (N, PARAMS_PER_SAMPLE):
                 raise ValueError(f"params must be [{N}, {PARAMS_PER_SAMPLE}]")
             validate_params(p, H, W)
-        if w is None and q is None and lt is None:
-            dp, dr, _, _, _ = self._stage(p.to(torch.float32), r, images_u8.device)
-            return ops.augment_u8(images_u8, masks_u8, dp, dr, out=out)
-        if w is not None:
-            if tuple(w.shape) != (N, WARP_PER_SAMPLE):
-                raise ValueError(f"warp must be [{N}, {WARP_PER_SAMPLE}]")
-            validate_warp(w, p, H, W)
-            w = w.to(torch.float32)
-        if q is not None:
-            if tuple(q.shape) != (N, POST_PER_SAMPLE):
-                raise ValueError(f"post must be [{N}, {POST_PER_SAMPLE}]")
-            validate_post(q, H, W)
-            q = q.to(torch.float32)
-        if lt is None:
-            staged = self._stage(p.to(torch.float32), r, images_u8.device, warp=w, post=q)
-            return self._launch(images_u8, masks_u8, staged, out)
-        if tuple(lt.shape) != (N, LIGHT_PER_SAMPLE):
-            raise ValueError(f"light must be [{N}, {LIGHT_PER_SAMPLE}]")
-        validate_light(lt, H, W)
-        staged = self._stage(p.to(torch.float32), r, images_u8.device, warp=w, post=q,
-                             light=lt.to(torch.float32))
-        # whichever stage wrote the output before writes a second intermediate image; the light
-        # stage writes the output.  The mask is none of its business.
-        image_out, mask_out = out if out is not None else (None, None)
-        mid, workspace = self._light_buffers(N, H, W, images_u8.device)
-        if masks_u8 is not None and mask_out is None:
-            mask_out = torch.empty_like(masks_u8)
-        res = self._launch(images_u8, masks_u8, staged[:5], (mid, mask_out))
-        return ops.augment_light_u8(mid, staged[5], staged[1], out=image_out,
-                                    workspace=workspace), res[1]
+        optional = {"warp": w, "post": q, "light": lt}
+        for kind, rec in optional.items():
+            if rec is not None:
+                if tuple(rec.shape) != (N, RECORDS[kind].width):
+                    raise ValueError(f"{kind} must be [{N}, {RECORDS[kind].width}]")
+                VALIDATE[kind](rec, p, H, W)
+                optional[kind] = rec.to(torch.float32)
+        s = self._stage(p.to(torch.float32), r, images_u8.device, **optional)
 
-    def _launch(self, images_u8, masks_u8, staged, out):
-        """the gather (behind the field kernel with a warp record) and the post stage"""
-        dp, dr, dw, dq, dr0 = staged
-        N, H, W, _ = images_u8.shape
-        if dw is None and dq is None:
-            return ops.augment_u8(images_u8, masks_u8, dp, dr, out=out)
-        image_out, mask_out = out if out is not None else (None, None)
-        if dq is not None:
-            # the gather writes an intermediate image with salt / pepper off; the post stage
-            # applies it last, with the same word and rule
-            gather_rng, (mid, workspace) = dr0, self._post_buffers(N, H, W, images_u8.device)
+        # The chain: the gather (behind the field kernel with a warp record), then the post and
+        # the light stage where their records are there.  A stage writes the intermediate image
+        # of the stage behind it, the last one the caller's; the mask is the gather's business
+        # alone.  In front of a post stage the gather runs with salt / pepper off: the post
+        # stage applies it last, with the same word and rule.
+        dev = images_u8.device
+        later = [kind for kind in ("post", "light") if getattr(s, kind) is not None]
+        scratch = {kind: self._scratch_for(kind, N, H, W, dev) for kind in later}
+        gather_out = out
+        if later:
+            image_out, mask_out = out if out is not None else (None, None)
             if masks_u8 is not None and mask_out is None:
                 mask_out = torch.empty_like(masks_u8)
-            gather_out = (mid, mask_out)
+            gather_out = (scratch[later[0]][0], mask_out)
+        gather_rng = s.rng if s.post is None else s.gather_rng
+        if s.warp is None:
+            image, mask = ops.augment_u8(images_u8, masks_u8, s.params, gather_rng,
+                                         out=gather_out)
         else:
-            gather_rng, gather_out = dr, out
-        if dw is None:
-            res = ops.augment_u8(images_u8, masks_u8, dp, gather_rng, out=gather_out)
-        else:
-            field = self._field_buffer(N, H, W, images_u8.device)
-            ops.elastic_field(dw, dr, (H, W), out=field)
-            res = ops.augment_warp_u8(images_u8, masks_u8, dp, gather_rng, dw, field,
-                                      out=gather_out)
-        if dq is None:
-            return res
-        return ops.augment_post_u8(mid, dq, dr, out=image_out, workspace=workspace), res[1]
+            field = self._scratch_for("field", N, H, W, dev)
+            ops.elastic_field(s.warp, s.rng, (H, W), out=field)
+            image, mask = ops.augment_warp_u8(images_u8, masks_u8, s.params, gather_rng, s.warp,
+                                              field, out=gather_out)
+        for kind, behind in zip(later, later[1:] + [None]):
+            stage = ops.augment_post_u8 if kind == "post" else ops.augment_light_u8
+            image = stage(image, getattr(s, kind), s.rng, workspace=scratch[kind][1],
+                          out=image_out if behind is None else scratch[behind][0])
+        return image, mask

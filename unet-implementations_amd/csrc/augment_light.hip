@@ -43,10 +43,6 @@ constexpr size_t LIGHT_SUM_BYTES = 2 * sizeof(unsigned long long);   // per samp
 constexpr int L_BODY = 16;                     // first value of a mode's list
 constexpr double HUE_BELOW_360 = 0x1.67fffffffffffp+8;               // the largest double below 360
 
-__device__ __forceinline__ unsigned char to_byte(float v) {
-  return (unsigned char)fminf(fmaxf(rintf(v), 0.f), 255.f);       // fmaxf(NaN, 0) = 0
-}
-
 // a record value as a count: clamped in float (a NaN becomes lo), then truncated
 __device__ __forceinline__ int clamp_count(float v, float lo, float hi) {
   return (int)fminf(fmaxf(v, lo), hi);
@@ -118,13 +114,6 @@ __global__ __launch_bounds__(256) void light_stats_kernel(
     __syncthreads();
   }
   if (tid < 2 && red[tid][0] != 0ull) atomicAdd(&sums[2 * (size_t)n + tid], red[tid][0]);
-}
-
-// -t -> t, size - 1 + t -> size - 1 - t, then into 0 .. size - 1 whatever x was
-__device__ __forceinline__ int reflect(int x, int size) {
-  if (x < 0) x = -x;
-  if (x > size - 1) x = 2 * (size - 1) - x;
-  return min(max(x, 0), size - 1);
 }
 
 // what the modes read of a record once per workgroup; every count is already range-tested
@@ -384,27 +373,10 @@ namespace {
 int light_launch(const char* name, bool stats, bool apply, const uint8_t* image,
                  uint8_t* image_out, const float* light, const uint32_t* rng, void* workspace,
                  size_t workspace_bytes, int N, int H, int W, hipStream_t stream) {
-  UNET_REQUIRE(image && light && (image_out || !apply),
-               "%s: null pointer (image, image_out, light)", name);
-  UNET_REQUIRE(aug_shape_ok(N, H, W),
-               "%s: bad shape (N in 1..65535, H, W in 1..32768, H * W <= 2^30)", name);
   const size_t need = unet_augment_light_workspace_bytes(N);
-  UNET_REQUIRE(workspace && workspace_bytes >= need,
-               "%s: workspace is null or smaller than unet_augment_light_workspace_bytes(N) = %zu",
-               name, need);
-  UNET_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
-               "%s: workspace is not 16-byte aligned", name);
-  const size_t bytes = (size_t)N * H * W * 3;
-  const void* ins[4] = {image, light, rng, workspace};
-  const size_t in_bytes[4] = {bytes, (size_t)N * LIGHT * sizeof(float),
-                              (size_t)N * 4 * sizeof(uint32_t), need};
-  for (int i = 0; i < 4; ++i)
-    UNET_REQUIRE(!aug_overlap(image_out, bytes, ins[i], in_bytes[i]),
-                 "%s: image_out overlaps image, light, rng or workspace (the fog reads a "
-                 "neighbourhood; it cannot run in place)", name);
-  for (int i = 0; i < 3; ++i)
-    UNET_REQUIRE(!aug_overlap(workspace, need, ins[i], in_bytes[i]),
-                 "%s: workspace overlaps image, light or rng", name);
+  if (const int rc = aug_stage_check(name, "light", "fog", apply, image, image_out, light, LIGHT, rng, workspace,
+                                     workspace_bytes, need, N, H, W))
+    return rc;
   // workspace: sums [N][2] uint64 (zeroed here, every call)
   unsigned long long* sums = static_cast<unsigned long long*>(workspace);
   if (stats) {

@@ -36,10 +36,6 @@ constexpr size_t POST_COUNT_BYTES = 3 * 256 * sizeof(unsigned);   // per sample
 constexpr size_t POST_LUT_BYTES = HIST_WG * 256;                  // per sample
 constexpr float HUE_BELOW_180 = 0x1.67fffep+7f;                   // the largest float below 180
 
-__device__ __forceinline__ unsigned char to_byte(float v) {
-  return (unsigned char)fminf(fmaxf(rintf(v), 0.f), 255.f);       // fmaxf(NaN, 0) = 0
-}
-
 // HueSaturationValue on one pixel, in place (hue in half-degrees, S and V in levels)
 __device__ __forceinline__ void hsv_shift(float dh, float ds, float dv, unsigned char (&p)[3]) {
 #pragma clang fp contract(off)
@@ -174,13 +170,6 @@ __global__ __launch_bounds__(256) void post_hist_kernel(
   const float scale = __fdiv_rn(255.f, (float)area);
   luts[((size_t)n * HIST_WG + k) * 256 + tid] =
       (unsigned char)fminf(rintf(((float)cdf * scale)), 255.f);
-}
-
-// -t -> t, size - 1 + t -> size - 1 - t, then into 0 .. size - 1 whatever x was
-__device__ __forceinline__ int reflect(int x, int size) {
-  if (x < 0) x = -x;
-  if (x > size - 1) x = 2 * (size - 1) - x;
-  return min(max(x, 0), size - 1);
 }
 
 // grid (tiles in x, tiles in y, N), 256 threads
@@ -339,27 +328,10 @@ namespace {
 int post_launch(const char* name, bool hist, bool apply, const uint8_t* image, uint8_t* image_out,
                 const float* post, const uint32_t* rng, void* workspace, size_t workspace_bytes,
                 int N, int H, int W, hipStream_t stream) {
-  UNET_REQUIRE(image && post && (image_out || !apply),
-               "%s: null pointer (image, image_out, post)", name);
-  UNET_REQUIRE(aug_shape_ok(N, H, W),
-               "%s: bad shape (N in 1..65535, H, W in 1..32768, H * W <= 2^30)", name);
   const size_t need = unet_augment_post_workspace_bytes(N);
-  UNET_REQUIRE(workspace && workspace_bytes >= need,
-               "%s: workspace is null or smaller than unet_augment_post_workspace_bytes(N) = %zu",
-               name, need);
-  UNET_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
-               "%s: workspace is not 16-byte aligned", name);
-  const size_t bytes = (size_t)N * H * W * 3;
-  const void* ins[4] = {image, post, rng, workspace};
-  const size_t in_bytes[4] = {bytes, (size_t)N * POST * sizeof(float),
-                              (size_t)N * 4 * sizeof(uint32_t), need};
-  for (int i = 0; i < 4; ++i)
-    UNET_REQUIRE(!aug_overlap(image_out, bytes, ins[i], in_bytes[i]),
-                 "%s: image_out overlaps image, post, rng or workspace (the blur reads a "
-                 "neighbourhood; it cannot run in place)", name);
-  for (int i = 0; i < 3; ++i)
-    UNET_REQUIRE(!aug_overlap(workspace, need, ins[i], in_bytes[i]),
-                 "%s: workspace overlaps image, post or rng", name);
+  if (const int rc = aug_stage_check(name, "post", "blur", apply, image, image_out, post, POST, rng, workspace,
+                                     workspace_bytes, need, N, H, W))
+    return rc;
   // workspace: counts [N][3][256] uint32 (zeroed here, every call), then LUTs [N][64][256] bytes
   unsigned* counts = static_cast<unsigned*>(workspace);
   unsigned char* luts = static_cast<unsigned char*>(workspace) + (size_t)N * POST_COUNT_BYTES;

@@ -1519,37 +1519,23 @@ def gradcam_heatmap(cam, ws, size):
 
 
 # ---- online batch augmentation (augment.hip) -------------------------------------------------
-def _augment_args(what, image, mask, params, rng, out):
-    """The argument checks `augment_u8` and `augment_warp_u8` share -> (image_out, mask_out)."""
+def _check_u8_image(what, image):
+    """`what` (the caller) takes a contiguous uint8 [N,H,W,3] image on the device -> (N, H, W)"""
     if not torch.is_tensor(image) or not image.is_cuda:
         raise RuntimeError(f"unet-implementations_amd.{what} runs on MI355X only "
                            "(no CPU fallback exists)")
     if image.dim() != 4 or image.shape[3] != 3 or image.dtype != torch.uint8 or \
             not image.is_contiguous():
         raise TypeError(f"{what} takes a contiguous uint8 [N,H,W,3] image")
-    N, H, W, _ = image.shape
-    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (N, H, W) or
-                             not mask.is_contiguous() or mask.device != image.device):
-        raise TypeError("mask must be a contiguous uint8 [N,H,W] tensor on the image's device")
-    nrec = lib().unet_augment_params_per_sample()
-    if params.dtype != torch.float32 or tuple(params.shape) != (N, nrec) or \
-            not params.is_contiguous() or params.device != image.device:
-        raise TypeError(f"params must be a contiguous fp32 [N, {nrec}] tensor on the image's device")
-    _check_rng(rng, N, image.device)
-    if out is None:
-        image_out = torch.empty_like(image)
-        mask_out = torch.empty_like(mask) if mask is not None else None
-    else:
-        image_out, mask_out = out
-        for o, like, name in ((image_out, image, "image_out"), (mask_out, mask, "mask_out")):
-            if like is None:
-                continue
-            if o is None or o.dtype != torch.uint8 or o.shape != like.shape or \
-                    not o.is_contiguous() or o.device != image.device:
-                raise TypeError(f"{name} must be a contiguous uint8 tensor of its input's shape")
-        if mask is None:
-            mask_out = None
-    return image_out, mask_out
+    return image.shape[:3]
+
+
+def _check_record(kind, rec, N, k, device):
+    """the record named `kind` ("params", "warp", "post", "light") is a contiguous fp32 [N, k]
+    tensor on `device`"""
+    if not torch.is_tensor(rec) or rec.dtype != torch.float32 or tuple(rec.shape) != (N, k) or \
+            not rec.is_contiguous() or rec.device != device:
+        raise TypeError(f"{kind} must be a contiguous fp32 [N, {k}] tensor on the image's device")
 
 
 def _check_rng(rng, N, device):
@@ -1560,11 +1546,39 @@ def _check_rng(rng, N, device):
                         "device")
 
 
-def _check_warp(warp, N, device):
-    nrec = lib().unet_augment_warp_params_per_sample()
-    if not torch.is_tensor(warp) or warp.dtype != torch.float32 or \
-            tuple(warp.shape) != (N, nrec) or not warp.is_contiguous() or warp.device != device:
-        raise TypeError(f"warp must be a contiguous fp32 [N, {nrec}] tensor on the image's device")
+def _check_u8_out(out, like, name="out", whose="the image's"):
+    """`out` is a contiguous uint8 tensor of the shape and on the device of `like` -> out"""
+    if out is None or out.dtype != torch.uint8 or out.shape != like.shape or \
+            not out.is_contiguous() or out.device != like.device:
+        raise TypeError(f"{name} must be a contiguous uint8 tensor of {whose} shape")
+    return out
+
+
+def _stage_workspace(workspace, need, device):
+    """a stage's workspace: a fresh uint8 tensor of `need` bytes, or the caller's, checked"""
+    if workspace is None:
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or \
+            workspace.device != device:
+        raise TypeError("workspace must be a contiguous uint8 tensor on the image's device")
+    return workspace
+
+
+def _augment_args(what, image, mask, params, rng, out):
+    """The argument checks `augment_u8` and `augment_warp_u8` share -> (image_out, mask_out)."""
+    N, H, W = _check_u8_image(what, image)
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (N, H, W) or
+                             not mask.is_contiguous() or mask.device != image.device):
+        raise TypeError("mask must be a contiguous uint8 [N,H,W] tensor on the image's device")
+    _check_record("params", params, N, lib().unet_augment_params_per_sample(), image.device)
+    _check_rng(rng, N, image.device)
+    if out is None:
+        return torch.empty_like(image), torch.empty_like(mask) if mask is not None else None
+    image_out, mask_out = out
+    _check_u8_out(image_out, image, "image_out", "its input's")
+    if mask is None:
+        return image_out, None
+    return image_out, _check_u8_out(mask_out, mask, "mask_out", "its input's")
 
 
 def augment_u8(image, mask, params, rng=None, out=None):
@@ -1590,7 +1604,7 @@ def elastic_field(warp, rng, size, out=None):
         raise RuntimeError("unet-implementations_amd.elastic_field runs on MI355X only "
                            "(no CPU fallback exists)")
     N, H, W = warp.shape[0], int(size[0]), int(size[1])
-    _check_warp(warp, N, warp.device)
+    _check_record("warp", warp, N, lib().unet_augment_warp_params_per_sample(), warp.device)
     _check_rng(rng, N, warp.device)
     if out is None:
         out = torch.zeros((N, H, W, 2), dtype=torch.float32, device=warp.device)
@@ -1609,7 +1623,7 @@ def augment_warp_u8(image, mask, params, rng, warp, field=None, out=None):
     `elastic_field` wrote (None: elastic samples get a zero displacement)."""
     image_out, mask_out = _augment_args("augment_warp_u8", image, mask, params, rng, out)
     N, H, W, _ = image.shape
-    _check_warp(warp, N, image.device)
+    _check_record("warp", warp, N, lib().unet_augment_warp_params_per_sample(), image.device)
     if field is not None and (field.dtype != torch.float32 or
                               tuple(field.shape) != (N, H, W, 2) or not field.is_contiguous() or
                               field.device != image.device):
@@ -1627,30 +1641,12 @@ def augment_post_u8(image, post, rng=None, out=None, workspace=None):
     tensors the kernels read.  out names the tensor to write (it must not overlap image);
     workspace is a uint8 tensor of at least `unet_augment_post_workspace_bytes(N)` bytes that a
     caller may keep between calls (None: one is allocated)."""
-    if not torch.is_tensor(image) or not image.is_cuda:
-        raise RuntimeError("unet-implementations_amd.augment_post_u8 runs on MI355X only "
-                           "(no CPU fallback exists)")
-    if image.dim() != 4 or image.shape[3] != 3 or image.dtype != torch.uint8 or \
-            not image.is_contiguous():
-        raise TypeError("augment_post_u8 takes a contiguous uint8 [N,H,W,3] image")
-    N, H, W, _ = image.shape
-    nrec = lib().unet_augment_post_params_per_sample()
-    if not torch.is_tensor(post) or post.dtype != torch.float32 or \
-            tuple(post.shape) != (N, nrec) or not post.is_contiguous() or \
-            post.device != image.device:
-        raise TypeError(f"post must be a contiguous fp32 [N, {nrec}] tensor on the image's device")
+    N, H, W = _check_u8_image("augment_post_u8", image)
+    _check_record("post", post, N, lib().unet_augment_post_params_per_sample(), image.device)
     _check_rng(rng, N, image.device)
-    if out is None:
-        out = torch.empty_like(image)
-    elif out.dtype != torch.uint8 or out.shape != image.shape or not out.is_contiguous() or \
-            out.device != image.device:
-        raise TypeError("out must be a contiguous uint8 tensor of the image's shape")
-    need = lib().unet_augment_post_workspace_bytes(N)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=image.device)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or \
-            workspace.device != image.device:
-        raise TypeError("workspace must be a contiguous uint8 tensor on the image's device")
+    out = torch.empty_like(image) if out is None else _check_u8_out(out, image)
+    workspace = _stage_workspace(workspace, lib().unet_augment_post_workspace_bytes(N),
+                                 image.device)
     check(lib().unet_augment_post_u8(_ptr(image), _ptr(out), _ptr(post),
                                      rng.data_ptr() if rng is not None else None,
                                      _ptr(workspace), workspace.numel(), N, H, W, _stream()))
@@ -1659,32 +1655,13 @@ def augment_post_u8(image, post, rng=None, out=None, workspace=None):
 
 def _light_args(name, image, light, rng, out, workspace, need_out):
     """The argument checks of `augment_light_u8` and its two halves -> (out, workspace)."""
-    if not torch.is_tensor(image) or not image.is_cuda:
-        raise RuntimeError(f"unet-implementations_amd.{name} runs on MI355X only "
-                           "(no CPU fallback exists)")
-    if image.dim() != 4 or image.shape[3] != 3 or image.dtype != torch.uint8 or \
-            not image.is_contiguous():
-        raise TypeError(f"{name} takes a contiguous uint8 [N,H,W,3] image")
-    N = image.shape[0]
-    nrec = lib().unet_augment_light_params_per_sample()
-    if not torch.is_tensor(light) or light.dtype != torch.float32 or \
-            tuple(light.shape) != (N, nrec) or not light.is_contiguous() or \
-            light.device != image.device:
-        raise TypeError(f"light must be a contiguous fp32 [N, {nrec}] tensor on the image's device")
+    N, _, _ = _check_u8_image(name, image)
+    _check_record("light", light, N, lib().unet_augment_light_params_per_sample(), image.device)
     _check_rng(rng, N, image.device)
     if need_out:
-        if out is None:
-            out = torch.empty_like(image)
-        elif out.dtype != torch.uint8 or out.shape != image.shape or not out.is_contiguous() or \
-                out.device != image.device:
-            raise TypeError("out must be a contiguous uint8 tensor of the image's shape")
-    if workspace is None:
-        workspace = torch.empty(lib().unet_augment_light_workspace_bytes(N), dtype=torch.uint8,
-                                device=image.device)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or \
-            workspace.device != image.device:
-        raise TypeError("workspace must be a contiguous uint8 tensor on the image's device")
-    return out, workspace
+        out = torch.empty_like(image) if out is None else _check_u8_out(out, image)
+    return out, _stage_workspace(workspace, lib().unet_augment_light_workspace_bytes(N),
+                                 image.device)
 
 
 def augment_light_u8(image, light, rng=None, out=None, workspace=None):
