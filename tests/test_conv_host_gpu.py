@@ -6,7 +6,10 @@ tests/data/conv_host_gpu.json (tests/tools/make_conv_host_gpu_table.py, recorded
 a build of the parent commit; every row identical in two runs) lists per call the demangled launch
 list, the reported stats_px / tiles_out and a CRC32 of every output the call writes.  The inputs
 are seeded on the CPU and the kernels use no atomics, so the library under test reproduces all
-three columns exactly: the same kernels on the same IgemmParams.  One test per export family;
+three columns exactly: the same kernels on the same IgemmParams.  The output bits of the seven
+rows that launch conv_patch_split_kernel were recorded again when that kernel moved its five
+correction products into a second accumulator (launch lists and reports unchanged; the results
+themselves are held to fp64 by tests/test_bf16x3_step_kernels_gpu.py).  One test per export family;
 tests/test_conv_host_cpu.py re-asserts the coverage of the table."""
 import importlib.util
 import os

@@ -18,6 +18,17 @@ DEV = "cuda"
 SLOPE = 0.01
 
 
+def _fp64_refs():
+    """tests/tools/fp64_layer_refs.py: float64 references evaluated on the GPU"""
+    import importlib.util
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "fp64_layer_refs.py")
+    spec = importlib.util.spec_from_file_location("fp64_layer_refs", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
 def to_nhwc(t):
     return t.permute(0, 2, 3, 1).contiguous().to(DEV)
 
@@ -405,6 +416,13 @@ def test_data_gradient_split_bf16_emits_reductions(ua, case):
     g = ua.ops.conv3x3_bwd_data(dy, wd, 0, Ccols, H, W, stride, out=base.clone() if acc else None,
                                 accumulate=acc, nxt=nn, bf16="bf16x3", wd3=wd3)
     check(g, ref, 2e-5, "bf16x3 data gradient vs fp32 MFMA")
+    # ... and against float64 on the same operands, one image at a time on the GPU: two kernels
+    # that agree with each other can still share an error
+    R = _fp64_refs()
+    g64 = R.ref_dgrad(R.nchw64(dy), w.double().to(DEV), stride, H, W)
+    if acc:
+        g64 += R.nchw64(base)
+    check(R.nchw64(g), g64, 2e-5, "bf16x3 data gradient vs fp64")
     assert nn.tiles > 0
     _in_bwd_both_ways(ua, g, nn, y, st, gamma, beta, mask)
 

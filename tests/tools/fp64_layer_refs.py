@@ -1,8 +1,10 @@
 """Operands and float64 references shared by the per-layer kernel tests (tests/test_fp32_step_
-kernels_gpu.py): the operand recipe of tests/test_bf16_bench_layers_gpu.py (device-seeded
-tensors, activation coefficients with ~15 % dropped channels, He-scaled weights, the layer a
-BSTATS epilogue reduces for) for fp32 tensors, and plain fp64 evaluations of every operation of
-the train step, one image at a time, on the GPU.  Nothing here calls the library."""
+kernels_gpu.py, tests/test_bf16x3_step_kernels_gpu.py): the operand recipe of tests/test_bf16_
+bench_layers_gpu.py (device-seeded tensors, activation coefficients with ~15 % dropped channels,
+He-scaled weights, the layer a BSTATS epilogue reduces for) for fp32 tensors, plain fp64
+evaluations of every operation of the train step, one image at a time, on the GPU, and the
+float64 emulation of the split-bf16 operand mode's six products (with one left out on request).
+Nothing here calls the library."""
 import torch
 import torch.nn.functional as F
 
@@ -142,6 +144,60 @@ def ref_in_bwd(g, y, gamma, beta, mask, eps=EPS):
         dgm += gg
         dbt += gb
     return torch.cat(dy), dgm, dbt
+
+
+# --------------------------------------------------------------------------- split-bf16 terms
+# The split-bf16 ("bf16x3") operand mode (csrc/common.h split3, csrc/conv_lowp.hip): an fp32
+# operand x is staged as x = h + m + l and a product a b is formed as the six terms of weight
+# >= 2^-16.  The pairs are (term of the first operand, term of the second), 0 = h, 1 = m, 2 = l.
+SIX_PRODUCTS = ((0, 0), (0, 1), (1, 0), (0, 2), (1, 1), (2, 0))
+THIRD_ORDER = ((0, 2), (1, 1), (2, 0))        # the three products of weight 2^-16
+
+
+def split3(t):
+    """h = bf16(t), m = bf16(t - h), l = bf16(t - h - m) -> three float64 tensors.  For an fp32
+    tensor these are the loaders' terms bit for bit (both differences are exact in fp32); a
+    float64 operand (an activated source, which a loader holds rounded to fp32) keeps its own
+    value as the target, so that the emulation's residual stays at the 2^-24 of the three
+    dropped products and not at the rounding of the activation."""
+    t = t.double()
+    h = t.to(torch.bfloat16).double()
+    m = (t - h).to(torch.bfloat16).double()
+    l = (t - h - m).to(torch.bfloat16).double()
+    return h, m, l
+
+
+def split_products(fn, a, b):
+    """fn is bilinear in (a, b) (ref_conv without a bias, ref_dgrad, ref_wgrad as a callable of the
+    two operands): its float64 value on each of the six term pairs -> {(i, j): fn(a_i, b_j)}"""
+    sa, sb = split3(a), split3(b)
+    return {(i, j): fn(sa[i], sb[j]) for i, j in SIX_PRODUCTS}
+
+
+def six_products(fn, a, b, leave_out=None, terms=None):
+    """The float64 evaluation of fn on the six-product expansion of its two operands, optionally
+    with one product (a pair of SIX_PRODUCTS) left out; terms: split_products(fn, a, b) when the
+    caller already has them."""
+    terms = split_products(fn, a, b) if terms is None else terms
+    assert leave_out is None or leave_out in terms
+    return sum(v for k, v in terms.items() if k != leave_out)
+
+
+def rel_l2(out, ref):
+    ref = ref.double()
+    return ((out.double() - ref).norm() / (ref.norm() + 1e-300)).item()
+
+
+def term_check(fn, a, b, exact, extra=None):
+    """-> (e_drop, e_six): relative L2 error, against the exact float64 reference `exact`, of the
+    six-product emulation with the least harmful third-order product left out, and of the full
+    six-product emulation.  extra: what the reference adds to the bilinear part (a bias)."""
+    terms = split_products(fn, a, b)
+    add = 0 if extra is None else extra
+    e_six = rel_l2(six_products(fn, a, b, terms=terms) + add, exact)
+    e_drop = min(rel_l2(six_products(fn, a, b, leave_out=k, terms=terms) + add, exact)
+                 for k in THIRD_ORDER)
+    return e_drop, e_six
 
 
 # --------------------------------------------------------------------------- comparisons
