@@ -17,17 +17,28 @@ Each case
 test_every_bf16_step_kernel_is_held records one whole bs-8 training step and requires every
 kernel it launches to be one of the table's - or a non-convolution kernel of ALLOWED, each held
 against a reference by the test named next to it.  The references are evaluated on the GPU in
-float64, one image at a time."""
+float64, one image at a time (tests/tools/fp64_layer_refs.py); the step recorder and the kernel
+names that do not depend on the operand mode are those of tests/tools/step_kernel_harness.py, the
+harness of the fp32 and split-bf16 tables.  This file keeps its own runners: they run at the
+bench shape, on bf16 operands, against the two-figure bounds below."""
+import importlib.util
 import math
+import os
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
+
+_spec = importlib.util.spec_from_file_location("step_kernel_harness", os.path.join(
+    os.path.dirname(os.path.abspath(__file__)), "tools", "step_kernel_harness.py"))
+HS = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(HS)
+R = HS.R
+DEV, SLOPE = R.DEV, R.SLOPE
+grand, coeffs, nchw64 = R.grand, R.coeffs, R.nchw64
 BF = torch.bfloat16
-SLOPE = 0.01             # nn.LeakyReLU's default: the network's slope
 N, HW = 8, 512           # the bench configuration
 ULP = 2.0 ** -8          # one bf16 ulp of a tensor's max magnitude
 WGRAD_MAX = 5e-3         # fp32 weight gradients: max error / max |ref| (test_conv_in_bwd_weight_b16)
@@ -35,43 +46,23 @@ WGRAD_L2 = 1e-4          # ... and relative L2: ~3x the largest measured (2.4e-7
 
 
 # --------------------------------------------------------------------------- operands
-def grand(shape, seed, scale=1.0):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    return torch.randn(shape, generator=g, device=DEV) * scale
-
-
+# (device-seeded tensors, activation coefficients, layouts: tests/tools/fp64_layer_refs.py)
 def b16(shape, seed, scale=1.0, shift=0.0):
     return (grand(shape, seed, scale) + shift).to(BF)
 
 
-def coeffs(n, c, seed):
-    """Activation coefficients alpha / beta [n, c] with ~15 % dropped channels (alpha = beta = 0)."""
-    al, be = grand((n, c), seed) * 0.5 + 1.0, grand((n, c), seed + 1) * 0.7
-    g = torch.Generator(device=DEV).manual_seed(seed + 2)
-    drop = torch.rand((n, c), generator=g, device=DEV) < 0.15
-    return (torch.where(drop, torch.zeros_like(al), al).contiguous(),
-            torch.where(drop, torch.zeros_like(be), be).contiguous())
-
-
-def act64(x, al, be, rounded=True):
-    """NHWC bf16 raw tensor -> NCHW float64 activated operand: fp32 activation as the loaders
-    compute it, then (rounded=True) the bf16 operand rounding."""
+def act_f32(x, al, be):
+    """NHWC bf16 raw tensor -> NCHW float64 activated operand: the fp32 activation as the loaders
+    compute it, WITHOUT the bf16 operand rounding of R.act64(.., rounded=True) - what the
+    up-sampling loader blends and the head kernels read."""
     a = F.leaky_relu(x.float() * al[:, None, None, :] + be[:, None, None, :], SLOPE)
-    if rounded:
-        a = a.to(BF)
     return a.double().permute(0, 3, 1, 2)
-
-
-def nchw64(t):
-    return t.double().permute(0, 3, 1, 2)
 
 
 def weights(ua, cout, cin, seed, fan):
     """fp32 OIHW weights and their pack (fp32 layouts + the bf16 plane the network passes)."""
     w = grand((cout, cin, 3, 3), seed, scale=math.sqrt(2.0 / fan))
-    table = ua.ops.PackTable([w], 1, None)
-    table.run()
-    return w, table
+    return w, HS.pack_one(ua, w, 1)
 
 
 def next_norm(ua, H, W, C, seed):
@@ -87,43 +78,6 @@ def next_norm(ua, H, W, C, seed):
     g = torch.Generator(device=DEV).manual_seed(seed + 3)
     mask = ((torch.rand((N, C), generator=g, device=DEV) < 0.8).float() / 0.8).contiguous()
     return ua.ops.NextNorm(y, st, gamma, beta, mask, SLOPE)
-
-
-# --------------------------------------------------------------------------- fp64 references
-def ref_conv(a, w, b, stride):
-    return torch.cat([F.conv2d(a[i:i + 1].contiguous(), w, b, stride=stride, padding=1)
-                      for i in range(a.shape[0])])
-
-
-def ref_dgrad(dy, w, stride, H, W):
-    return torch.cat([torch.nn.grad.conv2d_input((1, w.shape[1], H, W), w, dy[i:i + 1].contiguous(),
-                                                 stride=stride, padding=1)
-                      for i in range(dy.shape[0])])
-
-
-def ref_wgrad(a, dy, stride):
-    shape = (dy.shape[1], a.shape[1], 3, 3)
-    dw = torch.zeros(shape, dtype=torch.double, device=DEV)
-    for i in range(a.shape[0]):
-        dw += torch.nn.grad.conv2d_weight(a[i:i + 1].contiguous(), shape, dy[i:i + 1].contiguous(),
-                                          stride=stride, padding=1)
-    return dw
-
-
-def ref_taps(dy):
-    """D[n, i, j, t C + c] = (U^T shift_t(dy))[n, c, i, j] with U the bilinear 2x up-sampling,
-    shift_t(dy)[P] = dy[P - (ky - 1, kx - 1)] (zero outside), t = 3 ky + kx.  dy: NCHW fp64."""
-    n, C, H2, W2 = dy.shape
-    out = []
-    for i in range(n):
-        p = F.pad(dy[i:i + 1], (1, 1, 1, 1))
-        sh = torch.cat([p[:, :, 2 - ky:2 - ky + H2, 2 - kx:2 - kx + W2]
-                        for ky in range(3) for kx in range(3)], 1)
-        low = torch.zeros(1, 9 * C, H2 // 2, W2 // 2, dtype=torch.double, device=DEV,
-                          requires_grad=True)
-        up = F.interpolate(low, scale_factor=2, mode="bilinear", align_corners=False)
-        out.append(torch.autograd.grad(up, low, sh)[0].permute(0, 2, 3, 1))
-    return torch.cat(out)
 
 
 # --------------------------------------------------------------------------- comparisons
@@ -196,10 +150,10 @@ def run_fwd(ua, H, W, C0, C1, Cout, stride):
         y, st = ua.ops.conv_in_fwd(s0, s1, SLOPE, table.wf[0], b, 3, stride, gamma, beta, 1e-5,
                                    None, b16=True, w3=table.wf3[0])
     assert y.dtype == BF
-    a = act64(x0, *c0)
+    a = R.act64(x0, *c0, rounded=True)
     if C1:
-        a = torch.cat([a, act64(x1, *c1)], 1)
-    y_ref = ref_conv(a, w.to(BF).double(), b.double(), stride)
+        a = torch.cat([a, R.act64(x1, *c1, rounded=True)], 1)
+    y_ref = R.ref_conv(a, w.to(BF).double(), b.double(), stride)
     return rec.names, [m_b16("y", nchw64(y), y_ref)] + fused_stats(y_ref, st)
 
 
@@ -217,11 +171,11 @@ def run_up_fwd(ua, h, w, C0, C1, Cout):
                                       w3=table.wf3[0])
     assert y.dtype == BF
     # the loader blends the ACTIVATED fp32 taps in PyTorch's order and rounds once
-    a_low = act64(low, *cl, rounded=False).float()
+    a_low = act_f32(low, *cl).float()
     a_up = F.interpolate(a_low, scale_factor=2, mode="bilinear", align_corners=False).to(BF)
-    a = torch.cat([a_up.double(), act64(skip, *cs)], 1)
+    a = torch.cat([a_up.double(), R.act64(skip, *cs, rounded=True)], 1)
     del a_low, a_up
-    y_ref = ref_conv(a, wt.to(BF).double(), b.double(), 1)
+    y_ref = R.ref_conv(a, wt.to(BF).double(), b.double(), 1)
     return rec.names, [m_b16("y", nchw64(y), y_ref)] + fused_stats(y_ref, st)
 
 
@@ -234,7 +188,7 @@ def run_stem_fwd(ua):
         y, st = ua.ops.conv_in_fwd(ua.ops.Act(x), None, SLOPE, table.wf[0], b, 3, 1, gamma, beta,
                                    1e-5, None, b16=True, w3=table.wf3[0])
     assert y.dtype == BF
-    y_ref = ref_conv(nchw64(x), w.double(), b.double(), 1)
+    y_ref = R.ref_conv(nchw64(x), w.double(), b.double(), 1)
     return rec.names, [m_b16("y", nchw64(y), y_ref)] + fused_stats(y_ref, st)
 
 
@@ -256,7 +210,7 @@ def run_dgrad(ua, H, W, Cin, Cout, stride, nxt=False, acc=False, ci_off=0, cin_t
                                      out=base.clone() if acc else None, accumulate=acc, bf16="bf16",
                                      wd3=wd3, nxt=nn)
     assert dx.dtype == BF
-    ref = ref_dgrad(nchw64(dy), w.to(BF).double()[:, ci_off:ci_off + Cin], stride, H, W)
+    ref = R.ref_dgrad(nchw64(dy), w.to(BF).double()[:, ci_off:ci_off + Cin], stride, H, W)
     if acc:
         ref += nchw64(base)
     metrics = [m_b16("dx", nchw64(dx), ref)]
@@ -285,16 +239,16 @@ def run_wgrad(ua, H, W, Cx, Cout, stride, ci_off=0, cin_total=None, drop_row=Non
         ua.ops.conv_in_bwd_weight(ua.ops.Act(x, *coef), SLOPE, dy, dw, ci_off, 3, stride)
     outside = torch.cat([dw[:, :ci_off], dw[:, ci_off + Cx:]], 1)
     assert not outside.any(), "the weight gradient wrote outside its input-channel slice"
-    a, dyd = act64(x, *coef), nchw64(dy)
+    a, dyd = R.act64(x, *coef, rounded=True), nchw64(dy)
     got = dw[:, ci_off:ci_off + Cx]
-    metrics = [m_wgrad("dw", got, ref_wgrad(a, dyd, stride))]
+    metrics = [m_wgrad("dw", got, R.ref_wgrad(a, dyd, stride))]
     if drop_row is None:
         return rec.names, metrics
     n, r = drop_row
     dyd = dyd.clone()
     dyd[n, :, r, :] = 0
     return rec.names, metrics, [m_wgrad("dw against the reference without one dy row", got,
-                                        ref_wgrad(a, dyd, stride))]
+                                        R.ref_wgrad(a, dyd, stride))]
 
 
 def run_stem_wgrad(ua):
@@ -304,7 +258,7 @@ def run_stem_wgrad(ua):
     dw = torch.zeros(32, 3, 3, 3, device=DEV)
     with ua.ops.record_launches() as rec:
         ua.ops.conv_in_bwd_weight(ua.ops.Act(x), SLOPE, dy, dw, 0, 3, 1)
-    return rec.names, [m_wgrad("dw", dw, ref_wgrad(nchw64(x), nchw64(dy), 1))]
+    return rec.names, [m_wgrad("dw", dw, R.ref_wgrad(nchw64(x), nchw64(dy), 1))]
 
 
 def run_taps(ua, h, w, C):
@@ -313,7 +267,7 @@ def run_taps(ua, h, w, C):
     with ua.ops.record_launches() as rec:
         D = ua.ops.upsample2x_bwd_taps(dy)
     assert D.dtype == BF
-    return rec.names, [m_b16("D", D, ref_taps(nchw64(dy)))]
+    return rec.names, [m_b16("D", D, R.ref_taps(nchw64(dy)))]
 
 
 def run_up_wgrad(ua, h, w, Cx, Cout, cin_total):
@@ -325,7 +279,7 @@ def run_up_wgrad(ua, h, w, Cx, Cout, cin_total):
     with ua.ops.record_launches() as rec:
         ua.ops.conv3x3_up_bwd_weight(ua.ops.Act(low, *coef), SLOPE, D, dw, 0)
     assert not dw[:, Cx:].any(), "the weight gradient wrote outside its input-channel slice"
-    a = act64(low, *coef)
+    a = R.act64(low, *coef, rounded=True)
     ref = torch.zeros(Cx, 9 * Cout, dtype=torch.double, device=DEV)
     for i in range(N):
         ref += a[i].reshape(Cx, h * w) @ D[i].double().reshape(h * w, 9 * Cout)
@@ -358,7 +312,7 @@ def run_head_fwd(ua):
     w, b = grand((3, 32), 2, 0.2), grand((3,), 3, 0.1)
     with ua.ops.record_launches() as rec:
         logits = ua.ops.head1x1_in_fwd(ua.ops.Act(y, *coef), SLOPE, w, b)
-    a = act64(y, *coef, rounded=False)
+    a = act_f32(y, *coef)
     ref = torch.einsum("nchw,kc->nkhw", a, w.double()) + b.double()[None, :, None, None]
     return rec.names, [metric("logits", logits, ref, 1e-4)]
 
@@ -374,7 +328,7 @@ def run_head_bwd(ua):
     with ua.ops.record_launches() as rec:
         da = ua.ops.head1x1_in_bwd(x, SLOPE, dl, w, dw, db, nxt=nn)
     assert da.dtype == BF
-    a = act64(nn.y, nn.st[2], nn.st[3], rounded=False)
+    a = act_f32(nn.y, nn.st[2], nn.st[3])
     dld = dl.double()
     metrics = [m_b16("da", nchw64(da), torch.einsum("nkhw,kc->nchw", dld, w.double())),
                metric("dw", dw, torch.einsum("nkhw,nchw->kc", dld, a), 1e-4),
@@ -384,15 +338,18 @@ def run_head_bwd(ua):
 
 # --------------------------------------------------------------------------- the table
 # Kernel names as ops.record_launches reports them: demangled, except where the demangler gives
-# up on the __bf16 template arguments (mangled, as in profiles/*_kernel_stats.csv).
-_NS, _AN = "unet_conv::(anonymous namespace)::", "(anonymous namespace)::"
+# up on the __bf16 template arguments (mangled, as in profiles/*_kernel_stats.csv).  The names
+# that do not depend on the operand mode: tests/tools/step_kernel_harness.py.
+_NS, _AN = HS._NS, HS._AN
+REDUCE, FIN_GRP, FIN_COMB, FIN_EQ = HS.REDUCE, HS.FIN_GRP, HS.FIN_COMB, HS.FIN_EQ
+HEAD_BWD_FIN = HS.HEAD_BWD_FIN
 
 
 def patch(targs):
     return f"void {_NS}conv_patch_b16_kernel<{targs}>(unet_conv::IgemmParams)"
 
 
-def dgrad_s2(targs):
+def dgrad_s2_b16(targs):
     return f"void {_NS}conv_dgrad_s2_patch_b16_kernel<{targs}>(unet_conv::IgemmParams)"
 
 
@@ -402,31 +359,22 @@ def ring(targs):
     return f"void {_AN}conv_wgrad_b16_ring_kernel<{targs}>({_AN}WgradParams)"
 
 
-def wtaps(targs):
+def wtaps_b16(targs):
     return f"void {_AN}conv_wgrad_taps_b16_kernel<{targs}>({_AN}WgradParams)"
 
 
-def igemm(bm, bn, wm, wn, dense, kg, mode):
+def igemm_b16(bm, bn, wm, wn, dense, kg, mode):
     """conv_igemm_bf16_kernel<BM, BN, WM, WN, __bf16, __bf16, FUSED, KG, MODE>"""
     return (f"_ZN9unet_conv12_GLOBAL__N_122conv_igemm_bf16_kernelILi{bm}ELi{bn}ELi{wm}ELi{wn}"
             f"EDF16bDF16bLb{dense}ELi{kg}ELi{mode}EEEvNS_11IgemmParamsE")
 
 
-REDUCE = f"{_AN}wgrad_reduce_batched_kernel({_AN}ReduceTable)"
-_F2 = "HIP_vector_type<float, 2u>"
-FIN_GRP = f"{_AN}in_stats_finalize_grp_kernel({_F2} const*, {_F2}*, int, int, float)"
-FIN_COMB = (f"{_AN}in_stats_finalize_comb_kernel({_F2} const*, {_F2} const*, float const*, "
-            "float const*, float, float const*, float*, float*, float*, float*, int, int, int, int, "
-            "float)")
-FIN_EQ = (f"{_AN}in_stats_finalize_eq_kernel({_F2} const*, float const*, float const*, float, "
-          "float const*, float*, float*, float*, float*, int, int, int, float)")
-STEM_FWD = ("_ZN9unet_conv12_GLOBAL__N_125conv_stem_fwd_walk_kernelIfDF16bLi8EEEvPKT_PKfS6_PT0_iiii"
-            "P15HIP_vector_typeIfLj2EENS0_8StemNormE")
-STEM_WGRAD = "_ZN12_GLOBAL__N_127conv_stem_wgrad_rows_kernelIfDF16bEEvPKT_PKT0_PfiiiiixNS_9StemNormWE"
-HEAD_FWD = "_ZN12_GLOBAL__N_115head_fwd_kernelIDF16bEEvPKT_PKfS5_PfxiiS5_S5_f"
-HEAD_BWD = "_ZN12_GLOBAL__N_115head_bwd_kernelIDF16bEEvPKT_PKfS5_PS1_PfxiixS5_S5_fNS_6HeadBsE"
-HEAD_BWD_FIN = f"{_AN}head_bwd_finalize_kernel(float const*, float*, float*, int, int)"
-TAPS = "_ZN12_GLOBAL__N_126upsample2x_bwd_taps_kernelIDF16bLi2EEEvPKT_PS1_iiix"
+STEM_FWD_B16 = ("_ZN9unet_conv12_GLOBAL__N_125conv_stem_fwd_walk_kernelIfDF16bLi8EEEvPKT_PKfS6_PT0_iiii"
+                "P15HIP_vector_typeIfLj2EENS0_8StemNormE")
+STEM_WGRAD_B16 = "_ZN12_GLOBAL__N_127conv_stem_wgrad_rows_kernelIfDF16bEEvPKT_PKT0_PfiiiiixNS_9StemNormWE"
+HEAD_FWD_B16 = "_ZN12_GLOBAL__N_115head_fwd_kernelIDF16bEEvPKT_PKfS5_PfxiiS5_S5_f"
+HEAD_BWD_B16 = "_ZN12_GLOBAL__N_115head_bwd_kernelIDF16bEEvPKT_PKfS5_PS1_PfxiixS5_S5_fNS_6HeadBsE"
+TAPS_B16 = "_ZN12_GLOBAL__N_126upsample2x_bwd_taps_kernelIDF16bLi2EEEvPKT_PS1_iiix"
 
 # (id, the layers of UNet() it stands for, runner, arguments, expected kernel names in launch
 # order).  Encoder stage e, conv k: "e<e>.<k>"; decoder stage d: "d<d>.<k>"; inputs of the
@@ -435,7 +383,7 @@ TAPS = "_ZN12_GLOBAL__N_126upsample2x_bwd_taps_kernelIDF16bLi2EEEvPKT_PS1_iiix"
 LAYERS = [
     # ---- forward
     ("stem fwd 3->32 512", "e0.0", run_stem_fwd, dict(),
-     [STEM_FWD, FIN_GRP, FIN_COMB]),
+     [STEM_FWD_B16, FIN_GRP, FIN_COMB]),
     ("fwd 32->32 512", "e0.1 d4.1", run_fwd, dict(H=512, W=512, C0=32, C1=0, Cout=32, stride=1),
      [patch("32, 64, 32, 8, true, true, false, true, false, 1"), FIN_GRP, FIN_COMB]),
     ("fwd 32->64 s2 512", "e1.0", run_fwd, dict(H=512, W=512, C0=32, C1=0, Cout=64, stride=2),
@@ -455,9 +403,9 @@ LAYERS = [
     ("fwd 512->512 32", "e4.1 d0.1", run_fwd, dict(H=32, W=32, C0=512, C1=0, Cout=512, stride=1),
      [patch("128, 64, 64, 4, true, true, false, true, false, 1"), FIN_EQ]),
     ("fwd 512->512 s2 32", "e5.0", run_fwd, dict(H=32, W=32, C0=512, C1=0, Cout=512, stride=2),
-     [igemm(64, 64, 32, 32, 1, 4, 1), FIN_EQ]),
+     [igemm_b16(64, 64, 32, 32, 1, 4, 1), FIN_EQ]),
     ("fwd 512->512 16", "e5.1", run_fwd, dict(H=16, W=16, C0=512, C1=0, Cout=512, stride=1),
-     [igemm(64, 64, 32, 32, 1, 4, 1), FIN_EQ]),
+     [igemm_b16(64, 64, 32, 32, 1, 4, 1), FIN_EQ]),
     ("up fwd 512+512->512 32", "d0.0", run_up_fwd, dict(h=16, w=16, C0=512, C1=512, Cout=512),
      [patch("64, 64, 32, 4, true, true, false, true, true, 1"), FIN_EQ]),
     ("up fwd 512+256->256 64", "d1.0", run_up_fwd, dict(h=32, w=32, C0=512, C1=256, Cout=256),
@@ -469,22 +417,22 @@ LAYERS = [
     ("up fwd 64+32->32 512", "d4.0", run_up_fwd, dict(h=256, w=256, C0=64, C1=32, Cout=32),
      [patch("32, 64, 32, 8, true, true, false, true, true, 1"), FIN_GRP, FIN_COMB]),
     ("head fwd 32->3 512", "head", run_head_fwd, dict(),
-     [HEAD_FWD]),
+     [HEAD_FWD_B16]),
     # ---- backward: head, decoder (last to first), encoder (last to first)
     ("head bwd 32->3 512", "head", run_head_bwd, dict(),
-     [HEAD_BWD, HEAD_BWD_FIN]),
+     [HEAD_BWD_B16, HEAD_BWD_FIN]),
     ("dgrad 32<-32 512 bstats", "d4.1 e0.1", run_dgrad, dict(H=512, W=512, Cin=32, Cout=32, stride=1, nxt=True),
      [patch("32, 64, 32, 8, false, false, true, true, false, 1")]),
     ("wgrad 32->32 512", "d4.1 e0.1", run_wgrad, dict(H=512, W=512, Cx=32, Cout=32, stride=1),
      [ring("32, 32, 64, true, 2, 1, 1"), REDUCE, REDUCE, REDUCE]),
     ("taps 32 512", "d4.0", run_taps, dict(h=256, w=256, C=32),
-     [TAPS]),
+     [TAPS_B16]),
     ("up wgrad 64->32 256", "d4.0", run_up_wgrad, dict(h=256, w=256, Cx=64, Cout=32, cin_total=96),
-     [wtaps("32, 32, 64, true"), REDUCE, REDUCE]),
+     [wtaps_b16("32, 32, 64, true"), REDUCE, REDUCE]),
     ("wgrad skip 32->32 512", "d4.0", run_wgrad, dict(H=512, W=512, Cx=32, Cout=32, stride=1, ci_off=64, cin_total=96),
      [ring("32, 32, 64, true, 2, 1, 1"), REDUCE, REDUCE, REDUCE]),
     ("up dgrad 64<-32 256 bstats", "d4.0", run_up_dgrad, dict(h=256, w=256, C0=64, Cout=32, cin_total=96),
-     [igemm(64, 64, 32, 32, 0, 1, 2)]),
+     [igemm_b16(64, 64, 32, 32, 0, 1, 2)]),
     ("dgrad skip 32<-32 512", "d4.0", run_dgrad, dict(H=512, W=512, Cin=32, Cout=32, stride=1, ci_off=64, cin_total=96),
      [patch("32, 64, 32, 8, false, false, false, true, false, 1")]),
     ("dgrad 64<-64 256 bstats", "d3.1 e1.1", run_dgrad, dict(H=256, W=256, Cin=64, Cout=64, stride=1, nxt=True),
@@ -492,13 +440,13 @@ LAYERS = [
     ("wgrad 64->64 256", "d3.1 e1.1", run_wgrad, dict(H=256, W=256, Cx=64, Cout=64, stride=1),
      [ring("64, 64, 32, true, 2, 2, 1"), REDUCE, REDUCE]),
     ("taps 64 256", "d3.0", run_taps, dict(h=128, w=128, C=64),
-     [TAPS]),
+     [TAPS_B16]),
     ("up wgrad 128->64 128", "d3.0", run_up_wgrad, dict(h=128, w=128, Cx=128, Cout=64, cin_total=192),
-     [wtaps("64, 64, 16, true"), REDUCE, REDUCE]),
+     [wtaps_b16("64, 64, 16, true"), REDUCE, REDUCE]),
     ("wgrad skip 64->64 256", "d3.0", run_wgrad, dict(H=256, W=256, Cx=64, Cout=64, stride=1, ci_off=128, cin_total=192),
      [ring("64, 64, 32, true, 2, 2, 1"), REDUCE, REDUCE]),
     ("up dgrad 128<-64 128 bstats", "d3.0", run_up_dgrad, dict(h=128, w=128, C0=128, Cout=64, cin_total=192),
-     [igemm(64, 64, 32, 32, 0, 1, 2)]),
+     [igemm_b16(64, 64, 32, 32, 0, 1, 2)]),
     ("dgrad skip 64<-64 256", "d3.0", run_dgrad, dict(H=256, W=256, Cin=64, Cout=64, stride=1, ci_off=128, cin_total=192),
      [patch("64, 64, 64, 8, false, false, false, true, false, 1")]),
     ("dgrad 128<-128 128 bstats", "d2.1 e2.1", run_dgrad, dict(H=128, W=128, Cin=128, Cout=128, stride=1, nxt=True),
@@ -506,13 +454,13 @@ LAYERS = [
     ("wgrad 128->128 128", "d2.1 e2.1", run_wgrad, dict(H=128, W=128, Cx=128, Cout=128, stride=1),
      [ring("64, 64, 32, true, 2, 2, 1"), REDUCE, REDUCE]),
     ("taps 128 128", "d2.0", run_taps, dict(h=64, w=64, C=128),
-     [TAPS]),
+     [TAPS_B16]),
     ("up wgrad 256->128 64", "d2.0", run_up_wgrad, dict(h=64, w=64, Cx=256, Cout=128, cin_total=384),
-     [wtaps("64, 64, 16, true"), REDUCE, REDUCE]),
+     [wtaps_b16("64, 64, 16, true"), REDUCE, REDUCE]),
     ("wgrad skip 128->128 128", "d2.0", run_wgrad, dict(H=128, W=128, Cx=128, Cout=128, stride=1, ci_off=256, cin_total=384),
      [ring("64, 64, 32, true, 2, 2, 1"), REDUCE, REDUCE]),
     ("up dgrad 256<-128 64 bstats", "d2.0", run_up_dgrad, dict(h=64, w=64, C0=256, Cout=128, cin_total=384),
-     [igemm(64, 64, 32, 32, 0, 1, 2)]),
+     [igemm_b16(64, 64, 32, 32, 0, 1, 2)]),
     ("dgrad skip 128<-128 128", "d2.0", run_dgrad, dict(H=128, W=128, Cin=128, Cout=128, stride=1, ci_off=256, cin_total=384),
      [patch("64, 64, 64, 8, false, false, false, true, false, 1")]),
     ("dgrad 256<-256 64 bstats", "d1.1 e3.1", run_dgrad, dict(H=64, W=64, Cin=256, Cout=256, stride=1, nxt=True),
@@ -520,13 +468,13 @@ LAYERS = [
     ("wgrad 256->256 64", "d1.1 e3.1", run_wgrad, dict(H=64, W=64, Cx=256, Cout=256, stride=1),
      [ring("64, 64, 32, true, 2, 2, 1"), REDUCE]),
     ("taps 256 64", "d1.0", run_taps, dict(h=32, w=32, C=256),
-     [TAPS]),
+     [TAPS_B16]),
     ("up wgrad 512->256 32", "d1.0", run_up_wgrad, dict(h=32, w=32, Cx=512, Cout=256, cin_total=768),
-     [wtaps("64, 64, 16, true"), REDUCE]),
+     [wtaps_b16("64, 64, 16, true"), REDUCE]),
     ("wgrad skip 256->256 64", "d1.0", run_wgrad, dict(H=64, W=64, Cx=256, Cout=256, stride=1, ci_off=512, cin_total=768),
      [ring("64, 64, 32, true, 2, 2, 1"), REDUCE]),
     ("up dgrad 512<-256 32 bstats", "d1.0", run_up_dgrad, dict(h=32, w=32, C0=512, Cout=256, cin_total=768),
-     [igemm(64, 64, 32, 32, 0, 1, 2)]),
+     [igemm_b16(64, 64, 32, 32, 0, 1, 2)]),
     ("dgrad skip 256<-256 64", "d1.0", run_dgrad, dict(H=64, W=64, Cin=256, Cout=256, stride=1, ci_off=512, cin_total=768),
      [patch("64, 64, 64, 8, false, false, false, true, false, 1")]),
     ("dgrad 512<-512 32 bstats", "d0.1 e4.1", run_dgrad, dict(H=32, W=32, Cin=512, Cout=512, stride=1, nxt=True),
@@ -534,41 +482,41 @@ LAYERS = [
     ("wgrad 512->512 32", "d0.1 e4.1", run_wgrad, dict(H=32, W=32, Cx=512, Cout=512, stride=1),
      [ring("64, 64, 32, true, 2, 1, 1"), REDUCE]),
     ("taps 512 32", "d0.0", run_taps, dict(h=16, w=16, C=512),
-     [TAPS]),
+     [TAPS_B16]),
     ("up wgrad 512->512 16", "d0.0", run_up_wgrad, dict(h=16, w=16, Cx=512, Cout=512, cin_total=1024),
-     [wtaps("64, 64, 16, true"), REDUCE]),
+     [wtaps_b16("64, 64, 16, true"), REDUCE]),
     ("wgrad skip 512->512 32", "d0.0", run_wgrad, dict(H=32, W=32, Cx=512, Cout=512, stride=1, ci_off=512, cin_total=1024),
      [ring("64, 64, 32, true, 2, 1, 1"), REDUCE]),
     ("up dgrad 512<-512 16 bstats", "d0.0", run_up_dgrad, dict(h=16, w=16, C0=512, Cout=512, cin_total=1024),
-     [igemm(64, 64, 32, 32, 0, 4, 2)]),
+     [igemm_b16(64, 64, 32, 32, 0, 4, 2)]),
     ("dgrad skip 512<-512 32", "d0.0", run_dgrad, dict(H=32, W=32, Cin=512, Cout=512, stride=1, ci_off=512, cin_total=1024),
      [patch("128, 64, 64, 4, false, false, false, true, false, 1")]),
     ("dgrad 512<-512 16 bstats", "e5.1", run_dgrad, dict(H=16, W=16, Cin=512, Cout=512, stride=1, nxt=True),
-     [igemm(64, 64, 32, 32, 0, 4, 1)]),
+     [igemm_b16(64, 64, 32, 32, 0, 4, 1)]),
     ("wgrad 512->512 16", "e5.1", run_wgrad, dict(H=16, W=16, Cx=512, Cout=512, stride=1),
      [ring("64, 64, 16, true, 2, 1, 1"), REDUCE]),
     ("dgrad s2 512<-512 32 bstats acc", "e5.0", run_dgrad, dict(H=32, W=32, Cin=512, Cout=512, stride=2, nxt=True, acc=True, emits=False),
-     [igemm(64, 64, 32, 32, 0, 4, 1)] * 4),
+     [igemm_b16(64, 64, 32, 32, 0, 4, 1)] * 4),
     ("wgrad s2 512->512 32", "e5.0", run_wgrad, dict(H=32, W=32, Cx=512, Cout=512, stride=2),
      [ring("64, 64, 16, true, 2, 1, 2"), REDUCE]),
     ("dgrad s2 256<-512 64 bstats acc", "e4.0", run_dgrad, dict(H=64, W=64, Cin=256, Cout=512, stride=2, nxt=True, acc=True),
-     [dgrad_s2("64, 32, 64, 4, true")]),
+     [dgrad_s2_b16("64, 32, 64, 4, true")]),
     ("wgrad s2 256->512 64", "e4.0", run_wgrad, dict(H=64, W=64, Cx=256, Cout=512, stride=2),
      [ring("64, 64, 16, true, 2, 1, 2"), REDUCE]),
     ("dgrad s2 128<-256 128 bstats acc", "e3.0", run_dgrad, dict(H=128, W=128, Cin=128, Cout=256, stride=2, nxt=True, acc=True),
-     [dgrad_s2("64, 32, 64, 4, true")]),
+     [dgrad_s2_b16("64, 32, 64, 4, true")]),
     ("wgrad s2 128->256 128", "e3.0", run_wgrad, dict(H=128, W=128, Cx=128, Cout=256, stride=2),
      [ring("64, 64, 16, true, 2, 2, 2"), REDUCE, REDUCE]),
     ("dgrad s2 64<-128 256 bstats acc", "e2.0", run_dgrad, dict(H=256, W=256, Cin=64, Cout=128, stride=2, nxt=True, acc=True),
-     [dgrad_s2("64, 32, 64, 4, true")]),
+     [dgrad_s2_b16("64, 32, 64, 4, true")]),
     ("wgrad s2 64->128 256", "e2.0", run_wgrad, dict(H=256, W=256, Cx=64, Cout=128, stride=2),
      [ring("64, 64, 16, true, 2, 2, 2"), REDUCE, REDUCE]),
     ("dgrad s2 32<-64 512 bstats acc", "e1.0", run_dgrad, dict(H=512, W=512, Cin=32, Cout=64, stride=2, nxt=True, acc=True),
-     [dgrad_s2("32, 64, 32, 8, true")]),
+     [dgrad_s2_b16("32, 64, 32, 8, true")]),
     ("wgrad s2 32->64 512", "e1.0", run_wgrad, dict(H=512, W=512, Cx=32, Cout=64, stride=2),
      [ring("32, 64, 32, true, 2, 1, 2"), REDUCE, REDUCE, REDUCE]),
     ("stem wgrad 3->32 512", "e0.0", run_stem_wgrad, dict(),
-     [STEM_WGRAD, REDUCE, REDUCE, REDUCE]),
+     [STEM_WGRAD_B16, REDUCE, REDUCE, REDUCE]),
 
 ]
 
@@ -586,27 +534,22 @@ def test_bench_layer_b16(ua, row):
 # instantiation against a reference.
 ALLOWED = {
     # layout of the input image: test_kernels_gpu.py::test_layout_roundtrip
-    f"{_AN}nchw_to_nhwc_kernel(float const*, float*, int, long long, long long)",
+    HS.NCHW_TO_NHWC,
     # the once-per-step weight pack (incl. the bf16 plane):
     # test_kernels_gpu.py::test_pack_weights_batched_matches_per_layer
-    f"{_AN}pack_w_batched_kernel(unet_pack_entry const*, int)",
+    HS.PACK_W,
     # loss forward / finalize / gradient of SimpleLoss (module backward):
     # test_kernels_gpu.py::test_loss_gradient_pass_applies_the_upstream_scalar
-    f"{_AN}loss_reduce_kernel(float const*, long long const*, float*, int, int)",
-    f"{_AN}loss_finalize_kernel(float const*, int, int, float, float, float, int, float const*, "
-    f"float, float*, {_AN}LossCoef*, float*)",
-    f"{_AN}loss_grad_kernel(float const*, long long const*, {_AN}LossCoef const*, float const*, "
-    "float*, int, int, float const*)",
+    HS.LOSS_REDUCE, HS.LOSS_FINALIZE, HS.LOSS_GRAD,
     # InstanceNorm + LeakyReLU + dropout backward on bf16 tensors, stand-alone reduction and the
     # apply pass: test_bf16_gpu.py::test_instnorm_bwd_upsample_head_b16; fed by BSTATS summaries:
     # test_bf16_gpu.py::test_data_gradient_b16_emits_next_norm_reductions (and the rows above)
     "_ZN12_GLOBAL__N_120in_bwd_reduce_kernelIDF16bEEvPKT_S3_PKfS5_S5_S5_S5_fP15HIP_vector_typeIfLj2EEiii",
-    f"{_AN}in_bwd_finalize1_kernel({_F2} const*, {_F2}*, {_F2}*, int, int, int)",
+    HS.IN_FIN1,
     "_ZN12_GLOBAL__N_119in_bwd_apply_kernelIDF16bEEvPKT_S3_PKfS5_S5_S5_S5_fPK15HIP_vector_typeIfLj2EE"
     "PS1_PfiiiS9_SB_SB_SB_",
     # SGD-Nesterov: test_kernels_gpu.py::test_sgd_golden
-    f"{_AN}sgd_nesterov_kernel(float*, float const*, float*, long long, float, float, float, int, "
-    "float, float const*)",
+    HS.SGD,
 }
 
 
@@ -614,22 +557,7 @@ def test_every_bf16_step_kernel_is_held(ua):
     """One bs-8 512 x 512 training step of UNet() in the mixed-precision mode (forward, loss,
     backward, SGD) launches only kernels that a row of LAYERS or an entry of ALLOWED holds: a
     dispatch change that brings in another bf16 kernel fails here until a case holds it."""
-    from oracle import unet_ref as O
-    torch.manual_seed(0)
-    model = ua.UNet().to(DEV).train()
-    model.matmul_precision = "bf16"
-    opt = ua.create_optimizer(model)
-    lossf = ua.get_loss_function()
-    img, tgt = O.synthetic_batch(1234, N, HW, HW)
-    img, tgt = img.to(DEV), tgt.to(DEV)
-    with ua.ops.record_launches() as rec:
-        loss = ua.train_step(model, opt, lossf, img, tgt)
-        torch.cuda.synchronize()
-    assert torch.isfinite(loss)
-    held = set(ALLOWED).union(*(r[4] for r in LAYERS))
-    stray = sorted(set(rec.names) - held)
-    assert len(rec.names) > 100 and not stray, "kernels of the bf16 step no case holds:\n" + \
-        "\n".join(stray)
+    HS.check_step_is_held(HS.record_step(ua, "bf16"), "bf16", LAYERS, ALLOWED)
 
 
 def test_weight_gradient_check_sees_one_missing_row(ua):

@@ -5,7 +5,8 @@ multiply into three bf16 terms on chip (six bf16 MFMA products per multiply).  I
 switch on tile counts, and a shape without a split tile silently runs an fp32 kernel behind
 the same entry, so a small test shape says nothing about the kernel the step runs unless the
 launch is asserted.  This file is the third of its kind, after tests/test_fp32_step_kernels_gpu.py
-and tests/test_bf16_bench_layers_gpu.py, and is built like the first: each row of LAYERS is one
+and tests/test_bf16_bench_layers_gpu.py; like the first it runs its table through the runners of
+tests/tools/step_kernel_harness.py and holds only its operand mode (MODE): each row of LAYERS is one
 call of the step - the same `ops` function with the operand mode unet.py uses in this mode (the
 planes w3 / wd3 of a PackTable(convs, 3, None), x3=True on conv_in_bwd_weight, bf16="bf16x3" with
 wd3 and a NextNorm where layer_bwd passes one, a PLAIN first source + activated skip for the
@@ -19,7 +20,7 @@ wgrad_reduce_batched_kernel stages.  Each case
   * records the launches of the call and asserts they are the row's names;
   * holds the result to a float64 evaluation of the SAME fp32 operands, one image at a time on
     the GPU (tests/tools/fp64_layer_refs.py), within the bound the existing x3 test of the same
-    entry point uses (TOL_* below: the fp32 file's values);
+    entry point uses (TOL_* of the harness: one set of values for both modes);
   * forward rows check mean, rstd, alpha, beta; BSTATS rows check that the gradient is bit-equal
     to the call without the epilogue and drive the InstanceNorm backward from the summaries;
     accumulating rows start from a non-zero buffer; column-slice rows fill dw with a sentinel;
@@ -121,80 +122,19 @@ import os
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
+_spec = importlib.util.spec_from_file_location("step_kernel_harness", os.path.join(
+    os.path.dirname(os.path.abspath(__file__)), "tools", "step_kernel_harness.py"))
+HS = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(HS)
+R = HS.R
 
-def _load(name, *where):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", *where, name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-R = _load("fp64_layer_refs", "tools")
-DEV, SLOPE, EPS = R.DEV, R.SLOPE, R.EPS
-grand, coeffs, nchw64, act64, metric = R.grand, R.coeffs, R.nchw64, R.act64, R.metric
-
-# The bounds of the existing small-shape tests of the same entry points in this operand mode
-# (relative to the tensor's max magnitude unless a scale is given): the values of
-# tests/test_fp32_step_kernels_gpu.py.
-TOL_Y = 2e-5         # test_fused_gpu.py::test_conv_in_fwd_split_bf16: y, mean on max |y| + 1
-TOL_STAT = 5e-5      # ... rstd (alpha and beta on their own scale as test_conv_in_fwd has them)
-TOL_DX = 2e-5        # test_fused_gpu.py::test_data_gradient_split_bf16_emits_reductions
-TOL_DW = 3e-5        # test_fused_gpu.py::test_conv_in_bwd_weight[bf16x3]
-TOL_UP = 3e-5        # test_fused_gpu.py::test_conv3x3_up_backward_at_low_resolution (dw and g)
-TOL_TAPS = 1e-6      # test_kernels_gpu.py::test_upsample2x (the same stencil, 4-term sums)
-TOL_BS = 2e-5        # test_fused_gpu.py::_in_bwd_both_ways (summaries vs reduction pass)
-TOL_IN = 5e-5        # test_kernels_gpu.py::test_instnorm_lrelu_drop (dy, dgamma, dbeta)
-TOL_HEAD = 2e-5      # test_kernels_gpu.py::test_head1x1: 1e-5 (logits, da) .. 2e-5 (dw, db)
-TOL_HEAD_X = 1e-5
 # The term check: a kernel's relative L2 error must stay below half the error of a six-product
 # evaluation that lacks one 2^-16 product, and the full six-product evaluation must sit at least
 # 100 x below that error (both from the float64 reference alone).
 TERM_MARGIN = 2.0
 TERM_FLOOR = 100.0
-
-
-# --------------------------------------------------------------------------- weight forms
-def pack(ua, w):
-    """The PackTable of one 3x3 layer as _Walk builds it in this mode: the packed fp32 layouts
-    plus the three bf16 planes of both (none for the RGB stem), no Winograd form."""
-    table = ua.ops.PackTable([w], 3, None)
-    table.run()
-    return table
-
-
-def summaries(ua, g, nn):
-    """The BSTATS summaries drive the InstanceNorm backward like the stand-alone reduction pass
-    over the same gradient does (test_fused_gpu.py::_in_bwd_both_ways)."""
-    assert nn.tiles > 0, "no BSTATS epilogue ran"
-    C = nn.y.shape[3]
-    outs = []
-    for partials in ((nn.partial, nn.tiles), None):
-        dg, db, dbias = (torch.empty(C, device=DEV) for _ in range(3))
-        dz = ua.ops.instnorm_lrelu_drop_bwd(g.clone(), nn.y, nn.st[0], nn.st[1], nn.gamma, nn.beta,
-                                            nn.mask, SLOPE, dg, db, dbias, partials=partials)
-        outs.append((dz, dg, db))
-    return [metric(what + " via summaries", a, b, TOL_BS)
-            for a, b, what in zip(outs[0], outs[1], ("dz", "dgamma", "dbeta"))]
-
-
-def next_norm(ua, n, H, W, C, seed):
-    return ua.ops.NextNorm(*R.norm_layer(n, H, W, C, seed), SLOPE)
-
-
-def fused_stats(y_ref, st, gamma, beta, mask):
-    """mean, rstd, alpha, beta of the fused forward against fp64 (test_conv_in_fwd's rules)"""
-    mean = y_ref.mean(dim=(2, 3))
-    rstd = 1.0 / torch.sqrt(y_ref.var(dim=(2, 3), unbiased=False) + EPS)
-    gm, mk = gamma.double()[None], mask.double()
-    scale = (beta.abs().max() + (mean * gm * rstd).abs().max()).item() / 0.7
-    return [metric("mean", st[0], mean, TOL_Y, scale=y_ref.abs().max().item() + 1),
-            metric("rstd", st[1], rstd, TOL_STAT),
-            metric("alpha", st[2], gm * rstd * mk, TOL_STAT),
-            metric("beta", st[3], (beta.double()[None] - mean * gm * rstd) * mk, TOL_STAT,
-                   scale=scale)]
 
 
 def term(fn, a, b, got, exact, extra=None):
@@ -213,268 +153,42 @@ def term_failures(t):
     return bad
 
 
-# --------------------------------------------------------------------------- one runner per call
-# Each returns a dict: names (recorded kernel names), metrics, and where they apply term (the
-# term-check figures), bad (metrics against an altered reference), eq32 (the result is bit-equal
-# to the same call in the fp32 operand mode).  N, H, W: the layer's input grid.  drop_row = (image,
-# row): the check of the check - the reference is evaluated a second time with that row zeroed
-# (input row for a forward, dy row for gradients).
-def run_fwd(ua, N, H, W, C0, C1, Cout, stride, plain0=False, x3=True, drop_row=None):
-    """unet_conv_in_fwd_bf16x3 as _Walk.run_layer_fused calls it in this mode: sources activated
-    on load with per-image coefficients, the weight planes w3, dropout mask folded into alpha /
-    beta.  plain0: the first source is a plain tensor (the materialised activated up-sampling of
-    a decoder stage's first convolution), the second the activated skip.  x3: the split kernel
-    runs (term check); else an fp32 kernel behind the same entry, compared bit for bit with the
-    fp32 entry."""
-    x0, c0 = grand((N, H, W, C0), 1), (() if plain0 else coeffs(N, C0, 10))
-    x1, c1 = (grand((N, H, W, C1), 2), coeffs(N, C1, 20)) if C1 else (None, None)
-    w = R.he_weight(Cout, C0 + C1, 3, 9 * (C0 + C1))
-    b, gamma, beta = grand((Cout,), 4, 0.3), grand((Cout,), 5) * 0.2 + 1.0, grand((Cout,), 6) * 0.2
-    mask = R.keep_mask(N, Cout, 7, 0.7)
-    table = pack(ua, w)
-    s0 = ua.ops.Act(x0, *c0)
-    s1 = ua.ops.Act(x1, *c1) if C1 else None
-
-    def call(w3):
-        return ua.ops.conv_in_fwd(s0, s1, SLOPE, table.wf[0], b, 3, stride, gamma, beta, EPS, mask,
-                                  w3=w3)
-
-    with ua.ops.c32_winograd_scope(True):
-        with ua.ops.record_launches() as rec:
-            y, st = call(table.wf3[0])
-        y32 = None if x3 else call(None)[0]
-    a = nchw64(x0) if plain0 else act64(x0, *c0)
-    if C1:
-        a = torch.cat([a, act64(x1, *c1)], 1)
-    wd_, bd = w.double(), b.double()
-    y_ref = R.ref_conv(a, wd_, bd, stride)
-    out = dict(names=rec.names,
-               metrics=[metric("y", nchw64(y), y_ref, TOL_Y)] + fused_stats(y_ref, st, gamma, beta, mask))
-    if x3:
-        out["term"] = term(lambda p, q: R.ref_conv(p, q, None, stride), a, wd_, nchw64(y), y_ref,
-                           extra=bd[None, :, None, None])
-    else:
-        out["eq32"] = torch.equal(y, y32)
-    if drop_row is not None:
-        a[drop_row[0], :, drop_row[1], :] = 0
-        out["bad"] = [metric("y against the reference without one input row", nchw64(y),
-                             R.ref_conv(a, wd_, bd, stride), TOL_Y)]
-    return out
+# --------------------------------------------------------------------------- the operand mode
+def pack(ua, w, stride):
+    """The PackTable of one 3x3 layer as _Walk builds it in this mode: the packed fp32 layouts
+    plus the three bf16 planes of both (none for the RGB stem), no Winograd form."""
+    return HS.pack_one(ua, w, 3)
 
 
-def run_stem_fwd(ua, N, H, W):
-    """unet_conv_in_fwd on the plain RGB image (3 -> 32): the PackTable holds no planes for it, so
-    the walk passes w3 = None and the call is the fp32 mode's."""
-    x = grand((N, H, W, 3), 1)
-    w = R.he_weight(32, 3, 2, 27)
-    b, gamma, beta = grand((32,), 3, 0.1), grand((32,), 5) * 0.2 + 1.0, grand((32,), 6) * 0.2
-    mask = torch.ones(N, 32, device=DEV)
-    table = pack(ua, w)
-    assert table.wf3[0] is None
-    with ua.ops.c32_winograd_scope(True), ua.ops.record_launches() as rec:
-        y, st = ua.ops.conv_in_fwd(ua.ops.Act(x), None, SLOPE, table.wf[0], b, 3, 1, gamma, beta,
-                                   EPS, None, w3=table.wf3[0])
-    y_ref = R.ref_conv(nchw64(x), w.double(), b.double(), 1)
-    return dict(names=rec.names, metrics=[metric("y", nchw64(y), y_ref, TOL_Y)] +
-                fused_stats(y_ref, st, gamma, beta, mask))
+def forms(ua, op, table, grid=None, held=True):
+    """The planes w3 / wd3, bf16 = "bf16x3" on the data gradient, x3 = True on the weight gradient
+    (as the walk passes it for every layer of this mode); the low-resolution data gradient reads
+    fp32 D, so the walk passes no planes.  No "up_fwd": this mode materialises the up-sampling."""
+    return {"fwd": lambda: dict(w3=table.wf3[0]),
+            "dgrad": lambda: dict(bf16="bf16x3", wd3=table.wd3[0]),
+            "wgrad": lambda: dict(x3=True),
+            "up_dgrad": lambda: dict(wd3=None)}[op]()
 
 
-def run_dgrad(ua, N, H, W, Cin, Cout, stride, nxt=False, acc=False, ci_off=0, cin_total=None,
-              x3=True, drop_row=None):
-    """unet_conv3x3_bwd_data[_bs]_bf16x3 as _Walk.layer_bwd calls it in this mode (bf16 =
-    "bf16x3", the planes wd3, no Winograd form): dx[N, H, W, Cin] (+)= the data gradient of dy for
-    input channels [ci_off, ci_off + Cin) of a layer with cin_total inputs; nxt = with the BSTATS
-    epilogue; acc = accumulate into the gradient the decoder left in the skip.  x3 as in run_fwd."""
-    cin_total = cin_total or Cin
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    dy = grand((N, Ho, Wo, Cout), 1)
-    w = R.he_weight(Cout, cin_total, 2, 9 * Cout)
-    base = grand((N, H, W, Cin), 3) if acc else None
-    nn = next_norm(ua, N, H, W, Cin, 10) if nxt else None
-    table = pack(ua, w)
-
-    def call(nxt_, mode="bf16x3"):
-        return ua.ops.conv3x3_bwd_data(dy, table.wd[0], ci_off, Cin, H, W, stride,
-                                       out=base.clone() if acc else None, accumulate=acc,
-                                       bf16=mode, wd3=table.wd3[0] if mode == "bf16x3" else None,
-                                       nxt=nxt_)
-
-    with ua.ops.c32_winograd_scope(True):
-        with ua.ops.record_launches() as rec:
-            dx = call(nn)
-        # (without the epilogue: the same entry where the split kernel runs; where the entry lands
-        # on an fp32 kernel - which at stride 2 it does only WITH the epilogue - the fp32 entry)
-        plain = call(None, "bf16x3" if x3 else "fp32") if nxt else None
-        dx32 = None if x3 else call(next_norm(ua, N, H, W, Cin, 10) if nxt else None, "fp32")
-    wsl = w.double()[:, ci_off:ci_off + Cin]
-    dyd = nchw64(dy)
-    ref = R.ref_dgrad(dyd, wsl, stride, H, W)
-    if acc:
-        ref += nchw64(base)
-    out = dict(names=rec.names, metrics=[metric("dx", nchw64(dx), ref, TOL_DX)])
-    if nxt:
-        assert torch.equal(plain, dx), "the BSTATS epilogue changed the gradient"
-        out["metrics"] += summaries(ua, dx, nn)
-    if x3:
-        out["term"] = term(lambda p, q: R.ref_dgrad(p, q, stride, H, W), dyd, wsl, nchw64(dx), ref,
-                           extra=nchw64(base) if acc else None)
-    else:
-        out["eq32"] = torch.equal(dx, dx32)
-    if drop_row is not None:
-        dyd = dyd.clone()
-        dyd[drop_row[0], :, drop_row[1], :] = 0
-        bad = R.ref_dgrad(dyd, wsl, stride, H, W) + (nchw64(base) if acc else 0)
-        out["bad"] = [metric("dx against the reference without one dy row", nchw64(dx), bad, TOL_DX)]
-    return out
-
-
-def run_wgrad(ua, N, H, W, Cx, Cout, stride, ci_off=0, cin_total=None, x3=True, drop_row=None):
-    """unet_conv_in_bwd_weight_bf16x3 (x3=True on ops.conv_in_bwd_weight, as the walk passes it
-    for every layer of this mode): dw[:, ci_off : ci_off + Cx] of a layer with cin_total inputs,
-    operand x [N, H, W, Cx] activated on load; the other columns keep a sentinel.  x3 here: the
-    split kernel runs (stride 1); else the entry's fp32 kernel, compared with the fp32 entry."""
-    cin_total = cin_total or Cx
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    x, coef = grand((N, H, W, Cx), 1), coeffs(N, Cx, 30)
-    dy = grand((N, Ho, Wo, Cout), 2)
-    src = ua.ops.Act(x, *coef)
-
-    def call(mode3):
-        dw = torch.full((Cout, cin_total, 3, 3), 7.0, device=DEV)
-        with ua.ops.c32_winograd_scope(True), ua.ops.record_launches() as rec:
-            ua.ops.conv_in_bwd_weight(src, SLOPE, dy, dw, ci_off, 3, stride, x3=mode3)
-        outside = torch.cat([dw[:, :ci_off], dw[:, ci_off + Cx:]], 1)
-        assert bool((outside == 7.0).all()), "the weight gradient wrote outside its input-channel slice"
-        return rec.names, dw[:, ci_off:ci_off + Cx]
-
-    names, got = call(True)
-    a, dyd = act64(x, *coef), nchw64(dy)
-    ref = R.ref_wgrad(a, dyd, stride)
-    out = dict(names=names, metrics=[metric("dw", got, ref, TOL_DW)])
-    if x3:
-        out["term"] = term(lambda p, q: R.ref_wgrad(p, q, stride), a, dyd, got, ref)
-    else:
-        out["eq32"] = torch.equal(got, call(False)[1])
-    if drop_row is not None:
-        dyd = dyd.clone()
-        dyd[drop_row[0], :, drop_row[1], :] = 0
-        out["bad"] = [metric("dw against the reference without one dy row", got,
-                             R.ref_wgrad(a, dyd, stride), TOL_DW)]
-    return out
-
-
-def run_stem_wgrad(ua, N, H, W):
-    """unet_conv_in_bwd_weight_bf16x3 of the stem: the plain RGB image (no split form: K = 27)."""
-    x = grand((N, H, W, 3), 1)
-    dy = grand((N, H, W, 32), 2)
-    dws = []
-    for mode3 in (True, False):
-        dw = torch.zeros(32, 3, 3, 3, device=DEV)
-        with ua.ops.c32_winograd_scope(True), ua.ops.record_launches() as rec:
-            ua.ops.conv_in_bwd_weight(ua.ops.Act(x), SLOPE, dy, dw, 0, 3, 1, x3=mode3)
-        dws.append((rec.names, dw))
-    return dict(names=dws[0][0], eq32=torch.equal(dws[0][1], dws[1][1]),
-                metrics=[metric("dw", dws[0][1], R.ref_wgrad(nchw64(x), nchw64(dy), 1), TOL_DW)])
-
-
-def run_taps(ua, N, h, w, C):
-    """unet_upsample2x_bwd_taps: D[N, h, w, 9 C] from dy[N, 2h, 2w, C]."""
-    dy = grand((N, 2 * h, 2 * w, C), 1)
-    with ua.ops.record_launches() as rec:
-        D = ua.ops.upsample2x_bwd_taps(dy)
-    return dict(names=rec.names, metrics=[metric("D", D, R.ref_taps(nchw64(dy)), TOL_TAPS)])
-
-
-def run_up_wgrad(ua, N, h, w, Cx, Cout, cin_total):
-    """unet_conv3x3_up_bwd_weight: dw[:, 0:Cx] of conv3x3(upsample2x(act(low))) as a GEMM over the
-    low-resolution pixels; the skip's columns keep a sentinel."""
-    low, coef = grand((N, h, w, Cx), 1), coeffs(N, Cx, 40)
-    D = grand((N, h, w, 9 * Cout), 2)
-    dw = torch.full((Cout, cin_total, 3, 3), 7.0, device=DEV)
-    with ua.ops.record_launches() as rec:
-        ua.ops.conv3x3_up_bwd_weight(ua.ops.Act(low, *coef), SLOPE, D, dw, 0)
-    assert bool((dw[:, Cx:] == 7.0).all()), "the weight gradient wrote outside its input-channel slice"
-    ref = R.ref_up_wgrad(act64(low, *coef), D.double())
-    return dict(names=rec.names, metrics=[metric("dw", dw[:, :Cx], ref, TOL_UP)])
-
-
-def run_up_dgrad(ua, N, h, w, C0, Cout, cin_total):
-    """unet_conv3x3_up_bwd_data_bs: the low-resolution data gradient of the up-sampled operand as a
-    GEMM g = D B (fp32 D, so the walk passes no planes), with the BSTATS epilogue of the layer
-    that produced the low-resolution tensor."""
-    wt = R.he_weight(Cout, cin_total, 3, 9 * Cout)
-    table = pack(ua, wt)
-    D = grand((N, h, w, 9 * Cout), 5)
-    nn = next_norm(ua, N, h, w, C0, 20)
-    with ua.ops.record_launches() as rec:
-        g = ua.ops.conv3x3_up_bwd_data(D, table.wd[0], 0, C0, nxt=nn, wd3=None)
-    ref = R.ref_up_dgrad(D.double(), wt.double()[:, :C0])
-    plain = ua.ops.conv3x3_up_bwd_data(D, table.wd[0], 0, C0)
-    assert torch.equal(plain, g), "the BSTATS epilogue changed the gradient"
-    return dict(names=rec.names, metrics=[metric("g", g, ref, TOL_UP)] + summaries(ua, g, nn))
-
-
-def run_head_fwd(ua, N, H, W):
-    """unet_head1x1_in_fwd: logits (NCHW) of the 1x1 head over the activated last decoder output."""
-    y, coef = grand((N, H, W, 32), 1), coeffs(N, 32, 50)
-    w, b = grand((3, 32), 2, 0.2), grand((3,), 3, 0.1)
-    with ua.ops.record_launches() as rec:
-        logits = ua.ops.head1x1_in_fwd(ua.ops.Act(y, *coef), SLOPE, w, b)
-    ref = torch.einsum("nchw,kc->nkhw", act64(y, *coef), w.double()) + b.double()[None, :, None, None]
-    return dict(names=rec.names, metrics=[metric("logits", logits, ref, TOL_HEAD_X)])
-
-
-def run_head_bwd(ua, N, H, W):
-    """unet_head1x1_in_bwd_bs: da = W^T dlogits, dW, db and the InstanceNorm-backward reductions
-    of the last decoder layer (whose raw output the head reads)."""
-    nn = next_norm(ua, N, H, W, 32, 60)
-    al, be = (nn.st[2] * nn.mask).contiguous(), (nn.st[3] * nn.mask).contiguous()
-    x = ua.ops.Act(nn.y, al, be)
-    dl = grand((N, 3, H, W), 2)
-    w = grand((3, 32), 3, 0.2)
-    dw, db = torch.empty(3, 32, device=DEV), torch.empty(3, device=DEV)
-    with ua.ops.record_launches() as rec:
-        da = ua.ops.head1x1_in_bwd(x, SLOPE, dl, w, dw, db, nxt=nn)
-    a, dld = act64(nn.y, al, be), dl.double()
-    metrics = [metric("da", nchw64(da), torch.einsum("nkhw,kc->nchw", dld, w.double()), TOL_HEAD_X),
-               metric("dw", dw, torch.einsum("nkhw,nchw->kc", dld, a), TOL_HEAD),
-               metric("db", db, dld.sum(dim=(0, 2, 3)), TOL_HEAD)]
-    return dict(names=rec.names, metrics=metrics + summaries(ua, da, nn))
-
-
-def run_in_bwd(ua, N, H, W, C, fed):
-    """unet_instnorm_lrelu_drop_bwd[_partials]: InstanceNorm + LeakyReLU + dropout backward
-    against fp64 autograd.  fed: the reductions come as BSTATS summaries of the producer of g (here
-    the stand-alone up data gradient with Cout = 32); else the stand-alone reduction pass runs."""
-    y, st, gamma, beta, mask = R.norm_layer(N, H, W, C, 70)
-    partials = None
-    if fed:
-        nn = ua.ops.NextNorm(y, st, gamma, beta, mask, SLOPE)
-        wt = R.he_weight(32, C, 3, 9 * 32)
-        g = ua.ops.conv3x3_up_bwd_data(grand((N, H, W, 9 * 32), 5), pack(ua, wt).wd[0], 0, C, nxt=nn)
-        assert nn.tiles > 0, "no BSTATS epilogue ran"
-        partials = (nn.partial, nn.tiles)
-    else:
-        g = grand((N, H, W, C), 71)
-    dz_ref, dg_ref, db_ref = R.ref_in_bwd(g, y, gamma, beta, mask)
-    dg, db, dbias = (torch.empty(C, device=DEV) for _ in range(3))
-    with ua.ops.record_launches() as rec:
-        dz = ua.ops.instnorm_lrelu_drop_bwd(g.clone(), y, st[0], st[1], gamma, beta, mask, SLOPE,
-                                            dg, db, dbias, partials=partials)
-    return dict(names=rec.names,
-                metrics=[metric("dz", dz, dz_ref, TOL_IN), metric("dgamma", dg, dg_ref, TOL_IN),
-                         metric("dbeta", db, db_ref, TOL_IN),
-                         # the conv-bias gradient = sum of dz: mathematically 0
-                         metric("dbias", dbias, torch.zeros(C, dtype=torch.double, device=DEV), 1e-3,
-                                scale=max(1.0, dz_ref.abs().sum().item() / C))])
-
+# The rows' x3 argument: True (the default) = the split kernel runs and the runner returns the
+# term check's figures; False = an fp32 kernel behind the same entry, and the runner compares
+# the result bit for bit with the same call through the fp32 entry (HS.FP32_ENTRY).
+MODE = HS.Mode("bf16x3", 3, pack, forms, term)
 
 # --------------------------------------------------------------------------- the table
-# Kernel names as ops.record_launches reports them (demangled).
-_NS, _AN = "unet_conv::(anonymous namespace)::", "(anonymous namespace)::"
-_F2 = "HIP_vector_type<float, 2u>"
+# The runners and the kernel names more than one table uses: tests/tools/step_kernel_harness.py.
+run_fwd, run_stem_fwd, run_dgrad, run_wgrad = HS.run_fwd, HS.run_stem_fwd, HS.run_dgrad, HS.run_wgrad
+run_stem_wgrad, run_taps, run_up_wgrad = HS.run_stem_wgrad, HS.run_taps, HS.run_up_wgrad
+run_up_dgrad, run_head_fwd, run_head_bwd, run_in_bwd = \
+    HS.run_up_dgrad, HS.run_head_fwd, HS.run_head_bwd, HS.run_in_bwd
+patch_s2, dgrad_s2, igemm, wgrad, wtaps = HS.patch_s2, HS.dgrad_s2, HS.igemm, HS.wgrad, HS.wtaps
+REDUCE, FIN_GRP, FIN_COMB, FIN_EQ, TAPS = HS.REDUCE, HS.FIN_GRP, HS.FIN_COMB, HS.FIN_EQ, HS.TAPS
+STEM_FWD, STEM_WGRAD, HEAD_FWD, HEAD_BWD = HS.STEM_FWD, HS.STEM_WGRAD, HS.HEAD_FWD, HS.HEAD_BWD
+HEAD_BWD_FIN, IN_FIN1, IN_APPLY = HS.HEAD_BWD_FIN, HS.IN_FIN1, HS.IN_APPLY
+_NS, _AN = HS._NS, HS._AN
 
 
+# The split kernels of this mode.
 def split(tile, form):
     """conv_patch_split_kernel<BN, WM, WN, TH, ACT, STATS, BSTATS>: form "fwd" = the fused forward
     (activation on load, statistics epilogue), "bs" = the data gradient of the fused pipeline
@@ -486,60 +200,13 @@ def split(tile, form):
 T128, T64T, T64, T32T = "128, 64, 64, 4", "64, 128, 32, 8", "64, 64, 32, 4", "32, 64, 32, 8"
 
 
-def patch_s2(targs):
-    return f"void {_NS}conv_patch_s2_kernel<{targs}>(unet_conv::IgemmParams)"
-
-
-def dgrad_s2(targs):
-    return f"void {_NS}conv_dgrad_s2_patch_kernel<{targs}>(unet_conv::IgemmParams)"
-
-
-def igemm(bm, bn, wm, wn, act, kg):
-    """conv_igemm_kernel<BM, BN, WM, WN, 32, ACT, KG>: KG = K groups of a workgroup"""
-    return (f"void {_NS}conv_igemm_kernel<{bm}, {bn}, {wm}, {wn}, 32, {'true' if act else 'false'}, "
-            f"{kg}>(unet_conv::IgemmParams)")
-
-
-def wgrad(targs):
-    """conv_wgrad_kernel<CI_T, CO_T, S, STRIDE, ACT, float, float, waves>"""
-    return f"void {_AN}conv_wgrad_kernel<{targs}>({_AN}WgradParams)"
-
-
 def wgrad3(targs):
     """conv_wgrad_bf16_kernel<CI_T, CO_T, S, 3 planes, single buffer, float, float, ACT>"""
     return f"void {_AN}conv_wgrad_bf16_kernel<{targs}>({_AN}WgradParams)"
 
 
-def wtaps(targs):
-    return f"void {_AN}conv_wgrad_taps_kernel<{targs}>({_AN}WgradParams)"
-
-
 WG3_32 = wgrad3("32, 32, 64, 3, true, float, float, true, 1")
 WG3_64 = wgrad3("64, 64, 16, 3, false, float, float, true, 1")
-REDUCE = f"{_AN}wgrad_reduce_batched_kernel({_AN}ReduceTable)"
-FIN_GRP = f"{_AN}in_stats_finalize_grp_kernel({_F2} const*, {_F2}*, int, int, float)"
-FIN_COMB = (f"{_AN}in_stats_finalize_comb_kernel({_F2} const*, {_F2} const*, float const*, "
-            "float const*, float, float const*, float*, float*, float*, float*, int, int, int, int, "
-            "float)")
-FIN_EQ = (f"{_AN}in_stats_finalize_eq_kernel({_F2} const*, float const*, float const*, float, "
-          "float const*, float*, float*, float*, float*, int, int, int, float)")
-STEM_FWD = (f"void {_NS}conv_stem_fwd_walk_kernel<float, float, 8>(float const*, float const*, "
-            f"float const*, float*, int, int, int, int, {_F2}*, {_NS}StemNorm)")
-STEM_WGRAD = (f"void {_AN}conv_stem_wgrad_rows_kernel<float, float>(float const*, float const*, "
-              f"float*, int, int, int, int, int, long long, {_AN}StemNormW)")
-HEAD_FWD = (f"void {_AN}head_fwd_kernel<float>(float const*, float const*, float const*, float*, "
-            "long long, int, int, float const*, float const*, float)")
-HEAD_BWD = (f"void {_AN}head_bwd_kernel<float>(float const*, float const*, float const*, float*, "
-            f"float*, long long, int, int, long long, float const*, float const*, float, {_AN}HeadBs)")
-HEAD_BWD_FIN = f"{_AN}head_bwd_finalize_kernel(float const*, float*, float*, int, int)"
-TAPS = (f"void {_AN}upsample2x_bwd_taps_kernel<float, 1>(float const*, float*, int, int, int, "
-        "long long)")
-IN_FIN1 = f"{_AN}in_bwd_finalize1_kernel({_F2} const*, {_F2}*, {_F2}*, int, int, int)"
-IN_APPLY = (f"void {_AN}in_bwd_apply_kernel<float>(float const*, float const*, float const*, "
-            "float const*, float const*, float const*, float const*, float, "
-            f"{_F2} const*, float*, float*, int, int, int, {_F2} const*, float*, float*, float*)")
-IN_REDUCE = (f"void {_AN}in_bwd_reduce_kernel<float>(float const*, float const*, float const*, "
-             f"float const*, float const*, float const*, float const*, float, {_F2}*, int, int, int)")
 
 # (id, the layers of UNet() it stands for, runner, arguments, expected kernel names in launch
 # order, kind).  Encoder stage e, conv k: "e<e>.<k>"; decoder stage d: "d<d>.<k>".  Layers with the
@@ -828,20 +495,21 @@ LAYERS = [
     ("stem wgrad 3->32", "e0.0", run_stem_wgrad, dict(N=2, H=136, W=512),
      [STEM_WGRAD, REDUCE, REDUCE, REDUCE], SAME32),
 ]
+
+
 def _row(ident):
     return next(r for r in LAYERS if r[0] == ident)
 
 
 def _run(ua, row, **extra):
-    return row[2](ua, **row[3], **extra)
+    return row[2](ua, MODE, **row[3], **extra)
 
 
 def line(row, out):
     """One line of profiles/bf16x3_step_kernels_error.txt."""
     ident, layers, runner, kw, expected, kind = row
     shape = " ".join(f"{k}={v}" for k, v in kw.items() if k not in ("x3",))
-    kernels = " + ".join(dict.fromkeys(
-        n.replace(_NS, "").replace(_AN, "").replace("void ", "").split("(")[0] for n in out["names"]))
+    kernels = " + ".join(dict.fromkeys(HS.short(n) for n in out["names"]))
     s = f"{ident} | {shape} | {kernels} | {R.report(out['metrics'])}"
     if "term" in out:
         t = out["term"]
@@ -855,7 +523,7 @@ def line(row, out):
 def fp32_names():
     """Every kernel name a row of tests/test_fp32_step_kernels_gpu.py expects (by lookup: nothing
     of that file runs here)."""
-    F = _load("test_fp32_step_kernels_gpu")
+    F = HS.load("test_fp32_step_kernels_gpu")
     return set().union(*(r[4] for r in F.LAYERS))
 
 
@@ -898,7 +566,7 @@ def test_term_check_sees_one_missing_product():
     """The term check on the reference alone: a six-product evaluation without one 2^-16
     product is rejected by the criterion the rows apply to the kernel (at e_drop by construction),
     the full one passes it with the 100 x floor to spare - for the K of the smallest row."""
-    a = torch.nn.functional.leaky_relu(grand((2, 32, 16, 32), 1).double(), SLOPE)
+    a = torch.nn.functional.leaky_relu(HS.grand((2, 32, 16, 32), 1).double(), HS.SLOPE)
     w = R.he_weight(32, 32, 2, 9 * 32).double()
 
     def fn(p, q):
@@ -915,110 +583,40 @@ def test_term_check_sees_one_missing_product():
 
 
 # --------------------------------------------------------------------------- the other kernels
-# The kernels of the step that are neither convolutions nor norm / head kernels with a row
-# above: name -> (the existing test that holds it against a reference, that test's smallest
-# call).  test_allowed_kernel_is_launched_by_its_test runs the call and requires the name, so an
-# entry is a checked claim.
-def _call_layout(ua):
-    ua.ops.nchw_to_nhwc(grand((2, 3, 10, 14), 1))
+# HS.ALLOWED (name -> the test that holds it, that test's smallest call) plus this mode's own.
+def _call_upsample(ua, mode):
+    ua.ops.upsample2x_in_fwd(ua.ops.Act(HS.grand((1, 1, 1, 32), 1), *HS.coeffs(1, 32, 40)), HS.SLOPE)
 
 
-def _call_pack(ua):
-    ua.ops.PackTable([grand((32, 3, 3, 3), 1), grand((64, 32, 3, 3), 2)], True).run()
+ALLOWED = dict(HS.ALLOWED)
+# the activated up-sampling this mode materialises for the decoder's first convolutions
+ALLOWED[f"void {_AN}upsample2x_fwd_kernel<float>(float const*, float*, int, int, int, long long, "
+        "float const*, float const*, float)"] = \
+    ("test_fused_gpu.py::test_upsample2x_in_fwd", _call_upsample)
 
 
-def _call_upsample(ua):
-    ua.ops.upsample2x_in_fwd(ua.ops.Act(grand((1, 1, 1, 32), 1), *coeffs(1, 32, 40)), SLOPE)
-
-
-def _call_loss(ua):
-    g = torch.Generator(device=DEV).manual_seed(1)
-    lg = torch.randn((2, 3, 24, 40), generator=g, device=DEV) * 2.0
-    tg = torch.randint(0, 3, (2, 24, 40), generator=g, device=DEV)
-    tg[:, :2, :] = 255
-    ua.ops.dice_wce_loss_fwd_bwd(lg, tg, 1e-5, 1.0, 1.0, 255, True)
-
-
-def _call_sgd(ua):
-    p, gr = grand((1003,), 30), grand((1003,), 31)
-    ua.ops.sgd_nesterov_step(p, gr, torch.zeros_like(p), 0.005, 0.99, 1e-4, True)
-
-
-_LOSS_TEST = "test_kernels_gpu.py::test_loss_vs_oracle"
-ALLOWED = {
-    f"{_AN}nchw_to_nhwc_kernel(float const*, float*, int, long long, long long)":
-        ("test_kernels_gpu.py::test_layout_roundtrip", _call_layout),
-    # (the three bf16 planes of this mode come from the same launch)
-    f"{_AN}pack_w_batched_kernel(unet_pack_entry const*, int)":
-        ("test_kernels_gpu.py::test_pack_weights_batched_matches_per_layer", _call_pack),
-    # the activated up-sampling this mode materialises for the decoder's first convolutions
-    f"void {_AN}upsample2x_fwd_kernel<float>(float const*, float*, int, int, int, long long, "
-    "float const*, float const*, float)":
-        ("test_fused_gpu.py::test_upsample2x_in_fwd", _call_upsample),
-    f"{_AN}loss_reduce_kernel(float const*, long long const*, float*, int, int)":
-        (_LOSS_TEST, _call_loss),
-    f"{_AN}loss_finalize_kernel(float const*, int, int, float, float, float, int, float const*, "
-    f"float, float*, {_AN}LossCoef*, float*)":
-        (_LOSS_TEST, _call_loss),
-    f"{_AN}loss_grad_kernel(float const*, long long const*, {_AN}LossCoef const*, float const*, "
-    "float*, int, int, float const*)":
-        (_LOSS_TEST, _call_loss),
-    f"{_AN}sgd_nesterov_kernel(float*, float const*, float*, long long, float, float, float, int, "
-    "float, float const*)":
-        ("test_kernels_gpu.py::test_sgd_odd_length", _call_sgd),
-}
-_CONV_WORDS = ("conv", "wgrad", "taps", "wino_up", "wino32", "igemm", "patch")
-
-
-@pytest.mark.parametrize("name", sorted(ALLOWED),
-                         ids=[n.replace(_NS, "").replace(_AN, "").split("(")[0] for n in sorted(ALLOWED)])
+@pytest.mark.parametrize("name", sorted(ALLOWED), ids=HS.allowed_ids(ALLOWED))
 def test_allowed_kernel_is_launched_by_its_test(ua, name):
-    held_by, call = ALLOWED[name]
-    kernel = name.replace(_NS, "").replace(_AN, "").replace("void ", "").split("(")[0]
-    assert not any(w in kernel for w in _CONV_WORDS), \
-        f"{name}: a convolution kernel needs a row of LAYERS"
-    with ua.ops.record_launches() as rec:
-        call(ua)
-    assert name in rec.names, f"the call of {held_by} launched {rec.names}"
+    HS.check_allowed(ua, MODE, ALLOWED, name)
 
 
 # --------------------------------------------------------------------------- closure
 @pytest.fixture(scope="module")
 def step_names(ua):
-    """The launches of one eager bf16x3 training step of UNet() at N = 8, 512 x 512 (forward,
-    loss, backward, SGD), c32 switch as the network sets it: the authority for the name set."""
-    from oracle import unet_ref as O
-    torch.manual_seed(0)
-    model = ua.UNet().to(DEV).train()
-    model.matmul_precision = "bf16x3"
-    opt = ua.create_optimizer(model)
-    lossf = ua.get_loss_function()
-    img, tgt = O.synthetic_batch(1234, 8, 512, 512)
-    img, tgt = img.to(DEV), tgt.to(DEV)
-    with ua.ops.record_launches() as rec:
-        loss = ua.train_step(model, opt, lossf, img, tgt)
-        torch.cuda.synchronize()
-    assert torch.isfinite(loss)
-    return rec.names
+    """The launches of one eager bf16x3 training step of UNet() at N = 8, 512 x 512."""
+    return HS.record_step(ua, MODE.name)
 
 
 def test_every_bf16x3_step_kernel_is_held(step_names):
     """Every kernel of the step is one a row of LAYERS or an entry of ALLOWED holds: a dispatch
     change that sends a layer to another tile, or to the fp32 fallback, fails here or in its row."""
-    assert len(step_names) > 100
-    held = set(ALLOWED).union(*(r[4] for r in LAYERS))
-    stray = sorted(set(step_names) - held)
-    assert not stray, "kernels of the bf16x3 step no case holds:\n" + "\n".join(stray)
+    HS.check_step_is_held(step_names, MODE.name, LAYERS, ALLOWED)
 
 
 def test_every_row_kernel_runs_in_the_step(step_names):
     """The converse: a row (or an ALLOWED entry) for a kernel the step no longer launches is dead
     weight that still looks like coverage."""
-    step = set(step_names)
-    dead = sorted((r[0], n) for r in LAYERS for n in set(r[4]) if n not in step)
-    dead += sorted(("ALLOWED", n) for n in ALLOWED if n not in step)
-    assert not dead, "rows for kernels the bf16x3 step does not launch:\n" + \
-        "\n".join(f"{i}: {n}" for i, n in dead)
+    HS.check_rows_run_in_the_step(step_names, MODE.name, LAYERS, ALLOWED)
 
 
 def test_the_step_runs_all_twelve_split_forms(step_names):

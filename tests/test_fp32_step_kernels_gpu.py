@@ -2,7 +2,9 @@
 
 The benchmark's default mode is the fp32 step (N = 8, 512 x 512).  Its selectors switch on tile
 counts as well as on shape, so a small test shape says nothing about the kernel the step runs
-unless the launch is asserted.  Each row of LAYERS is one call of that step - the same `ops`
+unless the launch is asserted.  The runners, bounds and shared kernel names are those of
+tests/tools/step_kernel_harness.py; this file holds the fp32 operand mode (MODE) and its table.
+Each row of LAYERS is one call of that step - the same `ops`
 function with the operand mode unet.py uses for the layer (activation on load with per-image
 coefficients, two sources where the layer has two, the Winograd weight forms of the PackTable
 the network builds, a NextNorm where the network passes one, ci_offset / accumulate where it
@@ -23,7 +25,7 @@ chunk and column-tile counts differ.  Each case
   * records the launches of the call (ops.record_launches) and asserts they are the row's names;
   * holds the result to a float64 evaluation of the SAME fp32 operands, one image at a time on
     the GPU (tests/tools/fp64_layer_refs.py), within the bound the existing small-shape test of
-    the same entry point uses (TOL_* below: 2e-5 on y and dx, 5e-5 on rstd / alpha / beta,
+    the same entry point uses (TOL_* of the harness: 2e-5 on y and dx, 5e-5 on rstd / alpha / beta,
     3e-5 on dw and the low-resolution gradients, 1e-5..2e-5 on the head, 5e-5 on the
     InstanceNorm backward);
   * forward rows check mean, rstd, alpha, beta; BSTATS rows check that the gradient is bit-equal
@@ -105,337 +107,58 @@ import importlib.util
 import os
 
 import pytest
-import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(
-        name, os.path.join(ROOT, "tests", "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+_spec = importlib.util.spec_from_file_location("step_kernel_harness", os.path.join(
+    os.path.dirname(os.path.abspath(__file__)), "tools", "step_kernel_harness.py"))
+HS = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(HS)
+R = HS.R
 
 
-R = _load("fp64_layer_refs")
-DEV, SLOPE, EPS = R.DEV, R.SLOPE, R.EPS
-grand, coeffs, nchw64, act64, metric = R.grand, R.coeffs, R.nchw64, R.act64, R.metric
-
-# The bounds of the existing small-shape tests of the same entry points (relative to the
-# tensor's max magnitude unless a scale is given).
-TOL_Y = 2e-5         # test_fused_gpu.py::test_conv_in_fwd: y, and mean on the scale max |y| + 1
-TOL_STAT = 5e-5      # ... rstd, alpha, and beta on its own scale
-TOL_DX = 2e-5        # test_kernels_gpu.py::test_conv3x3_bwd_data
-TOL_DW = 3e-5        # test_fused_gpu.py::test_conv_in_bwd_weight, test_kernels_gpu.py (dw)
-TOL_UP = 3e-5        # test_fused_gpu.py::test_conv3x3_up_backward_at_low_resolution (dw and g)
-TOL_TAPS = 1e-6      # test_kernels_gpu.py::test_upsample2x (the same stencil, 4-term sums)
-TOL_BS = 2e-5        # test_fused_gpu.py::_in_bwd_both_ways (summaries vs reduction pass)
-TOL_IN = 5e-5        # test_kernels_gpu.py::test_instnorm_lrelu_drop (dy, dgamma, dbeta)
-TOL_HEAD = 2e-5      # test_kernels_gpu.py::test_head1x1: 1e-5 (logits, da) .. 2e-5 (dw, db)
-TOL_HEAD_X = 1e-5
-
-
-# --------------------------------------------------------------------------- weight forms
+# --------------------------------------------------------------------------- the operand mode
 def pack(ua, w, stride):
     """The PackTable of one 3x3 layer as _Walk builds it in the fp32 mode: the packed layouts plus
     the Winograd forms of a stride-1 layer with >= 64 channels on both sides."""
     co, ci = w.shape[0], w.shape[1]
     s1 = stride == 1 and min(co, ci) >= 64
-    table = ua.ops.PackTable([w], False, [(s1 and co % 64 == 0 and ci % 8 == 0,
-                                          s1 and ci % 64 == 0 and co % 8 == 0)])
-    table.run()
-    return table
+    return HS.pack_one(ua, w, False, [(s1 and co % 64 == 0 and ci % 8 == 0,
+                                      s1 and ci % 64 == 0 and co % 8 == 0)])
 
 
-def summaries(ua, g, nn):
-    """The BSTATS summaries drive the InstanceNorm backward like the stand-alone reduction pass
-    over the same gradient does (test_fused_gpu.py::_in_bwd_both_ways)."""
-    assert nn.tiles > 0, "no BSTATS epilogue ran"
-    C = nn.y.shape[3]
-    outs = []
-    for partials in ((nn.partial, nn.tiles), None):
-        dg, db, dbias = (torch.empty(C, device=DEV) for _ in range(3))
-        dz = ua.ops.instnorm_lrelu_drop_bwd(g.clone(), nn.y, nn.st[0], nn.st[1], nn.gamma, nn.beta,
-                                            nn.mask, SLOPE, dg, db, dbias, partials=partials)
-        outs.append((dz, dg, db))
-    return [metric(what + " via summaries", a, b, TOL_BS)
-            for a, b, what in zip(outs[0], outs[1], ("dz", "dgamma", "dbeta"))]
+def forms(ua, op, table, grid=None, held=True):
+    """wu / ud: the Winograd form where the PackTable holds one, the walk holds it for this source
+    and the Winograd kernel tiles the grid; bf16 = "fp32" on the data gradient."""
+    def form(u, supported):
+        return u if u is not None and held and supported(*grid) else None
+
+    if op == "fwd":
+        return dict(wu=form(table.uf[0], ua.ops.conv_wino_supported))
+    if op == "up_fwd":
+        return dict(wu=form(table.uf[0], ua.ops.conv_up_wino_supported))
+    if op == "dgrad":
+        return dict(bf16="fp32", ud=form(table.ud[0], ua.ops.conv_wino_supported))
+    return {}
 
 
-def next_norm(ua, n, H, W, C, seed):
-    return ua.ops.NextNorm(*R.norm_layer(n, H, W, C, seed), SLOPE)
-
-
-def fused_stats(y_ref, st, gamma, beta, mask):
-    """mean, rstd, alpha, beta of the fused forward against fp64 (test_conv_in_fwd's rules)"""
-    mean = y_ref.mean(dim=(2, 3))
-    rstd = 1.0 / torch.sqrt(y_ref.var(dim=(2, 3), unbiased=False) + EPS)
-    gm, mk = gamma.double()[None], mask.double()
-    scale = (beta.abs().max() + (mean * gm * rstd).abs().max()).item() / 0.7
-    return [metric("mean", st[0], mean, TOL_Y, scale=y_ref.abs().max().item() + 1),
-            metric("rstd", st[1], rstd, TOL_STAT),
-            metric("alpha", st[2], gm * rstd * mk, TOL_STAT),
-            metric("beta", st[3], (beta.double()[None] - mean * gm * rstd) * mk, TOL_STAT,
-                   scale=scale)]
-
-
-# --------------------------------------------------------------------------- one runner per call
-# Each returns (recorded kernel names, metrics[, metrics against an altered reference]).  N, H, W:
-# the layer's input grid.  drop_row = (image, row): the check of the check - the reference is
-# evaluated a second time with that row zeroed (input row for a forward, dy row for gradients).
-def run_fwd(ua, N, H, W, C0, C1, Cout, stride, drop_row=None):
-    """unet_conv_in_fwd / unet_conv_in_fwd_wino as _Walk.run_layer_fused calls it: sources
-    activated on load with per-image coefficients, dropout mask folded into alpha / beta."""
-    x0, c0 = grand((N, H, W, C0), 1), coeffs(N, C0, 10)
-    x1, c1 = (grand((N, H, W, C1), 2), coeffs(N, C1, 20)) if C1 else (None, None)
-    w = R.he_weight(Cout, C0 + C1, 3, 9 * (C0 + C1))
-    b, gamma, beta = grand((Cout,), 4, 0.3), grand((Cout,), 5) * 0.2 + 1.0, grand((Cout,), 6) * 0.2
-    mask = R.keep_mask(N, Cout, 7, 0.7)
-    table = pack(ua, w, stride)
-    wu = table.uf[0] if table.uf[0] is not None and \
-        ua.ops.conv_wino_supported(N, H, W, C0, C1, Cout) else None
-    s0 = ua.ops.Act(x0, *c0)
-    s1 = ua.ops.Act(x1, *c1) if C1 else None
-    with ua.ops.c32_winograd_scope(True), ua.ops.record_launches() as rec:
-        y, st = ua.ops.conv_in_fwd(s0, s1, SLOPE, table.wf[0], b, 3, stride, gamma, beta, EPS, mask,
-                                   wu=wu)
-    a = act64(x0, *c0)
-    if C1:
-        a = torch.cat([a, act64(x1, *c1)], 1)
-    y_ref = R.ref_conv(a, w.double(), b.double(), stride)
-    metrics = [metric("y", nchw64(y), y_ref, TOL_Y)] + fused_stats(y_ref, st, gamma, beta, mask)
-    if drop_row is None:
-        return rec.names, metrics
-    a[drop_row[0], :, drop_row[1], :] = 0
-    return rec.names, metrics, [metric("y against the reference without one input row", nchw64(y),
-                                       R.ref_conv(a, w.double(), b.double(), stride), TOL_Y)]
-
-
-def run_stem_fwd(ua, N, H, W):
-    """unet_conv_in_fwd on the plain RGB image (3 -> 32)."""
-    x = grand((N, H, W, 3), 1)
-    w = R.he_weight(32, 3, 2, 27)
-    b, gamma, beta = grand((32,), 3, 0.1), grand((32,), 5) * 0.2 + 1.0, grand((32,), 6) * 0.2
-    mask = torch.ones(N, 32, device=DEV)
-    table = pack(ua, w, 1)
-    with ua.ops.c32_winograd_scope(True), ua.ops.record_launches() as rec:
-        y, st = ua.ops.conv_in_fwd(ua.ops.Act(x), None, SLOPE, table.wf[0], b, 3, 1, gamma, beta,
-                                   EPS, None)
-    y_ref = R.ref_conv(nchw64(x), w.double(), b.double(), 1)
-    return rec.names, [metric("y", nchw64(y), y_ref, TOL_Y)] + \
-        fused_stats(y_ref, st, gamma, beta, mask)
-
-
-def run_up_fwd(ua, N, h, w, C0, C1, Cout):
-    """unet_conv_up_in_fwd / _wino as _Walk.run_up_layer calls it: bilinear 2x up-sampling of the
-    activated low-resolution source [N, h, w, C0] in the loader, activated skip [N, 2h, 2w, C1]."""
-    low, cl = grand((N, h, w, C0), 1), coeffs(N, C0, 10)
-    skip, cs = grand((N, 2 * h, 2 * w, C1), 2), coeffs(N, C1, 20)
-    wt = R.he_weight(Cout, C0 + C1, 3, 9 * (C0 + C1))
-    b, gamma, beta = grand((Cout,), 4, 0.3), grand((Cout,), 5) * 0.2 + 1.0, grand((Cout,), 6) * 0.2
-    mask = R.keep_mask(N, Cout, 7, 0.7)
-    table = pack(ua, wt, 1)
-    s_low, s_skip = ua.ops.Act(low, *cl), ua.ops.Act(skip, *cs)
-    with ua.ops.c32_winograd_scope(True):
-        assert ua.ops.conv_up_in_fwd_supported(s_low, s_skip, Cout)    # what run_up_layer asks
-        wu = table.uf[0] if table.uf[0] is not None and \
-            ua.ops.conv_up_wino_supported(N, 2 * h, 2 * w, C0, C1, Cout) else None
-        with ua.ops.record_launches() as rec:
-            y, st = ua.ops.conv_up_in_fwd(s_low, s_skip, SLOPE, table.wf[0], b, gamma, beta, EPS,
-                                          mask, wu=wu)
-    a = torch.cat([R.upsample64(act64(low, *cl)), act64(skip, *cs)], 1)
-    y_ref = R.ref_conv(a, wt.double(), b.double(), 1)
-    metrics = [metric("y", nchw64(y), y_ref, TOL_Y)] + fused_stats(y_ref, st, gamma, beta, mask)
-    return rec.names, metrics
-
-
-def run_dgrad(ua, N, H, W, Cin, Cout, stride, nxt=False, acc=False, ci_off=0, cin_total=None,
-              drop_row=None):
-    """unet_conv3x3_bwd_data[_bs][_wino] as _Walk.layer_bwd calls it: dx[N, H, W, Cin] (+)= the
-    data gradient of dy for input channels [ci_off, ci_off + Cin) of a layer with cin_total
-    inputs; nxt = with the BSTATS epilogue; acc = accumulate into the gradient the decoder left in
-    the skip.  The Winograd form where the network holds one (lone source, or the skip half of a
-    decoder stage's first convolution)."""
-    cin_total = cin_total or Cin
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    dy = grand((N, Ho, Wo, Cout), 1)
-    w = R.he_weight(Cout, cin_total, 2, 9 * Cout)
-    base = grand((N, H, W, Cin), 3) if acc else None
-    nn = next_norm(ua, N, H, W, Cin, 10) if nxt else None
-    table = pack(ua, w, stride)
-    # (weight_forms: ud for a lone source, ud1 for the skip half - the same test on (Cout, Cin))
-    ud = table.ud[0] if table.ud[0] is not None and (cin_total == Cin or ci_off) and \
-        ua.ops.conv_wino_supported(N, H, W, Cout, 0, Cin) else None
-
-    def call(nxt_):
-        return ua.ops.conv3x3_bwd_data(dy, table.wd[0], ci_off, Cin, H, W, stride,
-                                       out=base.clone() if acc else None, accumulate=acc,
-                                       bf16="fp32", nxt=nxt_, ud=ud)
-
-    with ua.ops.c32_winograd_scope(True):
-        with ua.ops.record_launches() as rec:
-            dx = call(nn)
-        plain = call(None) if nxt else None
-    wsl = w.double()[:, ci_off:ci_off + Cin]
-    dyd = nchw64(dy)
-    ref = R.ref_dgrad(dyd, wsl, stride, H, W)
-    if acc:
-        ref += nchw64(base)
-    metrics = [metric("dx", nchw64(dx), ref, TOL_DX)]
-    if nxt:
-        assert torch.equal(plain, dx), "the BSTATS epilogue changed the gradient"
-        metrics += summaries(ua, dx, nn)
-    if drop_row is None:
-        return rec.names, metrics
-    dyd = dyd.clone()
-    dyd[drop_row[0], :, drop_row[1], :] = 0
-    bad = R.ref_dgrad(dyd, wsl, stride, H, W) + (nchw64(base) if acc else 0)
-    return rec.names, metrics, [metric("dx against the reference without one dy row", nchw64(dx),
-                                       bad, TOL_DX)]
-
-
-def run_wgrad(ua, N, H, W, Cx, Cout, stride, ci_off=0, cin_total=None, drop_row=None):
-    """unet_conv_in_bwd_weight: dw[:, ci_off : ci_off + Cx] of a layer with cin_total inputs,
-    operand x [N, H, W, Cx] activated on load; the other columns keep a sentinel."""
-    cin_total = cin_total or Cx
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    x, coef = grand((N, H, W, Cx), 1), coeffs(N, Cx, 30)
-    dy = grand((N, Ho, Wo, Cout), 2)
-    dw = torch.full((Cout, cin_total, 3, 3), 7.0, device=DEV)
-    with ua.ops.c32_winograd_scope(True), ua.ops.record_launches() as rec:
-        ua.ops.conv_in_bwd_weight(ua.ops.Act(x, *coef), SLOPE, dy, dw, ci_off, 3, stride)
-    outside = torch.cat([dw[:, :ci_off], dw[:, ci_off + Cx:]], 1)
-    assert bool((outside == 7.0).all()), "the weight gradient wrote outside its input-channel slice"
-    a, dyd = act64(x, *coef), nchw64(dy)
-    got = dw[:, ci_off:ci_off + Cx]
-    ref = R.ref_wgrad(a, dyd, stride)
-    metrics = [metric("dw", got, ref, TOL_DW)]
-    if drop_row is None:
-        return rec.names, metrics
-    dyd = dyd.clone()
-    dyd[drop_row[0], :, drop_row[1], :] = 0
-    return rec.names, metrics, [metric("dw against the reference without one dy row", got,
-                                       R.ref_wgrad(a, dyd, stride), TOL_DW)]
-
-
-def run_stem_wgrad(ua, N, H, W):
-    """unet_conv_in_bwd_weight of the stem: the plain RGB image."""
-    x = grand((N, H, W, 3), 1)
-    dy = grand((N, H, W, 32), 2)
-    dw = torch.zeros(32, 3, 3, 3, device=DEV)
-    with ua.ops.c32_winograd_scope(True), ua.ops.record_launches() as rec:
-        ua.ops.conv_in_bwd_weight(ua.ops.Act(x), SLOPE, dy, dw, 0, 3, 1)
-    return rec.names, [metric("dw", dw, R.ref_wgrad(nchw64(x), nchw64(dy), 1), TOL_DW)]
-
-
-def run_taps(ua, N, h, w, C, drop_row=None):
-    """unet_upsample2x_bwd_taps: D[N, h, w, 9 C] from dy[N, 2h, 2w, C]."""
-    dy = grand((N, 2 * h, 2 * w, C), 1)
-    with ua.ops.record_launches() as rec:
-        D = ua.ops.upsample2x_bwd_taps(dy)
-    dyd = nchw64(dy)
-    metrics = [metric("D", D, R.ref_taps(dyd), TOL_TAPS)]
-    if drop_row is None:
-        return rec.names, metrics
-    dyd = dyd.clone()
-    dyd[drop_row[0], :, drop_row[1], :] = 0
-    return rec.names, metrics, [metric("D against the reference without one dy row", D,
-                                       R.ref_taps(dyd), TOL_TAPS)]
-
-
-def run_up_wgrad(ua, N, h, w, Cx, Cout, cin_total):
-    """unet_conv3x3_up_bwd_weight: dw[:, 0:Cx] of conv3x3(upsample2x(act(low))) as a GEMM over the
-    low-resolution pixels; the skip's columns keep a sentinel."""
-    low, coef = grand((N, h, w, Cx), 1), coeffs(N, Cx, 40)
-    D = grand((N, h, w, 9 * Cout), 2)
-    dw = torch.full((Cout, cin_total, 3, 3), 7.0, device=DEV)
-    with ua.ops.record_launches() as rec:
-        ua.ops.conv3x3_up_bwd_weight(ua.ops.Act(low, *coef), SLOPE, D, dw, 0)
-    assert bool((dw[:, Cx:] == 7.0).all()), "the weight gradient wrote outside its input-channel slice"
-    a = act64(low, *coef)
-    ref = R.ref_up_wgrad(a, D.double())
-    return rec.names, [metric("dw", dw[:, :Cx], ref, TOL_UP)]
-
-
-def run_up_dgrad(ua, N, h, w, C0, Cout, cin_total):
-    """unet_conv3x3_up_bwd_data_bs: the low-resolution data gradient of the up-sampled operand as a
-    GEMM g = D B, with the BSTATS epilogue of the layer that produced the low-resolution tensor."""
-    wt = R.he_weight(Cout, cin_total, 3, 9 * Cout)
-    table = pack(ua, wt, 1)
-    D = grand((N, h, w, 9 * Cout), 5)
-    nn = next_norm(ua, N, h, w, C0, 20)
-    with ua.ops.record_launches() as rec:
-        g = ua.ops.conv3x3_up_bwd_data(D, table.wd[0], 0, C0, nxt=nn)
-    ref = R.ref_up_dgrad(D.double(), wt.double()[:, :C0])
-    plain = ua.ops.conv3x3_up_bwd_data(D, table.wd[0], 0, C0)
-    assert torch.equal(plain, g), "the BSTATS epilogue changed the gradient"
-    return rec.names, [metric("g", g, ref, TOL_UP)] + summaries(ua, g, nn)
-
-
-def run_head_fwd(ua, N, H, W):
-    """unet_head1x1_in_fwd: logits (NCHW) of the 1x1 head over the activated last decoder output."""
-    y, coef = grand((N, H, W, 32), 1), coeffs(N, 32, 50)
-    w, b = grand((3, 32), 2, 0.2), grand((3,), 3, 0.1)
-    with ua.ops.record_launches() as rec:
-        logits = ua.ops.head1x1_in_fwd(ua.ops.Act(y, *coef), SLOPE, w, b)
-    ref = torch.einsum("nchw,kc->nkhw", act64(y, *coef), w.double()) + b.double()[None, :, None, None]
-    return rec.names, [metric("logits", logits, ref, TOL_HEAD_X)]
-
-
-def run_head_bwd(ua, N, H, W):
-    """unet_head1x1_in_bwd_bs: da = W^T dlogits, dW, db and the InstanceNorm-backward reductions
-    of the last decoder layer (whose raw output the head reads)."""
-    nn = next_norm(ua, N, H, W, 32, 60)
-    al, be = (nn.st[2] * nn.mask).contiguous(), (nn.st[3] * nn.mask).contiguous()
-    x = ua.ops.Act(nn.y, al, be)
-    dl = grand((N, 3, H, W), 2)
-    w = grand((3, 32), 3, 0.2)
-    dw, db = torch.empty(3, 32, device=DEV), torch.empty(3, device=DEV)
-    with ua.ops.record_launches() as rec:
-        da = ua.ops.head1x1_in_bwd(x, SLOPE, dl, w, dw, db, nxt=nn)
-    a, dld = act64(nn.y, al, be), dl.double()
-    metrics = [metric("da", nchw64(da), torch.einsum("nkhw,kc->nchw", dld, w.double()), TOL_HEAD_X),
-               metric("dw", dw, torch.einsum("nkhw,nchw->kc", dld, a), TOL_HEAD),
-               metric("db", db, dld.sum(dim=(0, 2, 3)), TOL_HEAD)]
-    return rec.names, metrics + summaries(ua, da, nn)
-
-
-def run_in_bwd(ua, N, H, W, C, fed):
-    """unet_instnorm_lrelu_drop_bwd[_partials]: InstanceNorm + LeakyReLU + dropout backward
-    against fp64 autograd.  fed: the reductions come as BSTATS summaries of the producer of g (here
-    the stand-alone up data gradient with Cout = 32), as in the step; else the stand-alone
-    reduction pass runs."""
-    y, st, gamma, beta, mask = R.norm_layer(N, H, W, C, 70)
-    partials = None
-    if fed:
-        nn = ua.ops.NextNorm(y, st, gamma, beta, mask, SLOPE)
-        wt = R.he_weight(32, C, 3, 9 * 32)
-        g = ua.ops.conv3x3_up_bwd_data(grand((N, H, W, 9 * 32), 5), pack(ua, wt, 1).wd[0], 0, C,
-                                       nxt=nn)
-        assert nn.tiles > 0, "no BSTATS epilogue ran"
-        partials = (nn.partial, nn.tiles)
-    else:
-        g = grand((N, H, W, C), 71)
-    dz_ref, dg_ref, db_ref = R.ref_in_bwd(g, y, gamma, beta, mask)
-    dg, db, dbias = (torch.empty(C, device=DEV) for _ in range(3))
-    with ua.ops.record_launches() as rec:
-        dz = ua.ops.instnorm_lrelu_drop_bwd(g.clone(), y, st[0], st[1], gamma, beta, mask, SLOPE,
-                                            dg, db, dbias, partials=partials)
-    return rec.names, [metric("dz", dz, dz_ref, TOL_IN), metric("dgamma", dg, dg_ref, TOL_IN),
-                       metric("dbeta", db, db_ref, TOL_IN),
-                       # the conv-bias gradient = sum of dz: mathematically 0 (test_kernels_gpu.py's rule)
-                       metric("dbias", dbias, torch.zeros(C, dtype=torch.double, device=DEV), 1e-3,
-                              scale=max(1.0, dz_ref.abs().sum().item() / C))]
-
+MODE = HS.Mode("fp32", False, pack, forms)
 
 # --------------------------------------------------------------------------- the table
-# Kernel names as ops.record_launches reports them (demangled).
-_NS, _AN = "unet_conv::(anonymous namespace)::", "(anonymous namespace)::"
-_F2 = "HIP_vector_type<float, 2u>"
+# The runners and the kernel names more than one table uses: tests/tools/step_kernel_harness.py.
+run_fwd, run_stem_fwd, run_up_fwd, run_dgrad = HS.run_fwd, HS.run_stem_fwd, HS.run_up_fwd, HS.run_dgrad
+run_wgrad, run_stem_wgrad, run_taps, run_up_wgrad = \
+    HS.run_wgrad, HS.run_stem_wgrad, HS.run_taps, HS.run_up_wgrad
+run_up_dgrad, run_head_fwd, run_head_bwd, run_in_bwd = \
+    HS.run_up_dgrad, HS.run_head_fwd, HS.run_head_bwd, HS.run_in_bwd
+patch_s2, dgrad_s2, igemm, wgrad, wtaps = HS.patch_s2, HS.dgrad_s2, HS.igemm, HS.wgrad, HS.wtaps
+REDUCE, FIN_GRP, FIN_COMB, FIN_EQ, TAPS = HS.REDUCE, HS.FIN_GRP, HS.FIN_COMB, HS.FIN_EQ, HS.TAPS
+STEM_FWD, STEM_WGRAD, HEAD_FWD, HEAD_BWD = HS.STEM_FWD, HS.STEM_WGRAD, HS.HEAD_FWD, HS.HEAD_BWD
+HEAD_BWD_FIN, IN_FIN1, IN_APPLY, IN_REDUCE = HS.HEAD_BWD_FIN, HS.IN_FIN1, HS.IN_APPLY, HS.IN_REDUCE
+_NS, _AN = HS._NS, HS._AN
 
 
+# The Winograd kernels of this mode.
 def wino(act, stats, bstats, up):
     """conv_wino_kernel<ACT, STATS, BSTATS, UP>"""
     t = ", ".join("true" if f else "false" for f in (act, stats, bstats, up))
@@ -446,56 +169,9 @@ def wino32q(fused):
     return f"void {_NS}conv_wino32q_kernel<{'true' if fused else 'false'}>(unet_conv::IgemmParams, int)"
 
 
-def patch_s2(targs):
-    return f"void {_NS}conv_patch_s2_kernel<{targs}>(unet_conv::IgemmParams)"
-
-
-def dgrad_s2(targs):
-    return f"void {_NS}conv_dgrad_s2_patch_kernel<{targs}>(unet_conv::IgemmParams)"
-
-
-def igemm(bm, bn, wm, wn, act, kg):
-    """conv_igemm_kernel<BM, BN, WM, WN, 32, ACT, KG>: KG = K groups of a workgroup"""
-    return (f"void {_NS}conv_igemm_kernel<{bm}, {bn}, {wm}, {wn}, 32, {'true' if act else 'false'}, "
-            f"{kg}>(unet_conv::IgemmParams)")
-
-
-def wgrad(targs):
-    """conv_wgrad_kernel<CI_T, CO_T, S, STRIDE, ACT, float, float, waves>"""
-    return f"void {_AN}conv_wgrad_kernel<{targs}>({_AN}WgradParams)"
-
-
-def wtaps(targs):
-    return f"void {_AN}conv_wgrad_taps_kernel<{targs}>({_AN}WgradParams)"
-
-
 WINO_UP32 = f"{_NS}conv_wino_up32_kernel(unet_conv::IgemmParams, int)"
 WGRAD_WINO = f"void {_AN}conv_wgrad_wino_kernel<true>({_AN}WgradParams)"
 WGRAD_WINO32 = f"void {_AN}conv_wgrad_wino32_kernel<true>({_AN}WgradParams, int)"
-REDUCE = f"{_AN}wgrad_reduce_batched_kernel({_AN}ReduceTable)"
-FIN_GRP = f"{_AN}in_stats_finalize_grp_kernel({_F2} const*, {_F2}*, int, int, float)"
-FIN_COMB = (f"{_AN}in_stats_finalize_comb_kernel({_F2} const*, {_F2} const*, float const*, "
-            "float const*, float, float const*, float*, float*, float*, float*, int, int, int, int, "
-            "float)")
-FIN_EQ = (f"{_AN}in_stats_finalize_eq_kernel({_F2} const*, float const*, float const*, float, "
-          "float const*, float*, float*, float*, float*, int, int, int, float)")
-STEM_FWD = (f"void {_NS}conv_stem_fwd_walk_kernel<float, float, 8>(float const*, float const*, "
-            f"float const*, float*, int, int, int, int, {_F2}*, {_NS}StemNorm)")
-STEM_WGRAD = (f"void {_AN}conv_stem_wgrad_rows_kernel<float, float>(float const*, float const*, "
-              f"float*, int, int, int, int, int, long long, {_AN}StemNormW)")
-HEAD_FWD = (f"void {_AN}head_fwd_kernel<float>(float const*, float const*, float const*, float*, "
-            "long long, int, int, float const*, float const*, float)")
-HEAD_BWD = (f"void {_AN}head_bwd_kernel<float>(float const*, float const*, float const*, float*, "
-            f"float*, long long, int, int, long long, float const*, float const*, float, {_AN}HeadBs)")
-HEAD_BWD_FIN = f"{_AN}head_bwd_finalize_kernel(float const*, float*, float*, int, int)"
-TAPS = (f"void {_AN}upsample2x_bwd_taps_kernel<float, 1>(float const*, float*, int, int, int, "
-        "long long)")
-IN_FIN1 = f"{_AN}in_bwd_finalize1_kernel({_F2} const*, {_F2}*, {_F2}*, int, int, int)"
-IN_APPLY = (f"void {_AN}in_bwd_apply_kernel<float>(float const*, float const*, float const*, "
-            "float const*, float const*, float const*, float const*, float, "
-            f"{_F2} const*, float*, float*, int, int, int, {_F2} const*, float*, float*, float*)")
-IN_REDUCE = (f"void {_AN}in_bwd_reduce_kernel<float>(float const*, float const*, float const*, "
-             f"float const*, float const*, float const*, float const*, float, {_F2}*, int, int, int)")
 
 # (id, the layers of UNet() it stands for, runner, arguments, expected kernel names in launch
 # order).  Encoder stage e, conv k: "e<e>.<k>"; decoder stage d: "d<d>.<k>".  Layers with the same
@@ -744,7 +420,7 @@ LAYERS = [
 
 # The stand-alone reduction pass of the InstanceNorm backward: the fp32 step never launches it
 # (every gradient comes with BSTATS summaries), the stand-alone pipeline and odd shapes do, and
-# `summaries` above compares against it - so it is held against fp64 here too, outside LAYERS.
+# HS.summaries compares against it - so it is held against fp64 here too, outside LAYERS.
 EXTRA = [
     ("in bwd 32 reduce", "stand-alone pipeline", run_in_bwd, dict(N=2, H=16, W=32, C=32, fed=False)),
     ("in bwd 512 reduce", "stand-alone pipeline", run_in_bwd, dict(N=2, H=8, W=16, C=512, fed=False)),
@@ -754,20 +430,21 @@ EXTRA = [
 @pytest.mark.parametrize("row", LAYERS, ids=[r[0] for r in LAYERS])
 def test_step_layer_fp32(ua, row):
     ident, layers, runner, kw, expected = row
-    names, metrics = runner(ua, **kw)
-    print(f"{ident}: {R.report(metrics)}")
-    assert names == list(expected), f"{ident} ({layers}) launched {names}"
-    bad = R.failures(metrics)
+    out = runner(ua, MODE, **kw)
+    print(f"{ident}: {R.report(out['metrics'])}")
+    assert out["names"] == list(expected), f"{ident} ({layers}) launched {out['names']}"
+    bad = R.failures(out["metrics"])
     assert not bad, f"{ident} ({layers}):\n" + "\n".join(bad)
 
 
 @pytest.mark.parametrize("row", EXTRA, ids=[r[0] for r in EXTRA])
 def test_instnorm_backward_reduction_pass(ua, row):
     ident, layers, runner, kw = row
-    names, metrics = runner(ua, **kw)
-    print(f"{ident}: {R.report(metrics)}")
+    out = runner(ua, MODE, **kw)
+    names = out["names"]
+    print(f"{ident}: {R.report(out['metrics'])}")
     assert IN_REDUCE in names and names[-1] == IN_APPLY, f"{ident} launched {names}"
-    bad = R.failures(metrics)
+    bad = R.failures(out["metrics"])
     assert not bad, f"{ident} ({layers}):\n" + "\n".join(bad)
 
 
@@ -782,111 +459,44 @@ MISSING_ROW = [("fwd 64->64", (1, 77)), ("dgrad 64<-64 bstats", (1, 77)), ("wgra
 @pytest.mark.parametrize("ident,drop_row", MISSING_ROW, ids=[m[0] for m in MISSING_ROW])
 def test_check_sees_one_missing_row(ua, ident, drop_row):
     row = next(r for r in LAYERS if r[0] == ident)
-    _, good, bad = row[2](ua, drop_row=drop_row, **row[3])
-    assert not R.failures(good), R.failures(good)
-    assert R.failures(bad), f"the check cannot see a missing row: {bad}"
+    out = row[2](ua, MODE, drop_row=drop_row, **row[3])
+    assert not R.failures(out["metrics"]), R.failures(out["metrics"])
+    assert R.failures(out["bad"]), f"the check cannot see a missing row: {out['bad']}"
 
 
 # --------------------------------------------------------------------------- the other kernels
-# The kernels of the fp32 step that are neither convolutions nor norm / head kernels with a row
-# above: name -> (the existing test that holds it against a reference, that test's smallest
-# call).  test_allowed_kernel_is_launched_by_its_test runs the call and requires the name, so an
-# entry is a checked claim.
-def _call_layout(ua):
-    ua.ops.nchw_to_nhwc(grand((2, 3, 10, 14), 1))
-
-
-def _call_pack(ua):
-    ua.ops.PackTable([grand((32, 3, 3, 3), 1), grand((64, 32, 3, 3), 2)], False).run()
-
-
-def _call_wino_pack(ua):
-    ua.ops.PackTable([grand((64, 64, 3, 3), 1), grand((32, 32, 3, 3), 4)], False,
+# HS.ALLOWED (name -> the test that holds it, that test's smallest call) plus this mode's own.
+def _call_wino_pack(ua, mode):
+    ua.ops.PackTable([HS.grand((64, 64, 3, 3), 1), HS.grand((32, 32, 3, 3), 4)], False,
                      [(True, True), (False, False)]).run()
 
 
-def _call_loss(ua):
-    g = torch.Generator(device=DEV).manual_seed(1)
-    lg = torch.randn((2, 3, 24, 40), generator=g, device=DEV) * 2.0
-    tg = torch.randint(0, 3, (2, 24, 40), generator=g, device=DEV)
-    tg[:, :2, :] = 255
-    ua.ops.dice_wce_loss_fwd_bwd(lg, tg, 1e-5, 1.0, 1.0, 255, True)
+ALLOWED = dict(HS.ALLOWED)
+ALLOWED[f"{_NS}wino_pack_batched_kernel(unet_wino_pack_entry const*, int)"] = \
+    ("test_fused_gpu.py::test_winograd_weight_packing_in_one_launch", _call_wino_pack)
 
 
-def _call_sgd(ua):
-    p, gr = grand((1003,), 30), grand((1003,), 31)
-    ua.ops.sgd_nesterov_step(p, gr, torch.zeros_like(p), 0.005, 0.99, 1e-4, True)
-
-
-_LOSS_TEST = "test_kernels_gpu.py::test_loss_vs_oracle"
-ALLOWED = {
-    f"{_AN}nchw_to_nhwc_kernel(float const*, float*, int, long long, long long)":
-        ("test_kernels_gpu.py::test_layout_roundtrip", _call_layout),
-    f"{_AN}pack_w_batched_kernel(unet_pack_entry const*, int)":
-        ("test_kernels_gpu.py::test_pack_weights_batched_matches_per_layer", _call_pack),
-    f"{_NS}wino_pack_batched_kernel(unet_wino_pack_entry const*, int)":
-        ("test_fused_gpu.py::test_winograd_weight_packing_in_one_launch", _call_wino_pack),
-    f"{_AN}loss_reduce_kernel(float const*, long long const*, float*, int, int)":
-        (_LOSS_TEST, _call_loss),
-    f"{_AN}loss_finalize_kernel(float const*, int, int, float, float, float, int, float const*, "
-    f"float, float*, {_AN}LossCoef*, float*)":
-        (_LOSS_TEST, _call_loss),
-    f"{_AN}loss_grad_kernel(float const*, long long const*, {_AN}LossCoef const*, float const*, "
-    "float*, int, int, float const*)":
-        (_LOSS_TEST, _call_loss),
-    f"{_AN}sgd_nesterov_kernel(float*, float const*, float*, long long, float, float, float, int, "
-    "float, float const*)":
-        ("test_kernels_gpu.py::test_sgd_odd_length", _call_sgd),
-}
-_CONV_WORDS = ("conv", "wgrad", "taps", "wino_up", "wino32", "igemm", "patch")
-
-
-@pytest.mark.parametrize("name", sorted(ALLOWED),
-                         ids=[n.replace(_NS, "").replace(_AN, "").split("(")[0] for n in sorted(ALLOWED)])
+@pytest.mark.parametrize("name", sorted(ALLOWED), ids=HS.allowed_ids(ALLOWED))
 def test_allowed_kernel_is_launched_by_its_test(ua, name):
-    held_by, call = ALLOWED[name]
-    kernel = name.replace(_NS, "").replace(_AN, "").replace("void ", "").split("(")[0]
-    assert not any(w in kernel for w in _CONV_WORDS), \
-        f"{name}: a convolution kernel needs a row of LAYERS"
-    with ua.ops.record_launches() as rec:
-        call(ua)
-    assert name in rec.names, f"the call of {held_by} launched {rec.names}"
+    HS.check_allowed(ua, MODE, ALLOWED, name)
 
 
 # --------------------------------------------------------------------------- closure
 @pytest.fixture(scope="module")
 def step_names(ua):
-    """The launches of one eager fp32 training step of UNet() at N = 8, 512 x 512 (forward, loss,
-    backward, SGD), c32 switch as the network sets it: the authority for the name set."""
-    from oracle import unet_ref as O
-    torch.manual_seed(0)
-    model = ua.UNet().to(DEV).train()
-    model.matmul_precision = "fp32"
-    opt = ua.create_optimizer(model)
-    lossf = ua.get_loss_function()
-    img, tgt = O.synthetic_batch(1234, 8, 512, 512)
-    img, tgt = img.to(DEV), tgt.to(DEV)
-    with ua.ops.record_launches() as rec:
-        loss = ua.train_step(model, opt, lossf, img, tgt)
-        torch.cuda.synchronize()
-    assert torch.isfinite(loss)
-    return rec.names
+    """The launches of one eager fp32 training step of UNet() at N = 8, 512 x 512."""
+    return HS.record_step(ua, MODE.name)
 
 
 def test_every_fp32_step_kernel_is_held(step_names):
     """Every kernel of the step is one a row of LAYERS or an entry of ALLOWED holds: a dispatch
     change that brings in another fp32 kernel fails here until a case holds it."""
-    assert len(step_names) > 100
-    held = set(ALLOWED).union(*(r[4] for r in LAYERS))
-    stray = sorted(set(step_names) - held)
-    assert not stray, "kernels of the fp32 step no case holds:\n" + "\n".join(stray)
+    HS.check_step_is_held(step_names, MODE.name, LAYERS, ALLOWED)
 
 
 def test_every_row_kernel_runs_in_the_step(step_names):
     """The converse: a row (or an ALLOWED entry) for a kernel the step no longer launches is dead
     weight that still looks like coverage."""
-    step = set(step_names)
-    dead = sorted((r[0], n) for r in LAYERS for n in set(r[4]) if n not in step)
-    dead += sorted(("ALLOWED", n) for n in ALLOWED if n not in step)
-    assert not dead, "rows for kernels the fp32 step does not launch:\n" + \
-        "\n".join(f"{i}: {n}" for i, n in dead)
+    HS.check_rows_run_in_the_step(step_names, MODE.name, LAYERS, ALLOWED)
+
+

@@ -1,8 +1,9 @@
-"""Operands and float64 references shared by the per-layer kernel tests (tests/test_fp32_step_
-kernels_gpu.py, tests/test_bf16x3_step_kernels_gpu.py): the operand recipe of tests/test_bf16_
-bench_layers_gpu.py (device-seeded tensors, activation coefficients with ~15 % dropped channels,
-He-scaled weights, the layer a BSTATS epilogue reduces for) for fp32 tensors, plain fp64
-evaluations of every operation of the train step, one image at a time, on the GPU, and the
+"""Operands and float64 references shared by the per-layer kernel tests: the harness tests/tools/
+step_kernel_harness.py (tests/test_fp32_step_kernels_gpu.py, tests/test_bf16x3_step_kernels_gpu.py),
+tests/test_bf16_bench_layers_gpu.py, tests/test_fused_gpu.py, tests/test_fullres_folds_gpu.py and
+tests/test_wgrad32_folds_gpu.py.  The operand recipe (device-seeded tensors, activation
+coefficients with ~15 % dropped channels, He-scaled weights, the layer a BSTATS epilogue reduces
+for) for fp32 tensors, plain fp64 evaluations of every operation of the train step, one image at a time, on the GPU, and the
 float64 emulation of the split-bf16 operand mode's six products (with one left out on request).
 Nothing here calls the library."""
 import torch
