@@ -11,9 +11,14 @@
  *   - extern "C", plain pointers and sizes; no torch / C++ types.
  *   - every function returns 0 on success or a negative UNET_E_* code;
  *     unet_last_error() returns a thread-local message for the last failure.
- *   - all pointers are DEVICE pointers owned by the caller (no ownership
- *     transfer, no hidden allocation); workspaces are caller-provided and sized
- *     by the matching *_workspace_bytes() query.
+ *   - all data pointers are DEVICE pointers owned by the caller (no ownership
+ *     transfer, no hidden allocation) unless the parameter is marked UNET_HOST
+ *     (see the macro below); workspaces are caller-provided and sized by the
+ *     matching *_workspace_bytes() query.
+ *   - the Python binding is derived from this file by a small parser
+ *     (unet-implementations_amd/_header.py) that refuses what it does not know:
+ *     keep to one declaration per export, the scalar types int / float / double /
+ *     size_t / int64_t / uint64_t, plain pointers and `typedef struct` records.
  *   - every launch is asynchronous on `stream` (a hipStream_t passed as void*).
  *   - activations are NHWC fp32 ("pixel-major": [N][H][W][C]); logits and the
  *     input image cross the module boundary as NCHW, exactly like the reference.
@@ -38,6 +43,18 @@ extern "C" {
 #define UNET_E_WORKSPACE (-3) /* workspace too small */
 
 typedef void* unet_stream_t; /* hipStream_t */
+
+/* Where a pointer lives, for readers and for the Python binding, which parses this header; both
+ * macros expand to nothing.
+ *   UNET_HOST    A pointer to data (float*, void*, ...) is a device address unless marked so: then
+ *                the library dereferences it on the host during the call, and the binding types
+ *                `T* UNET_HOST p` as POINTER(T) instead of an address.  (The char buffer of
+ *                unet_debug_recorded_launches is host memory too and stays an address.)
+ *   UNET_DEVICE  A pointer to one of the records below (unet_act_src*, unet_bwd_stats*) is read
+ *                on the host during the call unless marked so: then it is a table in device
+ *                memory that the kernels read, an address to the binding. */
+#define UNET_HOST
+#define UNET_DEVICE
 
 const char* unet_last_error(void);
 int unet_abi_version(void);
@@ -155,8 +172,8 @@ typedef struct unet_pack_entry {
   int reserved;     /* planes: 0 or 3 = the three planes of the split-bf16 form; 1 = only plane 0,
                        the bf16-rounded weight (what the mixed-precision kernels stage) */
 } unet_pack_entry;
-int unet_pack_conv3x3_weights_batched(const unet_pack_entry* table_device, int n, int total_tiles,
-                                      unet_stream_t stream);
+int unet_pack_conv3x3_weights_batched(const unet_pack_entry* UNET_DEVICE table_device, int n,
+                                      int total_tiles, unet_stream_t stream);
 int unet_conv3x3_fwd_bf16x3(const float* x0, int C0, const float* x1, int C1, const float* wf,
                             const uint16_t* wf3, const float* bias, float* y, int N, int H, int W,
                             int Cout, int stride, unet_stream_t stream);
@@ -706,8 +723,8 @@ int unet_augment_light_apply(const uint8_t* image, uint8_t* image_out, const flo
  * > 2 other than 255 mapped to 0): PetSegmentationDataset.__getitem__, src/train.py:300-311.
  * mean3 / std3 are HOST pointers to 3 floats. */
 int unet_preprocess_u8(const uint8_t* image_hwc, const uint8_t* mask, float* out_nhwc,
-                       int64_t* target, int N, int H, int W, const float* mean3, const float* std3,
-                       unet_stream_t stream);
+                       int64_t* target, int N, int H, int W, const float* UNET_HOST mean3,
+                       const float* UNET_HOST std3, unet_stream_t stream);
 
 /* ---- SGD with Nesterov momentum over a flat arena -------------------------- */
 
@@ -758,8 +775,8 @@ typedef struct unet_act_src {
 size_t unet_conv_in_fwd_workspace_bytes(int N, int H, int W, int Cout, int stride);
 int unet_conv_in_fwd(const unet_act_src* s0, const unet_act_src* s1, float slope, const float* w,
                      const float* bias, int ksize, int stride, float* y, void* workspace,
-                     size_t workspace_bytes, int* stats_px_out, int N, int H, int W, int Cout,
-                     unet_stream_t stream);
+                     size_t workspace_bytes, int* UNET_HOST stats_px_out, int N, int H, int W,
+                     int Cout, unet_stream_t stream);
 /* The same in the split-bf16 ("bf16x3") operand mode: fp32 tensors, fp32-class accuracy on the
  * bf16 matrix cores.  w3 = the pre-split planes of unet_pack_conv3x3_weights_bf16x3 (forward
  * layout; may be NULL for ksize 1).  Stride-1 3x3 shapes that tile as 4 x 32 pixels run the
@@ -768,7 +785,8 @@ int unet_conv_in_fwd(const unet_act_src* s0, const unet_act_src* s1, float slope
 int unet_conv_in_fwd_bf16x3(const unet_act_src* s0, const unet_act_src* s1, float slope,
                             const float* w, const uint16_t* w3, const float* bias, int ksize,
                             int stride, float* y, void* workspace, size_t workspace_bytes,
-                            int* stats_px_out, int N, int H, int W, int Cout, unet_stream_t stream);
+                            int* UNET_HOST stats_px_out, int N, int H, int W, int Cout,
+                            unet_stream_t stream);
 /* InstanceNorm statistics of y [N][HoWo][Cout] from the summaries unet_conv_in_fwd left in
  * `workspace` (stats_px > 0: a few-microsecond merge) or from y itself (stats_px == 0), and the
  * folded coefficients for y's consumers: mean, rstd, alpha_out, beta_out [N][Cout]
@@ -789,8 +807,8 @@ int unet_conv_in_stats_finalize(const float* y, void* workspace, size_t workspac
 int unet_conv_up_in_fwd_supported(int N, int H, int W, int C0, int C1, int Cout);
 int unet_conv_up_in_fwd(const unet_act_src* low, const unet_act_src* skip, float slope,
                         const float* wf, const float* bias, float* y, void* workspace,
-                        size_t workspace_bytes, int* stats_px_out, int N, int H, int W, int Cout,
-                        unet_stream_t stream);
+                        size_t workspace_bytes, int* UNET_HOST stats_px_out, int N, int H, int W,
+                        int Cout, unet_stream_t stream);
 
 /* RGB stem straight from the dataset's uint8 HWC image [N][H][W][3]: the normalisation
  * ((v / 255) - mean[c]) / std[c] of PetSegmentationDataset.__getitem__ (Our_UNet/src/train.py:
@@ -798,24 +816,27 @@ int unet_conv_up_in_fwd(const unet_act_src* low, const unet_act_src* skip, float
  * fp32 image is never written (12x less input traffic).  mean3 / std3 are HOST pointers.
  * W % 128 == 0; other widths go through unet_preprocess_u8.  Workspaces / *stats_px_out as
  * unet_conv_in_fwd (stride 1) and unet_conv3x3_bwd_weight (Cx = 3). */
-int unet_stem_u8_fwd(const uint8_t* image_hwc, const float* mean3, const float* std3,
-                     const float* wf, const float* bias, float* y, void* workspace,
-                     size_t workspace_bytes, int* stats_px_out, int N, int H, int W, int Cout,
-                     unet_stream_t stream);
-int unet_stem_u8_bwd_weight(const uint8_t* image_hwc, const float* mean3, const float* std3,
-                            const float* dy, float* dw_oihw, void* workspace,
+int unet_stem_u8_fwd(const uint8_t* image_hwc, const float* UNET_HOST mean3,
+                     const float* UNET_HOST std3, const float* wf, const float* bias, float* y,
+                     void* workspace, size_t workspace_bytes, int* UNET_HOST stats_px_out, int N,
+                     int H, int W, int Cout, unet_stream_t stream);
+int unet_stem_u8_bwd_weight(const uint8_t* image_hwc, const float* UNET_HOST mean3,
+                            const float* UNET_HOST std3, const float* dy, float* dw_oihw,
+                            void* workspace,
                             size_t workspace_bytes, int N, int H, int W, int Cout,
                             unet_stream_t stream);
 /* The same on the mixed-precision pipeline: y / dy are bf16 tensors (statistics, workspace and
  * *stats_px_out as unet_conv_in_fwd_b16; dw stays fp32).  The fp32 accumulators are those of
  * the fp32 forms, so the results equal unet_conv_in_fwd_b16 / unet_conv_in_bwd_weight_b16 on the
  * image unet_preprocess_u8 writes, bit for bit. */
-int unet_stem_u8_fwd_b16(const uint8_t* image_hwc, const float* mean3, const float* std3,
-                         const float* wf, const float* bias, uint16_t* y, void* workspace,
-                         size_t workspace_bytes, int* stats_px_out, int N, int H, int W, int Cout,
+int unet_stem_u8_fwd_b16(const uint8_t* image_hwc, const float* UNET_HOST mean3,
+                         const float* UNET_HOST std3, const float* wf, const float* bias,
+                         uint16_t* y, void* workspace, size_t workspace_bytes,
+                         int* UNET_HOST stats_px_out, int N, int H, int W, int Cout,
                          unet_stream_t stream);
-int unet_stem_u8_bwd_weight_b16(const uint8_t* image_hwc, const float* mean3, const float* std3,
-                                const uint16_t* dy, float* dw_oihw, void* workspace,
+int unet_stem_u8_bwd_weight_b16(const uint8_t* image_hwc, const float* UNET_HOST mean3,
+                                const float* UNET_HOST std3, const uint16_t* dy, float* dw_oihw,
+                                void* workspace,
                                 size_t workspace_bytes, int N, int H, int W, int Cout,
                                 unet_stream_t stream);
 
@@ -830,8 +851,9 @@ int unet_stem_u8_bwd_weight_b16(const uint8_t* image_hwc, const float* mean3, co
  * gradients.  x: the fp32 image [N][H][W][3], or NULL with the uint8 image and its mean3 / std3
  * (HOST pointers). */
 size_t unet_stem_in_bwd_weight_fold_workspace_bytes(int N, int H, int W, int Cout);
-int unet_stem_in_bwd_weight_fold(const float* x, const uint8_t* image_hwc, const float* mean3,
-                                 const float* std3, const float* g, const float* y,
+int unet_stem_in_bwd_weight_fold(const float* x, const uint8_t* image_hwc,
+                                 const float* UNET_HOST mean3, const float* UNET_HOST std3,
+                                 const float* g, const float* y,
                                  const float* mean, const float* rstd, const float* gamma,
                                  const float* beta, const float* mask, float slope,
                                  const void* partial, int tiles, float* dw_oihw, float* dgamma,
@@ -992,14 +1014,14 @@ typedef struct unet_wino_pack_entry {
   int Cout, Cin;
   int block_begin, reserved;
 } unet_wino_pack_entry;
-int unet_pack_wino_weights_batched(const unet_wino_pack_entry* table_device, int n,
+int unet_pack_wino_weights_batched(const unet_wino_pack_entry* UNET_DEVICE table_device, int n,
                                    int total_blocks, unet_stream_t stream);
 /* unet_conv_in_fwd (ksize 3, stride 1) on the Winograd kernel: y = conv3x3(cat(act(s0),
  * act(s1))) + bias and the per-tile statistics of y (256 pixels per tile). */
 int unet_conv_in_fwd_wino(const unet_act_src* s0, const unet_act_src* s1, float slope,
                           const float* uf, const float* bias, float* y, void* workspace,
-                          size_t workspace_bytes, int* stats_px_out, int N, int H, int W, int Cout,
-                          unet_stream_t stream);
+                          size_t workspace_bytes, int* UNET_HOST stats_px_out, int N, int H, int W,
+                          int Cout, unet_stream_t stream);
 /* 1 when unet_conv3x3_bwd_weight / unet_conv_in_bwd_weight (ksize 3, fp32 tensors) run this
  * shape on the Winograd F(3x3,2x2) weight-gradient kernel (bench.py: executed FLOPs). */
 int unet_conv3x3_bwd_weight_is_winograd(int N, int H, int W, int Cx, int Cout, int stride);
@@ -1008,8 +1030,8 @@ int unet_conv3x3_bwd_weight_is_winograd(int N, int H, int W, int Cx, int Cout, i
 int unet_conv_up_wino_supported(int N, int H, int W, int C0, int C1, int Cout);
 int unet_conv_up_in_fwd_wino(const unet_act_src* low, const unet_act_src* skip, float slope,
                              const float* uf, const float* bias, float* y, void* workspace,
-                             size_t workspace_bytes, int* stats_px_out, int N, int H, int W,
-                             int Cout, unet_stream_t stream);
+                             size_t workspace_bytes, int* UNET_HOST stats_px_out, int N, int H,
+                             int W, int Cout, unet_stream_t stream);
 /* unet_conv3x3_bwd_data_bs (stride 1, accumulate 0) on the Winograd kernel; ud covers the whole
  * weight [Cout][Cin_total], ci_offset % 64 == 0; bs may be NULL. */
 int unet_conv3x3_bwd_data_bs_wino(const float* dy, const float* ud, int Cin_total, int ci_offset,
@@ -1058,15 +1080,16 @@ int unet_instnorm_lrelu_drop_bwd_partials_b16(const uint16_t* ga, const uint16_t
  * statistics come from the fp32 accumulators before y is rounded. */
 int unet_conv_in_fwd_b16(const unet_act_src* s0, const unet_act_src* s1, float slope,
                          const float* w, const float* bias, int ksize, int stride, uint16_t* y,
-                         void* workspace, size_t workspace_bytes, int* stats_px_out, int N, int H,
-                         int W, int Cout, unet_stream_t stream);
+                         void* workspace, size_t workspace_bytes, int* UNET_HOST stats_px_out,
+                         int N, int H, int W, int Cout, unet_stream_t stream);
 /* unet_conv_in_fwd_b16 with the weights also given pre-rounded to bf16 (wb = [9][Cout][Cin],
  * plane 0 of unet_pack_conv3x3_weights_batched's wf3; may be null): the stride-1 patch kernel
  * stages its weight panels without the conversion, at half the L2 traffic; bit-identical. */
 int unet_conv_in_fwd_b16_wb(const unet_act_src* s0, const unet_act_src* s1, float slope,
                             const float* w, const uint16_t* wb, const float* bias, int ksize,
                             int stride, uint16_t* y, void* workspace, size_t workspace_bytes,
-                            int* stats_px_out, int N, int H, int W, int Cout, unet_stream_t stream);
+                            int* UNET_HOST stats_px_out, int N, int H, int W, int Cout,
+                            unet_stream_t stream);
 /* unet_conv3x3_bwd_data_bs_b16 likewise (wdb = [9][Cin_total][Cout] bf16, plane 0 of wd3). */
 int unet_conv3x3_bwd_data_bs_b16_wb(const uint16_t* dy, const float* wd, const uint16_t* wdb,
                                     int Cin_total, int ci_offset, uint16_t* dx, int N, int H,
@@ -1101,8 +1124,8 @@ int unet_upsample2x_in_fwd_b16(const unet_act_src* x, float slope, uint16_t* up,
 int unet_conv_up_in_fwd_b16_supported(int N, int H, int W, int C0, int C1, int Cout);
 int unet_conv_up_in_fwd_b16(const unet_act_src* low, const unet_act_src* skip, float slope,
                             const float* wf, const uint16_t* w3, const float* bias, uint16_t* y,
-                            void* workspace, size_t workspace_bytes, int* stats_px_out, int N,
-                            int H, int W, int Cout, unet_stream_t stream);
+                            void* workspace, size_t workspace_bytes, int* UNET_HOST stats_px_out,
+                            int N, int H, int W, int Cout, unet_stream_t stream);
 int unet_upsample2x_bwd_taps_b16(const uint16_t* dy, uint16_t* D, int N, int h, int w, int C,
                                  unet_stream_t stream);
 int unet_conv3x3_up_bwd_weight_b16(const unet_act_src* x, float slope, const uint16_t* D,
@@ -1236,8 +1259,8 @@ int unet_adam_step(float* params, const float* grads, float* exp_avg, float* exp
  * fixed-order finalize whose order depends on (C, H, W) only: an image's values are bit-identical
  * in any batch. */
 size_t unet_ssim_workspace_bytes(int N, int C, int H, int W);
-int unet_ssim_fwd(const float* pred_nchw, const void* target, int target_u8, const float* gauss11,
-                  float c1, float c2, double* ssim_per_image, double* sq_per_image,
+int unet_ssim_fwd(const float* pred_nchw, const void* target, int target_u8,
+                  const float* UNET_HOST gauss11, float c1, float c2, double* ssim_per_image, double* sq_per_image,
                   float* loss_out, double w_ssim, double w_mse, void* workspace,
                   size_t workspace_bytes, int N, int C, int H, int W, unet_stream_t stream);
 /* autograd of L = up * [w_ssim * (1 - mean SSIM) + w_mse * mean (pred - t)^2] (SSIMLoss /
@@ -1247,7 +1270,7 @@ int unet_ssim_fwd(const float* pred_nchw, const void* target, int target_u8, con
  * upstream: a device float array or NULL (= 1; not with upstream_per_image).  No saved maps: the
  * moments are recomputed on a 10-pixel halo. */
 int unet_ssim_grad(const float* pred_nchw, const void* target, int target_u8,
-                   const float* gauss11, float c1, float c2, const float* upstream,
+                   const float* UNET_HOST gauss11, float c1, float c2, const float* upstream,
                    int upstream_per_image, double w_ssim, double w_mse, float* dpred_nchw, int N,
                    int C, int H, int W, unet_stream_t stream);
 
@@ -1269,8 +1292,8 @@ int unet_ssim_grad(const float* pred_nchw, const void* target, int target_u8,
  * (target_u8 == 0) or the dataset's uint8 NHWC image (target_u8 == 1, v / 255 rounded once to
  * fp32 as unet_mse_loss_fwd).  mean3 / std3: 3 host floats each. */
 int unet_perceptual_prep(const float* out_nchw, const void* target, int target_u8,
-                         const float* mean3, const float* std3, float* xn, int N, int H, int W,
-                         unet_stream_t stream);
+                         const float* UNET_HOST mean3, const float* UNET_HOST std3, float* xn,
+                         int N, int H, int W, unet_stream_t stream);
 /* nn.ReLU + nn.MaxPool2d(2, 2) of the trunk (torchvision configuration "D"): raw y [M][H][W][C]
  * -> plain p [M][H/2][W/2][C] = max(0, max of the 2x2 window); floor semantics, an odd last row
  * or column is ignored.  H, W >= 2. */
@@ -1299,7 +1322,7 @@ int unet_perceptual_relu_bwd(const float* y_o, const float* y_t, float coef, con
 /* Data gradient of conv1_1 with the normalisation's 1/std folded in: dout_nchw [N,3,H,W] =
  * conv3x3_transpose(dz [N][H][W][Cout], w_oihw [Cout][3][3][3])[c] / std3[c] (3 host floats), the
  * gradient with respect to the loss's `output` argument (:150).  Cout % 32 == 0, any H, W. */
-int unet_perceptual_stem_bwd_data(const float* dz, const float* w_oihw, const float* std3,
+int unet_perceptual_stem_bwd_data(const float* dz, const float* w_oihw, const float* UNET_HOST std3,
                                   float* dout_nchw, int N, int H, int W, int Cout,
                                   unet_stream_t stream);
 
@@ -1344,8 +1367,8 @@ int unet_gradcam_heatmap(const float* cam, const void* workspace, size_t workspa
  * [N,H,W,3] with (v / 255 - mean3[c]) / std3[c] folded in (3 host floats each).  H x W != R x R:
  * F.interpolate(mode="bilinear", align_corners=False) of the normalised image (:595), sampled while
  * gathering. */
-int unet_vit_patchify(const void* image, int image_u8, const float* mean3, const float* std3,
-                      void* patches, int N, int H, int W, int R, int P, int Kp,
+int unet_vit_patchify(const void* image, int image_u8, const float* UNET_HOST mean3,
+                      const float* UNET_HOST std3, void* patches, int N, int H, int W, int R, int P, int Kp,
                       unet_stream_t stream);
 /* out [M][Nout] = a [M][K] w[Nout][K]^T, a and w bf16 with K contiguous, any M, Nout % 64 == 0,
  * K % 16 == 0; rows >= M of `out` are not touched.  epilogue:

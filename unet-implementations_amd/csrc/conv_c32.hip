@@ -18,6 +18,7 @@
 //     order) AFTER the tile's barrier, so the 256-pixel summaries cost no barrier of their own.
 // FUSED = the fused-layer forward (activation on load, bias, statistics); otherwise the data
 // gradient form (optional accumulate, optional BSTATS epilogue).
+#include "common.h"
 #include "conv_params.h"
 #include "lds_asm.h"
 #include <stdlib.h>

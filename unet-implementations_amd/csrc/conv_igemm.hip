@@ -16,6 +16,7 @@
 //
 // Replaces nn.Conv2d forward / aten::convolution_backward(data) of
 // Our_UNet/models/unet.py:106-115 (reference is NCHW via oneDNN/cuDNN).
+#include "common.h"
 #include "conv_host.h"
 
 namespace unet_conv {

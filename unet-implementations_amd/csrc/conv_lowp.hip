@@ -2,6 +2,7 @@
 // (v_mfma_f32_32x32x16_bf16, fp32 accumulation): bf16 mixed precision (BASELINE config 4) and the
 // split-bf16 form used where the patch-staged kernel does not apply (stride-2 forward, per-class
 // stride-2 data gradient).
+#include "common.h"
 #include "conv_params.h"
 
 namespace unet_conv {

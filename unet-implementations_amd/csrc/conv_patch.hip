@@ -6,6 +6,7 @@
 //
 // Replaces nn.Conv2d forward / aten::convolution_backward(data) of
 // Our_UNet/models/unet.py:106-115 for every stride-1 layer whose image tiles as TH x 32.
+#include "common.h"
 #include "conv_params.h"
 
 #include <utility>

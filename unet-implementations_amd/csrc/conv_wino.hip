@@ -30,6 +30,7 @@
 // Replaces nn.Conv2d forward / aten::convolution_backward(data) of the C -> C stride-1 layers
 // (Our_UNet/models/unet.py:106-115), reached through unet_conv_in_fwd_wino /
 // unet_conv3x3_bwd_data_bs_wino.
+#include "common.h"
 #include "conv_params.h"
 #include "lds_asm.h"
 #include <utility>

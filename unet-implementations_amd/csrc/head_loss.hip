@@ -5,6 +5,7 @@
 //
 // Replaces segmentation_output (Our_UNet/models/unet.py:374-381,:430) and
 // SimpleLoss.forward + autograd (Our_UNet/models/losses.py:24-121).
+#include "common.h"
 #include "conv_params.h"
 
 namespace {

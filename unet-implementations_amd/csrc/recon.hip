@@ -5,6 +5,7 @@
 //
 // Replaces reconstruction_output (AE_pretrained/reconstruction/models/autoencoder.py:377-387),
 // nn.MSELoss (AE_pretrained/reconstruction/src/train.py:420-437) and optim.Adam (:377-397).
+#include "common.h"
 #include "conv_params.h"
 
 namespace {

@@ -16,12 +16,11 @@ launches).
 """
 import ctypes
 import functools
-import struct
 import threading
 
 import torch
 
-from ._lib import ActSrc, BwdStats, check, lib
+from ._lib import ActSrc, BwdStats, PackEntry, WinoPackEntry, check, lib
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -304,9 +303,9 @@ class PackTable:
         if self._wino_jobs:
             rawu = b""
             for w, uf, ud, cout, cin in self._wino_jobs:
-                rawu += struct.pack("<3Q4i", w.data_ptr(), 0 if uf is None else uf.data_ptr(),
-                                    0 if ud is None else ud.data_ptr(), cout, cin,
-                                    self._wino_blocks, 0)
+                rawu += bytes(WinoPackEntry(w.data_ptr(), 0 if uf is None else uf.data_ptr(),
+                                            0 if ud is None else ud.data_ptr(), cout, cin,
+                                            self._wino_blocks, 0))
                 self._wino_blocks += (cout * cin // 8 + 255) // 256
             self._wino_table = torch.frombuffer(bytearray(rawu), dtype=torch.uint8).to(
                 weights[0].device)
@@ -325,10 +324,11 @@ class PackTable:
                 wf3 = torch.empty((npl, 9, cout, cin), dtype=torch.bfloat16, device=w.device)
                 wd3 = torch.empty((npl, 9, cin, cout), dtype=torch.bfloat16, device=w.device)
             self.wf.append(wf); self.wd.append(wd); self.wf3.append(wf3); self.wd3.append(wd3)
-            raw += struct.pack("<5Q4i", w.data_ptr(), wf.data_ptr(), wd.data_ptr(),
-                               0 if wf3 is None else wf3.data_ptr(),
-                               0 if wd3 is None else wd3.data_ptr(), cout, cin, tiles,
-                               1 if (wf3 is not None and wf3.shape[0] == 1) else 0)
+            # the last member, `reserved`, carries the planes flag
+            raw += bytes(PackEntry(w.data_ptr(), wf.data_ptr(), wd.data_ptr(),
+                                   0 if wf3 is None else wf3.data_ptr(),
+                                   0 if wd3 is None else wd3.data_ptr(), cout, cin, tiles,
+                                   1 if (wf3 is not None and wf3.shape[0] == 1) else 0))
             tiles += (cout // 32) * ((cin + 31) // 32)
         self.n, self.tiles = len(weights), tiles
         self.table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(weights[0].device)
