@@ -217,6 +217,48 @@ def _rows():
     # kernels (no layer is bound to a chunk), not the fused pipeline's
     rows += [R("bs", "conv3x3_bwd_data_bs_bf16x3", N=8, H=4, W=32, Cout=32, Ccols=32, bs="ok", lim=3),
              R("bs", "conv3x3_bwd_data_bs_bf16x3", N=2, H=4, W=32, Cout=32, Ccols=32, bs="ok")]
+    # ---- the remaining rungs of the patch ladders (csrc/conv_tiles.h), each in every role its
+    # family has: plain, fused forward, BSTATS gradient.  One image; 128 x 512 or 256 x 512 pixels
+    # reach a floor of 256 or 512 tiles of 4 x 32 or 8 x 32 pixels at 64 or 32 columns, H = 68
+    # keeps the 8-row tile of the bf16 weight plane out.
+    wide, tall = dict(N=1, H=128, W=512), dict(N=1, H=256, W=512)
+    odd, odd512 = dict(N=1, H=68, W=512), dict(N=2, H=68, W=128)
+    rows += [   # fp32 <64, 64, 32, 4> and <32, 64, 32, 8>
+        R("fwd", "conv3x3_fwd", **wide, C0=32, Cout=64),
+        R("inp", "conv_in_fwd", **wide, C0=32, Cout=64),
+        R("bs", "conv3x3_bwd_data_bs", **wide, Cout=32, Ccols=64, bs="ok"),
+        R("fwd", "conv3x3_fwd", **tall, C0=64, Cout=32),
+        R("inp", "conv_in_fwd", **tall, C0=64, Cout=32),
+        R("bs", "conv3x3_bwd_data_bs", **tall, Cout=64, Ccols=32, bs="ok"),
+        # split <64, 128, 32, 8> and <32, 64, 32, 8>; the plain <128, 64, 64, 4> and <64, 64, 32, 4>
+        R("fwd", "conv3x3_fwd_bf16x3", **tall, C0=32, Cout=64),
+        R("inp", "conv_in_fwd_bf16x3", **tall, C0=32, Cout=64),
+        R("bs", "conv3x3_bwd_data_bs_bf16x3", **tall, Cout=32, Ccols=64, bs="ok"),
+        R("fwd", "conv3x3_fwd_bf16x3", **tall, C0=32, Cout=32),
+        R("inp", "conv_in_fwd_bf16x3", **tall, C0=32, Cout=32),
+        R("bs", "conv3x3_bwd_data_bs_bf16x3", **tall, Cout=32, Ccols=32, bs="ok"),
+        R("fwd", "conv3x3_fwd_bf16x3", N=2, H=64, W=128, C0=32, Cout=512),
+        R("fwd", "conv3x3_fwd_bf16x3", N=1, H=4, W=32, C0=32, Cout=64),
+        # bf16 tensors, no epilogue: every tile, fp32 weight panels and (_wb) the bf16 plane
+        R("bwd", "conv3x3_bwd_data_b16", N=2, H=64, W=128, Cout=32, Ccols=512),
+        R("bwd", "conv3x3_bwd_data_b16", **odd, Cout=32, Ccols=64),
+        R("bwd", "conv3x3_bwd_data_b16", **wide, Cout=32, Ccols=32),
+        R("bs", "conv3x3_bwd_data_bs_b16_wb", **tall, Cout=32, Ccols=64),
+        R("bs", "conv3x3_bwd_data_bs_b16_wb", **odd512, Cout=32, Ccols=512),
+        R("bs", "conv3x3_bwd_data_bs_b16_wb", **odd, Cout=32, Ccols=64),
+        R("bs", "conv3x3_bwd_data_bs_b16_wb", **wide, Cout=32, Ccols=32),
+        # ... <128, 64, 64, 4> with the bf16 plane, <32, 64, 32, 8> with and without it
+        R("bs", "conv3x3_bwd_data_bs_b16_wb", **odd512, Cout=32, Ccols=512, bs="ok"),
+        R("inp", "conv_in_fwd_b16_wb", **odd512, C0=32, Cout=512),
+        R("inp", "conv_in_fwd_b16", **wide, C0=32, Cout=32),
+        R("inp", "conv_in_fwd_b16_wb", **wide, C0=32, Cout=32),
+        R("bs", "conv3x3_bwd_data_bs_b16", **wide, Cout=32, Ccols=32, bs="ok"),
+        R("bs", "conv3x3_bwd_data_bs_b16_wb", **wide, Cout=32, Ccols=32, bs="ok"),
+        # stride-2 data gradient <32, 64, 32, 8>: fp32, bf16 with fp32 panels / the bf16 plane
+        R("bs2", "conv3x3_bwd_data_bs", N=1, H=512, W=512, Cout=32, Ccols=32, stride=2, bs="ok"),
+        R("bs2", "conv3x3_bwd_data_bs_b16", N=1, H=512, W=512, Cout=32, Ccols=32, stride=2, bs="ok"),
+        R("bs2", "conv3x3_bwd_data_bs_b16_wb", N=1, H=512, W=512, Cout=32, Ccols=32, stride=2,
+          bs="ok")]
     for i, r in enumerate(rows):
         r["id"] = i
     return rows

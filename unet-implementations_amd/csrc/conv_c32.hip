@@ -20,6 +20,7 @@
 // gradient form (optional accumulate, optional BSTATS epilogue).
 #include "common.h"
 #include "conv_params.h"
+#include "conv_launch.h"
 #include "lds_asm.h"
 #include <stdlib.h>
 
@@ -1097,29 +1098,15 @@ int launch_c32(const IgemmParams& p0, int fused, hipStream_t stream, int* tile_p
   // of rule as for the wider layers' Winograd kernels), or always on request (tests)
   if (c32_winograd_flag() == 2 || (c32_winograd_flag() == 1 && ntiles >= 512)) {
     const int grid2 = ntiles < 512 ? ntiles : 512;
-    if (fused) {
-      auto kern = conv_wino32q_kernel<true>;
-      UNET_SET_DYN_LDS(kern, Q_LDS);
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid2), dim3(256), Q_LDS, stream, p, ntiles);
-    } else {
-      auto kern = conv_wino32q_kernel<false>;
-      UNET_SET_DYN_LDS(kern, Q_LDS);
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid2), dim3(256), Q_LDS, stream, p, ntiles);
-    }
-    UNET_CHECK_LAUNCH("conv_wino32q");
-    return UNET_OK;
+    return with_bool(fused != 0, [&](auto f) {
+      return launch_kernel<conv_wino32q_kernel<decltype(f)::value>>(
+          "conv_wino32q", dim3((unsigned)grid2), 256, Q_LDS, stream, p, ntiles);
+    });
   }
-  if (fused) {
-    auto kern = conv_c32_kernel<true>;
-    UNET_SET_DYN_LDS(kern, C32_LDS);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), C32_LDS, stream, p, ntiles);
-  } else {
-    auto kern = conv_c32_kernel<false>;
-    UNET_SET_DYN_LDS(kern, C32_LDS);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), C32_LDS, stream, p, ntiles);
-  }
-  UNET_CHECK_LAUNCH("conv_c32");
-  return UNET_OK;
+  return with_bool(fused != 0, [&](auto f) {
+    return launch_kernel<conv_c32_kernel<decltype(f)::value>>(
+        "conv_c32", dim3((unsigned)grid), 512, C32_LDS, stream, p, ntiles);
+  });
 }
 
 }  // namespace unet_conv
@@ -1143,7 +1130,7 @@ extern "C" int unet_conv_c32_is_winograd(int N, int H, int W, int Cin, int Cout,
 
 namespace unet_conv {
 // (64 up-sampled + 32 skip) -> 32 channels, both sources activated on load, whole 8 x 32 tiles,
-// a tile for every CU: the Winograd form of launch_patch_up<32, ...> (conv_patch.hip)
+// a tile for every CU: the Winograd form of launch_patch_up_auto's 32-column rung (conv_patch.hip)
 bool wino_up32_applicable(const IgemmParams& p) {
   const int f = c32_winograd_flag();
   if (!(f && p.C0 == 64 && p.C1 == 32 && p.Ncols == 32 && p.ntaps == 9 && p.Hin % 8 == 0 &&

@@ -18,6 +18,8 @@
 // Our_UNet/models/unet.py:106-115 (reference is NCHW via oneDNN/cuDNN).
 #include "common.h"
 #include "conv_host.h"
+#include "conv_launch.h"
+#include "conv_tiles.h"
 
 namespace unet_conv {
 namespace {
@@ -34,9 +36,12 @@ namespace {
 // cannot hide the load latency of its K loop): KG groups of four waves share the tile, group g
 // runs K steps [g, g+1) * KS / KG through its own pair of LDS stages, and the partial
 // accumulators are summed through LDS in group order before the common epilogue.
+template <int BM, int BN, int BK, int KG>   // 144-B (80-B) rows: conflict-free ds_read_b128 across 16 rows
+using IgemmGeom = GemmLds<float, BM, BN, BK + 4, KG>;
 template <int BM, int BN, int WM, int WN, int BK, bool FUSED = false, int KG = 1>
 __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void conv_igemm_kernel(const IgemmParams p) {
-  constexpr int LDA = BK + 4;  // 144-B (80-B) rows: conflict-free ds_read_b128 across 16 rows
+  using G = IgemmGeom<BM, BN, BK, KG>;
+  constexpr int LDA = G::LDA;
   constexpr int SEGS = BK / 4;         // 16-B segments per tile row
   constexpr int ROWS = 256 / SEGS;     // tile rows covered by one loader pass
   constexpr int TM = WM / 32, TN = WN / 32;
@@ -44,7 +49,7 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void conv_igemm_kernel(c
   static_assert((BM / WM) * (BN / WN) == 4, "4 waves per block");
   constexpr int A_PASSES = BM / ROWS;
   constexpr int B_PASSES = BN / ROWS;
-  constexpr int A_TILE = BM * LDA, B_TILE = BN * LDA;
+  constexpr int A_TILE = G::A_TILE, B_TILE = G::B_TILE;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   // K group: uniform per wave, kept in an SGPR so the K-step bookkeeping stays scalar
   const int grp = KG > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)) : 0;
@@ -381,16 +386,10 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void conv_igemm_kernel(c
 
 template <int BM, int BN, int WM, int WN, int BK = 32, bool FUSED = false, int KG = 1>
 int launch_igemm(const IgemmParams& p, hipStream_t stream) {
-  constexpr int LDA = BK + 4;
-  constexpr size_t lds = KG * 2 * (size_t)(BM + BN) * LDA * sizeof(float);
-  static_assert(lds <= 160 * 1024, "LDS stages of every K group fit one CU");
-  auto kern = conv_igemm_kernel<BM, BN, WM, WN, BK, FUSED, KG>;
-  UNET_SET_DYN_LDS(kern, lds);
   const long long M = (long long)p.N * p.Hl * p.Wl;
   const long long tiles = ceil_div64(M, BM) * (p.Ncols / BN);
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256 * KG), lds, stream, p);
-  UNET_CHECK_LAUNCH("conv_igemm");
-  return UNET_OK;
+  return launch_kernel<conv_igemm_kernel<BM, BN, WM, WN, BK, FUSED, KG>>(
+      "conv_igemm", dim3((unsigned)tiles), 256 * KG, IgemmGeom<BM, BN, BK, KG>::lds_bytes, stream, p);
 }
 
 
@@ -403,23 +402,35 @@ int launch_igemm(const IgemmParams& p, hipStream_t stream) {
 // along.  3x less A traffic and 3x fewer barriers per MFMA than the per-tap K loop.
 // ---------------------------------------------------------------------------
 // FUSED: activation on load + statistics epilogue of the fused layer pipeline (IgemmParams).
+template <int BM, int BN, int WM, bool PW>
+struct IgemmRfGeom {
+  static constexpr int BK = 32, LDA = BK + 4;
+  static constexpr int AR = BM + 2;                       // staged pixels per K step
+  static constexpr int A_TILE = AR * LDA, B_TILE = 3 * BN * LDA;
+  static constexpr int B_STAGES = PW ? 3 : 2;   // PW: [3 ky][3 shifts][BN][LDA], else 2 x [3 shifts][BN][LDA]
+  // two A stages, the weight stages, the statistics scratch of (BM / WM) waves x BN columns
+  static constexpr size_t lds_bytes = (size_t)(2 * A_TILE + B_STAGES * B_TILE) * sizeof(float) +
+                                      (size_t)(BM / WM) * BN * sizeof(float2);
+};
+
 template <int BM, int BN, int WM, int WN, bool PW, bool FUSED = false>
 __global__ __launch_bounds__(256, 2) void conv_igemm_rf_kernel(const IgemmParams p, int ntiles) {
   // PW (persistent weights): Ktot == 32, so all nine [BN][32] weight tiles are loaded into LDS
   // once per workgroup and only the A rows stream through the double buffer.
-  constexpr int BK = 32, LDA = BK + 4;
+  using Geo = IgemmRfGeom<BM, BN, WM, PW>;
+  constexpr int BK = Geo::BK, LDA = Geo::LDA;
   constexpr int TM = WM / 32, TN = WN / 32;
   constexpr int WAVES_N = BN / WN;
   static_assert((BM / WM) * (BN / WN) == 4, "4 waves per block");
-  constexpr int AR = BM + 2;                       // staged pixels per K step
+  constexpr int AR = Geo::AR;
   constexpr int A_PASSES = (AR + 31) / 32;
   constexpr int B_PASSES = PW ? 0 : 3 * BN / 32;
-  constexpr int A_TILE = AR * LDA, B_TILE = 3 * BN * LDA;
+  constexpr int A_TILE = Geo::A_TILE, B_TILE = Geo::B_TILE;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* As = smem;
-  float* Bs = smem + 2 * A_TILE;   // PW: [3 ky][3 shifts][BN][LDA], else 2 x [3 shifts][BN][LDA]
+  float* Bs = smem + 2 * A_TILE;
   // FUSED: scratch of the statistics epilogue behind the pipeline buffers
-  float2* red = reinterpret_cast<float2*>(Bs + (PW ? 3 : 2) * B_TILE);
+  float2* red = reinterpret_cast<float2*>(Bs + Geo::B_STAGES * B_TILE);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
@@ -681,12 +692,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_rf_kernel(const IgemmParams
 
 template <int BM, int BN, int WM, int WN, bool PW, bool FUSED = false>
 int launch_igemm_rf(const IgemmParams& p, int flip, hipStream_t stream, int* stats_px = nullptr) {
-  constexpr int LDA = 36;
-  constexpr size_t lds = (PW ? (size_t)(2 * (BM + 2) + 9 * BN) * LDA * sizeof(float)
-                             : 2 * (size_t)((BM + 2) + 3 * BN) * LDA * sizeof(float)) +
-                         (size_t)(BM / WM) * BN * sizeof(float2);   // statistics scratch
-  auto kern = conv_igemm_rf_kernel<BM, BN, WM, WN, PW, FUSED>;
-  UNET_SET_DYN_LDS(kern, lds);
+  constexpr size_t lds = IgemmRfGeom<BM, BN, WM, PW>::lds_bytes;
   IgemmParams q = p;
   q.sin = flip;
   if (FUSED && stats_px) {
@@ -701,9 +707,8 @@ int launch_igemm_rf(const IgemmParams& p, int flip, hipStream_t stream, int* sta
   const int ntiles = (int)(M / BM);
   const int resident = 256 * (int)((160 * 1024) / lds);   // CUs x workgroups that fit in LDS
   const int grid = ntiles < resident ? ntiles : resident;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, q, ntiles);
-  UNET_CHECK_LAUNCH("conv_igemm_rf");
-  return UNET_OK;
+  return launch_kernel<conv_igemm_rf_kernel<BM, BN, WM, WN, PW, FUSED>>(
+      "conv_igemm_rf", dim3((unsigned)grid), 256, lds, stream, q, ntiles);
 }
 
 // stride-1 3x3 with rows that tile exactly: use the row-fused kernel for narrow outputs
@@ -734,10 +739,17 @@ template <> struct S2Shift<2> { static constexpr int n = 2, oy = 1, ox = 0;
 template <> struct S2Shift<3> { static constexpr int n = 1, oy = 1, ox = 1;
   static constexpr S2Tap t[4] = {{0, 0, 3}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}; };
 
+struct DgradS2GemmGeom {
+  static constexpr int BM = 128, BN = 32, BK = 32, LDA = BK + 4;
+  static constexpr int A_TILE = BM * LDA, B_TILE = 4 * BN * LDA;   // the four shifts' weights
+  static constexpr int STAGE = A_TILE + B_TILE;
+  static constexpr size_t lds_bytes = 2 * (size_t)STAGE * sizeof(float);
+};
+
 __global__ __launch_bounds__(256, 2) void conv_dgrad_s2_kernel(const IgemmParams p) {
-  constexpr int BM = 128, BN = 32, BK = 32, LDA = BK + 4;
-  constexpr int A_TILE = BM * LDA, B_TILE = 4 * BN * LDA;
-  constexpr int STAGE = A_TILE + B_TILE;
+  using G = DgradS2GemmGeom;
+  constexpr int BM = G::BM, BN = G::BN, BK = G::BK, LDA = G::LDA;
+  constexpr int A_TILE = G::A_TILE, STAGE = G::STAGE;
   extern __shared__ __attribute__((aligned(16))) float smem[];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -919,48 +931,24 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2_kernel(const IgemmParams
 }
 
 int launch_dgrad_s2(const IgemmParams& p, hipStream_t stream) {
-  constexpr size_t lds = 2 * (size_t)(128 + 4 * 32) * 36 * sizeof(float);
-  UNET_SET_DYN_LDS(conv_dgrad_s2_kernel, lds);
+  using G = DgradS2GemmGeom;
   const long long M = (long long)p.N * p.Hl * p.Wl;
-  const long long tiles = ceil_div64(M, 128) * (p.Ncols / 32);
-  hipLaunchKernelGGL(conv_dgrad_s2_kernel, dim3((unsigned)tiles), dim3(256), lds, stream, p);
-  UNET_CHECK_LAUNCH("conv_dgrad_s2");
-  return UNET_OK;
+  const long long tiles = ceil_div64(M, G::BM) * (p.Ncols / G::BN);
+  return launch_kernel<conv_dgrad_s2_kernel>("conv_dgrad_s2", dim3((unsigned)tiles), 256,
+                                             G::lds_bytes, stream, p);
 }
 
 }  // namespace
 
-// stats_px != nullptr: the fused-layer call (activation on load; statistics epilogue into
-// p.stats when every tile lies inside one image, reported as *stats_px = pixels per statistics
-// tile, else *stats_px = 0 and the caller runs the stand-alone statistics kernel).
+// One gather-GEMM launch with its epilogue bound (bind_gemm_epilogue, conv_tiles.h): stats_px =
+// the fused-layer call (activation on load, statistics), else the plain kernel, with the BSTATS
+// epilogue where bs_px asks for it.
 template <int BM, int BN, int WM, int WN, int KG = 1>
-static int launch_igemm_fused(IgemmParams p, hipStream_t stream, int* stats_px) {
-  const int HlWl = p.Hl * p.Wl;
-  const bool direct = p.sout == 1 && p.Hl == p.Hout && p.Wl == p.Wout;
-  if (direct && p.stats && HlWl % BM == 0) { *stats_px = BM; p.stats_tiles = HlWl / BM; }
-  else { *stats_px = 0; p.stats = nullptr; }
-  return launch_igemm<BM, BN, WM, WN, 32, true, KG>(p, stream);
-}
-
-// plain gather-GEMM launch; with bs_px (data gradient whose output is final for a layer) the
-// BSTATS epilogue runs where every tile lies inside one image, else *bs_px = 0
-template <int BM, int BN, int WM, int WN, int KG = 1>
-static int launch_igemm_bs(IgemmParams p, hipStream_t stream, int* bs_px) {
-  if (bs_px) {
-    const int HlWl = p.Hl * p.Wl;
-    if (p.bs_partial && HlWl % BM == 0) { *bs_px = BM; p.bs_tiles = HlWl / BM * (p.sout * p.sout); }
-    else { *bs_px = 0; p.bs_partial = nullptr; }
-  } else {
-    p.bs_partial = nullptr;
-  }
-  return launch_igemm<BM, BN, WM, WN, 32, false, KG>(p, stream);
-}
-
-static int launch_igemm_deep(IgemmParams p, hipStream_t stream, int* bs_px) {
-  const int kg = deep_k_groups(p);
-  return kg == 4   ? launch_igemm_bs<64, 64, 32, 32, 4>(p, stream, bs_px)
-         : kg == 2 ? launch_igemm_bs<64, 64, 32, 32, 2>(p, stream, bs_px)
-                   : launch_igemm_bs<64, 64, 32, 32>(p, stream, bs_px);
+static int launch_igemm_ep(IgemmParams p, hipStream_t stream, int* stats_px, int* bs_px) {
+  bind_gemm_epilogue(p, BM, stats_px, bs_px);
+  return with_bool(stats_px != nullptr, [&](auto fused) {
+    return launch_igemm<BM, BN, WM, WN, 32, decltype(fused)::value, KG>(p, stream);
+  });
 }
 
 int dispatch_igemm(const IgemmParams& p, hipStream_t stream, int* stats_px, int* bs_px) {
@@ -970,46 +958,25 @@ int dispatch_igemm(const IgemmParams& p, hipStream_t stream, int* stats_px, int*
     const int rc = launch_patch_f32_auto(p, stream, stats_px, bs_px);
     if (rc != kNoTileFits) return rc;
   }
-  if (stats_px) {
-    if (patch_s2_applicable(p)) {   // conv_patch.hip (kNoTileFits: too few tiles)
-      const int rc = launch_patch_s2_auto(p, stream, stats_px);
-      if (rc != kNoTileFits) return rc;
-    }
-    if (nc % 128 == 0 && ceil_div64(M, 128) * (nc / 128) >= 256)
-      return launch_igemm_fused<128, 128, 64, 64>(p, stream, stats_px);
-    if (nc % 64 == 0 && ceil_div64(M, 128) * (nc / 64) >= 256)
-      return launch_igemm_fused<128, 64, 64, 32>(p, stream, stats_px);
-    if (nc % 64 == 0 && M <= 128 * 256) {
-      const int kg = deep_k_groups(p);
-      return kg == 4   ? launch_igemm_fused<64, 64, 32, 32, 4>(p, stream, stats_px)
-             : kg == 2 ? launch_igemm_fused<64, 64, 32, 32, 2>(p, stream, stats_px)
-                       : launch_igemm_fused<64, 64, 32, 32>(p, stream, stats_px);
-    }
-    return launch_igemm_fused<128, 32, 32, 32>(p, stream, stats_px);
+  if (stats_px && patch_s2_applicable(p)) {   // conv_patch.hip (kNoTileFits: too few tiles)
+    const int rc = launch_patch_s2_auto(p, stream, stats_px);
+    if (rc != kNoTileFits) return rc;
   }
   // low-resolution data gradient of the up-sampled operand ("channel taps": a plain GEMM over
   // K = 9 Cout): 64 x 64 tiles at four workgroups per CU where the larger tiles leave the chip
   // half filled or the layer has 64 columns (tools/bench_lowres_b16.py --fp32: 199 -> 188 us at
   // 8192 x 512 x 2304, 242 -> 226 at 524288 x 64 x 288; the other three shapes +-0)
-  if (p.tap_cstride != 0 && nc % 64 == 0 && M % 64 == 0 && (M / 64) * (nc / 64) >= 512 &&
-      (nc == 64 || ceil_div64(M, 128) * (nc / 128) < 512))
-    return launch_igemm_bs<64, 64, 32, 32>(p, stream, bs_px);
-  if (bs_px) {   // per-class launches of one stride-2 gradient pass bs_tile0 themselves
-    if (nc % 128 == 0 && ceil_div64(M, 128) * (nc / 128) >= 256)
-      return launch_igemm_bs<128, 128, 64, 64>(p, stream, bs_px);
-    if (nc % 64 == 0 && ceil_div64(M, 128) * (nc / 64) >= 256)
-      return launch_igemm_bs<128, 64, 64, 32>(p, stream, bs_px);
-    if (nc % 64 == 0 && M <= 128 * 256) return launch_igemm_deep(p, stream, bs_px);
-    return launch_igemm_bs<128, 32, 32, 32>(p, stream, bs_px);
-  }
-  // Largest tile that still yields >= 256 workgroups (one per CU); otherwise the
-  // small 64x64 tile.
-  if (nc % 128 == 0 && ceil_div64(M, 128) * (nc / 128) >= 256)
-    return launch_igemm<128, 128, 64, 64>(p, stream);
-  if (nc % 64 == 0 && ceil_div64(M, 128) * (nc / 64) >= 256)
-    return launch_igemm<128, 64, 64, 32>(p, stream);
-  if (nc % 64 == 0 && M <= 128 * 256) return launch_igemm_deep(p, stream, nullptr);
-  return launch_igemm<128, 32, 32, 32>(p, stream);
+  if (!stats_px && p.tap_cstride != 0 && nc % 64 == 0 && M % 64 == 0 &&
+      (M / 64) * (nc / 64) >= 512 && (nc == 64 || ceil_div64(M, 128) * (nc / 128) < 512))
+    return launch_igemm_ep<64, 64, 32, 32>(p, stream, nullptr, bs_px);
+  // the ladder (conv_tiles.h); the 64 x 64 tile of the deep layers in K groups
+  return with_gemm_tile_kg(gemm_tile(M, nc), p, [&](auto shape, auto groups) {
+    using S = decltype(shape);
+    constexpr int KG = decltype(groups)::value;
+    // (a plain call keeps p.bs_partial as the caller set it, except on the 64 x 64 tile)
+    if (!stats_px && !bs_px && S::BM != 64) return launch_igemm<S::BM, S::BN, S::WM, S::WN>(p, stream);
+    return launch_igemm_ep<S::BM, S::BN, S::WM, S::WN, KG>(p, stream, stats_px, bs_px);
+  });
 }
 
 namespace {
@@ -1467,14 +1434,11 @@ static int conv3x3_bwd_data_impl(const void* dy, const float* wd, int Cin_total,
       return bsb.done_px(rc, H * W);
     }
     // stride 2, in one launch for all four parity classes where a form has the tiles for it:
-    if (m.cores == Cores::F32 && !b16) {   // conv_patch.hip: the dy patch staged once per chunk
-      const int rc = launch_dgrad_s2_patch_auto(p, stream, bsb.report());
+    // conv_patch.hip: the dy patch staged once per chunk (fp32, and the mixed-precision pipeline)
+    if (m.cores == Cores::F32 || b16) {
+      const int rc = launch_dgrad_s2_patch_auto(p, b16, stream, bsb.report());
       if (rc != kNoTileFits) return bsb.done_tiles(rc, bsb.reported());
-    }
-    if (b16) {   // mixed-precision pipeline: one launch instead of four per class
-      const int rc = launch_dgrad_s2_patch_b16_auto(p, stream, bsb.report());
-      if (rc != kNoTileFits) return bsb.done_tiles(rc, bsb.reported());
-      p.bs_partial = nullptr;   // (the per-class gather-GEMM launches below: no epilogue)
+      if (b16) p.bs_partial = nullptr;   // (the per-class gather-GEMM launches below: no epilogue)
     }
     const long long tiles = ceil_div64((long long)b.count * p.Hl * p.Wl, 128) * (Ccols / 32);
     if (m.cores != Cores::BF16 && !b16 && tiles >= 512) {   // enough tiles to fill the chip

@@ -3,7 +3,8 @@
 // split-bf16 form used where the patch-staged kernel does not apply (stride-2 forward, per-class
 // stride-2 data gradient).
 #include "common.h"
-#include "conv_params.h"
+#include "conv_launch.h"
+#include "conv_tiles.h"
 
 namespace unet_conv {
 namespace {
@@ -34,6 +35,8 @@ namespace {
 // from L2 or further), 16-byte loads on both operands, the weights from their bf16 plane (p.w3,
 // no conversion, half the L2 traffic), half the barriers.  A K step may straddle taps (C0 = 32)
 // and the last one may be ragged (9 * 32 = 4.5 steps): lanes past K read zeros.
+template <int BM, int BN, int KG = 1, int MODE = 0>   // rows of BK + 8 bf16; WIDE / DENSE: BK = 64
+using IgemmBf16Geom = GemmLds<__bf16, BM, BN, (MODE != 0 ? 64 : 32) + 8, KG>;
 template <int BM, int BN, int WM, int WN, typename TS = float, typename TO = float,
           bool FUSED = false, int KG = 1, int MODE = 0>
 __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void conv_igemm_bf16_kernel(const IgemmParams p) {
@@ -43,8 +46,10 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void conv_igemm_bf16_ker
   constexpr bool DENSE = MODE == 2, WIDE = MODE != 0;
   static_assert(!WIDE || sizeof(TS) == 2, "WIDE / DENSE: bf16 rows");
   static_assert(!DENSE || !FUSED, "DENSE: no activation");
+  using G = IgemmBf16Geom<BM, BN, KG, MODE>;
   constexpr int BK = WIDE ? 64 : 32;
-  constexpr int LDA = BK + 8;  // bf16 elements per LDS row
+  constexpr int LDA = G::LDA;  // bf16 elements per LDS row
+  static_assert(LDA == BK + 8, "the launcher's rows are these");
   constexpr int EPS = WIDE ? 8 : 4;   // elements per loader segment
   constexpr int SEGS = BK / EPS;       // loader segments per tile row
   constexpr int ROWS = 256 / SEGS;     // tile rows covered by one loader pass
@@ -53,7 +58,7 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void conv_igemm_bf16_ker
   static_assert((BM / WM) * (BN / WN) == 4, "4 waves per block");
   constexpr int A_PASSES = BM / ROWS;
   constexpr int B_PASSES = BN / ROWS;
-  constexpr int A_TILE = BM * LDA, B_TILE = BN * LDA;
+  constexpr int A_TILE = G::A_TILE, B_TILE = G::B_TILE;
   extern __shared__ __attribute__((aligned(16))) __bf16 smem_h[];
   // K group: uniform per wave, kept in an SGPR so the K-step bookkeeping stays scalar
   const int grp = KG > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)) : 0;
@@ -479,10 +484,12 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void conv_igemm_bf16_ker
 // three planes of both double-buffered tiles fit twice per CU; the global loads run two K
 // steps ahead of the MFMAs (registers), the split one step ahead (LDS).
 // ---------------------------------------------------------------------------
+template <int BM, int BN>   // three planes; 16 + 8 bf16 per LDS row (48 B: conflict-free b128)
+using IgemmSplitGeom = GemmLds<__bf16, BM, BN, 16 + 8, 1, 3>;
 template <int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256, 2) void conv_igemm_split_kernel(const IgemmParams p) {
-  constexpr int BK = 16;
-  constexpr int LDA = BK + 8;          // bf16 elements per LDS row (48 B: conflict-free b128)
+  using G = IgemmSplitGeom<BM, BN>;
+  constexpr int BK = 16, LDA = G::LDA;
   constexpr int SEGS = BK / 4;         // 16-B fp32 segments per tile row
   constexpr int ROWS = 256 / SEGS;     // 64 tile rows per loader pass
   constexpr int TM = WM / 32, TN = WN / 32;
@@ -493,7 +500,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_split_kernel(const IgemmPar
   // weights arrive pre-split (three bf16 planes): slot = (plane, row, 8-element half row)
   constexpr int B_SLOTS = BN * 6;
   constexpr int B_PASSES = (B_SLOTS + 255) / 256;
-  constexpr int A_TILE = BM * LDA, B_TILE = BN * LDA;
+  constexpr int A_TILE = G::A_TILE, B_TILE = G::B_TILE;
   extern __shared__ __attribute__((aligned(16))) __bf16 smem_h[];
   __bf16* As = smem_h;                    // [buf][plane][BM][LDA]
   __bf16* Bs = smem_h + 2 * 3 * A_TILE;   // [buf][plane][BN][LDA]
@@ -685,97 +692,54 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_split_kernel(const IgemmPar
   }
 }
 
+// one workgroup (of KG groups of four waves) per BM x BN tile of the logical grid
+template <int BM, int BN>
+dim3 igemm_grid(const IgemmParams& p) {
+  const long long M = (long long)p.N * p.Hl * p.Wl;
+  return dim3((unsigned)(ceil_div64(M, BM) * (p.Ncols / BN)));
+}
+
 template <int BM, int BN, int WM, int WN>
 int launch_igemm_bf16(const IgemmParams& p, hipStream_t stream) {
-  constexpr size_t lds = 2 * (size_t)(BM + BN) * 40 * sizeof(__bf16);
-  const long long M = (long long)p.N * p.Hl * p.Wl;
-  const long long tiles = ceil_div64(M, BM) * (p.Ncols / BN);
-  hipLaunchKernelGGL((conv_igemm_bf16_kernel<BM, BN, WM, WN>), dim3((unsigned)tiles), dim3(256), lds,
-                     stream, p);
-  UNET_CHECK_LAUNCH("conv_igemm_bf16");
-  return UNET_OK;
+  return launch_kernel<conv_igemm_bf16_kernel<BM, BN, WM, WN>>(
+      "conv_igemm_bf16", igemm_grid<BM, BN>(p), 256, IgemmBf16Geom<BM, BN>::lds_bytes, stream, p);
 }
 
 // bf16 STORAGE (the real mixed-precision pipeline): sources and output are bf16 tensors.
 // stats_px: the fused-layer forward (statistics epilogue where every tile lies in one image);
 // bs_px: a data gradient whose output is final for a layer (BSTATS epilogue, same condition).
+// MODE 1 = WIDE, 2 = DENSE (a data gradient only: no activation on load).
 template <int BM, int BN, int WM, int WN, int KG = 1, int MODE = 0>
 int launch_igemm_b16(IgemmParams p, hipStream_t stream, int* stats_px, int* bs_px = nullptr) {
-  constexpr size_t lds = KG * 2 * (size_t)(BM + BN) * (MODE ? 72 : 40) * sizeof(__bf16);
-  static_assert(lds <= 160 * 1024, "LDS stages of every K group fit one CU");
-  const long long M = (long long)p.N * p.Hl * p.Wl;
-  const long long tiles = ceil_div64(M, BM) * (p.Ncols / BN);
-  const int HlWl = p.Hl * p.Wl;
-  if constexpr (MODE != 0) {
-    if (stats_px) {   // WIDE fused layer forward
-      const bool direct = p.sout == 1 && p.Hl == p.Hout && p.Wl == p.Wout;
-      if (direct && p.stats && HlWl % BM == 0) { *stats_px = BM; p.stats_tiles = HlWl / BM; }
-      else { *stats_px = 0; p.stats = nullptr; }
-      p.bs_partial = nullptr;
-      if constexpr (MODE == 1) {
-        auto kern = conv_igemm_bf16_kernel<BM, BN, WM, WN, __bf16, __bf16, true, KG, 1>;
-        UNET_SET_DYN_LDS(kern, lds);
-        hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256 * KG), lds, stream, p);
-      }
-      UNET_CHECK_LAUNCH("conv_igemm_b16");
-      return UNET_OK;
-    }
-    if (bs_px && p.bs_partial && HlWl % BM == 0 && M % BM == 0) {
-      *bs_px = BM; p.bs_tiles = HlWl / BM * (p.sout * p.sout);
-    } else {
-      if (bs_px) *bs_px = 0;
-      p.bs_partial = nullptr;
-    }
-    auto kern = conv_igemm_bf16_kernel<BM, BN, WM, WN, __bf16, __bf16, false, KG, MODE>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256 * KG), lds, stream, p);
-  } else
-  if (stats_px) {   // fused layer forward
-    const bool direct = p.sout == 1 && p.Hl == p.Hout && p.Wl == p.Wout;
-    if (direct && p.stats && HlWl % BM == 0) { *stats_px = BM; p.stats_tiles = HlWl / BM; }
-    else { *stats_px = 0; p.stats = nullptr; }
-    p.bs_partial = nullptr;
-    auto kern = conv_igemm_bf16_kernel<BM, BN, WM, WN, __bf16, __bf16, true, KG>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256 * KG), lds, stream, p);
+  bind_gemm_epilogue(p, BM, stats_px, bs_px);
+  auto launch = [&](auto fused) {
+    return launch_kernel<conv_igemm_bf16_kernel<BM, BN, WM, WN, __bf16, __bf16,
+                                                decltype(fused)::value, KG, MODE>>(
+        "conv_igemm_b16", igemm_grid<BM, BN>(p), 256 * KG,
+        IgemmBf16Geom<BM, BN, KG, MODE>::lds_bytes, stream, p);
+  };
+  if constexpr (MODE == 2) {
+    UNET_REQUIRE(!stats_px, "conv_igemm_b16: the plain-GEMM form has no fused forward");
+    return launch(std::false_type{});
   } else {
-    if (bs_px && p.bs_partial && HlWl % BM == 0 && M % BM == 0) {
-      *bs_px = BM; p.bs_tiles = HlWl / BM * (p.sout * p.sout);
-    } else {
-      if (bs_px) *bs_px = 0;
-      p.bs_partial = nullptr;
-    }
-    auto kern = conv_igemm_bf16_kernel<BM, BN, WM, WN, __bf16, __bf16, false, KG>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256 * KG), lds, stream, p);
+    return with_bool(stats_px != nullptr, launch);
   }
-  UNET_CHECK_LAUNCH("conv_igemm_b16");
-  return UNET_OK;
 }
 
 template <int BM, int BN, int WM, int WN>
 int launch_igemm_split(const IgemmParams& p, hipStream_t stream) {
-  constexpr size_t lds = 2 * 3 * (size_t)(BM + BN) * 24 * sizeof(__bf16);
-  auto kern = conv_igemm_split_kernel<BM, BN, WM, WN>;
-  UNET_SET_DYN_LDS(kern, lds);
-  const long long M = (long long)p.N * p.Hl * p.Wl;
-  const long long tiles = ceil_div64(M, BM) * (p.Ncols / BN);
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, stream, p);
-  UNET_CHECK_LAUNCH("conv_igemm_split");
-  return UNET_OK;
+  return launch_kernel<conv_igemm_split_kernel<BM, BN, WM, WN>>(
+      "conv_igemm_split", igemm_grid<BM, BN>(p), 256, IgemmSplitGeom<BM, BN>::lds_bytes, stream, p);
 }
 
 }  // namespace
 
+// (the bf16-cores and split families have no K groups)
 int dispatch_igemm_bf16(const IgemmParams& p, hipStream_t stream) {
-  const long long M = (long long)p.N * p.Hl * p.Wl;
-  const int nc = p.Ncols;
-  if (nc % 128 == 0 && ceil_div64(M, 128) * (nc / 128) >= 256)
-    return launch_igemm_bf16<128, 128, 64, 64>(p, stream);
-  if (nc % 64 == 0 && ceil_div64(M, 128) * (nc / 64) >= 256)
-    return launch_igemm_bf16<128, 64, 64, 32>(p, stream);
-  if (nc % 64 == 0 && M <= 128 * 256) return launch_igemm_bf16<64, 64, 32, 32>(p, stream);
-  return launch_igemm_bf16<128, 32, 32, 32>(p, stream);
+  return with_gemm_tile(gemm_tile(p), [&](auto shape) {
+    using S = decltype(shape);
+    return launch_igemm_bf16<S::BM, S::BN, S::WM, S::WN>(p, stream);
+  });
 }
 
 // bf16-storage gather-GEMM (sources / output bf16 in HBM); stats_px != nullptr: the fused-layer
@@ -806,38 +770,29 @@ int dispatch_igemm_b16(const IgemmParams& p, hipStream_t stream, int* stats_px, 
       return launch_igemm_b16<64, 64, 32, 32, 4, 2>(p, stream, nullptr, bs_px);
     return launch_igemm_b16<64, 64, 32, 32, 1, 2>(p, stream, nullptr, bs_px);
   }
-  if (nc % 128 == 0 && ceil_div64(M, 128) * (nc / 128) >= 256)
-    return launch_igemm_b16<128, 128, 64, 64>(p, stream, stats_px, bs_px);
-  if (nc % 64 == 0 && ceil_div64(M, 128) * (nc / 64) >= 256)
-    return launch_igemm_b16<128, 64, 64, 32>(p, stream, stats_px, bs_px);
+  const GemmTile tile = gemm_tile(M, nc);
   // data gradients of the 1/32-resolution stage (at most one 64 x 64 tile per CU) with the bf16
   // weight plane: the gather form on 64-wide K steps (WIDE), four K groups
-  if (p.w3 && p.tap_cstride == 0 && nc % 64 == 0 && p.C0 % 64 == 0 &&
+  if (!fills_128_rows(tile) && p.w3 && p.tap_cstride == 0 && nc % 64 == 0 && p.C0 % 64 == 0 &&
       p.C1 % 64 == 0 && ceil_div64(M, 64) * (nc / 64) <= 256 &&
       (p.ntaps * ((p.C0 + p.C1) / 64)) % 4 == 0 && p.ntaps * ((p.C0 + p.C1) / 64) >= 8)
     return launch_igemm_b16<64, 64, 32, 32, 4, 1>(p, stream, stats_px, bs_px);
-  if (nc % 64 == 0 && M <= 128 * 256) {
-    const int kg = deep_k_groups(p);
-    return kg == 4   ? launch_igemm_b16<64, 64, 32, 32, 4>(p, stream, stats_px, bs_px)
-           : kg == 2 ? launch_igemm_b16<64, 64, 32, 32, 2>(p, stream, stats_px, bs_px)
-                     : launch_igemm_b16<64, 64, 32, 32>(p, stream, stats_px, bs_px);
-  }
-  return launch_igemm_b16<128, 32, 32, 32>(p, stream, stats_px, bs_px);
+  return with_gemm_tile_kg(tile, p, [&](auto shape, auto groups) {
+    using S = decltype(shape);
+    return launch_igemm_b16<S::BM, S::BN, S::WM, S::WN, decltype(groups)::value>(p, stream,
+                                                                                 stats_px, bs_px);
+  });
 }
 
 int dispatch_igemm_split(const IgemmParams& p, hipStream_t stream) {
-  const long long M = (long long)p.N * p.Hl * p.Wl;
-  const int nc = p.Ncols;
   // images narrower than one 32-pixel patch row (the 1/32-resolution stage): too few tiles for
   // the split kernels to win, the fp32 matrix-core kernel is faster there
   if (p.Wl < 32 && p.sout == 1) return dispatch_igemm(p, stream);
   if (patch_split_applicable(p)) return launch_patch_split_auto(p, stream);
-  if (nc % 128 == 0 && ceil_div64(M, 128) * (nc / 128) >= 256)
-    return launch_igemm_split<128, 128, 64, 64>(p, stream);
-  if (nc % 64 == 0 && ceil_div64(M, 128) * (nc / 64) >= 256)
-    return launch_igemm_split<128, 64, 64, 32>(p, stream);
-  if (nc % 64 == 0 && M <= 128 * 256) return launch_igemm_split<64, 64, 32, 32>(p, stream);
-  return launch_igemm_split<128, 32, 32, 32>(p, stream);
+  return with_gemm_tile(gemm_tile(p), [&](auto shape) {
+    using S = decltype(shape);
+    return launch_igemm_split<S::BM, S::BN, S::WM, S::WN>(p, stream);
+  });
 }
 
 }  // namespace unet_conv

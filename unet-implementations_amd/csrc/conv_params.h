@@ -77,6 +77,15 @@ inline int batch_chunk(int N, long long per_image_bytes) {
   return (int)(n < N ? n : N);
 }
 
+// LDS layout of a gather-GEMM kernel - what the kernel carves up and what its launcher asks for
+// (lds_bytes): per K group two stages of PLANES x (BM + BN) rows of LDA elements of T.
+template <typename T, int BM, int BN, int LDA_, int KG = 1, int PLANES = 1>
+struct GemmLds {
+  static constexpr int LDA = LDA_, A_TILE = BM * LDA, B_TILE = BN * LDA;
+  static constexpr size_t lds_bytes = KG * 2 * PLANES * (size_t)(A_TILE + B_TILE) * sizeof(T);
+  static_assert(lds_bytes <= 160 * 1024, "LDS stages of every K group fit one CU");
+};
+
 // "No tile shape fits this launch: try the next form" - what the launch_*_auto functions answer
 // besides UNET_OK / UNET_E_*.  Distinct from every UNET_* code (those are <= 0); it stays
 // between the dispatchers and never leaves an export.
@@ -257,27 +266,26 @@ __device__ __forceinline__ bool block_col_stats(float2* red, int wave_m, int col
 #endif  // __HIPCC__
 
 // ---- dispatchers implemented in the other translation units -------------------------------
-bool patch_f32_applicable(const IgemmParams& p);              // conv_patch.hip
-int launch_patch_f32_auto(const IgemmParams& p, hipStream_t stream,    // kNoTileFits if none
-                          int* stats_px = nullptr, int* bs_px = nullptr);
+// (which tile a launch gets, and the applicability tests of the patch forms: conv_tiles.h)
+// conv_patch.hip: the first tile of the family's ladder that fits, kNoTileFits if none
+int launch_patch_f32_auto(const IgemmParams& p, hipStream_t stream, int* stats_px = nullptr,
+                          int* bs_px = nullptr);
 int launch_patch_up_auto(const IgemmParams& p, hipStream_t stream, int* stats_px);
+int launch_patch_s2_auto(const IgemmParams& p, hipStream_t stream, int* stats_px);
+int launch_dgrad_s2_patch_auto(const IgemmParams& p, bool b16, hipStream_t stream,
+                               int* bs_tiles_out);
+int launch_patch_split_auto(const IgemmParams& p, hipStream_t stream);
+int launch_patch_split_fused_auto(const IgemmParams& p, hipStream_t stream, int* stats_px,
+                                  int* bs_px);
+int launch_patch_b16_auto(const IgemmParams& p, hipStream_t stream, int* stats_px,   // bf16 tensors
+                          int* bs_px = nullptr);
+int launch_patch_b16_up_auto(const IgemmParams& p, hipStream_t stream, int* stats_px);
+int launch_patch_s2_b16_auto(const IgemmParams& p, hipStream_t stream, int* stats_px);
 int& c32_winograd_flag();                                      // unet_set_c32_winograd, conv_c32.hip
 bool c32_applicable(const IgemmParams& p);                    // 32 -> 32 channels, conv_c32.hip
 int launch_c32(const IgemmParams& p, int fused, hipStream_t stream, int* tile_px);
 bool wino_up32_applicable(const IgemmParams& p);              // (64 up + 32) -> 32, conv_c32.hip
 int launch_wino_up32(const IgemmParams& p, hipStream_t stream);
-bool patch_s2_applicable(const IgemmParams& p);               // stride-2 forward, conv_patch.hip
-int launch_patch_s2_auto(const IgemmParams& p, hipStream_t stream, int* stats_px);
-int launch_patch_s2_b16_auto(const IgemmParams& p, hipStream_t stream, int* stats_px);   // bf16 tensors
-int launch_dgrad_s2_patch_auto(const IgemmParams& p, hipStream_t stream, int* bs_tiles_out);
-int launch_patch_b16_up_auto(const IgemmParams& p, hipStream_t stream, int* stats_px);   // conv_patch.hip
-int launch_dgrad_s2_patch_b16_auto(const IgemmParams& p, hipStream_t stream, int* bs_tiles_out);   // bf16 tensors
-int launch_patch_split_auto(const IgemmParams& p, hipStream_t stream);
-int launch_patch_b16_auto(const IgemmParams& p, hipStream_t stream, int* stats_px,   // bf16 tensors
-                          int* bs_px = nullptr);
-int launch_patch_split_fused_auto(const IgemmParams& p, hipStream_t stream, int* stats_px,
-                                  int* bs_px);
-bool patch_split_applicable(const IgemmParams& p);
 int dispatch_igemm(const IgemmParams& p, hipStream_t stream,           // conv_igemm.hip
                    int* stats_px = nullptr, int* bs_px = nullptr);
 int dispatch_igemm_bf16(const IgemmParams& p, hipStream_t stream);     // conv_lowp.hip

@@ -7,7 +7,8 @@
 // Replaces nn.Conv2d forward / aten::convolution_backward(data) of
 // Our_UNet/models/unet.py:106-115 for every stride-1 layer whose image tiles as TH x 32.
 #include "common.h"
-#include "conv_params.h"
+#include "conv_launch.h"
+#include "conv_tiles.h"
 
 #include <utility>
 
@@ -24,6 +25,18 @@ __device__ __forceinline__ void for_range_p(F&& f) {
   for_range_p_impl<B>(std::make_integer_sequence<int, (E > B ? E - B : 0)>{}, f);
 }
 
+// LDS layout of a patch kernel - what the kernel carves up and what its launcher asks for
+// (lds_bytes): PLANES planes of a PH x PW-pixel patch in rows of LDA elements of T, two weight
+// stages of B_ROWS such rows, EXTRA bytes of scratch behind them.  Output tile: TH x 32 pixels
+// by BN columns.
+template <typename T, int BN_, int TH_, int LDA_, int PH, int PW_, int PLANES, int B_ROWS,
+          size_t EXTRA_ = 0>
+struct PatchLds {
+  static constexpr int BN = BN_, TH = TH_, LDA = LDA_, PW = PW_, PPIX = PH * PW;
+  static constexpr size_t EXTRA = EXTRA_;
+  static constexpr size_t lds_bytes = (size_t)(PLANES * PPIX + 2 * B_ROWS) * LDA * sizeof(T) + EXTRA;
+};
+
 // ---------------------------------------------------------------------------
 // Patch-staged split-bf16 kernel: stride-1 3x3 convolution (forward and data gradient) whose
 // image tiles as 4 rows x 32 columns.  Per 16-channel chunk the (4+2) x (32+2) input patch is
@@ -37,11 +50,14 @@ __device__ __forceinline__ void for_range_p(F&& f) {
 // ACT / STATS / BSTATS: the fused layer pipeline on this kernel, exactly as in
 // conv_patch_f32_kernel below (activation on load BEFORE the split, statistics of the output,
 // reductions of the next backward stage) - the split mode of the fused pipeline.
+template <int BN, int TH>   // three planes of the (TH + 2) x 34 patch, [buf][plane][BN] weight rows
+using PatchSplitGeom = PatchLds<__bf16, BN, TH, 16 + 8, TH + 2, 32 + 2, 3, 3 * BN>;
 template <int BN, int WM, int WN, int TH, bool ACT = false, bool STATS = false, bool BSTATS = false>
 __global__ __launch_bounds__(256, 2) void conv_patch_split_kernel(const IgemmParams p) {
-  constexpr int LDA = 24;                    // bf16 per LDS row: 16 + 8 pad (48 B)
-  constexpr int TW = 32, PW = TW + 2;
-  constexpr int PPIX = (TH + 2) * PW;        // patch pixels (204 for 4 rows, 340 for 8)
+  using G = PatchSplitGeom<BN, TH>;
+  constexpr int LDA = G::LDA;                // bf16 per LDS row: 16 + 8 pad (48 B)
+  constexpr int TW = 32, PW = G::PW;
+  constexpr int PPIX = G::PPIX;              // patch pixels (204 for 4 rows, 340 for 8)
   constexpr int P_PLANE = PPIX * LDA;
   constexpr int P_SLOTS = PPIX * 4;          // f32x4 slots: 16 channels per pixel
   constexpr int P_PASSES = (P_SLOTS + 255) / 256;
@@ -312,11 +328,12 @@ __global__ __launch_bounds__(256, 2) void conv_patch_split_kernel(const IgemmPar
 // per chunk; zero padding stays zero).  STATS: the epilogue emits the tile's per-column
 // (mean, M2) for the InstanceNorm that follows this convolution.
 // ---------------------------------------------------------------------------
+template <int BN, int TH>   // the (TH + 2) x 34 patch of a 32-channel chunk, [buf][BN] weight rows
+using PatchF32Geom = PatchLds<float, BN, TH, 32 + 4, TH + 2, 32 + 2, 1, BN>;
 template <int BN, int WM, int WN, int TH, bool ACT = false, bool STATS = false, bool BSTATS = false>
 __global__ __launch_bounds__(256, 2) void conv_patch_f32_kernel(const IgemmParams p) {
-  constexpr int BK = 32, LDA = BK + 4;
-  constexpr int TW = 32, PW = TW + 2;
-  constexpr int PPIX = (TH + 2) * PW;
+  using G = PatchF32Geom<BN, TH>;
+  constexpr int BK = 32, LDA = G::LDA, TW = 32, PW = G::PW, PPIX = G::PPIX;
   constexpr int P_SLOTS = PPIX * 8;          // f32x4 slots: 32 channels per pixel
   constexpr int P_PASSES = (P_SLOTS + 255) / 256;
   constexpr int B_SLOTS = BN * 8, B_PASSES = (B_SLOTS + 255) / 256;
@@ -588,12 +605,22 @@ __device__ unsigned long long g_stamps[256 * 16];   // (timing experiments only:
 // slots (kx = 0: even 0.., kx = 1: odd 0.., kx = 2: even 1..) and fragment rows of consecutive
 // output rows are two patch rows apart.  Everything else - K steps of three taps, panels,
 // statistics, the output tile through LDS - is the stride-1 code.
+// LDS: the patch in rows of 40 bf16, [buf][tap in row][BN] weight rows; UP: the (TH / 2 + 2) x 18
+// low-resolution pixels in fp32 rows of 36 floats behind them
+template <int BN, int TH, bool UP = false, int SD = 1>
+using PatchB16Geom = PatchLds<__bf16, BN, TH, 32 + 8, SD == 2 ? 2 * TH + 1 : TH + 2,
+                              SD == 2 ? 2 * 32 + 1 : 32 + 2, 1, 3 * BN,
+                              UP ? (TH / 2 + 2) * (32 / 2 + 2) * 36 * sizeof(float) : 0>;
+// workgroups per CU an instantiation is compiled for
+template <int WM, int WN, bool ACT, bool WB, bool UP, int SD>
+constexpr int kPatchB16Wgs = ((WM / 32) * (WN / 32) <= 2 && !UP && (WB || !ACT) && SD == 1) ? 3 : 2;
+
 template <int BN, int WM, int WN, int TH, bool ACT = false, bool STATS = false, bool BSTATS = false,
           bool WB = false, bool UP = false, int SD = 1>
 // (32-accumulator tiles without the up-sampling loader - and, when fused, with the pre-rounded
 // weight panels - stay under 170 registers and 48 KB of LDS: three workgroups per CU - the short K loops of the 32- and 64-channel layers expose one
 // HBM latency per chunk, and the third workgroup is what covers it)
-__global__ __launch_bounds__(256, ((WM / 32) * (WN / 32) <= 2 && !UP && (WB || !ACT) && SD == 1) ? 3 : 2)
+__global__ __launch_bounds__(256, (kPatchB16Wgs<WM, WN, ACT, WB, UP, SD>))
 void conv_patch_b16_kernel(const IgemmParams p) {
   static_assert(!UP || (ACT && STATS && !BSTATS), "UP is a fused-forward loader");
   static_assert(SD == 1 || (SD == 2 && ACT && STATS && !BSTATS && !UP), "stride 2: the fused forward");
@@ -605,12 +632,14 @@ void conv_patch_b16_kernel(const IgemmParams p) {
 #define STAMP() do { } while (0)
 #endif
   STAMP();
-  constexpr int BK = 32, LDA = BK + 8;       // bf16 elements per LDS row
-  constexpr int TW = 32, PW = SD == 2 ? 2 * TW + 1 : TW + 2;
+  using G = PatchB16Geom<BN, TH, UP, SD>;
+  constexpr int BK = 32, LDA = G::LDA;       // bf16 elements per LDS row
+  constexpr int TW = 32, PW = G::PW;
   constexpr int ODD0 = TW + 1;               // SD = 2: first odd-column slot of a patch row
-  constexpr int PPIX = (SD == 2 ? 2 * TH + 1 : TH + 2) * PW;
+  constexpr int PPIX = G::PPIX;
   constexpr int LW = TW / 2 + 2, LPIX = (TH / 2 + 2) * LW;   // UP: low-resolution scratch pixels
   constexpr int L_PASSES = (LPIX * 8 + 255) / 256, LLD = 36;  // fp32 scratch rows of 36 floats
+  static_assert(!UP || G::EXTRA == LPIX * LLD * sizeof(float), "the launcher's scratch is this one");
   constexpr int P_SLOTS = PPIX * 8;          // 4-channel slots: 32 channels per pixel
   constexpr int P_PASSES = (P_SLOTS + 255) / 256;
   // weight slots of a K step (three taps x BN rows x 32 channels): 4 fp32 channels per slot, or
@@ -1135,12 +1164,14 @@ void conv_patch_b16_kernel(const IgemmParams p) {
 // keep patch + weight panels at 67 KB (two workgroups per CU at BN = 128).  Always the fused
 // layer form: activation on load (plain sources pass null coefficients), statistics epilogue.
 // ---------------------------------------------------------------------------
+template <int BN, int TH>   // (2 TH + 1) x 65 input pixels of a 16-channel chunk, [buf][BN] weight rows
+using PatchS2Geom = PatchLds<float, BN, TH, 16 + 4, 2 * TH + 1, 2 * 32 + 1, 1, BN>;
 template <int BN, int WM, int WN, int TH>
 __global__ __launch_bounds__(256, 2) void conv_patch_s2_kernel(const IgemmParams p) {
-  constexpr int BK = 16, LDA = BK + 4, SEG = BK / 4;
-  constexpr int TW = 32, PWC = 2 * TW + 1, PH = 2 * TH + 1;
+  using G = PatchS2Geom<BN, TH>;
+  constexpr int BK = 16, LDA = G::LDA, SEG = BK / 4;
+  constexpr int TW = 32, PWC = G::PW, PPIX = G::PPIX;
   constexpr int ODD0 = TW + 1;               // first odd-column slot of a patch row
-  constexpr int PPIX = PH * PWC;
   constexpr int P_SLOTS = PPIX * SEG;        // f32x4 slots: 16 channels per pixel
   constexpr int P_PASSES = (P_SLOTS + 255) / 256;
   constexpr int B_SLOTS = BN * SEG, B_PASSES = (B_SLOTS + 255) / 256;
@@ -1386,11 +1417,17 @@ __device__ constexpr S2PTap kS2PTaps[9] = {{1, 1, 0, 0, 0}, {1, 2, 0, 0, 1}, {2,
                                            {2, 2, 0, 0, 3}, {1, 0, 0, 1, 1}, {2, 0, 0, 1, 3},
                                            {0, 1, 1, 0, 2}, {0, 2, 1, 0, 3}, {0, 0, 1, 1, 3}};
 
+// the (TH + 1) x 33 dy pixels of a 32-channel chunk; fp32: [buf][BN] weight rows of 36 floats, the
+// bf16 twin below: [buf][tap in step][BN] rows of 40 bf16
+template <int BN, int TH>
+using DgradS2Geom = PatchLds<float, BN, TH, 32 + 4, TH + 1, 32 + 1, 1, BN>;
+template <int BN, int TH>
+using DgradS2B16Geom = PatchLds<__bf16, BN, TH, 32 + 8, TH + 1, 32 + 1, 1, 3 * BN>;
+
 template <int BN, int WM, int WN, int TH>
 __global__ __launch_bounds__(256, 2) void conv_dgrad_s2_patch_kernel(const IgemmParams p) {
-  constexpr int BK = 32, LDA = BK + 4;
-  constexpr int TW = 32, PW = TW + 1, PH = TH + 1;
-  constexpr int PPIX = PH * PW;
+  using G = DgradS2Geom<BN, TH>;
+  constexpr int BK = 32, LDA = G::LDA, TW = 32, PW = G::PW, PPIX = G::PPIX;
   constexpr int P_SLOTS = PPIX * 8;
   constexpr int P_PASSES = (P_SLOTS + 255) / 256;
   constexpr int B_SLOTS = BN * 8, B_PASSES = (B_SLOTS + 255) / 256;
@@ -1601,9 +1638,8 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2_patch_kernel(const Igemm
 // ---------------------------------------------------------------------------
 template <int BN, int WM, int WN, int TH, bool WB = false>
 __global__ __launch_bounds__(256, 2) void conv_dgrad_s2_patch_b16_kernel(const IgemmParams p) {
-  constexpr int BK = 32, LDA = BK + 8;
-  constexpr int TW = 32, PW = TW + 1, PH = TH + 1;
-  constexpr int PPIX = PH * PW;
+  using G = DgradS2B16Geom<BN, TH>;
+  constexpr int BK = 32, LDA = G::LDA, TW = 32, PW = G::PW, PPIX = G::PPIX;
   constexpr int P_SLOTS = PPIX * 8;          // 4-channel slots
   constexpr int P_PASSES = (P_SLOTS + 255) / 256;
   // WB (round 4): the weights pre-rounded to bf16 (p.w3): 8-channel slots, no conversion, and TWO
@@ -1884,16 +1920,19 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2_patch_b16_kernel(const I
 // taps 3..7 blend, tap 8 writes the patch.  Chunks of source 1 (the skip tensor) are staged as
 // in conv_patch_f32_kernel.  Always the fused-layer form (activation on load, statistics).
 // ---------------------------------------------------------------------------
+template <int BN, int TH>   // the fp32 layout + the (TH / 2 + 2) x 18 low-resolution pixels, rows of 36
+using PatchUpGeom = PatchLds<float, BN, TH, 32 + 4, TH + 2, 32 + 2, 1, BN,
+                             (TH / 2 + 2) * (32 / 2 + 2) * (32 + 4) * sizeof(float)>;
 template <int BN, int WM, int WN, int TH>
 __global__ __launch_bounds__(256, 2) void conv_patch_up_kernel(const IgemmParams p) {
-  constexpr int BK = 32, LDA = BK + 4;
-  constexpr int TW = 32, PW = TW + 2;
-  constexpr int PPIX = (TH + 2) * PW;
+  using G = PatchUpGeom<BN, TH>;
+  constexpr int BK = 32, LDA = G::LDA, TW = 32, PW = G::PW, PPIX = G::PPIX;
   constexpr int P_SLOTS = PPIX * 8;
   constexpr int P_PASSES = (P_SLOTS + 255) / 256;
   constexpr int B_SLOTS = BN * 8, B_PASSES = (B_SLOTS + 255) / 256;
   constexpr int B_TILE = BN * LDA;
-  constexpr int LH = TH / 2 + 2, LW = TW / 2 + 2, LPIX = LH * LW;
+  constexpr int LW = TW / 2 + 2, LPIX = (TH / 2 + 2) * LW;
+  static_assert(G::EXTRA == LPIX * LDA * sizeof(float), "the launcher's scratch is this one");
   constexpr int L_SLOTS = LPIX * 8, L_PASSES = (L_SLOTS + 255) / 256;
   constexpr int BPER = (P_PASSES + 4) / 5;     // patch slots blended per tap (taps 3..7)
   constexpr int TM = WM / 32, TN = WN / 32;
@@ -2158,449 +2197,180 @@ __global__ __launch_bounds__(256, 2) void conv_patch_up_kernel(const IgemmParams
   }
 }
 
-template <int BN, int WM, int WN, int TH>
-int launch_patch_up(const IgemmParams& p, hipStream_t stream) {
-  constexpr size_t lds = ((size_t)((TH + 2) * 34) * 36 + 2 * (size_t)BN * 36 +
-                          (size_t)((TH / 2 + 2) * 18) * 36) * sizeof(float);
-  auto kern = conv_patch_up_kernel<BN, WM, WN, TH>;
-  UNET_SET_DYN_LDS(kern, lds);
-  const long long tiles = (long long)p.N * (p.Hin / TH) * (p.Win / 32) * (p.Ncols / BN);
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, stream, p);
-  UNET_CHECK_LAUNCH("conv_patch_up");
-  return UNET_OK;
-}
-
-template <int BN, int WM, int WN, int TH, bool ACT = false, bool STATS = false, bool BSTATS = false>
-int launch_patch_split(const IgemmParams& p, hipStream_t stream) {
-  constexpr size_t lds =
-      (3 * (size_t)((TH + 2) * 34) * 24 + 2 * 3 * (size_t)BN * 24) * sizeof(__bf16);
-  auto kern = conv_patch_split_kernel<BN, WM, WN, TH, ACT, STATS, BSTATS>;
-  UNET_SET_DYN_LDS(kern, lds);
-  const long long tiles = (long long)p.N * (p.Hin / TH) * (p.Win / 32) * (p.Ncols / BN);
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, stream, p);
-  UNET_CHECK_LAUNCH("conv_patch_split");
-  return UNET_OK;
-}
-
-template <int BN, int WM, int WN, int TH, bool ACT = false, bool STATS = false, bool BSTATS = false>
-int launch_patch_f32(const IgemmParams& p, hipStream_t stream) {
-  constexpr size_t lds = ((size_t)((TH + 2) * 34) * 36 + 2 * (size_t)BN * 36) * sizeof(float);
-  auto kern = conv_patch_f32_kernel<BN, WM, WN, TH, ACT, STATS, BSTATS>;
-  UNET_SET_DYN_LDS(kern, lds);
-  const long long tiles = (long long)p.N * (p.Hin / TH) * (p.Win / 32) * (p.Ncols / BN);
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, stream, p);
-  UNET_CHECK_LAUNCH("conv_patch_f32");
-  return UNET_OK;
-}
-
-template <int BN, int WM, int WN, int TH>
-int launch_patch_s2(const IgemmParams& p, hipStream_t stream) {
-  constexpr size_t lds = ((size_t)((2 * TH + 1) * 65) * 20 + 2 * (size_t)BN * 20) * sizeof(float);
-  auto kern = conv_patch_s2_kernel<BN, WM, WN, TH>;
-  UNET_SET_DYN_LDS(kern, lds);
-  const long long tiles = (long long)p.N * (p.Hl / TH) * (p.Wl / 32) * (p.Ncols / BN);
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, stream, p);
-  UNET_CHECK_LAUNCH("conv_patch_s2");
-  return UNET_OK;
-}
-
-template <int BN, int WM, int WN, int TH>
-int launch_dgrad_s2_patch(const IgemmParams& p, hipStream_t stream) {
-  constexpr size_t lds = ((size_t)((TH + 1) * 33) * 36 + 2 * (size_t)BN * 36) * sizeof(float);
-  auto kern = conv_dgrad_s2_patch_kernel<BN, WM, WN, TH>;
-  UNET_SET_DYN_LDS(kern, lds);
-  const long long tiles = (long long)p.N * (p.Hl / TH) * (p.Wl / 32) * (p.Ncols / BN);
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, stream, p);
-  UNET_CHECK_LAUNCH("conv_dgrad_s2_patch");
-  return UNET_OK;
+// ---- launching -------------------------------------------------------------------------------
+// One launch of the patch kernel Kern with the LDS layout G: a workgroup per tile of G::TH x 32
+// pixels of the Ho x Wo output image by G::BN columns, WGS of them on a CU.
+template <auto Kern, typename G, int WGS = 2>
+int launch_patch(const char* label, const IgemmParams& p, int Ho, int Wo, hipStream_t stream) {
+  static_assert(WGS * G::lds_bytes <= 160 * 1024, "the workgroups of a CU share its 160 KB of LDS");
+  const long long tiles = (long long)p.N * (Ho / G::TH) * (Wo / 32) * (p.Ncols / G::BN);
+  return launch_kernel<Kern>(label, dim3((unsigned)tiles), 256, G::lds_bytes, stream, p);
 }
 
 }  // namespace
 
-template <int BN, int WM, int WN, int TH>
-int launch_dgrad_s2_patch_b16(const IgemmParams& p, hipStream_t stream) {
-  constexpr size_t lds = ((size_t)((TH + 1) * 33) * 40 + 2 * 3 * (size_t)BN * 40) * sizeof(__bf16);
-  const long long tiles = (long long)p.N * (p.Hl / TH) * (p.Wl / 32) * (p.Ncols / BN);
-  if (p.w3) {   // the weights pre-rounded to bf16: two panel sets
-    auto kern = conv_dgrad_s2_patch_b16_kernel<BN, WM, WN, TH, true>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, stream, p);
-  } else {
-    auto kern = conv_dgrad_s2_patch_b16_kernel<BN, WM, WN, TH, false>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, stream, p);
-  }
-  UNET_CHECK_LAUNCH("conv_dgrad_s2_patch_b16");
-  return UNET_OK;
-}
+// Every chooser below: the first rung of its family's table (conv_tiles.h) that the shape
+// reaches, kNoTileFits when there is none (the caller keeps its gather-GEMM forms, or for the
+// up-sampling loaders materialises the up-sampled tensor).
 
-// The same for the mixed-precision pipeline (bf16 dy / dx / bs_y); BSTATS as the fp32 form.
-int launch_dgrad_s2_patch_b16_auto(const IgemmParams& p0, hipStream_t stream, int* bs_tiles_out) {
+// Stride-2 data gradient on the patch-staged kernel: p describes the dy grid (Hl x Wl, K = C0) and
+// dx = (2 Hl) x (2 Wl) x Ncols; b16 = bf16 dy / dx / bs_y (the mixed-precision pipeline).  With
+// p.bs_partial set the BSTATS epilogue runs and *bs_tiles_out receives the reduction tiles per
+// image.  (These kernels test p.bs_partial at run time: the fp32 entry leaves it as the caller
+// set it, the bf16 entry drops it when no report is asked for.)
+int launch_dgrad_s2_patch_auto(const IgemmParams& p0, bool b16, hipStream_t stream,
+                               int* bs_tiles_out) {
   IgemmParams p = p0;
   if (bs_tiles_out) *bs_tiles_out = 0;
-  if (p.Wl % 32 != 0 || p.C0 % 32 != 0 || p.Hout != 2 * p.Hl || p.Wout != 2 * p.Wl)
-    return kNoTileFits;
-  const long long pos = (long long)p.N * p.Hl * p.Wl;
-  const int nc = p.Ncols;
-  p.bs_tile0 = 0;
-  if (!bs_tiles_out) p.bs_partial = nullptr;
-  if (nc % 64 == 0 && p.Hl % 4 == 0 && pos / 128 * (nc / 64) >= 256) {
-    p.bs_tiles = p.Hl * p.Wl / 128;
+  if (b16 && !bs_tiles_out) p.bs_partial = nullptr;
+  return with_patch_rule<kDgradS2>(pick_dgrad_s2_patch(p), [&](auto t) {
+    using T = decltype(t);
+    p.bs_tile0 = 0;
+    p.bs_tiles = p.Hl * p.Wl / T::PX;
     if (bs_tiles_out) *bs_tiles_out = p.bs_partial ? p.bs_tiles : 0;
-    return launch_dgrad_s2_patch_b16<64, 32, 64, 4>(p, stream);
-  }
-  if (nc == 32 && p.Hl % 8 == 0 && pos / 256 >= 256) {
-    p.bs_tiles = p.Hl * p.Wl / 256;
-    if (bs_tiles_out) *bs_tiles_out = p.bs_partial ? p.bs_tiles : 0;
-    return launch_dgrad_s2_patch_b16<32, 64, 32, 8>(p, stream);
-  }
-  return kNoTileFits;
-}
-
-// Stride-2 data gradient on the patch-staged kernel: p describes the dy grid (Hl x Wl, K = C0,
-// fp32) and dx = (2 Hl) x (2 Wl) x Ncols.  Returns kNoTileFits when the shape does not tile or too
-// few tiles would run (the caller keeps its gather-GEMM forms).  With p.bs_partial set the BSTATS
-// epilogue runs and *bs_tiles_out receives the reduction tiles per image.
-int launch_dgrad_s2_patch_auto(const IgemmParams& p0, hipStream_t stream, int* bs_tiles_out) {
-  IgemmParams p = p0;
-  if (p.Wl % 32 != 0 || p.C0 % 32 != 0 || p.Hout != 2 * p.Hl || p.Wout != 2 * p.Wl)
-    return kNoTileFits;
-  const long long pos = (long long)p.N * p.Hl * p.Wl;
-  const int nc = p.Ncols;
-  p.bs_tile0 = 0;
-  if (nc % 64 == 0 && p.Hl % 4 == 0 && pos / 128 * (nc / 64) >= 256) {
-    p.bs_tiles = p.Hl * p.Wl / 128;
-    if (bs_tiles_out) *bs_tiles_out = p.bs_partial ? p.bs_tiles : 0;
-    return launch_dgrad_s2_patch<64, 32, 64, 4>(p, stream);
-  }
-  if (nc == 32 && p.Hl % 8 == 0 && pos / 256 >= 256) {
-    p.bs_tiles = p.Hl * p.Wl / 256;
-    if (bs_tiles_out) *bs_tiles_out = p.bs_partial ? p.bs_tiles : 0;
-    return launch_dgrad_s2_patch<32, 64, 32, 8>(p, stream);
-  }
-  return kNoTileFits;
-}
-
-// stride-2 3x3 forward whose OUTPUT tiles as 4 x 32 pixels, 16-channel chunks, standard taps
-bool patch_s2_applicable(const IgemmParams& p) {
-  IgemmParams std_taps{};
-  for (int t = 0; t < 9; ++t) set_tap(std_taps, t, t / 3 - 1, t % 3 - 1, t);
-  return p.ntaps == 9 && p.tap_cstride == 0 && p.src0_pitch == 0 && p.sin == 2 &&
-         p.sout == 1 && p.Hin == 2 * p.Hl && p.Win == 2 * p.Wl && p.Hl == p.Hout &&
-         p.Wl == p.Wout && p.Hl % 4 == 0 && p.Wl % 32 == 0 && p.C0 % 16 == 0 && p.C1 % 16 == 0 &&
-         !p.accumulate && p.tapw[0] == std_taps.tapw[0] && p.tapw[1] == std_taps.tapw[1] &&
-         p.tapw[2] == std_taps.tapw[2];
-}
-
-// fused forward with the up-sampling in the loader (source 0 = the low-resolution tensor)
-template <int BN, int WM, int WN, int TH>
-int launch_patch_b16_up_t(const IgemmParams& p, hipStream_t stream) {
-  constexpr size_t lds = ((size_t)((TH + 2) * 34) * 40 + 2 * 3 * (size_t)BN * 40) * sizeof(__bf16) +
-                         (size_t)((TH / 2 + 2) * 18) * 36 * sizeof(float);
-  static_assert(2 * lds <= 160 * 1024, "two workgroups per CU");
-  const long long tiles = (long long)p.N * (p.Hin / TH) * (p.Win / 32) * (p.Ncols / BN);
-  // (only the pre-rounded weight panels, p.w3: the fp32-panel form of the 64-column tile spills)
-  auto kern = conv_patch_b16_kernel<BN, WM, WN, TH, true, true, false, true, true>;
-  UNET_SET_DYN_LDS(kern, lds);
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, stream, p);
-  UNET_CHECK_LAUNCH("conv_patch_b16(up)");
-  return UNET_OK;
+    if (!b16)
+      return launch_patch<conv_dgrad_s2_patch_kernel<T::BN, T::WM, T::WN, T::TH>,
+                          DgradS2Geom<T::BN, T::TH>>("conv_dgrad_s2_patch", p, p.Hl, p.Wl, stream);
+    return with_bool(p.w3 != nullptr, [&](auto wb) {   // the weights pre-rounded to bf16: two panel sets
+      return launch_patch<
+          conv_dgrad_s2_patch_b16_kernel<T::BN, T::WM, T::WN, T::TH, decltype(wb)::value>,
+          DgradS2B16Geom<T::BN, T::TH>>("conv_dgrad_s2_patch_b16", p, p.Hl, p.Wl, stream);
+    });
+  });
 }
 
 // y = conv3x3(cat(upsample2x(act(low)), act(skip))) on bf16 tensors: p.src0 = low
-// [N][Hin/2][Win/2][C0], p.src1 = skip [N][Hin][Win][C1], both activated on load.  kNoTileFits when
-// no tile shape fits (the caller materialises the up-sampled tensor).
+// [N][Hin/2][Win/2][C0], p.src1 = skip [N][Hin][Win][C1], both activated on load.
+// (only the pre-rounded weight panels, p.w3: the fp32-panel form of the 64-column tile spills)
 int launch_patch_b16_up_auto(const IgemmParams& p0, hipStream_t stream, int* stats_px) {
   IgemmParams p = p0;
-  if (p.Hin % 4 || p.Win % 32 || p.C0 % 32 || p.C1 % 32 || p.C0 < 32 || !p.act0_alpha ||
-      (p.C1 && !p.act1_alpha) || !p.w3 || p.accumulate || (p.ldo & 7) ||
-      (reinterpret_cast<uintptr_t>(p.out) & 15))
-    return kNoTileFits;
-  const long long M = (long long)p.N * p.Hin * p.Win, mt = M / 128;
-  const int nc = p.Ncols;
-  p.bs_partial = nullptr;
-  if (nc % 64 == 0 && p.Hin % 8 == 0 && (M / 256) * (nc / 64) >= 512) {
-    *stats_px = p.stats ? 256 : 0; p.stats_tiles = p.Hin * p.Win / 256;
-    return launch_patch_b16_up_t<64, 64, 64, 8>(p, stream);
-  }
-  if (nc % 64 == 0 && mt * (nc / 64) >= 256) {
-    *stats_px = p.stats ? 128 : 0; p.stats_tiles = p.Hin * p.Win / 128;
-    return launch_patch_b16_up_t<64, 64, 32, 4>(p, stream);
-  }
-  if (nc == 32 && p.Hin % 8 == 0 && (M / 256) >= 256) {
-    *stats_px = p.stats ? 256 : 0; p.stats_tiles = p.Hin * p.Win / 256;
-    return launch_patch_b16_up_t<32, 64, 32, 8>(p, stream);
-  }
-  return kNoTileFits;
-}
-
-template <int BN, int WM, int WN, int TH, bool ACT, bool STATS, bool BSTATS = false>
-int launch_patch_b16_t(const IgemmParams& p, hipStream_t stream) {
-  constexpr size_t lds = ((size_t)((TH + 2) * 34) * 40 + 2 * 3 * (size_t)BN * 40) * sizeof(__bf16);
-  const long long tiles = (long long)p.N * (p.Hin / TH) * (p.Win / 32) * (p.Ncols / BN);
-  if (p.w3) {     // the weights pre-rounded to bf16: panels staged without conversion
-    auto kern = conv_patch_b16_kernel<BN, WM, WN, TH, ACT, STATS, BSTATS, true>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, stream, p);
-  } else if constexpr (TH == 8 && BN == 64) {
-    // (the 8-row 64-column tile exists for the pre-rounded panels only - launch_patch_b16_auto
-    // does not pick it without them: its fused form with fp32 panels spills)
-    unet_set_error("conv_patch_b16: the 8 x 32-pixel tile needs the bf16 weight plane");
-    return UNET_E_INVALID;
-  } else {
-    auto kern = conv_patch_b16_kernel<BN, WM, WN, TH, ACT, STATS, BSTATS, false>;
-    UNET_SET_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, stream, p);
-  }
-  UNET_CHECK_LAUNCH("conv_patch_b16");
-  return UNET_OK;
+  return with_patch_rule<kPatchB16Up>(pick_patch_b16_up(p), [&](auto t) {
+    using T = decltype(t);
+    using G = PatchB16Geom<T::BN, T::TH, true>;
+    bind_epilogue(p, Epilogue::FusedFwd, T::PX, p.Hin * p.Win / T::PX, stats_px);
+    return launch_patch<
+        conv_patch_b16_kernel<T::BN, T::WM, T::WN, T::TH, true, true, false, true, true>, G>(
+        "conv_patch_b16(up)", p, p.Hin, p.Win, stream);
+  });
 }
 
 // Mixed-precision pipeline (bf16 tensors): stride-1 3x3 whose image tiles as 4 x 32 pixels.
-// stats_px != nullptr = fused forward (activation on load + statistics), else data gradient.
-// Returns kNoTileFits when the shape does not qualify (the caller keeps the bf16 gather-GEMM).
+// stats_px != nullptr = fused forward (activation on load + statistics), else data gradient
+// (bs_px with p.bs_partial: the BSTATS epilogue, *bs_px = pixels per reduction tile).
 int launch_patch_b16_auto(const IgemmParams& p0, hipStream_t stream, int* stats_px, int* bs_px) {
   if (bs_px) *bs_px = 0;
-  if (!patch_f32_applicable(p0) || p0.src0_pitch) return kNoTileFits;
   IgemmParams p = p0;
-  const long long M = (long long)p.N * p.Hl * p.Wl;
-  const int nc = p.Ncols;
-  const long long mt = M / 128;
-  const bool fused = stats_px != nullptr;
-  // 8 x 32-pixel tiles of 64 columns where they still give two workgroups per CU: half the
-  // weight-panel traffic (L2 -> LDS) per output of the 4 x 32 tiles; measured -2..-16 % per
-  // launch on the 64..256-channel layers, -0.13 ms per step (profiles/r04_bf16_experiments.txt)
-  const bool th8 = p.w3 && nc % 64 == 0 && p.Hin % 8 == 0 && (M / 256) * (nc / 64) >= 512;
-  if (!fused && bs_px && p.bs_partial) {   // data gradient with the BSTATS epilogue
-    p.bs_tile0 = 0;
-    if (th8) {
-      *bs_px = 256; p.bs_tiles = p.Hin * p.Win / 256;
-      return launch_patch_b16_t<64, 64, 64, 8, false, false, true>(p, stream);
-    }
-    if (nc % 128 == 0 && mt * (nc / 128) >= 256) {
-      *bs_px = 128; p.bs_tiles = p.Hin * p.Win / 128;
-      return launch_patch_b16_t<128, 64, 64, 4, false, false, true>(p, stream);
-    }
-    if (nc % 64 == 0 && mt * (nc / 64) >= 256) {
-      *bs_px = 128; p.bs_tiles = p.Hin * p.Win / 128;
-      return launch_patch_b16_t<64, 64, 32, 4, false, false, true>(p, stream);
-    }
-    if (nc == 32 && p.Hin % 8 == 0 && (M / 256) >= 256) {
-      *bs_px = 256; p.bs_tiles = p.Hin * p.Win / 256;
-      return launch_patch_b16_t<32, 64, 32, 8, false, false, true>(p, stream);
-    }
-    return kNoTileFits;
-  }
-  p.bs_partial = nullptr;
-  if (th8) {
-    if (!fused) return launch_patch_b16_t<64, 64, 64, 8, false, false>(p, stream);
-    *stats_px = p.stats ? 256 : 0; p.stats_tiles = p.Hin * p.Win / 256;
-    return launch_patch_b16_t<64, 64, 64, 8, true, true>(p, stream);
-  }
-  if (nc % 128 == 0 && mt * (nc / 128) >= 256) {
-    if (!fused) return launch_patch_b16_t<128, 64, 64, 4, false, false>(p, stream);
-    *stats_px = p.stats ? 128 : 0; p.stats_tiles = p.Hin * p.Win / 128;
-    return launch_patch_b16_t<128, 64, 64, 4, true, true>(p, stream);
-  }
-  if (nc % 64 == 0 && mt * (nc / 64) >= 256) {
-    if (!fused) return launch_patch_b16_t<64, 64, 32, 4, false, false>(p, stream);
-    *stats_px = p.stats ? 128 : 0; p.stats_tiles = p.Hin * p.Win / 128;
-    return launch_patch_b16_t<64, 64, 32, 4, true, true>(p, stream);
-  }
-  if (nc == 32 && p.Hin % 8 == 0 && (M / 256) >= 256) {
-    if (!fused) return launch_patch_b16_t<32, 64, 32, 8, false, false>(p, stream);
-    *stats_px = p.stats ? 256 : 0; p.stats_tiles = p.Hin * p.Win / 256;
-    return launch_patch_b16_t<32, 64, 32, 8, true, true>(p, stream);
-  }
-  return kNoTileFits;
+  const Epilogue role = patch_role(p, stats_px, bs_px);
+  return with_patch_rule<kPatchB16>(pick_patch_b16(p), [&](auto t) {
+    using T = decltype(t);
+    using G = PatchB16Geom<T::BN, T::TH>;
+    bind_epilogue(p, role, T::PX, p.Hin * p.Win / T::PX, stats_px ? stats_px : bs_px);
+    return with_role(role, [&](auto fused, auto bstats) {
+      constexpr bool F = decltype(fused)::value, B = decltype(bstats)::value;
+      auto launch = [&](auto wb) {   // wb: panels staged from the bf16 plane, without conversion
+        constexpr bool WB = decltype(wb)::value;
+        return launch_patch<conv_patch_b16_kernel<T::BN, T::WM, T::WN, T::TH, F, F, B, WB>, G,
+                            kPatchB16Wgs<T::WM, T::WN, F, WB, false, 1>>("conv_patch_b16", p, p.Hin,
+                                                                        p.Win, stream);
+      };
+      // (a rung that needs the weight plane has no fp32-panel form)
+      if constexpr (T::W3) return launch(std::true_type{});
+      else return with_bool(p.w3 != nullptr, launch);
+    });
+  });
 }
 
-// Fused-layer stride-2 forward on the patch-staged kernel; kNoTileFits when no tile shape fills
-// the chip (the caller falls back to the gather-GEMM).  *stats_px = pixels per statistics tile.
-// Stride-2 fused forward on bf16 tensors (round 4): conv_patch_b16_kernel<.., SD = 2>.  kNoTileFits
-// when the shape does not tile or fill the chip (the caller keeps the bf16 gather-GEMM).
-template <int BN, int WM, int WN, int TH>
-int launch_patch_b16_s2_t(const IgemmParams& p, hipStream_t stream) {
-  constexpr size_t lds = ((size_t)((2 * TH + 1) * 65) * 40 + 2 * 3 * (size_t)BN * 40) * sizeof(__bf16);
-  static_assert(2 * lds <= 160 * 1024, "two workgroups per CU");
-  const long long tiles = (long long)p.N * (p.Hl / TH) * (p.Wl / 32) * (p.Ncols / BN);
-  auto kern = conv_patch_b16_kernel<BN, WM, WN, TH, true, true, false, true, false, 2>;
-  UNET_SET_DYN_LDS(kern, lds);
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, stream, p);
-  UNET_CHECK_LAUNCH("conv_patch_b16(stride 2)");
-  return UNET_OK;
-}
+// Stride-2 fused forward on bf16 tensors (round 4): conv_patch_b16_kernel<.., SD = 2>.
 int launch_patch_s2_b16_auto(const IgemmParams& p0, hipStream_t stream, int* stats_px) {
   IgemmParams p = p0;
-  if (!p.w3 || !patch_s2_applicable(p) || p.C0 % 32 || p.C1 % 32 || (p.ldo & 7) ||
-      (reinterpret_cast<uintptr_t>(p.out) & 15))
-    return kNoTileFits;
-  const long long mt = (long long)p.N * p.Hl * p.Wl / 128;
-  const int nc = p.Ncols;
-  if (nc % 64 == 0 && mt * (nc / 64) >= 512) {
-    *stats_px = p.stats ? 128 : 0;
-    p.stats_tiles = p.Hl * p.Wl / 128;
-    p.bs_partial = nullptr;
-    return launch_patch_b16_s2_t<64, 64, 32, 4>(p, stream);
-  }
-  return kNoTileFits;
+  return with_patch_rule<kPatchB16S2>(pick_patch_b16_s2(p), [&](auto t) {
+    using T = decltype(t);
+    using G = PatchB16Geom<T::BN, T::TH, false, 2>;
+    bind_epilogue(p, Epilogue::FusedFwd, T::PX, p.Hl * p.Wl / T::PX, stats_px);
+    return launch_patch<
+        conv_patch_b16_kernel<T::BN, T::WM, T::WN, T::TH, true, true, false, true, false, 2>, G>(
+        "conv_patch_b16(stride 2)", p, p.Hl, p.Wl, stream);
+  });
 }
 
+// Fused-layer stride-2 forward on the patch-staged kernel (the caller tests patch_s2_applicable);
+// *stats_px = pixels per statistics tile.
 int launch_patch_s2_auto(const IgemmParams& p0, hipStream_t stream, int* stats_px) {
   IgemmParams p = p0;
-  const long long mt = (long long)p.N * p.Hl * p.Wl / 128;
-  const int nc = p.Ncols;
-  *stats_px = p.stats ? 128 : 0;
-  p.stats_tiles = p.Hl * p.Wl / 128;
-  if (nc % 128 == 0 && mt * (nc / 128) >= 512) return launch_patch_s2<128, 64, 64, 4>(p, stream);
-  if (nc % 64 == 0 && mt * (nc / 64) >= 512) return launch_patch_s2<64, 64, 32, 4>(p, stream);
-  *stats_px = 0;
-  return kNoTileFits;
+  return with_patch_rule<kPatchS2>(pick_patch_s2(p), [&](auto t) {
+    using T = decltype(t);
+    bind_epilogue(p, Epilogue::FusedFwd, T::PX, p.Hl * p.Wl / T::PX, stats_px);
+    return launch_patch<conv_patch_s2_kernel<T::BN, T::WM, T::WN, T::TH>,
+                        PatchS2Geom<T::BN, T::TH>>("conv_patch_s2", p, p.Hl, p.Wl, stream);
+  });
 }
 
-// stride-1 3x3 over an image that tiles as 4 x 32 pixels, 16-channel chunks
-bool patch_split_applicable(const IgemmParams& p) {
-  return p.ntaps == 9 && p.sin == 1 && p.sout == 1 && p.Hl == p.Hin && p.Wl == p.Win &&
-         p.Hl == p.Hout && p.Wl == p.Wout && p.Hin % 4 == 0 && p.Win % 32 == 0 &&
-         p.C0 % 16 == 0 && p.C1 % 16 == 0;
-}
-
-// the same with 32-channel chunks (fp32 form)
-bool patch_f32_applicable(const IgemmParams& p) {
-  return p.ntaps == 9 && p.tap_cstride == 0 && p.sin == 1 && p.sout == 1 &&
-         p.Hl == p.Hin && p.Wl == p.Win && p.Hl == p.Hout && p.Wl == p.Wout && p.Hin % 4 == 0 &&
-         p.Win % 32 == 0 && p.C0 % 32 == 0 && p.C1 % 32 == 0;
-}
-
-// fp32: measured on the net's layers +5..19 % over the gather-GEMM at 64 and 128 columns, +8 %
-// at 32 columns when K > 32 (K = 32 stays on the row-fused kernel).  kNoTileFits when no tile
-// shape fits (too few tiles): the caller falls back to the gather-GEMM.
+// fp32 (the caller tests patch_f32_applicable; K = 32 at 32 columns stays on the row-fused kernel).
 // stats_px != nullptr selects the fused-layer instantiation (activation on load, statistics
 // epilogue into p.stats) and receives the number of pixels per statistics tile.
 // bs_px != nullptr (data gradient whose output is final for a layer): the BSTATS epilogue
 // (p.bs_*) runs and *bs_px receives the pixels per reduction tile.
 int launch_patch_f32_auto(const IgemmParams& p0, hipStream_t stream, int* stats_px, int* bs_px) {
   IgemmParams p = p0;
-  const long long M = (long long)p.N * p.Hl * p.Wl;
-  const int nc = p.Ncols;
-  const long long mt = M / 128;
-  const bool fused = stats_px != nullptr;
-  if (!fused && bs_px && p.bs_partial) {
-    p.bs_tile0 = 0;
-    if (nc % 128 == 0 && mt * (nc / 128) >= 512) {
-      *bs_px = 128; p.bs_tiles = p.Hin * p.Win / 128;
-      return launch_patch_f32<128, 64, 64, 4, false, false, true>(p, stream);
-    }
-    if (nc % 64 == 0 && mt * (nc / 64) >= 512) {
-      *bs_px = 128; p.bs_tiles = p.Hin * p.Win / 128;
-      return launch_patch_f32<64, 64, 32, 4, false, false, true>(p, stream);
-    }
-    if (nc == 32 && p.Hin % 8 == 0 && (M / 256) >= 512) {
-      *bs_px = 256; p.bs_tiles = p.Hin * p.Win / 256;
-      return launch_patch_f32<32, 64, 32, 8, false, false, true>(p, stream);
-    }
-    return kNoTileFits;
-  }
-  if (nc % 128 == 0 && mt * (nc / 128) >= 512) {
-    if (!fused) return launch_patch_f32<128, 64, 64, 4>(p, stream);
-    *stats_px = p.stats ? 128 : 0; p.stats_tiles = p.Hin * p.Win / 128;
-    return launch_patch_f32<128, 64, 64, 4, true, true>(p, stream);
-  }
-  if (nc % 64 == 0 && mt * (nc / 64) >= 512) {
-    if (!fused) return launch_patch_f32<64, 64, 32, 4>(p, stream);
-    *stats_px = p.stats ? 128 : 0; p.stats_tiles = p.Hin * p.Win / 128;
-    return launch_patch_f32<64, 64, 32, 4, true, true>(p, stream);
-  }
-  if (nc == 32 && p.Hin % 8 == 0 && (M / 256) >= 512) {
-    if (!fused) return launch_patch_f32<32, 64, 32, 8>(p, stream);
-    *stats_px = p.stats ? 256 : 0; p.stats_tiles = p.Hin * p.Win / 256;
-    return launch_patch_f32<32, 64, 32, 8, true, true>(p, stream);
-  }
-  return kNoTileFits;
+  const Epilogue role = patch_role(p, stats_px, bs_px);
+  return with_patch_rule<kPatchF32>(pick_patch_f32(p), [&](auto t) {
+    using T = decltype(t);
+    bind_epilogue(p, role, T::PX, p.Hin * p.Win / T::PX, stats_px ? stats_px : bs_px);
+    return with_role(role, [&](auto fused, auto bstats) {
+      constexpr bool F = decltype(fused)::value, B = decltype(bstats)::value;
+      return launch_patch<conv_patch_f32_kernel<T::BN, T::WM, T::WN, T::TH, F, F, B>,
+                          PatchF32Geom<T::BN, T::TH>>("conv_patch_f32", p, p.Hin, p.Win, stream);
+    });
+  });
 }
 
 // conv3x3(cat(upsample2x(act(src0 at half resolution)), act(src1))): the up-sampling in the
-// loader.  Same tile choice as launch_patch_f32_auto; kNoTileFits when no tile fits (the caller
-// then materialises the up-sampled operand).
+// loader.  Always the fused-layer form.
 int launch_patch_up_auto(const IgemmParams& p0, hipStream_t stream, int* stats_px) {
   IgemmParams p = p0;
-  const long long M = (long long)p.N * p.Hl * p.Wl;
-  const int nc = p.Ncols;
-  const long long mt = M / 128;
-  if (p.Hin % 4 != 0 || p.Win % 32 != 0 || p.C0 % 32 != 0 || p.C1 % 32 != 0 || p.C0 < 32)
-    return kNoTileFits;
-  if (nc % 128 == 0 && mt * (nc / 128) >= 512) {
-    *stats_px = p.stats ? 128 : 0; p.stats_tiles = p.Hin * p.Win / 128;
-    return launch_patch_up<128, 64, 64, 4>(p, stream);
-  }
-  if (nc % 64 == 0 && mt * (nc / 64) >= 512) {
-    *stats_px = p.stats ? 128 : 0; p.stats_tiles = p.Hin * p.Win / 128;
-    return launch_patch_up<64, 64, 32, 4>(p, stream);
-  }
-  if (wino_up32_applicable(p)) {   // conv_c32.hip: K = 96 as three register-resident Winograd chunks
-    *stats_px = p.stats ? 256 : 0; p.stats_tiles = p.Hin * p.Win / 256;
+  if (!patch_up_applicable(p)) return kNoTileFits;
+  const int rule = pick_patch_up(p);
+  // conv_c32.hip: K = 96 as three register-resident Winograd chunks, in front of the 32-column rung
+  if ((rule == kNoRule || rule >= kPatchUpWinoBefore) && wino_up32_applicable(p)) {
+    bind_epilogue(p, Epilogue::FusedFwd, 256, p.Hin * p.Win / 256, stats_px);
     return launch_wino_up32(p, stream);
   }
-  if (nc == 32 && p.Hin % 8 == 0 && (M / 256) >= 512) {
-    *stats_px = p.stats ? 256 : 0; p.stats_tiles = p.Hin * p.Win / 256;
-    return launch_patch_up<32, 64, 32, 8>(p, stream);
-  }
-  return kNoTileFits;
+  return with_patch_rule<kPatchF32>(rule, [&](auto t) {
+    using T = decltype(t);
+    bind_epilogue(p, Epilogue::FusedFwd, T::PX, p.Hin * p.Win / T::PX, stats_px);
+    return launch_patch<conv_patch_up_kernel<T::BN, T::WM, T::WN, T::TH>,
+                        PatchUpGeom<T::BN, T::TH>>("conv_patch_up", p, p.Hin, p.Win, stream);
+  });
 }
 
-// The split mode of the fused layer pipeline: stats_px != nullptr = fused forward (activation
-// on load, statistics epilogue), bs_px != nullptr = data gradient with the BSTATS epilogue.
-// kNoTileFits when no tile shape fills the chip (the caller runs the fp32 fused kernel instead).
+// The split mode of the fused layer pipeline (the caller tests patch_split_applicable):
+// stats_px != nullptr = fused forward (activation on load, statistics epilogue), else the data
+// gradient, always on the BSTATS instantiation (p.bs_partial with bs_px decides at run time).
+// kNoTileFits: the caller runs the fp32 fused kernel instead.
 int launch_patch_split_fused_auto(const IgemmParams& p0, hipStream_t stream, int* stats_px,
                                   int* bs_px) {
   IgemmParams p = p0;
-  const long long M = (long long)p.N * p.Hl * p.Wl;
-  const int nc = p.Ncols;
-  const bool fwd = stats_px != nullptr;
-  const bool tall = p.Hin % 8 == 0;
-  int px = 0;
-  int cls = 0;   // 1: <128,64,64,4>  2: <64,128,32,8>  3: <64,64,32,4>  4: <32,64,32,8>
-  if (nc % 128 == 0 && (M / 128) * (nc / 128) >= 512) { cls = 1; px = 128; }
-  else if (nc % 64 == 0 && tall && (M / 256) * (nc / 64) >= 512) { cls = 2; px = 256; }
-  else if (nc % 64 == 0 && (M / 128) * (nc / 64) >= 256) { cls = 3; px = 128; }
-  else if (nc == 32 && tall && (M / 256) >= 512) { cls = 4; px = 256; }
-  if (!cls) return kNoTileFits;
-  if (fwd) {
-    *stats_px = p.stats ? px : 0;
-    p.stats_tiles = p.Hin * p.Win / px;
-    p.bs_partial = nullptr;
-    switch (cls) {
-      case 1: return launch_patch_split<128, 64, 64, 4, true, true, false>(p, stream);
-      case 2: return launch_patch_split<64, 128, 32, 8, true, true, false>(p, stream);
-      case 3: return launch_patch_split<64, 64, 32, 4, true, true, false>(p, stream);
-      default: return launch_patch_split<32, 64, 32, 8, true, true, false>(p, stream);
-    }
-  }
-  p.stats = nullptr;
-  if (bs_px && p.bs_partial) { *bs_px = px; p.bs_tiles = p.Hin * p.Win / px; p.bs_tile0 = 0; }
-  else { if (bs_px) *bs_px = 0; p.bs_partial = nullptr; }
-  switch (cls) {
-    case 1: return launch_patch_split<128, 64, 64, 4, false, false, true>(p, stream);
-    case 2: return launch_patch_split<64, 128, 32, 8, false, false, true>(p, stream);
-    case 3: return launch_patch_split<64, 64, 32, 4, false, false, true>(p, stream);
-    default: return launch_patch_split<32, 64, 32, 8, false, false, true>(p, stream);
-  }
+  const Epilogue role = stats_px ? Epilogue::FusedFwd : Epilogue::DgradBs;
+  return with_patch_rule<kPatchSplitFused>(pick_patch_split_fused(p), [&](auto t) {
+    using T = decltype(t);
+    bind_epilogue(p, role, T::PX, p.Hin * p.Win / T::PX, stats_px ? stats_px : bs_px);
+    return with_bool(role == Epilogue::FusedFwd, [&](auto fused) {
+      constexpr bool F = decltype(fused)::value;
+      return launch_patch<conv_patch_split_kernel<T::BN, T::WM, T::WN, T::TH, F, F, !F>,
+                          PatchSplitGeom<T::BN, T::TH>>("conv_patch_split", p, p.Hin, p.Win, stream);
+    });
+  });
 }
 
+// plain split-bf16 forward / data gradient (the caller tests patch_split_applicable)
 int launch_patch_split_auto(const IgemmParams& p, hipStream_t stream) {
-  const long long M = (long long)p.N * p.Hl * p.Wl;
-  const int nc = p.Ncols;
-  const long long mt = M / 128;
-  if (nc % 128 == 0 && mt * (nc / 128) >= 512)
-    return launch_patch_split<128, 64, 64, 4>(p, stream);
-  // narrow outputs: taller tiles (two or four patch rows per wave) cut the LDS reads per MFMA
-  const bool tall = p.Hin % 8 == 0;
-  if (nc % 64 == 0) {
-    if (tall && (M / 256) * (nc / 64) >= 512) return launch_patch_split<64, 128, 32, 8>(p, stream);
-    return launch_patch_split<64, 64, 32, 4>(p, stream);
-  }
-  if (tall && (M / 256) * (nc / 32) >= 512) return launch_patch_split<32, 64, 32, 8>(p, stream);
-  return launch_patch_split<32, 32, 32, 4>(p, stream);
+  const int rule = pick_patch_split(p);
+  UNET_REQUIRE(rule != kNoRule, "conv_patch_split: %d columns are not a multiple of 32", p.Ncols);
+  return with_patch_rule<kPatchSplit>(rule, [&](auto t) {
+    using T = decltype(t);
+    return launch_patch<conv_patch_split_kernel<T::BN, T::WM, T::WN, T::TH>,
+                        PatchSplitGeom<T::BN, T::TH>>("conv_patch_split", p, p.Hin, p.Win, stream);
+  });
 }
 
 }  // namespace unet_conv

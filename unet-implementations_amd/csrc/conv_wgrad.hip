@@ -16,6 +16,7 @@
 // Replaces the weight-gradient half of aten::convolution_backward reached from
 // loss.backward() (Our_UNet/src/train.py:663).
 #include "conv_params.h"
+#include "conv_launch.h"
 #include <vector>
 #include "lds_asm.h"
 #include <type_traits>
@@ -24,6 +25,9 @@
 namespace {
 using unet_conv::act4;
 using unet_conv::act4f;
+using unet_conv::launch_kernel;
+using unet_conv::with_bool;
+using unet_conv::with_bools;
 template <int I> using template_ic = std::integral_constant<int, I>;
 // compile-time loop: f(integral_constant<int, I>) for I in [B, E)
 template <int B, int... I, typename F>
@@ -1742,29 +1746,6 @@ WgradPlan make_plan(int N, int H, int W, int Cx, int Cout, int stride, const Pla
 }
 
 // ---- launching --------------------------------------------------------------------------------
-// f(std::true_type | std::false_type) for a run-time bool: how a launcher picks the ACT / bf16
-// instantiation of its kernel
-template <typename F>
-int with_bool(bool b, F&& f) {
-  return b ? f(std::true_type{}) : f(std::false_type{});
-}
-template <typename F>
-int with_bools(bool a, bool b, F&& f) {
-  return with_bool(a, [&](auto ca) { return with_bool(b, [&](auto cb) { return f(ca, cb); }); });
-}
-
-// One launch of the kernel instantiation Kern: raises its dynamic-LDS limit (remembered per
-// instantiation and device), goes through the recording hipLaunchKernelGGL and reports a failed
-// launch under `label`.
-template <auto Kern, typename... Args>
-int launch_kernel(const char* label, dim3 grid, unsigned threads, size_t lds, hipStream_t stream,
-                  const Args&... args) {
-  if (lds) UNET_SET_DYN_LDS(Kern, lds);
-  hipLaunchKernelGGL(Kern, grid, dim3(threads), lds, stream, args...);
-  UNET_CHECK_LAUNCH(label);
-  return UNET_OK;
-}
-
 // one workgroup per (pixel split, channel tile)
 dim3 wgrad_grid(const WgradParams& p) { return dim3((unsigned)(p.split * p.ci_tiles * p.co_tiles)); }
 
