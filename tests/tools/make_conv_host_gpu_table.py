@@ -3,7 +3,9 @@ points of csrc/conv_igemm.hip do on the GPU over a small grid of calls - per row
 launch list (ops.record_launches), the reported stats_px / tiles_out and a CRC32 of the bytes of
 every output the call writes (y / dx / g, the statistics or BSTATS summaries up to the reported
 tile count, dx after an accumulate call onto a seeded non-zero dx).
-tests/test_conv_host_gpu.py holds the library under test to all three columns, exactly.
+tests/test_conv_host_gpu.py holds the library under test to all three columns, exactly;
+tests/test_conv_host_fp64_gpu.py makes the same calls (build_row with coherent weight planes,
+call_row) and holds their outputs to the float64 references of tests/tools/conv_host_refs.py.
 
 Inputs come from a seeded CPU generator and these kernels use no atomics, so the outputs are
 bit-reproducible: every row runs twice and no table is written when any row differs between its
@@ -274,8 +276,35 @@ def _crc(t):
     return zlib.crc32(t.contiguous().view(-1).view(torch.uint8).cpu().numpy().tobytes())
 
 
-def run_row(ua, row):
-    """Makes the call of `row` on seeded inputs; returns (launches, report, {output: crc32})."""
+def coherent_planes(w, planes):
+    """The bf16 weight planes a kernel may read in place of the fp32 weight `w` [taps, A, B], from
+    torch alone: [planes, 9, A, B] with h = bf16(w), m = bf16(w - h), l = bf16(w - h - m) (both
+    differences are exact in fp32) - or only h, round to nearest even, for a one-plane form.  A
+    1x1 weight is repeated over the nine taps (no 1x1 call reads its planes)."""
+    import torch
+    w = w.float().expand(9, *w.shape[1:])
+    h = w.to(torch.bfloat16)
+    if planes == 1:
+        return h[None].contiguous()
+    m = (w - h.float()).to(torch.bfloat16)
+    lo = (w - h.float() - m.float()).to(torch.bfloat16)
+    return torch.stack([h, m, lo]).contiguous()
+
+
+def build_row(ua, row, coherent=False):
+    """The operands of the call of `row` on seeded inputs -> a record (dict) with
+      args       the ctypes argument list (without the stream)
+      t          the named torch tensors the call reads: x0 x1 wf w3 bias (plain forward), dy wd w3
+                 base (the seeded dx of an accumulate row, a copy) by mean rstd gamma beta mask (the
+                 unet_bwd_stats operands), s0 a0 b0 s1 a1 b1 w w3 bias (fused forward; s0 = low and
+                 s1 = skip of the up-sampling one; a / b = activation coefficients or absent),
+                 image mean3 std3 wf bias (uint8 stem), y gamma beta mask tiles (finalize; tiles =
+                 the [N, tiles, Cout, 2] (mean, M2) pairs it merges when stats_px > 0)
+      out        the tensors the call writes: y / dx, or mean rstd alpha beta
+    and what call_row needs (the chunked tensor's bytes per image, the report cells, workspace).
+    coherent: the weight planes w3 are those of the row's fp32 weight (coherent_planes) instead of
+    an independent draw, so that the right answer does not depend on which kernel reads what;
+    every other operand, and the order of the draws, is the same."""
     import torch
     from unet_implementations_amd._lib import ActSrc, BwdStats
     lib = ua.lib()
@@ -293,16 +322,20 @@ def run_row(ua, row):
     stride, ksize = row.get("stride", 1), row.get("ksize", 3)
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     Cout = row["Cout"]
-    keep, out, v = [], {}, dict(N=N, H=H, W=W, Cout=Cout, stride=stride, ksize=ksize, slope=0.01,
-                                eps=1e-5, accumulate=row.get("acc", 0))
+    keep, out, t = [], {}, {}
+    v = dict(N=N, H=H, W=W, Cout=Cout, stride=stride, ksize=ksize, slope=0.01, eps=1e-5,
+             accumulate=row.get("acc", 0))
     planes = 1 if fn in ONE_PLANE else 3
-    per_image = 0      # bytes of one image of the tensor the entry point chunks by
+    built = dict(t=t, out=out, keep=keep, per_image=0, px=None, bs=None, ws=None, partial=None,
+                 Ho=Ho, Wo=Wo)
 
-    def src(C, h, w, act, dtype):
+    def src(C, h, w, act, dtype, name):
         x = rnd((N, h, w, C), dtype)
         a = rnd((N, C), scale=0.5) + 1.0 if act else None
         b = rnd((N, C), scale=0.1) if act else None
-        keep.extend([x, a, b])
+        t["s" + name] = x
+        if act:
+            t["a" + name], t["b" + name] = a, b
         s = ActSrc(x.data_ptr(), C, a.data_ptr() if act else None, b.data_ptr() if act else None)
         keep.append(s)
         return ctypes.byref(s)
@@ -313,13 +346,17 @@ def run_row(ua, row):
         x0, x1 = rnd((N, H, W, C0)), rnd((N, H, W, C1)) if C1 else None
         wf = rnd((taps, Cout, C0 + C1), scale=0.05)
         w3 = rnd((3, 9, Cout, C0 + C1), torch.bfloat16, 0.05)
+        if coherent:
+            w3 = coherent_planes(wf, 3)
         y = torch.zeros((N, Ho, Wo, Cout), device=dev)
         bias = rnd((Cout,))
-        keep += [x0, x1, wf, w3, bias]
+        t.update(x0=x0, wf=wf, w3=w3, bias=bias)
+        if C1:
+            t["x1"] = x1
         v.update(x0=x0.data_ptr(), C0=C0, x1=x1.data_ptr() if C1 else None, C1=C1,
                  wf=wf.data_ptr(), w3=w3.data_ptr(), bias=bias.data_ptr(), y=y.data_ptr())
         out["y"] = y
-        per_image = H * W * max(C0, C1) * 4
+        built["per_image"] = H * W * max(C0, C1) * 4
     elif "dy" in keys:                                 # data gradients
         Ccols = row["Ccols"]
         Cin_total = row.get("Cin_total", Ccols)
@@ -328,23 +365,30 @@ def run_row(ua, row):
         dy = rnd((N, Ho, Wo, (9 if up else 1) * Cout), tt)
         wd = rnd((taps, Cin_total, Cout), scale=0.05)
         w3 = rnd((planes, 9, Cin_total, Cout), torch.bfloat16, 0.05) if row.get("w3", 1) else None
+        if coherent and w3 is not None:
+            w3 = coherent_planes(wd, planes)
         dx = rnd((N, H, W, Ccols), tt) if row.get("acc") else torch.zeros((N, H, W, Ccols),
                                                                           dtype=tt, device=dev)
-        keep += [dy, wd, w3]
+        t.update(dy=dy, wd=wd)
+        if w3 is not None:
+            t["w3"] = w3
+        if row.get("acc"):
+            t["base"] = dx.clone()
         v.update(dy=dy.data_ptr(), wd=wd.data_ptr(), w3=w3.data_ptr() if w3 is not None else None,
                  Cin_total=Cin_total, ci_offset=row.get("ci_offset", 0), dx=dx.data_ptr(),
                  Ccols=Ccols, bs=None)
         out["dx"] = dx
-        per_image = Ho * Wo * (9 if up else 1) * Cout * es
+        built["per_image"] = Ho * Wo * (9 if up else 1) * Cout * es
         if row.get("bs"):
             by = rnd((N, H, W, Ccols), tt)
             st = [rnd((N, Ccols)), rnd((N, Ccols)).abs() + 0.5, rnd((Ccols,)), rnd((Ccols,)),
                   (rnd((N, Ccols)) > 0).float() * 2.0]
             nb = N * ((H * W + 63) // 64) * Ccols * 8
             partial = torch.zeros(nb, dtype=torch.uint8, device=dev)
-            bs = BwdStats(by.data_ptr(), *[t.data_ptr() for t in st], 0.01, partial.data_ptr(),
+            bs = BwdStats(by.data_ptr(), *[x.data_ptr() for x in st], 0.01, partial.data_ptr(),
                           nb - (1 if row["bs"] == "short" else 0), -7)
-            keep += [by, st, bs]
+            t.update(by=by, mean=st[0], rstd=st[1], gamma=st[2], beta=st[3], mask=st[4])
+            built.update(bs=bs, partial=partial)
             v["bs"] = ctypes.byref(bs)
     elif "s0" in keys or "low" in keys:                # fused forward
         C0, C1 = row["C0"], row.get("C1", 0)
@@ -352,24 +396,30 @@ def run_row(ua, row):
         upf = "low" in keys
         a, b = ("low", "skip") if upf else ("s0", "s1")
         v[a] = src(C0, H // 2 if upf else H, W // 2 if upf else W, "0" in act,
-                   torch.float32 if C0 == 3 else tt)
-        v[b] = src(C1, H, W, "1" in act, tt) if C1 else None
+                   torch.float32 if C0 == 3 else tt, "0")
+        v[b] = src(C1, H, W, "1" in act, tt, "1") if C1 else None
         w = rnd((ksize * ksize, Cout, C0 + C1), scale=0.05)
         w3 = rnd((planes, 9, Cout, C0 + C1), torch.bfloat16, 0.05) if row.get("w3", 1) else None
+        if coherent and w3 is not None:
+            w3 = coherent_planes(w, planes)
         bias = rnd((Cout,))
         y = torch.zeros((N, Ho, Wo, Cout), dtype=tt, device=dev)
-        keep += [w, w3, bias]
+        t.update(w=w, bias=bias)
+        if w3 is not None:
+            t["w3"] = w3
         v.update(w=w.data_ptr(), wf=w.data_ptr(), w3=w3.data_ptr() if w3 is not None else None,
                  bias=bias.data_ptr(), y=y.data_ptr())
         out["y"] = y
-        per_image = H * W * max(C0, C1) * es
+        built["per_image"] = H * W * max(C0, C1) * es
     elif "image" in keys:                              # RGB stem from uint8
         img = torch.randint(0, 256, (N, H, W, 3), generator=g, dtype=torch.uint8).to(dev)
         wf, bias = rnd((9, Cout, 3), scale=0.05), rnd((Cout,))
         y = torch.zeros((N, H, W, Cout), dtype=tt, device=dev)
-        keep += [img, wf, bias]
-        v.update(image=img.data_ptr(), mean3=(ctypes.c_float * 3)(0.485, 0.456, 0.406),
-                 std3=(ctypes.c_float * 3)(0.229, 0.224, 0.225), wf=wf.data_ptr(),
+        mean3, std3 = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+        t.update(image=img, wf=wf, bias=bias, mean3=torch.tensor(mean3, device=dev),
+                 std3=torch.tensor(std3, device=dev))
+        v.update(image=img.data_ptr(), mean3=(ctypes.c_float * 3)(*mean3),
+                 std3=(ctypes.c_float * 3)(*std3), wf=wf.data_ptr(),
                  bias=bias.data_ptr(), y=y.data_ptr())
         out["y"] = y
     else:                                              # statistics finalize
@@ -377,28 +427,49 @@ def run_row(ua, row):
         res = [torch.zeros((N, Cout), device=dev) for _ in range(4)]
         gamma, beta = rnd((Cout,)), rnd((Cout,))
         mask = (rnd((N, Cout)) > 0).float() * 2.0 if row.get("mask") else None
-        keep += [y, gamma, beta, mask]
+        t.update(y=y, gamma=gamma, beta=beta)
+        if mask is not None:
+            t["mask"] = mask
         v.update(y=y.data_ptr(), stats_px=row["stats_px"], gamma=gamma.data_ptr(),
                  beta=beta.data_ptr(), mask=mask.data_ptr() if mask is not None else None,
                  mean=res[0].data_ptr(), rstd=res[1].data_ptr(), alpha_out=res[2].data_ptr(),
                  beta_out=res[3].data_ptr(), HoWo=H * W)
         out.update(mean=res[0], rstd=res[1], alpha=res[2], beta=res[3])
-    ws = None
     if "ws" in keys:
         nws = lib.unet_conv_in_fwd_workspace_bytes(N, H, W, Cout, stride)
         if "stats_px" in keys:       # the producer's summaries: (mean, M2 >= 0) per tile
             ws = torch.zeros(nws, dtype=torch.uint8, device=dev)
             ws[:nws // 4 * 4] = rnd((nws // 4,)).abs().view(torch.uint8)
+            if row["stats_px"]:
+                tiles = H * W // row["stats_px"]
+                t["tiles"] = ws[:N * tiles * Cout * 8].view(torch.float32).view(
+                    N, tiles, Cout, 2).clone()
         else:
             ws = torch.zeros(nws, dtype=torch.uint8, device=dev)
-        px = ctypes.c_int(-7)
-        v.update(ws=ws.data_ptr(), ws_bytes=nws, px=ctypes.byref(px))
-    args = [v[k] for k in keys]
+        built["ws"] = ws
+        if "px" in keys:
+            built["px"] = ctypes.c_int(-7)
+        v.update(ws=ws.data_ptr(), ws_bytes=nws,
+                 px=ctypes.byref(built["px"]) if "px" in keys else None)
+    built["args"] = [v[k] for k in keys]
+    return built
+
+
+def call_row(ua, row, built):
+    """Makes the call of `row` on the operands of build_row under the row's chunk limit and c32
+    switch; returns (launches, report, {output: tensor}) - the outputs of build_row plus, where the
+    call reports them, `stats` / `partial` cut to the reported tile count (raw bytes)."""
+    import torch
+    lib = ua.lib()
+    fn = row["fn"]
+    keys = T.EXPORTS[fn]
+    out = dict(built["out"])
     prev = lib.unet_set_c32_winograd(row["c32"]) if "c32" in row else None
     torch.cuda.synchronize()
     try:
-        with T.chunk_limit(lib, row.get("lim", 0) * per_image), ua.ops.record_launches() as rec:
-            rc = getattr(lib, fn)(*args, ua.ops._stream())
+        with T.chunk_limit(lib, row.get("lim", 0) * built["per_image"]), \
+                ua.ops.record_launches() as rec:
+            rc = getattr(lib, fn)(*built["args"], ua.ops._stream())
     finally:
         if prev is not None:
             lib.unet_set_c32_winograd(prev)
@@ -406,14 +477,21 @@ def run_row(ua, row):
     torch.cuda.synchronize()
     report = -1
     if "px" in keys:
-        report = px.value
+        report = built["px"].value
         if report > 0:
-            out["stats"] = ws[:N * (Ho * Wo // report) * Cout * 8]
-    if v.get("bs") is not None:
-        report = bs.tiles_out
+            out["stats"] = built["ws"][:row["N"] * (built["Ho"] * built["Wo"] // report) *
+                                       row["Cout"] * 8]
+    if built["bs"] is not None:
+        report = built["bs"].tiles_out
         if report > 0:
-            out["partial"] = partial[:N * report * row["Ccols"] * 8]
-    return rec.names, report, {k: _crc(t) for k, t in out.items()}
+            out["partial"] = built["partial"][:row["N"] * report * row["Ccols"] * 8]
+    return rec.names, report, out
+
+
+def run_row(ua, row):
+    """Makes the call of `row` on seeded inputs; returns (launches, report, {output: crc32})."""
+    names, report, out = call_row(ua, row, build_row(ua, row))
+    return names, report, {k: _crc(t) for k, t in out.items()}
 
 
 # ---- coverage ------------------------------------------------------------------------------------
