@@ -1450,6 +1450,62 @@ int unet_letterbox_u8(const uint8_t* arena, size_t arena_bytes, const int64_t* t
 int unet_byte_histogram_u8(const uint8_t* arena, size_t arena_bytes, const int64_t* table, int B,
                            uint64_t* hist, unet_stream_t stream);
 
+/* ---- latent-space analysis (latent.hip) ----------------------------------------------
+ * analyze_latent_space of AE_pretrained/reconstruction/src/evaluate.py:380-440 from the code matrix
+ * x [N][D] (fp32, row-major, 16-byte aligned; N in 2..65536, D a multiple of 4).  Every sum has a
+ * fixed order: two runs are bit-identical. */
+
+/* Bytes of the workspace of unet_latent_col_mean / unet_latent_project.  0 for a bad shape. */
+size_t unet_latent_colsum_workspace_bytes(int N, int D);
+/* mean[d] = (sum_i x[i][d]) / N */
+int unet_latent_col_mean(const float* x, float* mean, void* workspace, size_t workspace_bytes,
+                         int N, int D, unet_stream_t stream);
+/* out[c][d] = sum_i (x[i][d] - mean[d]) w[i][c], c = 0, 1; w [N][2]: the principal axes from the
+ * dual eigenvectors (w = U / sqrt(lambda)). */
+int unet_latent_project(const float* x, const float* mean, const float* w, float* out,
+                        void* workspace, size_t workspace_bytes, int N, int D,
+                        unet_stream_t stream);
+
+/* g [N][N] = (x - mean)(x - mean)^T on the fp32 matrix cores (v_mfma_f32_32x32x2_f32, fp32 sums):
+ * the mean is subtracted while x is loaded; only the 128 x 128 tiles on or above the diagonal are
+ * formed, in unet_latent_gram_splitk(N, D) slabs of D that a second launch sums in ascending order
+ * and mirrors, so g is bitwise symmetric.  x may exceed 2 GiB (64-bit row offsets). */
+size_t unet_latent_gram_workspace_bytes(int N, int D);
+int unet_latent_gram_splitk(int N, int D);
+int unet_latent_gram(const float* x, const float* mean, float* g, void* workspace,
+                     size_t workspace_bytes, int N, int D, unet_stream_t stream);
+/* z [N][8] = g q for q [N][8]: the product of the block subspace iteration */
+int unet_latent_gram_apply(const float* g, const float* q, float* z, int N, unet_stream_t stream);
+
+/* Exact t-SNE (scikit-learn's method='exact' restated), N in 2..8192.
+ * cond_p: pc [N][N] = the conditional probabilities of sklearn's _binary_search_perplexity (100
+ *   steps, tolerance 1e-5 on the entropy) over the squared distances max(g_ii + g_jj - 2 g_ij, 0),
+ *   diag [N] = the diagonal of g; the row's minimum off-diagonal distance is subtracted before
+ *   exp; pc_ii = 0.  rowsum [N + 1] (double): the row sums of pc; entry N is scratch of joint_p.
+ * joint_p: p = max((pc + pc^T) / max(sum, eps), eps) off the diagonal, 0 on it (eps = DBL_EPSILON,
+ *   as _joint_probabilities). */
+int unet_tsne_cond_p(const float* g, const float* diag, float perplexity, float* pc,
+                     double* rowsum, int N, unet_stream_t stream);
+int unet_tsne_joint_p(const float* pc, double* rowsum, float* p, int N, unet_stream_t stream);
+/* One iteration of sklearn's _gradient_descent on _kl_divergence, two launches.
+ *   state [N][6] = (y0, y1, update0, update1, gains0, gains1), read from state_in, written to
+ *   state_out (which must differ); rows [N][8] scratch.  With q_ij = 1 / (1 + |y_i - y_j|^2),
+ *   Z = sum_{i != j} q_ij: grad_i = 4 (sum_j e p_ij q_ij (y_i - y_j) - sum_j q_ij^2 (y_i - y_j) / Z),
+ *   e = exaggeration; gains + 0.2 where update grad < 0, else gains 0.8, floored at 0.01;
+ *   update = momentum update - lr gains grad; y += update.
+ *   want_stats != 0: stats[0] = KL = sum_{i != j} e p log(e p Z / q), stats[1] = |gains grad|
+ *   (the norm _gradient_descent tests), both at state_in. */
+int unet_tsne_step(const float* p, const float* state_in, float* state_out, float* rows,
+                   double* stats, float exaggeration, float momentum, float lr, int want_stats,
+                   int N, unet_stream_t stream);
+
+/* out [H][W][3] (uint8) = the scatter picture on a white ground: centres [N][2] (int32 pixel
+ * x, y), labels [N] (uint8), palette [K][3] (uint8 RGB).  Point n covers the pixels with
+ * dx^2 + dy^2 <= radius^2; the covering points blend in index order,
+ * dst = (dst 77 + src 179 + 128) >> 8 per channel (alpha = 0.7).  A label >= K draws nothing. */
+int unet_latent_scatter(const int* centres, const uint8_t* labels, const uint8_t* palette, int K,
+                        uint8_t* out, int N, int H, int W, int radius, unet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,56 @@ def evaluate_reconstruction_quality(model, test_loader, device, output_dir=None,
     return {"mse": mse, "psnr": psnr, "ssim": ssim, "num_samples": num_samples}
 
 
+@torch.no_grad()
+def analyze_latent_space(model, test_loader, device, output_dir, perplexity=30.0):
+    """src/evaluate.py:380-440: eval mode, `model.encode` of every test image, the codes reduced to
+    2-D with PCA and with t-SNE, and the two scatter pictures coloured by `batch["label"]` written
+    to `latent_analysis/latent_space_pca.png` and `latent_space_tsne.png` under `output_dir`.
+    The codes go straight into one preallocated device matrix [len(dataset), D]; one centred Gram
+    matrix (`latent.gram`) serves both reductions, the t-SNE starting from the PCA scores.
+    Returns {"pca", "tsne" (the [N, 2] coordinates), "labels", "kl_divergence", "n_iter",
+    "pca_residuals", "explained_variance", "num_samples"}; the reference returns nothing."""
+    from . import latent
+    from .render import write_png
+    ds = getattr(test_loader, "dataset", None)
+    if ds is None:
+        raise TypeError("analyze_latent_space needs a DataLoader-like object with a .dataset")
+    total = len(ds)
+    latent_dir = os.path.join(str(output_dir), "latent_analysis")
+    os.makedirs(latent_dir, exist_ok=True)
+    model.eval()
+    codes, labels, n = None, torch.empty(total, dtype=torch.int64, device=device), 0
+    for batch in test_loader:
+        if "label" not in batch:
+            raise KeyError("label: analyze_latent_space colours the codes by batch['label'] (the "
+                           "reference's dataset yields int(mask.max()) per image)")
+        images = batch["image"].to(device, non_blocking=True)
+        z = model.encode(images)
+        if codes is None:
+            codes = torch.empty((total, z.shape[1]), dtype=torch.float32, device=device)
+        B = z.shape[0]
+        if n + B > total:
+            raise ValueError("analyze_latent_space: the loader yields more images than its dataset")
+        codes[n:n + B] = z
+        labels[n:n + B] = torch.as_tensor(batch["label"]).to(device).reshape(-1)
+        n += B
+    if n < 2:
+        raise ValueError("analyze_latent_space: fewer than two test images")
+    codes, labels = codes[:n], labels[:n]
+    G = latent.gram(codes)
+    pca = latent.pca_2d(G)
+    write_png(os.path.join(latent_dir, "latent_space_pca.png"),
+              latent.scatter_figure(pca.scores, labels))
+    s = pca.scores.double()
+    tsne = latent.tsne_2d(G, perplexity=perplexity, init=s / s[:, 0].std(unbiased=False) * 1e-4)
+    write_png(os.path.join(latent_dir, "latent_space_tsne.png"),
+              latent.scatter_figure(tsne.y, labels))
+    return {"pca": pca.scores, "tsne": tsne.y, "labels": labels,
+            "kl_divergence": tsne.kl_divergence, "n_iter": tsne.n_iter,
+            "pca_residuals": pca.residuals, "explained_variance": pca.explained_variance,
+            "num_samples": n}
+
+
 def save_checkpoint(model, optimizer, scheduler, epoch, best_loss, output_dir, is_best=False):
     """Same files and dictionary keys as src/train.py:556-600 (`best_loss`,
     `config.out_channels`); the config records the model's actual geometry."""

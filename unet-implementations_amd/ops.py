@@ -1518,6 +1518,120 @@ def gradcam_heatmap(cam, ws, size):
     return out
 
 
+# ---- latent-space analysis (latent.hip) ------------------------------------------------------
+TSNE_MAX_N = 8192
+
+
+def _latent_matrix(name, x):
+    """`name` takes a contiguous fp32 [N, D] matrix on the device, D a multiple of 4 -> (N, D)"""
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise RuntimeError(f"unet-implementations_amd.{name} runs on MI355X only "
+                           "(no CPU fallback exists)")
+    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_contiguous():
+        raise TypeError(f"{name} takes a contiguous fp32 [N, D] matrix")
+    N, D = x.shape
+    if not 2 <= N <= 65536 or D < 4 or D % 4:
+        raise ValueError(f"{name}: N must lie in 2..65536 and D be a multiple of 4, got {N} x {D}")
+    return N, D
+
+
+def latent_col_mean(x):
+    """mean fp32 [D] of x [N, D] over N, in a fixed order."""
+    N, D = _latent_matrix("latent_col_mean", x)
+    ws = _ws(lib().unet_latent_colsum_workspace_bytes(N, D), x)
+    mean = _f32((D,), x)
+    check(lib().unet_latent_col_mean(_ptr(x), _ptr(mean), _ptr(ws), ws.numel(), N, D, _stream()))
+    return mean
+
+
+def latent_gram_splitk(N, D):
+    """How many slabs of D `latent_gram` sums for an [N, D] matrix."""
+    return lib().unet_latent_gram_splitk(N, D)
+
+
+def latent_gram(x, mean):
+    """G fp32 [N, N] = (x - mean)(x - mean)^T on the fp32 matrix cores; bitwise symmetric."""
+    N, D = _latent_matrix("latent_gram", x)
+    if tuple(mean.shape) != (D,) or mean.dtype != torch.float32 or mean.device != x.device:
+        raise ValueError("latent_gram: mean must be an fp32 [D] tensor on x's device")
+    ws = _ws(lib().unet_latent_gram_workspace_bytes(N, D), x)
+    g = _f32((N, N), x)
+    t0 = _begin()
+    check(lib().unet_latent_gram(_ptr(x), _ptr(mean), _ptr(g), _ptr(ws), ws.numel(), N, D,
+                                 _stream()))
+    if t0 is not None:
+        _timer.end("latent_gram", 2.0 * N * N * D, 2, t0, executed=1.0 * N * (N + 128) * D)
+    return g
+
+
+def latent_gram_apply(g, q, out=None):
+    """z fp32 [N, 8] = g @ q for the 8-column block q of the subspace iteration."""
+    N = g.shape[0]
+    if tuple(g.shape) != (N, N) or tuple(q.shape) != (N, 8) or g.dtype != torch.float32 or \
+            q.dtype != torch.float32:
+        raise ValueError("latent_gram_apply takes an fp32 [N, N] matrix and an fp32 [N, 8] block")
+    z = _f32((N, 8), g) if out is None else out
+    check(lib().unet_latent_gram_apply(_ptr(g), _ptr(q), _ptr(z), N, _stream()))
+    return z
+
+
+def latent_project(x, mean, w):
+    """fp32 [2, D] = w^T (x - mean) for w [N, 2]: one pass over x."""
+    N, D = _latent_matrix("latent_project", x)
+    if tuple(w.shape) != (N, 2) or w.dtype != torch.float32 or tuple(mean.shape) != (D,):
+        raise ValueError("latent_project takes an fp32 [D] mean and fp32 [N, 2] weights")
+    ws = _ws(lib().unet_latent_colsum_workspace_bytes(N, D), x)
+    out = _f32((2, D), x)
+    check(lib().unet_latent_project(_ptr(x), _ptr(mean), _ptr(w), _ptr(out), _ptr(ws), ws.numel(),
+                                    N, D, _stream()))
+    return out
+
+
+def tsne_joint_p(g, perplexity):
+    """The joint probabilities P fp32 [N, N] of the exact t-SNE from the Gram matrix g (the squared
+    distances are formed on load) -> (P, the conditional probabilities)."""
+    N = g.shape[0]
+    if tuple(g.shape) != (N, N) or g.dtype != torch.float32 or not g.is_cuda:
+        raise ValueError("tsne_joint_p takes an fp32 [N, N] Gram matrix on the device")
+    diag = g.diagonal().contiguous()
+    pc, p = _f32((N, N), g), _f32((N, N), g)
+    rowsum = torch.empty(N + 1, dtype=torch.float64, device=g.device)
+    check(lib().unet_tsne_cond_p(_ptr(g), _ptr(diag), float(perplexity), _ptr(pc),
+                                 rowsum.data_ptr(), N, _stream()))
+    check(lib().unet_tsne_joint_p(_ptr(pc), rowsum.data_ptr(), _ptr(p), N, _stream()))
+    return p, pc
+
+
+def tsne_step(p, state_in, state_out, rows, exaggeration, momentum, lr, stats=None):
+    """One descent iteration: state [N, 6] = (y, update, gains) from state_in to state_out; `stats`
+    (a 2-element fp64 view, or None) receives the KL divergence and |gains grad| at state_in."""
+    N = p.shape[0]
+    check(lib().unet_tsne_step(_ptr(p), _ptr(state_in), _ptr(state_out), _ptr(rows),
+                               None if stats is None else stats.data_ptr(), float(exaggeration),
+                               float(momentum), float(lr), 0 if stats is None else 1, N,
+                               _stream()))
+
+
+def latent_scatter(centres, labels, palette, size, radius):
+    """uint8 [H, W, 3]: the scatter picture of int32 [N, 2] pixel centres (x, y), uint8 [N] labels
+    and a uint8 [K, 3] palette on a white ground."""
+    H, W = int(size[0]), int(size[1])
+    N, K = centres.shape[0], palette.shape[0]
+    if not (centres.is_cuda and labels.is_cuda and palette.is_cuda):
+        raise RuntimeError("unet-implementations_amd.latent_scatter runs on MI355X only "
+                           "(no CPU fallback exists)")
+    if centres.dtype != torch.int32 or tuple(centres.shape) != (N, 2) or \
+            labels.dtype != torch.uint8 or tuple(labels.shape) != (N,) or \
+            palette.dtype != torch.uint8 or tuple(palette.shape) != (K, 3):
+        raise ValueError("latent_scatter takes int32 [N, 2] centres, uint8 [N] labels and a uint8 "
+                         "[K, 3] palette")
+    out = torch.empty((H, W, 3), dtype=torch.uint8, device=centres.device)
+    check(lib().unet_latent_scatter(centres.contiguous().data_ptr(), _ptr(labels.contiguous()),
+                                    _ptr(palette.contiguous()), K, _ptr(out), N, H, W, int(radius),
+                                    _stream()))
+    return out
+
+
 # ---- online batch augmentation (augment.hip) -------------------------------------------------
 def _check_u8_image(what, image):
     """`what` (the caller) takes a contiguous uint8 [N,H,W,3] image on the device -> (N, H, W)"""
