@@ -280,6 +280,8 @@ int unet_wgrad_defer_end(unet_stream_t stream);
  * Replaces SimpleLoss.forward and its autograd backward
  * (Our_UNet/models/losses.py:24-62 class weights, :73-76 CE, :84-121 Dice).
  * class_weights: 3 floats on device used when dynamic_weights == 0 (NULL = unweighted).
+ * N <= 1024 images per call, here and in the _grad / _shard_stats / _shard_apply forms
+ * (UNET_E_INVALID beyond, before any launch).
  * global_counts (optional, may be NULL): when non-NULL the kernel pair is split
  * so the caller can all-reduce the 4 class/valid counts between the passes. */
 size_t unet_dice_wce_loss_workspace_bytes(int N, int H, int W);

@@ -889,7 +889,11 @@ def test_conv3x3_bench_size_layer(ua, mode):
 
 
 @pytest.mark.parametrize("case", [(2, 3, 64, 64, 128, 128), (1, 3, 48, 80, 96, 200),
-                                  (2, 5, 20, 12, 16, 16), (1, 4, 33, 17, 16, 40)])
+                                  (2, 5, 20, 12, 16, 16), (1, 4, 33, 17, 16, 40),
+                                  # the edges: one source pixel, one destination pixel, an odd
+                                  # non-integer ratio, the identity, both axes swapping roles
+                                  (2, 3, 1, 1, 5, 7), (2, 3, 5, 7, 1, 1), (1, 2, 7, 7, 16, 16),
+                                  (2, 3, 12, 20, 12, 20), (1, 2, 3, 64, 64, 3)])
 def test_resize_bilinear_matches_torch_interpolate(ua, case):
     """unet_resize_bilinear_fwd / _bwd (the logits resize of SimpleLoss, losses.py:66-68, and the
     CLIP feature resize, CLIP_UNet/models/unet.py:444-450) against F.interpolate(bilinear,

@@ -472,6 +472,14 @@ LOSS_FINALIZE = (f"{_AN}loss_finalize_kernel(float const*, int, int, float, floa
                  f"float const*, float, float*, {_AN}LossCoef*, float*)")
 LOSS_GRAD = (f"{_AN}loss_grad_kernel(float const*, long long const*, {_AN}LossCoef const*, "
              "float const*, float*, int, int, float const*)")
+# (their uint8-target twins and the two kernels of the sharded loss: no step launches them, so
+# they have no entry in ALLOWED; tests/test_loss_fp64_gpu.py asserts them)
+LOSS_REDUCE_U8 = f"{_AN}loss_reduce_u8_kernel(float const*, unsigned char const*, float*, int, int)"
+LOSS_GRAD_U8 = (f"{_AN}loss_grad_u8_kernel(float const*, unsigned char const*, {_AN}LossCoef const*, "
+                "float const*, float*, int, int, float const*)")
+LOSS_SHARD_STATS = f"{_AN}loss_shard_stats_kernel(float const*, int, int, float, double*, double*)"
+LOSS_SHARD_APPLY = (f"{_AN}loss_shard_apply_kernel(double const*, int, double const*, int, float, float, "
+                    f"float, int, float const*, float, float*, {_AN}LossCoef*, float*)")
 SGD = (f"{_AN}sgd_nesterov_kernel(float*, float const*, float*, long long, float, float, float, int, "
        "float, float const*)")
 
@@ -503,14 +511,14 @@ def _call_sgd(ua, mode):
     ua.ops.sgd_nesterov_step(p, gr, torch.zeros_like(p), 0.005, 0.99, 1e-4, True)
 
 
-_LOSS_TEST = "test_kernels_gpu.py::test_loss_vs_oracle"
+_LOSS_TEST = "test_loss_fp64_gpu.py::test_loss_case"
 ALLOWED = {
     NCHW_TO_NHWC: ("test_kernels_gpu.py::test_layout_roundtrip", _call_layout),
     PACK_W: ("test_kernels_gpu.py::test_pack_weights_batched_matches_per_layer", _call_pack),
     LOSS_REDUCE: (_LOSS_TEST, _call_loss),
     LOSS_FINALIZE: (_LOSS_TEST, _call_loss),
     LOSS_GRAD: (_LOSS_TEST, _call_loss),
-    SGD: ("test_kernels_gpu.py::test_sgd_odd_length", _call_sgd),
+    SGD: ("test_loss_fp64_gpu.py::test_sgd_case", _call_sgd),
 }
 _CONV_WORDS = ("conv", "wgrad", "taps", "wino_up", "wino32", "igemm", "patch")
 

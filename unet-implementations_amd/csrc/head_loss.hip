@@ -346,6 +346,7 @@ __global__ __launch_bounds__(256) void head_bwd_finalize_kernel(const float* __r
 // ------------------------------------------------------------------ loss
 constexpr int LQ = 13;  // cnt[3], nll[3], I[3], P[3], valid
 constexpr int LOSS_BLOCKS = 128;  // per image
+constexpr int LOSS_MAX_N = 1024;  // images per call (unet_hip.h); sizes loss_finalize_kernel's LDS opt-in
 
 struct LossCoef {  // written by finalize, read by the gradient kernel
   float w[3];
@@ -1068,7 +1069,7 @@ int loss_fwd_bwd_impl(const float* logits, const TT* target, float* loss_out, fl
                       float w_dice, float w_ce, int ignore_index, int dynamic_weights,
                       const float* class_weights, float grad_scale, hipStream_t stream) {
   UNET_REQUIRE(logits && target && loss_out && workspace, "dice_wce_loss: null pointer");
-  UNET_REQUIRE(N > 0 && N <= 1024 && H > 0 && W > 0, "dice_wce_loss: bad shape");
+  UNET_REQUIRE(N > 0 && N <= LOSS_MAX_N && H > 0 && W > 0, "dice_wce_loss: bad shape");
   int rc = check_ignore_index<TT>("dice_wce_loss", ignore_index);
   if (rc != UNET_OK) return rc;
   if (workspace_bytes < loss_ws_layout(N, nullptr, nullptr)) {
@@ -1080,6 +1081,9 @@ int loss_fwd_bwd_impl(const float* logits, const TT* target, float* loss_out, fl
   const int HW = H * W, blocks = loss_blocks_for(HW);
   rc = launch_loss_reduce(logits, target, ws.partial, N, HW, blocks, ignore_index, stream);
   if (rc != UNET_OK) return rc;
+  // N * 104 bytes of dynamic LDS pass the 64 KiB a launch may ask for unasked at N = 631: opt in,
+  // once per device, to what the largest admitted batch needs (104 KiB of the CU's 160)
+  UNET_SET_DYN_LDS(loss_finalize_kernel, (size_t)LOSS_MAX_N * LQ * sizeof(double));
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), (size_t)N * LQ * sizeof(double),
                      stream, ws.partial, N, blocks, smooth, w_dice, w_ce, dynamic_weights,
                      class_weights, grad_scale, loss_out, ws.coef, ws.dice_ab);
@@ -1094,7 +1098,7 @@ int loss_grad_impl(const float* logits, const TT* target, const void* workspace,
                    size_t workspace_bytes, const float* upstream, float* dlogits, int N, int H,
                    int W, int ignore_index, hipStream_t stream) {
   UNET_REQUIRE(logits && target && workspace && dlogits, "dice_wce_loss_grad: null pointer");
-  UNET_REQUIRE(N > 0 && N <= 1024 && H > 0 && W > 0, "dice_wce_loss_grad: bad shape");
+  UNET_REQUIRE(N > 0 && N <= LOSS_MAX_N && H > 0 && W > 0, "dice_wce_loss_grad: bad shape");
   const int rc = check_ignore_index<TT>("dice_wce_loss_grad", ignore_index);
   if (rc != UNET_OK) return rc;
   if (workspace_bytes < loss_ws_layout(N, nullptr, nullptr)) {
@@ -1139,7 +1143,7 @@ int loss_shard_stats_impl(const float* logits, const TT* target, double* stats, 
                           size_t workspace_bytes, int N, int H, int W, float smooth,
                           int ignore_index, hipStream_t stream) {
   UNET_REQUIRE(logits && target && stats && workspace, "loss_shard_stats: null pointer");
-  UNET_REQUIRE(N > 0 && N <= 1024 && H > 0 && W > 0, "loss_shard_stats: bad shape");
+  UNET_REQUIRE(N > 0 && N <= LOSS_MAX_N && H > 0 && W > 0, "loss_shard_stats: bad shape");
   int rc = check_ignore_index<TT>("loss_shard_stats", ignore_index);
   if (rc != UNET_OK) return rc;
   if (workspace_bytes < loss_ws_layout(N, nullptr, nullptr)) {
@@ -1165,7 +1169,7 @@ int loss_shard_apply_impl(const float* logits, const TT* target, const double* g
                           const float* class_weights, float grad_scale, hipStream_t stream) {
   UNET_REQUIRE(logits && target && global_stats && loss_out && workspace,
                "loss_shard_apply: null pointer");
-  UNET_REQUIRE(N > 0 && N <= 1024 && N_global >= N && H > 0 && W > 0,
+  UNET_REQUIRE(N > 0 && N <= LOSS_MAX_N && N_global >= N && H > 0 && W > 0,
                "loss_shard_apply: bad shape");
   const int rc = check_ignore_index<TT>("loss_shard_apply", ignore_index);
   if (rc != UNET_OK) return rc;
