@@ -250,7 +250,12 @@ int unet_upsample2x_bwd(const float* gy, float* gx, int N, int h, int w, int C, 
 
 /* logits_nchw[N][K][HW] = a[N][HW][C] . w[K][C] + b[K]; replaces
  * segmentation_output = nn.Conv2d(32, 3, 1) (Our_UNet/models/unet.py:374-381,:430).
- * C == 32, K <= 4. */
+ * C == 32, K <= UNET_MAX_CLASSES.  K <= 4 is the vector-unit kernel of the 3-class network;
+ * 5 <= K <= 32 runs on the fp32 matrix cores (one v_mfma_f32_32x32x2_f32 tile of 32 pixels x 32
+ * zero-padded classes per wave), here and in every unet_head1x1_* entry point below.  For K > 4
+ * the backward leaves no InstanceNorm-backward reductions (bs->tiles_out == 0) and
+ * unet_head1x1_in_bwd_fold returns plain da. */
+#define UNET_MAX_CLASSES 32
 int unet_head1x1_fwd(const float* a, const float* w, const float* b, float* logits_nchw, int N,
                      int HW, int C, int K, unet_stream_t stream);
 size_t unet_head1x1_bwd_workspace_bytes(int N, int HW, int C, int K);
@@ -381,6 +386,63 @@ int unet_argmax_dice_counts_u8(const float* logits_nchw, const uint8_t* target, 
 int unet_eval_confusion(const float* logits_nchw, const int64_t* target, const int64_t* dims,
                         uint64_t* cm, int B, int H, int W, int ignore_index,
                         unet_stream_t stream);
+
+/* ---- K classes, 2 <= K <= UNET_MAX_CLASSES: loss, counts, confusion ---------------------------
+ * The entry points above are the pet trimap's 3 classes and have no K argument; these carry it.
+ * Definitions are the reference's with 3 replaced by K (Our_UNet/models/losses.py:24-121):
+ * dynamic weights total / count (count 0 -> 1) renormalised to sum K, weighted CE over the valid
+ * pixels, soft Dice averaged over the images and then over the K classes.  At K == 3 they are
+ * the definitions of unet_dice_wce_loss_fwd_bwd (other kernels: the last bits may differ).
+ *   loss_out      float[3 + K] = {loss, CE, Dice, w[0..K-1]}
+ *   class_weights K floats on the device (dynamic_weights == 0; NULL = unweighted)
+ *   workspace     unet_dice_wce_lossk_workspace_bytes(N, K, H, W); kept by the caller between
+ *                 a dlogits == NULL call and unet_dice_wce_lossk_grad, whose dlogits are
+ *                 upstream * those of the one-call form (bit-identical for upstream == 1)
+ * Three launches (per-workgroup sums, one finalize workgroup in double, gradient), no float
+ * atomics: results are bit-reproducible.  The `_u8` forms take the dataset's uint8 mask and clean
+ * it on load with v >= K && v != ignore_index -> 0; they need ignore_index in K..255 and give the
+ * int64 forms' bits on a cleaned mask.  An int64 label outside 0..K-1 that is not ignore_index
+ * counts as a valid pixel of no class.
+ * Limits, UNET_E_INVALID before any launch: K outside 2..32; N > 1024 images per call (the
+ * finalize keeps its N (4K + 1) sums in the workspace, not in LDS, so the limit does not depend
+ * on K); K * H * W >= 2^31. */
+size_t unet_dice_wce_lossk_workspace_bytes(int N, int K, int H, int W);
+int unet_dice_wce_lossk_fwd_bwd(const float* logits_nchw, const int64_t* target, float* loss_out,
+                                float* dlogits_nchw, void* workspace, size_t workspace_bytes,
+                                int N, int K, int H, int W, float smooth, float w_dice, float w_ce,
+                                int ignore_index, int dynamic_weights, const float* class_weights,
+                                float grad_scale, unet_stream_t stream);
+int unet_dice_wce_lossk_fwd_bwd_u8(const float* logits_nchw, const uint8_t* target,
+                                   float* loss_out, float* dlogits_nchw, void* workspace,
+                                   size_t workspace_bytes, int N, int K, int H, int W,
+                                   float smooth, float w_dice, float w_ce, int ignore_index,
+                                   int dynamic_weights, const float* class_weights,
+                                   float grad_scale, unet_stream_t stream);
+int unet_dice_wce_lossk_grad(const float* logits_nchw, const int64_t* target,
+                             const void* workspace, size_t workspace_bytes, const float* upstream,
+                             float* dlogits_nchw, int N, int K, int H, int W, int ignore_index,
+                             unet_stream_t stream);
+int unet_dice_wce_lossk_grad_u8(const float* logits_nchw, const uint8_t* target,
+                                const void* workspace, size_t workspace_bytes,
+                                const float* upstream, float* dlogits_nchw, int N, int K, int H,
+                                int W, int ignore_index, unet_stream_t stream);
+
+/* preds[N][H][W] (uint8, optional) = argmax over the K class planes, first maximum wins;
+ * counts[K][3] (uint64, device; zeroed here) = per class {intersection, predicted, labelled},
+ * ignore_index pixels excluded.  target == NULL and counts == NULL: prediction only.
+ * N <= 65535. */
+int unet_argmax_countsk(const float* logits_nchw, const int64_t* target, uint8_t* preds,
+                        uint64_t* counts, int N, int K, int H, int W, int ignore_index,
+                        unet_stream_t stream);
+int unet_argmax_countsk_u8(const float* logits_nchw, const uint8_t* target, uint8_t* preds,
+                           uint64_t* counts, int N, int K, int H, int W, int ignore_index,
+                           unet_stream_t stream);
+
+/* unet_eval_confusion for K classes: cm[B][K][K] (uint64, device; zeroed here), the same dims
+ * rule and limits; ignore_index must not be a class index 0..K-1. */
+int unet_eval_confusionk(const float* logits_nchw, const int64_t* target, const int64_t* dims,
+                         uint64_t* cm, int B, int K, int H, int W, int ignore_index,
+                         unet_stream_t stream);
 
 /* One read of the logits, any subset of (NULL skips an output):
  *   probs[B][3][H][W]  fp32 softmax over the classes (visualize_confidence_maps_batch,

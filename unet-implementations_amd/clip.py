@@ -11,6 +11,7 @@ scalar (no per-step host sync).
 import torch
 
 from . import ops
+from .train import dice_scores
 
 
 def extract_clip_features(clip_extractor, batch, images, device, input_layout=None):
@@ -77,7 +78,7 @@ def validate(model, val_loader, loss_function, device, clip_extractor=None, igno
     stay on the device as in `train.validate`."""
     model.eval()
     val_loss = torch.zeros((), device=device)
-    dice_sum = torch.zeros(3, device=device, dtype=torch.float64)
+    dice_sum = None      # float64 [K], sized by the first batch's logits
     n = 0
     for batch in val_loader:
         images = batch["image"].to(device, non_blocking=True)
@@ -91,9 +92,8 @@ def validate(model, val_loader, loss_function, device, clip_extractor=None, igno
         _, counts = ops.argmax_dice_counts(outputs, masks, ignore_label, want_preds=False)
         inter = counts[:, 0].double()
         union = (counts[:, 1] + counts[:, 2]).double()
-        dice_sum += torch.where(union > 0, 2.0 * inter / (union + 1e-5), torch.ones_like(inter))
+        dice = torch.where(union > 0, 2.0 * inter / (union + 1e-5), torch.ones_like(inter))
+        dice_sum = dice if dice_sum is None else dice_sum + dice
         n += 1
     n = max(n, 1)
-    d = (dice_sum / n).tolist()
-    scores = {"background": d[0], "cat": d[1], "dog": d[2], "mean_foreground": (d[1] + d[2]) / 2.0}
-    return (val_loss / n).item(), scores
+    return (val_loss / n).item(), dice_scores(dice_sum, n)

@@ -792,9 +792,11 @@ int head_bwd_blocks(long long tiles) { return (int)(tiles < UNET_HEAD_BWD_BLOCKS
 extern "C" int unet_head1x1_fwd(const float* a, const float* w, const float* b, float* logits,
                                 int N, int HW, int C, int K, unet_stream_t stream) {
   UNET_REQUIRE(a && w && logits, "head1x1_fwd: null pointer");
-  UNET_REQUIRE(C == 32 && K >= 1 && K <= 4 && N > 0 && HW > 0,
-               "head1x1_fwd: needs C == 32, K <= 4 (got C=%d K=%d)", C, K);
+  UNET_REQUIRE(C == 32 && K >= 1 && K <= UNET_MAX_CLASSES && N > 0 && HW > 0,
+               "head1x1_fwd: needs C == 32, K <= 32 (got C=%d K=%d)", C, K);
   const long long M = (long long)N * HW;
+  if (K > 4)   // the matrix-core head of head_loss_k.hip
+    return unet_headk_fwd(a, 0, w, b, logits, M, HW, K, nullptr, nullptr, 0.f, (hipStream_t)stream);
   hipLaunchKernelGGL(head_fwd_kernel<float>, dim3((unsigned)ceil_div64(M, HT)), dim3(256), 0,
                      (hipStream_t)stream, a, w, b, logits, M, HW, K, (const float*)nullptr,
                      (const float*)nullptr, 0.f);
@@ -806,9 +808,13 @@ extern "C" int unet_head1x1_in_fwd(const unet_act_src* x, float slope, const flo
                                    const float* b, float* logits, int N, int HW, int K,
                                    unet_stream_t stream) {
   UNET_REQUIRE(x && x->x && w && logits, "head1x1_in_fwd: null pointer");
-  UNET_REQUIRE(x->C == 32 && K >= 1 && K <= 4 && N > 0 && HW > 0 && (!x->alpha || x->beta),
-               "head1x1_in_fwd: needs C == 32, K <= 4 (got C=%d K=%d)", x->C, K);
+  UNET_REQUIRE(x->C == 32 && K >= 1 && K <= UNET_MAX_CLASSES && N > 0 && HW > 0 &&
+                   (!x->alpha || x->beta),
+               "head1x1_in_fwd: needs C == 32, K <= 32 (got C=%d K=%d)", x->C, K);
   const long long M = (long long)N * HW;
+  if (K > 4)
+    return unet_headk_fwd(x->x, 0, w, b, logits, M, HW, K, x->alpha, x->beta, slope,
+                          (hipStream_t)stream);
   hipLaunchKernelGGL(head_fwd_kernel<float>, dim3((unsigned)ceil_div64(M, HT)), dim3(256), 0,
                      (hipStream_t)stream, x->x, w, b, logits, M, HW, K, x->alpha, x->beta, slope);
   UNET_CHECK_LAUNCH("head_fwd");
@@ -819,9 +825,13 @@ extern "C" int unet_head1x1_in_fwd_b16(const unet_act_src* x, float slope, const
                                        const float* b, float* logits, int N, int HW, int K,
                                        unet_stream_t stream) {
   UNET_REQUIRE(x && x->x && w && logits, "head1x1_in_fwd_b16: null pointer");
-  UNET_REQUIRE(x->C == 32 && K >= 1 && K <= 4 && N > 0 && HW > 0 && (!x->alpha || x->beta),
-               "head1x1_in_fwd_b16: needs C == 32, K <= 4 (got C=%d K=%d)", x->C, K);
+  UNET_REQUIRE(x->C == 32 && K >= 1 && K <= UNET_MAX_CLASSES && N > 0 && HW > 0 &&
+                   (!x->alpha || x->beta),
+               "head1x1_in_fwd_b16: needs C == 32, K <= 32 (got C=%d K=%d)", x->C, K);
   const long long M = (long long)N * HW;
+  if (K > 4)
+    return unet_headk_fwd(x->x, 1, w, b, logits, M, HW, K, x->alpha, x->beta, slope,
+                          (hipStream_t)stream);
   hipLaunchKernelGGL(head_fwd_kernel<__bf16>, dim3((unsigned)ceil_div64(M, HT)), dim3(256), 0,
                      (hipStream_t)stream, reinterpret_cast<const __bf16*>(x->x), w, b, logits, M,
                      HW, K, x->alpha, x->beta, slope);
@@ -919,8 +929,8 @@ static int head1x1_bwd_impl(const float* a, const float* dlogits, const float* w
                             float slope, unet_stream_t stream, int b16, unet_bwd_stats* bs,
                             const HeadFold* fold) {
   UNET_REQUIRE(a && dlogits && w && da && workspace, "head1x1_bwd: null pointer");
-  UNET_REQUIRE(C == 32 && K >= 1 && K <= 4 && N > 0 && HW > 0,
-               "head1x1_bwd: needs C == 32, K <= 4 (got C=%d K=%d)", C, K);
+  UNET_REQUIRE(C == 32 && K >= 1 && K <= UNET_MAX_CLASSES && N > 0 && HW > 0,
+               "head1x1_bwd: needs C == 32, K <= 32 (got C=%d K=%d)", C, K);
   if (workspace_bytes < unet_head1x1_bwd_workspace_bytes(N, HW, C, K)) {
     unet_set_error("head1x1_bwd: workspace too small");
     return UNET_E_WORKSPACE;
@@ -929,6 +939,14 @@ static int head1x1_bwd_impl(const float* a, const float* dlogits, const float* w
   const long long tiles = ceil_div64(M, HB);
   const int blocks = head_bwd_blocks(tiles);
   float* partial = reinterpret_cast<float*>(workspace);
+  if (K > 4) {
+    // the matrix-core head of head_loss_k.hip: plain da, no InstanceNorm-backward reductions
+    // (tiles_out == 0: the caller runs unet_instnorm_lrelu_drop_bwd, as for a shape that does
+    // not split evenly)
+    if (bs) bs->tiles_out = 0;
+    return unet_headk_bwd(a, b16, dlogits, w, da, dw, db, partial, blocks, M, HW, K, alpha, beta,
+                          slope, (hipStream_t)stream);
+  }
   HeadBs hb{};
   if (bs) {
     bs->tiles_out = head_bs_plan(a, alpha, M, HW, bs, &hb);
@@ -987,7 +1005,8 @@ extern "C" int unet_head1x1_in_bwd_fold(const unet_act_src* x, float slope, cons
                                         int K, unet_bwd_stats* bs, unet_stream_t stream) {
   UNET_REQUIRE(x && x->x && (!x->alpha || x->beta) && bs && workspace,
                "head1x1_in_bwd_fold: null pointer");
-  UNET_REQUIRE(N > 0 && HW > 0 && K >= 1 && K <= 4, "head1x1_in_bwd_fold: bad shape");
+  UNET_REQUIRE(N > 0 && HW > 0 && K >= 1 && K <= UNET_MAX_CLASSES,
+               "head1x1_in_bwd_fold: bad shape");
   if (workspace_bytes < unet_head1x1_in_bwd_fold_workspace_bytes(N, HW, K)) {
     unet_set_error("head1x1_in_bwd_fold: workspace too small");
     return UNET_E_WORKSPACE;

@@ -198,7 +198,8 @@ class DeviceLetterbox:
     mode          "letterbox" (the preprocessing scripts) or "stretch" (the dataset's resize)
     label_lut     None, a uint8 [256] table applied to every mask, or "trimap": the byte histogram
                   of each original mask (`ops.byte_histogram_u8`) decides its table as `trimap_lut`
-                  does, on the device; the batch must carry "is_cat" (bool per sample)
+                  does, on the device; the batch must carry "is_cat" (bool per sample).  The
+                  trimap rule is the pet dataset's: with `num_classes` other than 3 it raises
     image_format  "nhwc_u8" (default), or "nchw_f32": the image normalised with `mean` / `std` by
                   `ops.preprocess_u8`, as a [B, 3, S, S] view, for loops that call `model(images)`
                   without an input layout (`evaluate_model`, the `ae` loops)
@@ -207,7 +208,11 @@ class DeviceLetterbox:
 
     def __init__(self, loader, size=512, mode="letterbox", clip_size=None, label_lut=None,
                  device="cuda", image_format="nhwc_u8", mean=ops.IMAGENET_MEAN,
-                 std=ops.IMAGENET_STD, target=None):
+                 std=ops.IMAGENET_STD, target=None, num_classes=3):
+        if isinstance(label_lut, str) and label_lut == "trimap" and num_classes != 3:
+            raise NotImplementedError("label_lut='trimap' re-encodes the pet trimap's bytes into "
+                                      f"its 3 classes (got num_classes={num_classes}): pass a "
+                                      "uint8 [256] table, or None")
         if mode not in ("letterbox", "stretch"):
             raise ValueError("mode must be 'letterbox' or 'stretch'")
         if image_format not in ("nhwc_u8", "nchw_f32"):

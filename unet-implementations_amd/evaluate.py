@@ -42,7 +42,8 @@ def load_model(model_path, device):
 def evaluate_model(model, test_loader, device, visualize_samples=0, output_dir=None):
     """The dictionary of src/evaluate.py:239-268 (pixel accuracy, mean IoU, per-class dice / iou /
     precision / recall, `mean_foreground_dice`), every image counted at its original size, plus
-    `"confusion_matrix"`: int64 [3, 3] numpy, target class x predicted class, what the reference's
+    `"confusion_matrix"`: int64 [K, K] numpy (K = model.num_classes, 2..32; the per-class entries
+    are named class_0 .. class_{K-1} unless K == 3), target class x predicted class, what the reference's
     plot_confusion_matrix counts from the resized maps it keeps.
 
     With `visualize_samples > 0` and an `output_dir`, the first `visualize_samples` batches each
@@ -52,6 +53,10 @@ def evaluate_model(model, test_loader, device, visualize_samples=0, output_dir=N
     DESIGN.md section 9b) - the returned numbers are those of a `visualize_samples=0` run.
     Nothing is shown on a screen, so without an `output_dir` there is nowhere to put a picture and
     `visualize_samples > 0` raises."""
+    K = getattr(model, "num_classes", 3)
+    if visualize_samples > 0 and K != 3:
+        raise NotImplementedError("the rendered figures use the three-colour palette of the pet "
+                                  f"trimap (got {K} classes): use visualize_samples=0")
     if visualize_samples > 0 and output_dir is None:
         raise NotImplementedError("plots are not part of the HIP path (use visualize_samples=0; "
                                   "confidence_maps / error_maps / gradcam return the plotted "
@@ -75,11 +80,13 @@ def evaluate_model(model, test_loader, device, visualize_samples=0, output_dir=N
     metrics = accumulate_test_metrics(model, test_loader, device, on_batch=on_batch)
     results = {"pixel_accuracy": metrics.compute_pixel_accuracy(),
                "mean_iou": metrics.compute_mean_iou()}
-    for cls, name in enumerate(("background", "cat", "dog")):
+    # the reference's names for its 3 classes, class_0 .. class_{K-1} otherwise
+    names = ("background", "cat", "dog") if K == 3 else tuple(f"class_{c}" for c in range(K))
+    for cls, name in enumerate(names):
         results[name] = {"dice": metrics.compute_dice(cls), "iou": metrics.compute_iou(cls),
                          "precision": metrics.compute_precision(cls),
                          "recall": metrics.compute_recall(cls)}
-    fg = [d for d in (results["cat"]["dice"], results["dog"]["dice"]) if not np.isnan(d)]
+    fg = [d for d in (results[name]["dice"] for name in names[1:]) if not np.isnan(d)]
     results["mean_foreground_dice"] = float(np.mean(fg)) if fg else float("nan")
     results["confusion_matrix"] = metrics.confusion_matrix
     return results
@@ -95,8 +102,18 @@ def _eval_logits(model, images):
         model.train(was_training)
 
 
+def _three_classes_only(model, what):
+    """The visual helpers are the pet trimap's: refused for another class count before the
+    device is touched."""
+    K = getattr(model, "num_classes", 3)
+    if K != 3:
+        raise NotImplementedError(f"{what} covers the 3-class model (three-colour maps of the pet "
+                                  f"trimap); got {K} classes")
+
+
 def confidence_maps(model, images):
     """Softmax probabilities fp32 [B, 3, H, W] on the device (utils/visualize.py:117-119)."""
+    _three_classes_only(model, "confidence_maps")
     return ops.eval_maps(_eval_logits(model, images), want_classes=False)[0]
 
 
@@ -104,6 +121,7 @@ def error_maps(model, images, masks):
     """uint8 [B, H, W] on the device: the category create_error_visualization colours
     (utils/visualize.py:205-222) - 0 none, 1 true positive (green), 2 false positive (red),
     3 false negative (blue), 4 wrong class (yellow); 255 in the mask counts as background."""
+    _three_classes_only(model, "error_maps")
     if masks.dtype != torch.int64:
         masks = masks.long()
     return ops.eval_maps(_eval_logits(model, images), masks, want_probs=False,
@@ -155,6 +173,7 @@ def gradcam(model, images, target_class, target_layer=None, precision="fp32"):
     the gradient arena, model.training and dropout_mask_override as they were."""
     if precision not in (None, "fp32"):
         raise ValueError("precision must be 'fp32' or None (the model's own mode)")
+    _three_classes_only(model, "Grad-CAM")
     target = _gradcam_target(model, target_layer)
     K = model.segmentation_output.out_channels
     if not 0 <= int(target_class) < K:

@@ -22,7 +22,7 @@ class _LossFunction(torch.autograd.Function):
     def forward(ctx, logits, target, mod, class_weights):
         want_grad = ctx.needs_input_grad[0]
         world = mod._world()
-        if world > 1:
+        if world > 1:      # (K != 3 was refused in SimpleLoss.forward)
             import torch.distributed as dist
             stats, ws = ops.dice_wce_loss_shard_stats(logits, target, mod.smooth, mod.ignore_index)
             dist.all_reduce(stats, op=dist.ReduceOp.SUM, group=mod.process_group)
@@ -38,7 +38,8 @@ class _LossFunction(torch.autograd.Function):
                 want_grad=False, ws=ws)
         if want_grad:
             ctx.held = (logits, target, ws, mod.ignore_index)
-        mod.last_terms = out  # [total, ce, dice, w0, w1, w2, -, -] on device (no sync)
+        # [total, ce, dice, w0, w1, w2, -, -] on device (no sync); K != 3: [total, ce, dice, w[K]]
+        mod.last_terms = out
         return out[0].clone()
 
     @staticmethod
@@ -89,6 +90,17 @@ class SimpleLoss(nn.Module):
         return dist.get_world_size(self.process_group)
 
     def forward(self, input, target):
+        # (what this class count does not cover is refused first, before the device is touched)
+        K = input.shape[1]
+        if K != 3:
+            ops._check_classes(K, "SimpleLoss")
+            if self.batch_sync == "global":
+                raise NotImplementedError("SimpleLoss(batch_sync='global'), the sharded loss, "
+                                          f"covers exactly 3 classes (got {K})")
+        if not bool(self.dynamic_weights) and self.class_weights is not None and \
+                len(self.class_weights) != K:
+            raise ValueError(f"class_weights holds {len(self.class_weights)} values for {K} "
+                             "classes")
         if not input.is_cuda:
             raise RuntimeError("unet-implementations_amd.SimpleLoss runs on MI355X only "
                                "(no CPU fallback exists)")

@@ -27,12 +27,13 @@ from . import ops
 
 class SegmentationMetrics:
     def __init__(self, num_classes: int = 3, ignore_index: int = 255):
-        if num_classes != 3:
-            raise NotImplementedError("the HIP count kernel handles exactly 3 classes")
+        if not 2 <= num_classes <= ops.MAX_CLASSES:
+            raise NotImplementedError(f"the HIP count kernels handle 2 to {ops.MAX_CLASSES} "
+                                      f"classes (got {num_classes})")
         self.num_classes = num_classes
         self.ignore_index = ignore_index
-        self._counts = None      # int64 [3, 3] on the device: {inter, predicted, labelled} per class
-        self._cm = None          # int64 [3, 3]: target class x predicted class (original-size path)
+        self._counts = None      # int64 [K, 3] on the device: {inter, predicted, labelled} per class
+        self._cm = None          # int64 [K, K]: target class x predicted class (original-size path)
         self._cm_complete = True  # False once an update arrived without its confusion matrix
         self.reset()
 
@@ -53,14 +54,14 @@ class SegmentationMetrics:
             self._counts += counts
 
     def update_from_confusion(self, cm):
-        """Adds confusion matrices [3, 3] or [B, 3, 3] (integers, target class x predicted class;
+        """Adds confusion matrices [K, K] or [B, K, K] (integers, target class x predicted class;
         tensor on any device, or array): what `update_from_logits(..., original_dims)` does with
         the output of `unet_eval_confusion`.  Intersections are the diagonal, predicted pixels the
         column sums, labelled pixels the row sums; no host sync."""
         cm = torch.as_tensor(cm)
         if cm.dtype != torch.int64:
             cm = cm.to(torch.int64)
-        cm = cm.reshape(-1, 3, 3).sum(dim=0)
+        cm = cm.reshape(-1, self.num_classes, self.num_classes).sum(dim=0)
         if self._cm is None:
             self._cm = cm.clone()
         else:
@@ -70,13 +71,16 @@ class SegmentationMetrics:
         self._add(torch.stack([torch.diagonal(cm), cm.sum(dim=0), cm.sum(dim=1)], dim=1))
 
     def update_from_logits(self, logits, target, original_dims=None):
-        """logits fp32 [B, 3, H, W], target int64 [B, H, W], both on the device.
+        """logits fp32 [B, K, H, W], target int64 [B, H, W], both on the device.
         original_dims (int64 [B, 2] of (orig_h, orig_w), as the default collate builds it from the
         dataset's `original_dims`; a host tensor is copied over): count at each image's original
         size, both maps nearest-resized as evaluate_model does (src/evaluate.py:189-211)."""
         if not logits.is_cuda:
             raise RuntimeError("unet-implementations_amd.SegmentationMetrics runs on MI355X only "
                                "(no CPU fallback exists)")
+        if logits.dim() != 4 or logits.shape[1] != self.num_classes:
+            raise ValueError(f"logits [B, {self.num_classes}, H, W] expected (got "
+                             f"{tuple(logits.shape)})")
         if target.dtype != torch.int64:
             target = target.long()
         if original_dims is not None:
@@ -92,13 +96,13 @@ class SegmentationMetrics:
 
     @property
     def confusion_matrix(self):
-        """int64 [3, 3] (numpy), target class x predicted class, accumulated by the updates that
+        """int64 [K, K] (numpy), target class x predicted class, accumulated by the updates that
         carried one (`update_from_logits` with `original_dims`, `update_from_confusion`)."""
         if not self._cm_complete:
             raise RuntimeError("confusion_matrix: some updates came without original_dims (the "
                                "network-size kernel counts per class only)")
         if self._cm is None:
-            return np.zeros((3, 3), dtype=np.int64)
+            return np.zeros((self.num_classes, self.num_classes), dtype=np.int64)
         return self._cm.cpu().numpy()
 
     # reference: utils/metrics.py:36-57
@@ -116,7 +120,7 @@ class SegmentationMetrics:
     # ---- accumulators with the reference's names (float64 numpy arrays / integers) -------------
     def _host(self):
         if self._counts is None:
-            return np.zeros((3, 3), dtype=np.int64)
+            return np.zeros((self.num_classes, 3), dtype=np.int64)
         return self._counts.cpu().numpy()
 
     @property
@@ -144,7 +148,7 @@ class SegmentationMetrics:
 
     @property
     def total_pixels(self):
-        return int(self._host()[:, 2].sum())       # every valid pixel is labelled 0, 1 or 2
+        return int(self._host()[:, 2].sum())       # every valid pixel is labelled 0 .. K-1
 
     @property
     def correct_pixels(self):
@@ -221,14 +225,17 @@ def compute_pixel_accuracy(pred, target, ignore_index=255):
 
 
 @torch.no_grad()
-def accumulate_test_metrics(model, data_loader, device, ignore_index=255, on_batch=None):
+def accumulate_test_metrics(model, data_loader, device, ignore_index=255, on_batch=None,
+                            num_classes=None):
     """The loop of evaluate_model / evaluate_model_metrics: eval-mode forward, then one launch per
     batch for argmax, both nearest resizes to `original_dims` and all counting.  Nothing is read
     on the host until the returned SegmentationMetrics is asked for a value.
     on_batch(i, images, masks, logits), if given, sees every batch's device tensors after they
     were counted (evaluate_model renders its pictures from them: no second forward)."""
+    if num_classes is None:      # (the model's own count; the reference's loop is 3-class)
+        num_classes = getattr(model, "num_classes", 3)
     model.eval()
-    metrics = SegmentationMetrics(num_classes=3, ignore_index=ignore_index)
+    metrics = SegmentationMetrics(num_classes=num_classes, ignore_index=ignore_index)
     for i, batch in enumerate(data_loader):
         images = batch["image"].to(device, non_blocking=True)
         masks = batch["mask"].to(device, non_blocking=True)
@@ -243,7 +250,9 @@ def evaluate_model_metrics(model, data_loader, device, num_classes=3, ignore_ind
     """utils/metrics.py:305-358: `get_all_metrics()` over a dataset, every image counted at its
     original size."""
     if num_classes != 3:
-        raise NotImplementedError("the HIP count kernel handles exactly 3 classes")
+        raise NotImplementedError("evaluate_model_metrics is the reference's 3-class helper; for "
+                                  "K classes use SegmentationMetrics(num_classes=K) or "
+                                  "evaluate.evaluate_model")
     return accumulate_test_metrics(model, data_loader, device, ignore_index).get_all_metrics()
 
 

@@ -1121,6 +1121,16 @@ def head1x1_bwd(a, dlogits, w, dw, db):
     return da
 
 
+MAX_CLASSES = 32     # UNET_MAX_CLASSES: one 32-column matrix-core tile, per-class sums in registers
+
+
+def _check_classes(K, what):
+    """2..MAX_CLASSES classes, refused on the host before any launch."""
+    if not 2 <= K <= MAX_CLASSES:
+        raise ValueError(f"{what}: {K} classes; the HIP tail (head, loss, counts) covers 2 to "
+                         f"{MAX_CLASSES} classes (the cap is one 32-column matrix-core tile)")
+
+
 def _target_twin(name, target):
     """The export `name` for an int64 target, its `_u8` twin for the dataset's uint8 mask."""
     if target.dtype == torch.uint8:
@@ -1137,7 +1147,19 @@ def dice_wce_loss_fwd_bwd(logits, target, smooth, w_dice, w_ce, ignore_index, dy
     the four functions below) the dataset's uint8 mask as it is - raw or cleaned, 1 byte a pixel."""
     N, K, H, W = logits.shape
     if K != 3:
-        raise ValueError("the fused loss kernel handles exactly 3 classes")
+        # out = {loss, ce, dice, w[0..K-1]}: the K-class kernels (3 keeps its own, and its 8 floats)
+        _check_classes(K, "dice_wce_loss_fwd_bwd")
+        if class_weights is not None and class_weights.numel() != K:
+            raise ValueError(f"class_weights holds {class_weights.numel()} values for {K} classes")
+        out = _f32((3 + K,), logits)
+        dl = torch.empty_like(logits) if want_grad else None
+        if ws is None:
+            ws = dice_wce_loss_workspace(logits)
+        check(_target_twin("unet_dice_wce_lossk_fwd_bwd", target)(
+            _ptr(logits), _ptr(target), _ptr(out), _ptr(dl), _ptr(ws), ws.numel(), N, K, H, W,
+            smooth, w_dice, w_ce, ignore_index, 1 if dynamic_weights else 0, _ptr(class_weights),
+            grad_scale, _stream()))
+        return out, dl
     out = _f32((8,), logits)
     dl = torch.empty_like(logits) if want_grad else None
     if ws is None:
@@ -1151,6 +1173,13 @@ def dice_wce_loss_fwd_bwd(logits, target, smooth, w_dice, w_ce, ignore_index, dy
 
 def dice_wce_loss_workspace(logits):
     N, K, H, W = logits.shape
+    if K != 3:
+        _check_classes(K, "dice_wce_loss_workspace")
+        nbytes = lib().unet_dice_wce_lossk_workspace_bytes(N, K, H, W)
+        if nbytes == 0:
+            raise ValueError(f"dice_wce_loss: a batch of {N} images is outside the 1..1024 the "
+                             "loss kernels take per call")
+        return _ws(nbytes, logits)
     return _ws(lib().unet_dice_wce_loss_workspace_bytes(N, H, W), logits)
 
 
@@ -1162,6 +1191,12 @@ def dice_wce_loss_grad(logits, target, ws, upstream, ignore_index):
     dl = torch.empty_like(logits)
     if upstream is not None:
         upstream = upstream.reshape(1).float().contiguous()
+    if K != 3:
+        _check_classes(K, "dice_wce_loss_grad")
+        check(_target_twin("unet_dice_wce_lossk_grad", target)(
+            _ptr(logits), _ptr(target), _ptr(ws), ws.numel(), _ptr(upstream), _ptr(dl), N, K, H, W,
+            ignore_index, _stream()))
+        return dl
     check(_target_twin("unet_dice_wce_loss_grad", target)(
         _ptr(logits), _ptr(target), _ptr(ws), ws.numel(), _ptr(upstream), _ptr(dl), N, H, W,
         ignore_index, _stream()))
@@ -1172,7 +1207,8 @@ def dice_wce_loss_shard_stats(logits, target, smooth, ignore_index):
     """Phase 1 of the sharded-batch loss: (stats float64[10] on the device, workspace)."""
     N, K, H, W = logits.shape
     if K != 3:
-        raise ValueError("the fused loss kernel handles exactly 3 classes")
+        raise NotImplementedError("the sharded (batch_sync='global') loss covers exactly 3 "
+                                  f"classes (got {K}); use batch_sync='local'")
     stats = torch.empty((10,), dtype=torch.float64, device=logits.device)
     ws = _ws(lib().unet_dice_wce_loss_workspace_bytes(N, H, W), logits)
     check(_target_twin("unet_dice_wce_loss_shard_stats", target)(
@@ -1197,17 +1233,22 @@ def dice_wce_loss_shard_apply(logits, target, global_stats, n_global, ws, smooth
 
 # ---- validation metrics / input pipeline ---------------------------------------------------
 def argmax_dice_counts(logits, target, ignore_index=255, want_preds=True):
-    """Returns (preds uint8 [N,H,W] or None, counts int64 [3,3] = per class
+    """Returns (preds uint8 [N,H,W] or None, counts int64 [K,3] = per class
     {intersection, predicted, labelled}); everything stays on the device.  target: int64 labels
     or the dataset's uint8 mask."""
     N, K, H, W = logits.shape
     if K != 3:
-        raise ValueError("3 classes expected")
+        _check_classes(K, "argmax_dice_counts")
     logits, target = logits.contiguous(), target.contiguous()
     if logits.dtype != torch.float32 or target.dtype not in (torch.int64, torch.uint8):
         raise TypeError("argmax_dice_counts takes fp32 logits and int64 (or uint8) targets")
     preds = torch.empty((N, H, W), dtype=torch.uint8, device=logits.device) if want_preds else None
-    counts = torch.empty((3, 3), dtype=torch.int64, device=logits.device)
+    counts = torch.empty((K, 3), dtype=torch.int64, device=logits.device)
+    if K != 3:
+        check(_target_twin("unet_argmax_countsk", target)(
+            _ptr(logits), _ptr(target), _ptr(preds), counts.data_ptr(), N, K, H, W, ignore_index,
+            _stream()))
+        return preds, counts
     check(_target_twin("unet_argmax_dice_counts", target)(
         _ptr(logits), _ptr(target), _ptr(preds), counts.data_ptr(), N, H, W, ignore_index,
         _stream()))
@@ -1215,23 +1256,36 @@ def argmax_dice_counts(logits, target, ignore_index=255, want_preds=True):
 
 
 def argmax_classes(logits):
-    """uint8 [N,H,W] class map of fp32 logits [N,3,H,W] (first maximum wins, like torch.argmax)."""
+    """uint8 [N,H,W] class map of fp32 logits [N,K,H,W] (first maximum wins, like torch.argmax)."""
     N, K, H, W = logits.shape
-    if K != 3 or logits.dtype != torch.float32:
-        raise TypeError("argmax_classes takes fp32 logits with 3 classes")
+    if logits.dtype != torch.float32:
+        raise TypeError("argmax_classes takes fp32 logits")
+    if K != 3:
+        _check_classes(K, "argmax_classes")
     logits = logits.contiguous()
     preds = torch.empty((N, H, W), dtype=torch.uint8, device=logits.device)
+    if K != 3:
+        check(lib().unet_argmax_countsk(_ptr(logits), None, _ptr(preds), None, N, K, H, W, 255,
+                                        _stream()))
+        return preds
     check(lib().unet_argmax_dice_counts(_ptr(logits), None, _ptr(preds), None, N, H, W, 255,
                                         _stream()))
     return preds
 
 
-def _eval_operands(name, logits, target):
+def _eval_operands(name, logits, target, any_k=False):
+    """any_k: the caller has a K-class form; otherwise K != 3 is refused (NotImplementedError,
+    before the device is touched)."""
+    if torch.is_tensor(logits) and logits.dim() == 4 and logits.shape[1] != 3:
+        if not any_k:
+            raise NotImplementedError(f"{name} covers exactly 3 classes (the three-colour maps "
+                                      f"of the pet trimap); got {logits.shape[1]}")
+        _check_classes(logits.shape[1], name)
     if not torch.is_tensor(logits) or not logits.is_cuda:
         raise RuntimeError(f"unet-implementations_amd.{name} runs on MI355X only "
                            "(no CPU fallback exists)")
-    if logits.dim() != 4 or logits.shape[1] != 3:
-        raise ValueError("3 classes expected (logits [B, 3, H, W])")
+    if logits.dim() != 4:
+        raise ValueError("logits [B, K, H, W] expected")
     if logits.dtype != torch.float32:
         raise TypeError(f"{name} takes fp32 logits")
     if target is not None:
@@ -1244,20 +1298,24 @@ def _eval_operands(name, logits, target):
 
 
 def eval_confusion(logits, target, dims=None, ignore_index=255):
-    """Per-image confusion matrices int64 [B, 3, 3] = [target class][predicted class] of the
+    """Per-image confusion matrices int64 [B, K, K] = [target class][predicted class] of the
     argmax map and the mask, both nearest-resized to dims[b] = (orig_h, orig_w): the counting of
     evaluate_model (src/evaluate.py:189-211) in one launch.  dims: int64 [B, 2] on the device
     (never read on the host), or None for "at network size".  A size outside 1..16384 gives that
     image zero counts."""
-    logits, target = _eval_operands("eval_confusion", logits, target)
+    logits, target = _eval_operands("eval_confusion", logits, target, any_k=True)
     if target is None:
         raise TypeError("eval_confusion needs the target")
-    B, _, H, W = logits.shape
+    B, K, H, W = logits.shape
     if dims is not None:
         if not torch.is_tensor(dims) or dims.dtype != torch.int64 or tuple(dims.shape) != (B, 2):
             raise TypeError("dims must be an int64 [B, 2] tensor of (orig_h, orig_w)")
         dims = dims.contiguous()
-    cm = torch.empty((B, 3, 3), dtype=torch.int64, device=logits.device)
+    cm = torch.empty((B, K, K), dtype=torch.int64, device=logits.device)
+    if K != 3:
+        check(lib().unet_eval_confusionk(_ptr(logits), _ptr(target), _ptr(dims), cm.data_ptr(), B,
+                                         K, H, W, int(ignore_index), _stream()))
+        return cm
     check(lib().unet_eval_confusion(_ptr(logits), _ptr(target), _ptr(dims), cm.data_ptr(), B, H,
                                     W, int(ignore_index), _stream()))
     return cm

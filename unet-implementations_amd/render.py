@@ -84,6 +84,10 @@ def _batch_operands(batch, device):
 def _logits(model, images):
     """Eval-mode logits of a loader batch: normalised fp32 [B,3,H,W] or the uint8 [B,H,W,3]
     batch of the "nhwc_u8" input layout."""
+    K = getattr(model, "num_classes", 3)
+    if K != 3:      # (before the forward: nothing is launched for a figure that cannot be drawn)
+        raise NotImplementedError("the rendered figures use the three-colour palette of the pet "
+                                  f"trimap (got {K} classes)")
     if images.dtype != torch.uint8:
         return _eval_logits(model, images)
     was_training = model.training
@@ -97,6 +101,9 @@ def _logits(model, images):
 
 def figure(images, logits, masks, panels, heat=None, target_class=1):
     """uint8 [B * H, P * W, 3] on the device: one row of `panels` per image of the batch."""
+    if logits is not None and logits.dim() == 4 and logits.shape[1] != 3:
+        raise NotImplementedError("the rendered figures use the three-colour palette of the pet "
+                                  f"trimap (got {logits.shape[1]} classes)")
     out = ops.render_seg_panels(images, logits, masks, heat, panels, target_class)
     B, H, P, W, _ = out.shape
     return out.view(B * H, P * W, 3)

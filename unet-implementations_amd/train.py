@@ -173,7 +173,7 @@ def validate(model, val_loader, loss_function, device, ignore_label=255, input_l
     `target_layout="u8"` the counts kernel reads the uint8 masks as well."""
     model.eval()
     val_loss = torch.zeros((), device=device)
-    dice_sum = torch.zeros(3, device=device, dtype=torch.float64)
+    dice_sum = None      # float64 [K], sized by the first batch's logits
     n = 0
     for batch in val_loader:
         images = batch["image"].to(device, non_blocking=True)
@@ -187,12 +187,23 @@ def validate(model, val_loader, loss_function, device, ignore_label=255, input_l
         _, counts = ops.argmax_dice_counts(outputs, masks, ignore_label, want_preds=False)
         inter = counts[:, 0].double()
         union = (counts[:, 1] + counts[:, 2]).double()
-        dice_sum += torch.where(union > 0, 2.0 * inter / (union + 1e-5), torch.ones_like(inter))
+        dice = torch.where(union > 0, 2.0 * inter / (union + 1e-5), torch.ones_like(inter))
+        dice_sum = dice if dice_sum is None else dice_sum + dice
         n += 1
     n = max(n, 1)
-    d = (dice_sum / n).tolist()
-    scores = {"background": d[0], "cat": d[1], "dog": d[2], "mean_foreground": (d[1] + d[2]) / 2.0}
-    return (val_loss / n).item(), scores
+    return (val_loss / n).item(), dice_scores(dice_sum, n)
+
+
+def dice_scores(dice_sum, n):
+    """validate()'s score dictionary from the per-class sums of the batch Dice values: the
+    reference's background / cat / dog for 3 classes, class_0 .. class_{K-1} otherwise;
+    mean_foreground averages the classes 1 .. K-1 either way."""
+    d = [0.0] * 3 if dice_sum is None else (dice_sum / n).tolist()
+    K = len(d)
+    names = ("background", "cat", "dog") if K == 3 else tuple(f"class_{c}" for c in range(K))
+    scores = dict(zip(names, d))
+    scores["mean_foreground"] = sum(d[1:]) / (K - 1)
+    return scores
 
 
 def nearest_source_index(in_size, out_size):

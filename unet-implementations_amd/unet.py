@@ -397,8 +397,12 @@ class UNet(nn.Module):
 
     def _check_head(self):
         head = self.segmentation_output
-        if _as_int(head.kernel_size) != 1 or head.in_channels != 32 or head.out_channels != 3:
-            raise NotImplementedError("the HIP head kernel is the 32 -> 3 1x1 convolution")
+        if _as_int(head.kernel_size) != 1 or head.in_channels != 32 or \
+                not 2 <= head.out_channels <= ops.MAX_CLASSES:
+            raise NotImplementedError(
+                "the HIP head kernels are the 32 -> K 1x1 convolution for 2 <= K <= "
+                f"{ops.MAX_CLASSES} classes (got {head.in_channels} -> {head.out_channels}, "
+                f"kernel {_as_int(head.kernel_size)})")
 
     def _head_fwd(self, walk, cur):
         """NCHW fp32 output of the head over the last decoder layer's output `cur` (ops.Act on the
@@ -1117,8 +1121,11 @@ def stage_feature_and_gradient(model, x, target_class, target):
     dropout_mask_override are put back."""
     if type(model)._head_bwd is not UNet._head_bwd or model._fusion_layer is not None:
         raise NotImplementedError("Grad-CAM on the HIP path covers UNet (not CLIPUNet / Autoencoder)")
-    model._check_input(x)
     K = model._head_module().out_channels
+    if K != 3:
+        raise NotImplementedError(f"Grad-CAM on the HIP path covers the 3-class model (got {K} "
+                                  "classes)")
+    model._check_input(x)
     if not 0 <= int(target_class) < K:
         raise ValueError(f"target_class {target_class} is outside [0, {K})")
     was_training, override = model.training, model.dropout_mask_override
