@@ -454,6 +454,71 @@ int unet_eval_confusionk(const float* logits_nchw, const int64_t* target, const 
 int unet_eval_maps(const float* logits_nchw, const int64_t* target, float* probs,
                    uint8_t* classes, uint8_t* errors, int B, int H, int W, unet_stream_t stream);
 
+/* ---- mask post-processing (postprocess.hip): components, vote, hole fill ------------
+ * All integers.  The input is a uint8 class map [B][H][W] on the device (what unet_eval_maps /
+ * unet_argmax_countsk write) with K classes, 2 <= K <= UNET_MAX_CLASSES; a byte >= K reads as 0;
+ * class 0 is background; images never interact.
+ *
+ * Components.  unet_cc_label_u8 writes labels[B][H][W] and areas[B][H][W] (uint32):
+ *   mode UNET_CC_FOREGROUND  selects pixels != 0; neighbours join whatever their class
+ *   mode UNET_CC_CLASS       selects pixels != 0; neighbours join only if their bytes are equal
+ *   mode UNET_CC_BACKGROUND  selects pixels == 0
+ *   connectivity             4 or 8
+ *   labels  0 on unselected pixels, otherwise 1 + (y0 * W + x0) with (y0, x0) the component's
+ *           first pixel in raster order within its image (ranking the distinct labels in
+ *           increasing order gives the numbering of scipy.ndimage.label)
+ *   areas   the component's pixel count at that first pixel, 0 everywhere else
+ *
+ * Cleanup.  unet_mask_cleanup_u8 applies, in this order, each step skipped when it is off:
+ *   1. removal  (keep_largest != 0 or min_area > 0)  the foreground components (connectivity)
+ *      with area < min_area become 0; with keep_largest every component but the largest becomes
+ *      0, ties to the smaller label; the largest is chosen among ALL components, so an image
+ *      whose largest component is below min_area ends up empty.
+ *   2. vote  counts the surviving foreground pixels per class 1..K-1, ties to the lower class.
+ *      UNET_VOTE_IMAGE: every foreground pixel of an image takes the image's winning class (an
+ *      image without foreground is unchanged).  UNET_VOTE_COMPONENT: every foreground component
+ *      (the same components as in step 1) takes its own winning class.
+ *   3. holes  (fill_holes != 0)  the background of the current map is labelled with the DUAL
+ *      connectivity (4 when the foreground uses 8, 8 when it uses 4).  A background component that
+ *      touches no image edge and has area <= max_hole_area (0 = any area) is a hole and takes the
+ *      class of the pixel immediately left of the hole's first raster pixel, read from the map as
+ *      it stood before step 3.  That pixel exists and is foreground: the first pixel of a hole
+ *      that touches no edge has x > 0, and a background left neighbour would belong to the same
+ *      hole (left is a neighbour under both connectivities) and precede it in raster order.
+ * With every step off the call copies the map, bytes >= K becoming 0.  classes_in == classes_out
+ * is allowed.
+ *
+ * Nothing is read back on the host.  Every data-dependent loop in the kernels is bounded (H * W
+ * steps suffice); on overrun a kernel sets the uint32 status word at offset 0 of the workspace
+ * (zeroed by every call, 0 = all loops ended by themselves) and leaves; the caller reads the word
+ * if and when it wants to.  Workspaces: 4 bytes a pixel for the labelling, 16 bytes a pixel for
+ * the cleanup, plus O(B) words, independent of K; 0 is returned for a shape outside the limits.
+ * UNET_E_INVALID before any launch: a null pointer; B outside 1..65535; K outside 2..32; H or W
+ * outside 1..16384 or H * W > 2^30; connectivity not 4 or 8; an unknown mode or vote; a negative
+ * area; a workspace that is too small. */
+#define UNET_CC_FOREGROUND 0
+#define UNET_CC_CLASS 1
+#define UNET_CC_BACKGROUND 2
+#define UNET_VOTE_NONE 0
+#define UNET_VOTE_IMAGE 1
+#define UNET_VOTE_COMPONENT 2
+size_t unet_cc_workspace_bytes(int B, int H, int W);
+int unet_cc_label_u8(const uint8_t* classes, uint32_t* labels, uint32_t* areas, void* workspace,
+                     size_t workspace_bytes, int B, int K, int H, int W, int connectivity,
+                     int mode, unet_stream_t stream);
+size_t unet_mask_cleanup_workspace_bytes(int B, int K, int H, int W);
+int unet_mask_cleanup_u8(const uint8_t* classes_in, uint8_t* classes_out, void* workspace,
+                         size_t workspace_bytes, int B, int K, int H, int W, int connectivity,
+                         int vote, int keep_largest, int min_area, int fill_holes,
+                         int max_hole_area, unet_stream_t stream);
+
+/* unet_eval_confusionk with the class map given instead of the logits: preds[B][H][W] uint8 (a
+ * byte >= K reads as 0) takes the place of the argmax; the same dims rule, the same counts, the
+ * same limits (H, W <= 16384 here); ignore_index must not be a class index 0..K-1. */
+int unet_eval_confusion_classes(const uint8_t* preds, const int64_t* target, const int64_t* dims,
+                                uint64_t* cm, int B, int K, int H, int W, int ignore_index,
+                                unet_stream_t stream);
+
 /* ---- evaluation pictures (render.hip) -------------------------------------------------------
  * The tiles of the reference's figure functions as uint8 RGB, on the device; titles, legends and
  * colour bars are not drawn. */

@@ -23,12 +23,14 @@ from .autoencoder import Autoencoder  # noqa: F401
 from . import ae  # noqa: F401
 from . import evaluate  # noqa: F401
 from . import render  # noqa: F401
+from . import postprocess  # noqa: F401
+from .postprocess import MaskCleanup  # noqa: F401
 from . import latent  # noqa: F401
 from . import augment  # noqa: F401
 from . import dataprep  # noqa: F401
 from .augment import AugmentConfig, BatchAugment  # noqa: F401
 from .evaluate import generate_gradcam_heatmap, gradcam, gradcam_batch  # noqa: F401
 
-__all__ = ["UNet", "Autoencoder", "CLIPUNet", "ClipPatchExtractor", "ClipVisionTransformer", "clip", "ConvBlock", "UpBlock", "SpatialDropout2d", "SimpleLoss", "MSELoss", "SSIMLoss", "PerceptualLoss", "ReconstructionLoss", "calculate_psnr", "calculate_ssim", "evaluate_reconstructions", "SegmentationMetrics", "compute_dice", "compute_iou", "compute_pixel_accuracy", "evaluate_model_metrics", "evaluate", "render", "latent", "gradcam", "gradcam_batch", "generate_gradcam_heatmap", "FusedSGD", "FusedAdam", "ae", "augment", "dataprep", "AugmentConfig", "BatchAugment",
+__all__ = ["UNet", "Autoencoder", "CLIPUNet", "ClipPatchExtractor", "ClipVisionTransformer", "clip", "ConvBlock", "UpBlock", "SpatialDropout2d", "SimpleLoss", "MSELoss", "SSIMLoss", "PerceptualLoss", "ReconstructionLoss", "calculate_psnr", "calculate_ssim", "evaluate_reconstructions", "SegmentationMetrics", "compute_dice", "compute_iou", "compute_pixel_accuracy", "evaluate_model_metrics", "evaluate", "render", "postprocess", "MaskCleanup", "latent", "gradcam", "gradcam_batch", "generate_gradcam_heatmap", "FusedSGD", "FusedAdam", "ae", "augment", "dataprep", "AugmentConfig", "BatchAugment",
            "create_model", "create_optimizer", "create_lr_scheduler", "get_loss_function",
            "train_step", "GraphedTrainStep", "train_one_epoch", "save_checkpoint", "load_checkpoint", "validate", "predict_masks", "ops", "build", "lib", "UNetHipError", "LIB_PATH"]

@@ -220,6 +220,57 @@ __global__ __launch_bounds__(256) void eval_confusionk_kernel(
     if (tab[i]) atomicAdd(&cm[(size_t)b * K * K + i], tab[i]);
 }
 
+// eval_confusionk_kernel with the class map given: preds[b][p] (a byte >= K reads as 0) stands
+// where the argmax loop stood.  The same multiplicity rule, the same LDS table, the same grid.
+template <bool TABLE>
+__global__ __launch_bounds__(256) void eval_confusion_classes_kernel(
+    const unsigned char* __restrict__ preds, const long long* __restrict__ target,
+    const long long* __restrict__ dims, unsigned long long* __restrict__ cm, int K, int H, int W,
+    int ignore_index) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char eval_smem[];
+  unsigned long long* tab = reinterpret_cast<unsigned long long*>(eval_smem);       // [K][K]
+  unsigned int* rowm = reinterpret_cast<unsigned int*>(eval_smem + 8 * K * K);      // [H]
+  unsigned int* colm = rowm + H;                                                    // [W]
+  const int b = blockIdx.y;
+  const int HW = H * W;
+  const bool resize = dims != nullptr;
+  int oh = H, ow = W;
+  if (resize) {   // (an out-of-range size: zero counts, as eval_confusion_kernel)
+    const long long dh = dims[2 * b], dw = dims[2 * b + 1];
+    if (dh < 1 || dh > EVAL_MAX_DIM || dw < 1 || dw > EVAL_MAX_DIM) return;
+    oh = (int)dh;
+    ow = (int)dw;
+  }
+  const float sh = __fdiv_rn((float)H, (float)oh), sw = __fdiv_rn((float)W, (float)ow);
+  const float ish = (float)oh / (float)H, isw = (float)ow / (float)W;
+  for (int i = threadIdx.x; i < K * K; i += 256) tab[i] = 0;
+  if (TABLE && resize) {
+    for (int i = threadIdx.x; i < H; i += 256) rowm[i] = multiplicity(i, sh, ish, H, oh);
+    for (int i = threadIdx.x; i < W; i += 256) colm[i] = multiplicity(i, sw, isw, W, ow);
+  }
+  __syncthreads();
+  const size_t plane = (size_t)HW;
+  const unsigned char* pr = preds + (size_t)b * plane;
+  const long long* tg = target + (size_t)b * plane;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
+    const long long t = tg[p];
+    if (t == (long long)ignore_index || t < 0 || t >= K) continue;
+    int am = pr[p];
+    if (am >= K) am = 0;
+    unsigned int w = 1;
+    if (resize) {
+      const int y = p / W, x = p - y * W;
+      const unsigned int wy = TABLE ? rowm[y] : multiplicity(y, sh, ish, H, oh);
+      const unsigned int wx = TABLE ? colm[x] : multiplicity(x, sw, isw, W, ow);
+      w = wy * wx;                   // wy, wx <= 16384: the product fits 32 bits
+    }
+    if (w) atomicAdd(&tab[(int)t * K + am], (unsigned long long)w);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < K * K; i += 256)
+    if (tab[i]) atomicAdd(&cm[(size_t)b * K * K + i], tab[i]);
+}
+
 // error category of create_error_visualization (utils/visualize.py:205-222), both masks with
 // 255 mapped to background first: 0 none, 1 true positive, 2 false positive, 3 false negative,
 // 4 wrong class.  The prediction is an argmax (0..2), so only the mask can hold 255.
@@ -369,6 +420,38 @@ extern "C" int unet_eval_confusionk(const float* logits_nchw, const int64_t* tar
     hipLaunchKernelGGL(eval_confusionk_kernel<false>, grid, block, lds, stream, logits_nchw, tg,
                        dm, out, K, H, W, ignore_index);
   UNET_CHECK_LAUNCH("eval_confusionk");
+  return UNET_OK;
+}
+
+extern "C" int unet_eval_confusion_classes(const uint8_t* preds, const int64_t* target,
+                                           const int64_t* dims, uint64_t* cm, int B, int K, int H,
+                                           int W, int ignore_index, unet_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  UNET_REQUIRE(preds && target && cm, "eval_confusion_classes: null pointer");
+  UNET_REQUIRE(B > 0 && B <= 65535, "eval_confusion_classes: B = %d is outside 1..65535", B);
+  UNET_REQUIRE(K >= 2 && K <= UNET_MAX_CLASSES,
+               "eval_confusion_classes: K = %d is outside 2..%d", K, UNET_MAX_CLASSES);
+  UNET_REQUIRE(H > 0 && H <= EVAL_MAX_DIM && W > 0 && W <= EVAL_MAX_DIM &&
+                   (long long)H * W <= EVAL_MAX_PIXELS,
+               "eval_confusion_classes: H = %d, W = %d (each 1..16384, H * W <= 2^30)", H, W);
+  UNET_REQUIRE(ignore_index < 0 || ignore_index >= K,
+               "eval_confusion_classes: ignore_index %d is a class index", ignore_index);
+  const long long HW = (long long)H * W;
+  const size_t tab = (size_t)8 * K * K;
+  const bool table = !dims || tab + 4 * ((size_t)H + W) <= 64 * 1024;
+  const size_t lds = tab + ((dims && table) ? 4 * ((size_t)H + W) : 0);
+  UNET_HIP_CALL(hipMemsetAsync(cm, 0, (size_t)B * K * K * sizeof(uint64_t), stream));
+  const dim3 grid(eval_blocks(HW, 1), B), block(256);
+  const long long* tg = reinterpret_cast<const long long*>(target);
+  const long long* dm = reinterpret_cast<const long long*>(dims);
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(cm);
+  if (table)
+    hipLaunchKernelGGL(eval_confusion_classes_kernel<true>, grid, block, lds, stream, preds, tg,
+                       dm, out, K, H, W, ignore_index);
+  else
+    hipLaunchKernelGGL(eval_confusion_classes_kernel<false>, grid, block, lds, stream, preds, tg,
+                       dm, out, K, H, W, ignore_index);
+  UNET_CHECK_LAUNCH("eval_confusion_classes");
   return UNET_OK;
 }
 

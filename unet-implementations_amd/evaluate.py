@@ -39,7 +39,8 @@ def load_model(model_path, device):
     return model
 
 
-def evaluate_model(model, test_loader, device, visualize_samples=0, output_dir=None):
+def evaluate_model(model, test_loader, device, visualize_samples=0, output_dir=None, *,
+                   postprocess=None):
     """The dictionary of src/evaluate.py:239-268 (pixel accuracy, mean IoU, per-class dice / iou /
     precision / recall, `mean_foreground_dice`), every image counted at its original size, plus
     `"confusion_matrix"`: int64 [K, K] numpy (K = model.num_classes, 2..32; the per-class entries
@@ -52,8 +53,16 @@ def evaluate_model(model, test_loader, device, visualize_samples=0, output_dir=N
     one row per image, rendered on the device from the logits of the metrics pass (`ua.render`,
     DESIGN.md section 9b) - the returned numbers are those of a `visualize_samples=0` run.
     Nothing is shown on a screen, so without an `output_dir` there is nowhere to put a picture and
-    `visualize_samples > 0` raises."""
+    `visualize_samples > 0` raises.
+
+    postprocess: a `ua.MaskCleanup` (for this dataset `MaskCleanup.pet()`); every batch's argmax
+    map is cleaned on the device at network size before it is counted at the original sizes.  The
+    pictures are drawn from the logits, so `postprocess` with `visualize_samples > 0` raises."""
     K = getattr(model, "num_classes", 3)
+    if postprocess is not None and visualize_samples > 0:
+        raise ValueError("the pictures are drawn from the logits, not from the cleaned maps: use "
+                         "postprocess with visualize_samples=0 (rendering cleaned maps is not "
+                         "covered)")
     if visualize_samples > 0 and K != 3:
         raise NotImplementedError("the rendered figures use the three-colour palette of the pet "
                                   f"trimap (got {K} classes): use visualize_samples=0")
@@ -77,7 +86,10 @@ def evaluate_model(model, test_loader, device, visualize_samples=0, output_dir=N
                                  ("errors", render.ERROR_PANELS)):
                 render.write_png(os.path.join(str(output_dir), f"{stem}_batch{i}.png"),
                                  render.figure(images, logits, masks, panels))
-    metrics = accumulate_test_metrics(model, test_loader, device, on_batch=on_batch)
+    if postprocess is None:
+        metrics = accumulate_test_metrics(model, test_loader, device, on_batch=on_batch)
+    else:
+        metrics = accumulate_test_metrics(model, test_loader, device, postprocess=postprocess)
     results = {"pixel_accuracy": metrics.compute_pixel_accuracy(),
                "mean_iou": metrics.compute_mean_iou()}
     # the reference's names for its 3 classes, class_0 .. class_{K-1} otherwise

@@ -94,6 +94,25 @@ class SegmentationMetrics:
         self._cm_complete = False
         self._add(counts)
 
+    def update_from_classes(self, preds_u8, target, original_dims=None):
+        """preds_u8 uint8 [B, H, W] (a class map: `ops.argmax_classes`, or a `MaskCleanup` of it),
+        target int64 [B, H, W], both on the device: counted through `unet_eval_confusion_classes`,
+        at each image's original size with original_dims ([B, 2] of (orig_h, orig_w)), at network
+        size without.  Always carries a confusion matrix."""
+        if not torch.is_tensor(preds_u8) or preds_u8.dtype != torch.uint8:
+            raise TypeError("update_from_classes takes a uint8 class map [B, H, W]")
+        if not preds_u8.is_cuda:
+            raise RuntimeError("unet-implementations_amd.SegmentationMetrics runs on MI355X only "
+                               "(no CPU fallback exists)")
+        if target.dtype != torch.int64:
+            target = target.long()
+        dims = None
+        if original_dims is not None:
+            dims = torch.as_tensor(original_dims).to(device=preds_u8.device, dtype=torch.int64,
+                                                     non_blocking=True)
+        self.update_from_confusion(ops.eval_confusion_classes(
+            preds_u8, target, dims, self.num_classes, self.ignore_index))
+
     @property
     def confusion_matrix(self):
         """int64 [K, K] (numpy), target class x predicted class, accumulated by the updates that
@@ -226,21 +245,30 @@ def compute_pixel_accuracy(pred, target, ignore_index=255):
 
 @torch.no_grad()
 def accumulate_test_metrics(model, data_loader, device, ignore_index=255, on_batch=None,
-                            num_classes=None):
+                            num_classes=None, *, postprocess=None):
     """The loop of evaluate_model / evaluate_model_metrics: eval-mode forward, then one launch per
     batch for argmax, both nearest resizes to `original_dims` and all counting.  Nothing is read
     on the host until the returned SegmentationMetrics is asked for a value.
     on_batch(i, images, masks, logits), if given, sees every batch's device tensors after they
-    were counted (evaluate_model renders its pictures from them: no second forward)."""
+    were counted (evaluate_model renders its pictures from them: no second forward).
+    postprocess: a `MaskCleanup`; each batch then runs forward, argmax, the cleanup at network
+    size and the count of the cleaned map at the original sizes - still without a host read."""
     if num_classes is None:      # (the model's own count; the reference's loop is 3-class)
         num_classes = getattr(model, "num_classes", 3)
+    if postprocess is not None:
+        from .postprocess import _check_postprocess
+        _check_postprocess(postprocess)
     model.eval()
     metrics = SegmentationMetrics(num_classes=num_classes, ignore_index=ignore_index)
     for i, batch in enumerate(data_loader):
         images = batch["image"].to(device, non_blocking=True)
         masks = batch["mask"].to(device, non_blocking=True)
         logits = model(images)
-        metrics.update_from_logits(logits, masks, batch["original_dims"])
+        if postprocess is None:
+            metrics.update_from_logits(logits, masks, batch["original_dims"])
+        else:
+            preds = postprocess(ops.argmax_classes(logits.float()), num_classes)
+            metrics.update_from_classes(preds, masks, batch["original_dims"])
         if on_batch is not None:
             on_batch(i, images, masks, logits)
     return metrics

@@ -1342,6 +1342,132 @@ def eval_maps(logits, target=None, want_probs=True, want_classes=True, want_erro
     return probs, classes, errors
 
 
+# ---- mask post-processing (postprocess.hip; definitions: include/unet_hip.h) ------------------
+CC_MODES = {"foreground": 0, "class": 1, "background": 2}      # UNET_CC_*
+CLEANUP_VOTES = {None: 0, "image": 1, "component": 2}          # UNET_VOTE_*
+_rc = check     # (cc_label and mask_cleanup have a `check` argument of their own)
+
+
+def _class_map(name, classes, num_classes):
+    """A uint8 [B, H, W] class map on the device; what is wrong with the tensor itself is said
+    before the device is asked for anything."""
+    if not torch.is_tensor(classes):
+        raise TypeError(f"{name} takes a uint8 [B, H, W] tensor (got {type(classes).__name__})")
+    if classes.dtype != torch.uint8:
+        raise TypeError(f"{name} takes a uint8 class map (got {classes.dtype})")
+    if classes.dim() != 3 or 0 in classes.shape:
+        raise ValueError(f"{name}: class map [B, H, W] expected (got {tuple(classes.shape)})")
+    _check_classes(int(num_classes), name)
+    if not classes.is_cuda:
+        raise RuntimeError(f"unet-implementations_amd.{name} runs on MI355X only "
+                           "(no CPU fallback exists)")
+    return classes.contiguous()
+
+
+def postprocess_status(workspace):
+    """The status word of a cc_label / mask_cleanup workspace (one device-to-host read): 0 when
+    every bounded loop of the kernels ended by itself."""
+    return int(workspace[:4].view(torch.int32).item())
+
+
+def _check_status(name, workspace):
+    status = postprocess_status(workspace)
+    if status:
+        raise RuntimeError(f"{name}: a bounded loop of the labelling kernels ran into its limit "
+                           f"(status {status:#x}); the result is not valid")
+
+
+def cc_label(classes, connectivity=8, mode="foreground", num_classes=32, check=False,
+             workspace=None):
+    """(labels, areas), both uint32 [B, H, W]: the connected components of a uint8 class map.
+    labels = 0 on unselected pixels, otherwise 1 + the raster index (within the image) of the
+    component's first pixel; areas = the component's pixel count at that pixel, 0 elsewhere.
+    check=True reads the workspace's status word afterwards (a host sync) and raises if a kernel
+    loop ran into its bound."""
+    if mode not in CC_MODES:
+        raise ValueError(f"cc_label: mode is one of {sorted(CC_MODES)} (got {mode!r})")
+    if connectivity not in (4, 8):
+        raise ValueError(f"cc_label: connectivity is 4 or 8 (got {connectivity!r})")
+    classes = _class_map("cc_label", classes, num_classes)
+    B, H, W = classes.shape
+    need = lib().unet_cc_workspace_bytes(B, H, W)
+    if need == 0:
+        raise ValueError(f"cc_label: shape {tuple(classes.shape)} is outside B <= 65535, "
+                         "H, W <= 16384, H * W <= 2^30")
+    ws = workspace if workspace is not None else _ws(need, classes)
+    labels = torch.empty((B, H, W), dtype=torch.uint32, device=classes.device)
+    areas = torch.empty((B, H, W), dtype=torch.uint32, device=classes.device)
+    _rc(lib().unet_cc_label_u8(_ptr(classes), labels.data_ptr(), areas.data_ptr(), _ptr(ws),
+                               ws.numel(), B, int(num_classes), H, W, connectivity, CC_MODES[mode],
+                               _stream()))
+    if check:
+        _check_status("cc_label", ws)
+    return labels, areas
+
+
+def mask_cleanup_workspace(classes, num_classes):
+    """A workspace for mask_cleanup of maps of this shape (16 bytes a pixel)."""
+    B, H, W = classes.shape
+    need = lib().unet_mask_cleanup_workspace_bytes(B, int(num_classes), H, W)
+    if need == 0:
+        raise ValueError(f"mask_cleanup: shape {tuple(classes.shape)} is outside B <= 65535, "
+                         "H, W <= 16384, H * W <= 2^30")
+    return _ws(need, classes)
+
+
+def mask_cleanup(classes, num_classes, vote=None, keep_largest=False, min_area=0,
+                 fill_holes=False, max_hole_area=0, connectivity=8, out=None, check=False,
+                 workspace=None):
+    """The cleaned uint8 [B, H, W] map: component removal, class vote and hole filling in the
+    order and with the definitions of include/unet_hip.h.  out: the destination (may be `classes`
+    itself); check=True reads the status word afterwards (a host sync)."""
+    if vote not in CLEANUP_VOTES:
+        raise ValueError(f"mask_cleanup: vote is None, 'image' or 'component' (got {vote!r})")
+    if connectivity not in (4, 8):
+        raise ValueError(f"mask_cleanup: connectivity is 4 or 8 (got {connectivity!r})")
+    if int(min_area) < 0 or int(max_hole_area) < 0:
+        raise ValueError("mask_cleanup: min_area and max_hole_area are >= 0")
+    classes = _class_map("mask_cleanup", classes, num_classes)
+    B, H, W = classes.shape
+    if out is None:
+        out = torch.empty_like(classes)
+    elif out.dtype != torch.uint8 or out.shape != classes.shape or not out.is_contiguous() or \
+            out.device != classes.device:
+        raise ValueError("mask_cleanup: out must be a contiguous uint8 tensor of the map's shape "
+                         "on its device")
+    ws = workspace if workspace is not None else mask_cleanup_workspace(classes, num_classes)
+    _rc(lib().unet_mask_cleanup_u8(_ptr(classes), _ptr(out), _ptr(ws), ws.numel(), B,
+                                   int(num_classes), H, W, connectivity, CLEANUP_VOTES[vote],
+                                   1 if keep_largest else 0, int(min_area),
+                                   1 if fill_holes else 0, int(max_hole_area), _stream()))
+    if check:
+        _check_status("mask_cleanup", ws)
+    return out
+
+
+def eval_confusion_classes(preds, target, dims=None, num_classes=3, ignore_index=255):
+    """eval_confusion with the uint8 class map `preds` [B, H, W] in place of the logits' argmax (a
+    byte >= num_classes reads as 0): int64 [B, K, K] = [target class][predicted class], both maps
+    nearest-resized to dims[b] (int64 [B, 2] on the device, never read on the host; None = at
+    network size)."""
+    if torch.is_tensor(target) and target.dtype != torch.int64:
+        raise TypeError("eval_confusion_classes takes int64 targets")
+    preds = _class_map("eval_confusion_classes", preds, num_classes)
+    B, H, W = preds.shape
+    K = int(num_classes)
+    if not torch.is_tensor(target) or tuple(target.shape) != (B, H, W):
+        raise ValueError("target must be [B, H, W] of the class map's size")
+    target = target.contiguous()
+    if dims is not None:
+        if not torch.is_tensor(dims) or dims.dtype != torch.int64 or tuple(dims.shape) != (B, 2):
+            raise TypeError("dims must be an int64 [B, 2] tensor of (orig_h, orig_w)")
+        dims = dims.contiguous()
+    cm = torch.empty((B, K, K), dtype=torch.int64, device=preds.device)
+    check(lib().unet_eval_confusion_classes(_ptr(preds), _ptr(target), _ptr(dims), cm.data_ptr(),
+                                            B, K, H, W, int(ignore_index), _stream()))
+    return cm
+
+
 # ---- ragged uint8 batches to network size (letterbox.hip) ------------------------------------
 LETTERBOX_FIELDS = 8    # UNET_LETTERBOX_FIELDS: image offset, mask offset, h, w, out_h, out_w,
 #                         pad_y, pad_x

@@ -217,18 +217,24 @@ def nearest_source_index(in_size, out_size):
 
 
 @torch.no_grad()
-def predict_masks(model, images, original_dims=None):
+def predict_masks(model, images, original_dims=None, *, postprocess=None):
     """Inference as in Our_UNet/src/evaluate.py:185-207: eval-mode forward and per-pixel argmax,
     returned as a uint8 class map on the device.  With `original_dims` ([B, 2] of (orig_h,
     orig_w)) the result is a list of B uint8 device maps, each nearest-resized to its original
     size as the reference does on the CPU; the sizes are read on the host (output shapes depend on
-    them), so this is the visual path, not the metric path (see `evaluate.evaluate_model`)."""
+    them), so this is the visual path, not the metric path (see `evaluate.evaluate_model`).
+    postprocess: a `MaskCleanup`, applied at network size before the resize."""
+    if postprocess is not None:
+        from .postprocess import _check_postprocess
+        _check_postprocess(postprocess)
     was_training = model.training
     model.eval()
     try:
         preds = ops.argmax_classes(model(images))
     finally:
         model.train(was_training)
+    if postprocess is not None:
+        preds = postprocess(preds, getattr(model, "num_classes", 3))
     if original_dims is None:
         return preds
     H, W = preds.shape[1:]
