@@ -391,9 +391,22 @@ int unet_eval_confusion(const float* logits_nchw, const int64_t* target, const i
  * The entry points above are the pet trimap's 3 classes and have no K argument; these carry it.
  * Definitions are the reference's with 3 replaced by K (Our_UNet/models/losses.py:24-121):
  * dynamic weights total / count (count 0 -> 1) renormalised to sum K, weighted CE over the valid
- * pixels, soft Dice averaged over the images and then over the K classes.  At K == 3 they are
- * the definitions of unet_dice_wce_loss_fwd_bwd (other kernels: the last bits may differ).
- *   loss_out      float[3 + K] = {loss, CE, Dice, w[0..K-1]}
+ * pixels, soft Dice averaged over the images and then over the K classes.
+ * K == 3 IS the 3-class call: every entry point of this block then runs the kernels of its
+ * counterpart above (loss_reduce / loss_finalize / loss_grad, argmax_counts_kernel with its
+ * four-pixel form, eval_confusion_kernel with its vector form) and gives its bits, and the
+ * entry points above are these at K == 3.  A workspace sized by either
+ * unet_dice_wce_loss_workspace_bytes(N, H, W) or unet_dice_wce_lossk_workspace_bytes(N, 3, H, W)
+ * (equal for the N both admit) serves both, the sharded pair included.  Any other K runs the
+ * K-class kernels, instantiated for K padded to 4, 8, 16 or 32.
+ * One difference between the two kernel sets is visible at K == 3, in the `_u8` forms: the
+ * 3-class loaders clean a raw mask with the dataset's literal rule v > 2 && v != 255 -> 0, the
+ * K-class loaders with v >= K && v != ignore_index -> 0.  The two agree for ignore_index == 255,
+ * the value the Python surface passes with uint8 targets at 3 classes; for another ignore_index
+ * in 3..254 the 3-class loaders read a byte equal to ignore_index as class 0 and a byte 255 as a
+ * valid pixel of no class, where the K-class loaders ignore the former and read the latter as
+ * class 0.
+ *   loss_out     float[3 + K] = {loss, CE, Dice, w[0..K-1]}
  *   class_weights K floats on the device (dynamic_weights == 0; NULL = unweighted)
  *   workspace     unet_dice_wce_lossk_workspace_bytes(N, K, H, W); kept by the caller between
  *                 a dlogits == NULL call and unet_dice_wce_lossk_grad, whose dlogits are

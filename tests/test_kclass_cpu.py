@@ -1,7 +1,7 @@
 """The K-class tail (2..32 classes: head, loss, counts, confusion) without a GPU: the exports and
 the ABI version, what the Python surface accepts and what it refuses before touching a device,
 the C entry points' refusals before a launch, the references of tests/test_kclass_gpu.py against
-the oracle, and the build of csrc/head_loss_k.hip."""
+the oracle, and the build of csrc/head.hip and csrc/loss.hip."""
 import ctypes
 import importlib.util
 import os
@@ -138,6 +138,38 @@ def test_c_entry_points_refuse_before_any_launch(ua):
     assert L.unet_dice_wce_lossk_workspace_bytes(1024, 32, 8, 8) > 0
 
 
+def test_the_k_form_takes_3_classes_with_the_3_class_workspace_and_refusals(ua):
+    """K = 3 through the K-form: the workspace is byte for byte the 3-class one, and what the
+    3-class exports refuse - 1025 images, a uint8 ignore_index that is a class - is refused."""
+    L = ua.lib()
+    p = 4096
+    for N in (1, 8, 1024):
+        for H, W in ((8, 8), (512, 512)):
+            assert L.unet_dice_wce_lossk_workspace_bytes(N, 3, H, W) == \
+                L.unet_dice_wce_loss_workspace_bytes(N, H, W) > 0, (N, H, W)
+
+    def loss(fn, N, ignore, ws=1 << 40):
+        return fn(p, p, p, None, p, ws, N, 3, 8, 8, 1e-5, 1.0, 1.0, ignore, 1, None, 1.0, None)
+
+    def grad(fn, N, ignore, ws=1 << 40):
+        return fn(p, p, p, ws, None, p, N, 3, 8, 8, ignore, None)
+
+    for sfx in ("", "_u8"):
+        fwd, bwd = (getattr(L, f"unet_dice_wce_lossk_{n}{sfx}") for n in ("fwd_bwd", "grad"))
+        assert loss(fwd, 1025, 255) == UNET_E_INVALID and b"bad shape" in L.unet_last_error()
+        assert grad(bwd, 1025, 255) == UNET_E_INVALID and b"bad shape" in L.unet_last_error()
+        # (1024 images pass the checks and stop at the workspace size, still before a launch)
+        assert loss(fwd, 1024, 255, ws=16) == -3 and grad(bwd, 1024, 255, ws=16) == -3
+    assert L.unet_dice_wce_lossk_workspace_bytes(1025, 3, 8, 8) == 0
+    assert loss(L.unet_dice_wce_lossk_fwd_bwd_u8, 2, 2) == UNET_E_INVALID
+    assert b"ignore_index in 3..255" in L.unet_last_error()
+    assert grad(L.unet_dice_wce_lossk_grad_u8, 2, 2) == UNET_E_INVALID
+    assert b"ignore_index in 3..255" in L.unet_last_error()
+    assert L.unet_argmax_countsk_u8(p, p, p, p, 2, 3, 8, 8, 2, None) == UNET_E_INVALID
+    assert b"ignore_index in 3..255" in L.unet_last_error()
+    assert L.unet_eval_confusionk(p, p, None, p, 2, 3, 8, 8, 2, None) == UNET_E_INVALID
+
+
 # --------------------------------------------------------------------------- the references
 @pytest.mark.parametrize("dynamic", [True, False])
 def test_reference_at_3_classes_is_the_oracles_simple_loss_bit_for_bit(dynamic):
@@ -200,22 +232,31 @@ def test_gapped_logits_and_the_confusion_reference():
 
 
 # --------------------------------------------------------------------------- the build
-def test_head_loss_k_kernels_use_no_scratch_and_the_hazard_check_is_clean():
-    obj = os.path.join(ROOT, "unet-implementations_amd", "csrc", "build", "head_loss_k.o")
-    if not os.path.exists(obj):
-        pytest.skip("no built objects (run __graft_entry__.build() first)")
-    regs = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_regs.sh"), obj],
-                          capture_output=True, text=True, check=True).stdout
-    lines = [ln for ln in regs.splitlines() if " scratch " in ln]
-    names = " ".join(lines)
-    for kernel in ("headk_fwd_kernel", "headk_bwd_kernel", "headk_bwd_finalize_kernel",
-                   "lossk_reduce_kernel", "lossk_finalize_kernel", "lossk_grad_kernel",
-                   "argmax_countsk_kernel"):
-        assert kernel in names, kernel
-    assert lines and all(ln.split()[-1] == "0" for ln in lines), regs
-    # (--max-states: the 32-class instantiations are long straight-line kernels whose exact
-    # path-by-path walk takes minutes; past 300 states the tool walks merged paths instead, which
-    # is sound - it can only over-report)
-    r = subprocess.run(["python3", os.path.join(ROOT, "tools", "asm_hazard_check.py"),
-                        "--max-states=300", obj], capture_output=True, text=True)
-    assert r.returncode == 0 and " 0 hazards, 0 incomplete" in r.stdout, r.stdout[-2000:]
+TAIL_KERNELS = {
+    "head": ("head_fwd_kernel", "head_bwd_kernel", "head_bwd_finalize_kernel", "headk_fwd_kernel",
+             "headk_bwd_kernel", "headk_bwd_finalize_kernel"),
+    "loss": ("loss_reduce_kernel", "loss_reduce_u8_kernel", "loss_finalize_kernel",
+             "loss_shard_stats_kernel", "loss_shard_apply_kernel", "loss_grad_kernel",
+             "loss_grad_u8_kernel", "argmax_counts_kernel", "lossk_reduce_kernel",
+             "lossk_finalize_kernel", "lossk_grad_kernel", "argmax_countsk_kernel"),
+}
+
+
+def test_head_and_loss_kernels_use_no_scratch_and_the_hazard_check_is_clean():
+    for unit, kernels in TAIL_KERNELS.items():
+        obj = os.path.join(ROOT, "unet-implementations_amd", "csrc", "build", unit + ".o")
+        if not os.path.exists(obj):
+            pytest.skip("no built objects (run __graft_entry__.build() first)")
+        regs = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_regs.sh"), obj],
+                              capture_output=True, text=True, check=True).stdout
+        lines = [ln for ln in regs.splitlines() if " scratch " in ln]
+        names = " ".join(lines)
+        for kernel in kernels:
+            assert "N_1%d%s" % (len(kernel), kernel) in names, kernel      # (the mangled name)
+        assert lines and all(ln.split()[-1] == "0" for ln in lines), regs
+        # (--max-states: the 32-class instantiations are long straight-line kernels whose exact
+        # path-by-path walk takes minutes; past 300 states the tool walks merged paths instead,
+        # which is sound - it can only over-report)
+        r = subprocess.run(["python3", os.path.join(ROOT, "tools", "asm_hazard_check.py"),
+                            "--max-states=300", obj], capture_output=True, text=True)
+        assert r.returncode == 0 and " 0 hazards, 0 incomplete" in r.stdout, r.stdout[-2000:]

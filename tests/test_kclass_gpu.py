@@ -248,6 +248,98 @@ def test_loss_and_counts_at_3_classes_keep_their_kernels(ua):
     assert out.numel() == 8
 
 
+@pytest.mark.parametrize("shape", [(2, 17, 9), (2, 24, 40), (1, 48, 48)])
+def test_the_k_form_at_3_classes_is_the_3_class_call(ua, shape):
+    """The exports themselves, K-form with K = 3 against the 3-class export: the same launches
+    and the same bits.  2 x 17 x 9: 153 pixels are no multiple of 4 (the one-pixel counts kernel,
+    the non-vector confusion kernel); 2 x 24 x 40: aligned (four pixels per lane with uint8
+    targets, the vector confusion kernel); 1 x 48 x 48: 2304 pixels, two reduce slabs an image."""
+    L, ptr, stream = ua.lib(), ua.ops._ptr, ua.ops._stream()
+    N, H, W = shape
+    aligned = (H * W) % 4 == 0
+
+    def both(base, kform, u8):
+        """(export, its class argument) of the 3-class form and of the K-form"""
+        sfx = "_u8" if u8 else ""
+        return (getattr(L, base + sfx), ()), (getattr(L, kform + sfx), (3,))
+
+    def workspaces(dev):
+        n3 = L.unet_dice_wce_loss_workspace_bytes(N, H, W)
+        assert n3 == L.unet_dice_wce_lossk_workspace_bytes(N, 3, H, W) > 0
+        return [torch.zeros(n3, dtype=torch.uint8, device=dev) for _ in range(2)]
+
+    up = torch.tensor(-2.75, device=DEV)
+    for kind in ("missing", "image_ignored"):
+        lg, labels, raw = KR.make_loss_case(3, shape, kind, 31)
+        lgd = lg.to(DEV)
+        for u8, tgd in ((False, labels.to(DEV)), (True, raw.to(DEV))):
+            names = [HS.LOSS_REDUCE_U8 if u8 else HS.LOSS_REDUCE, HS.LOSS_FINALIZE,
+                     HS.LOSS_GRAD_U8 if u8 else HS.LOSS_GRAD]
+            for weights in ("dynamic", "fixed", "none"):
+                cw = KR.fixed_weights(3).to(DEV) if weights == "fixed" else None
+                got = []
+                for (fwd, k), (grad, _), ws in zip(
+                        both("unet_dice_wce_loss_fwd_bwd", "unet_dice_wce_lossk_fwd_bwd", u8),
+                        both("unet_dice_wce_loss_grad", "unet_dice_wce_lossk_grad", u8),
+                        workspaces(DEV)):
+                    out, out2 = torch.zeros(8, device=DEV), torch.zeros(8, device=DEV)
+                    dl, dl2 = torch.empty_like(lgd), torch.empty_like(lgd)
+                    tail = (1e-5, 0.7, 1.3, 255, 1 if weights == "dynamic" else 0, ptr(cw), 0.5,
+                            stream)
+                    with ua.ops.record_launches() as rec:
+                        ua._lib.check(fwd(ptr(lgd), ptr(tgd), ptr(out), ptr(dl), ptr(ws),
+                                          ws.numel(), N, *k, H, W, *tail))
+                    assert rec.names == names, rec.names
+                    # forward only, then the gradient on its own with an upstream scale
+                    with ua.ops.record_launches() as rec:
+                        ua._lib.check(fwd(ptr(lgd), ptr(tgd), ptr(out2), None, ptr(ws),
+                                          ws.numel(), N, *k, H, W, *tail))
+                        ua._lib.check(grad(ptr(lgd), ptr(tgd), ptr(ws), ws.numel(), ptr(up),
+                                           ptr(dl2), N, *k, H, W, 255, stream))
+                    assert rec.names == names, rec.names
+                    got.append((out[:6], dl, out2[:6], dl2))
+                # (bits, not values: the one image of 1 x 48 x 48, wholly ignored, has a NaN loss)
+                for a, b in zip(*got):
+                    assert torch.equal(a.view(torch.int32), b.view(torch.int32)), \
+                        (kind, u8, weights)
+            # argmax and counts
+            got = []
+            for fn, k in both("unet_argmax_dice_counts", "unet_argmax_countsk", u8):
+                preds = torch.full((N, H, W), 77, dtype=torch.uint8, device=DEV)
+                counts = torch.full((3, 3), -1, dtype=torch.int64, device=DEV)
+                with ua.ops.record_launches() as rec:
+                    ua._lib.check(fn(ptr(lgd), ptr(tgd), ptr(preds), counts.data_ptr(), N, *k, H,
+                                     W, 255, stream))
+                tt = "unsigned char" if u8 else "long long"
+                launched(rec.names, f"argmax_counts_kernel<{tt}, {4 if u8 and aligned else 1}>")
+                got.append((rec.names, preds, counts))
+            assert got[0][0] == got[1][0]
+            assert torch.equal(got[0][1], got[1][1]) and torch.equal(got[0][2], got[1][2])
+            assert torch.equal(got[0][1].cpu().long(), lg.argmax(1))
+        # confusion (int64 targets only): at network size, and with one image upscaled and - where
+        # there is a second one - that one given a zero size
+        tgd = labels.to(DEV)
+        some = torch.tensor([(2 * H + 1, 3 * W), (0, W)][:N], dtype=torch.int64, device=DEV)
+        for dims in (None, some):
+            got = []
+            for fn, k in both("unet_eval_confusion", "unet_eval_confusionk", False):
+                cm = torch.full((N, 3, 3), -1, dtype=torch.int64, device=DEV)
+                with ua.ops.record_launches() as rec:
+                    ua._lib.check(fn(ptr(lgd), ptr(tgd), ptr(dims), cm.data_ptr(), N, *k, H, W,
+                                     255, stream))
+                launched(rec.names, "eval_confusion_kernel<")
+                got.append((rec.names, cm))
+            assert got[0][0] == got[1][0] and torch.equal(got[0][1], got[1][1])
+            assert ("<true" in got[0][0][0]) == (W % 4 == 0), got[0][0]
+            if dims is None:
+                want = np.stack([KR.confusion(p, t, 3) for p, t in
+                                 zip(lg.argmax(1).numpy(), labels.numpy())])
+            else:
+                want = KR.resized_confusion(lg.argmax(1).numpy(), labels.numpy(),
+                                            some.cpu().tolist(), 3)
+            assert np.array_equal(got[0][1].cpu().numpy(), want)
+
+
 # --------------------------------------------------------------------------- counts, confusion
 @pytest.mark.parametrize("K", [2, 5, 32])
 def test_counts_and_confusion_are_exact(ua, K):

@@ -92,16 +92,6 @@ int unet_in_stats_masked(const float* y, const float* gamma, const float* beta, 
                          void* workspace, size_t workspace_bytes, int N, int HW, int C,
                          hipStream_t stream, int y_is_bf16 = 0);
 
-// head_loss_k.hip: the 1x1 head for 5 <= K <= 32 classes (the unet_head1x1_* entry points of
-// head_loss.hip check the operands and dispatch here for K > 4).  M = N * HW pixels; alpha / beta
-// (nullable) activate `a` on load; partial: max_blocks slabs of K * 32 + K floats.
-int unet_headk_fwd(const void* a, int a_is_bf16, const float* w, const float* b, float* logits,
-                   long long M, int HW, int K, const float* alpha, const float* beta, float slope,
-                   hipStream_t stream);
-int unet_headk_bwd(const void* a, int a_is_bf16, const float* dlogits, const float* w, void* da,
-                   float* dw, float* db, float* partial, int max_blocks, long long M, int HW,
-                   int K, const float* alpha, const float* beta, float slope, hipStream_t stream);
-
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline long long ceil_div64(long long a, long long b) { return (a + b - 1) / b; }

@@ -358,24 +358,44 @@ int eval_blocks(long long HW, int px_per_thread) {
 
 }  // namespace
 
-extern "C" int unet_eval_confusion(const float* logits_nchw, const int64_t* target,
-                                   const int64_t* dims, uint64_t* cm, int B, int H, int W,
-                                   int ignore_index, unet_stream_t stream_) {
+// K == 3 runs eval_confusion_kernel (four pixels per lane where W % 4 == 0 and the tensors are
+// 16-byte aligned), any other K eval_confusionk_kernel; both index a batch's planes with int.
+extern "C" int unet_eval_confusionk(const float* logits_nchw, const int64_t* target,
+                                    const int64_t* dims, uint64_t* cm, int B, int K, int H, int W,
+                                    int ignore_index, unet_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   UNET_REQUIRE(logits_nchw && target && cm, "eval_confusion: null pointer");
-  UNET_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W <= EVAL_MAX_PIXELS,
-               "eval_confusion: bad shape (B in 1..65535, H, W >= 1, H * W <= 2^30)");
-  UNET_REQUIRE(ignore_index < 0 || ignore_index > 2,
+  UNET_REQUIRE(K >= 2 && K <= UNET_MAX_CLASSES, "eval_confusion: needs 2 <= K <= %d (got %d)",
+               UNET_MAX_CLASSES, K);
+  UNET_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W <= EVAL_MAX_PIXELS &&
+                   (long long)H * W * K <= 0x7fffffffll,
+               "eval_confusion: bad shape (B in 1..65535, H * W <= 2^30, K * H * W < 2^31)");
+  UNET_REQUIRE(ignore_index < 0 || ignore_index >= K,
                "eval_confusion: ignore_index %d is a class index", ignore_index);
   const long long HW = (long long)H * W;
-  const bool vec = (W % 4 == 0) && aligned_to(logits_nchw, 16) && aligned_to(target, 16);
-  const bool table = !dims || H + (long long)W <= EVAL_TABLE_MAX;
-  const size_t lds = EVAL_RED_BYTES + ((dims && table) ? 4 * ((size_t)H + W) : 0);
-  UNET_HIP_CALL(hipMemsetAsync(cm, 0, (size_t)B * 9 * sizeof(uint64_t), stream));
-  const dim3 grid(eval_blocks(HW, vec ? 4 : 1), B), block(256);
+  UNET_HIP_CALL(hipMemsetAsync(cm, 0, (size_t)B * K * K * sizeof(uint64_t), stream));
+  const dim3 block(256);
   const long long* tg = reinterpret_cast<const long long*>(target);
   const long long* dm = reinterpret_cast<const long long*>(dims);
   unsigned long long* out = reinterpret_cast<unsigned long long*>(cm);
+  if (K != 3) {
+    const size_t tab = (size_t)8 * K * K;
+    const bool table = !dims || tab + 4 * ((size_t)H + W) <= 64 * 1024;
+    const size_t lds = tab + ((dims && table) ? 4 * ((size_t)H + W) : 0);
+    const dim3 grid(eval_blocks(HW, 1), B);
+    if (table)
+      hipLaunchKernelGGL(eval_confusionk_kernel<true>, grid, block, lds, stream, logits_nchw, tg,
+                         dm, out, K, H, W, ignore_index);
+    else
+      hipLaunchKernelGGL(eval_confusionk_kernel<false>, grid, block, lds, stream, logits_nchw, tg,
+                         dm, out, K, H, W, ignore_index);
+    UNET_CHECK_LAUNCH("eval_confusionk");
+    return UNET_OK;
+  }
+  const bool vec = (W % 4 == 0) && aligned_to(logits_nchw, 16) && aligned_to(target, 16);
+  const bool table = !dims || H + (long long)W <= EVAL_TABLE_MAX;
+  const size_t lds = EVAL_RED_BYTES + ((dims && table) ? 4 * ((size_t)H + W) : 0);
+  const dim3 grid(eval_blocks(HW, vec ? 4 : 1), B);
   if (vec && table)
     hipLaunchKernelGGL((eval_confusion_kernel<true, true>), grid, block, lds, stream, logits_nchw,
                        tg, dm, out, H, W, ignore_index);
@@ -392,35 +412,10 @@ extern "C" int unet_eval_confusion(const float* logits_nchw, const int64_t* targ
   return UNET_OK;
 }
 
-extern "C" int unet_eval_confusionk(const float* logits_nchw, const int64_t* target,
-                                    const int64_t* dims, uint64_t* cm, int B, int K, int H, int W,
-                                    int ignore_index, unet_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  UNET_REQUIRE(logits_nchw && target && cm, "eval_confusionk: null pointer");
-  UNET_REQUIRE(K >= 2 && K <= UNET_MAX_CLASSES, "eval_confusionk: needs 2 <= K <= %d (got %d)",
-               UNET_MAX_CLASSES, K);
-  UNET_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W <= EVAL_MAX_PIXELS &&
-                   (long long)H * W * K <= 0x7fffffffll,
-               "eval_confusionk: bad shape (B in 1..65535, H * W <= 2^30, K * H * W < 2^31)");
-  UNET_REQUIRE(ignore_index < 0 || ignore_index >= K,
-               "eval_confusionk: ignore_index %d is a class index", ignore_index);
-  const long long HW = (long long)H * W;
-  const size_t tab = (size_t)8 * K * K;
-  const bool table = !dims || tab + 4 * ((size_t)H + W) <= 64 * 1024;
-  const size_t lds = tab + ((dims && table) ? 4 * ((size_t)H + W) : 0);
-  UNET_HIP_CALL(hipMemsetAsync(cm, 0, (size_t)B * K * K * sizeof(uint64_t), stream));
-  const dim3 grid(eval_blocks(HW, 1), B), block(256);
-  const long long* tg = reinterpret_cast<const long long*>(target);
-  const long long* dm = reinterpret_cast<const long long*>(dims);
-  unsigned long long* out = reinterpret_cast<unsigned long long*>(cm);
-  if (table)
-    hipLaunchKernelGGL(eval_confusionk_kernel<true>, grid, block, lds, stream, logits_nchw, tg, dm,
-                       out, K, H, W, ignore_index);
-  else
-    hipLaunchKernelGGL(eval_confusionk_kernel<false>, grid, block, lds, stream, logits_nchw, tg,
-                       dm, out, K, H, W, ignore_index);
-  UNET_CHECK_LAUNCH("eval_confusionk");
-  return UNET_OK;
+extern "C" int unet_eval_confusion(const float* logits_nchw, const int64_t* target,
+                                   const int64_t* dims, uint64_t* cm, int B, int H, int W,
+                                   int ignore_index, unet_stream_t stream) {
+  return unet_eval_confusionk(logits_nchw, target, dims, cm, B, 3, H, W, ignore_index, stream);
 }
 
 extern "C" int unet_eval_confusion_classes(const uint8_t* preds, const int64_t* target,

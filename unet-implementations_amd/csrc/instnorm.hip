@@ -544,7 +544,7 @@ int unet_in_finalize_tiles(const void* partial, int tiles, int px_per_tile, cons
 }
 
 // Merge of the per-tile (S1, S2) summaries a producer of dL/da left (`tiles` per image), for
-// the callers that form dz themselves as well (head_loss.hip, conv_wgrad.hip)
+// the callers that form dz themselves as well (head.hip, conv_wgrad.hip)
 extern "C" int unet_instnorm_bwd_merge_partials(const void* partial, int tiles, void* coef,
                                                 void* sums, int N, int HW, int C,
                                                 unet_stream_t stream) {

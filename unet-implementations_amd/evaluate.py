@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import ops
 from .metrics import accumulate_test_metrics
-from .train import create_model
+from .train import class_names, create_model
 from .unet import stage_feature_and_gradient
 
 
@@ -92,8 +92,7 @@ def evaluate_model(model, test_loader, device, visualize_samples=0, output_dir=N
         metrics = accumulate_test_metrics(model, test_loader, device, postprocess=postprocess)
     results = {"pixel_accuracy": metrics.compute_pixel_accuracy(),
                "mean_iou": metrics.compute_mean_iou()}
-    # the reference's names for its 3 classes, class_0 .. class_{K-1} otherwise
-    names = ("background", "cat", "dog") if K == 3 else tuple(f"class_{c}" for c in range(K))
+    names = class_names(K)
     for cls, name in enumerate(names):
         results[name] = {"dice": metrics.compute_dice(cls), "iou": metrics.compute_iou(cls),
                          "precision": metrics.compute_precision(cls),

@@ -92,11 +92,10 @@ class SimpleLoss(nn.Module):
     def forward(self, input, target):
         # (what this class count does not cover is refused first, before the device is touched)
         K = input.shape[1]
-        if K != 3:
-            ops._check_classes(K, "SimpleLoss")
-            if self.batch_sync == "global":
-                raise NotImplementedError("SimpleLoss(batch_sync='global'), the sharded loss, "
-                                          f"covers exactly 3 classes (got {K})")
+        ops._check_classes(K, "SimpleLoss")
+        if K != 3 and self.batch_sync == "global":
+            raise NotImplementedError("SimpleLoss(batch_sync='global'), the sharded loss, "
+                                      f"covers exactly 3 classes (got {K})")
         if not bool(self.dynamic_weights) and self.class_weights is not None and \
                 len(self.class_weights) != K:
             raise ValueError(f"class_weights holds {len(self.class_weights)} values for {K} "

@@ -1146,41 +1146,30 @@ def dice_wce_loss_fwd_bwd(logits, target, smooth, w_dice, w_ce, ignore_index, dy
     later with dice_wce_loss_grad (want_grad=False here).  target: int64 labels, or (here and in
     the four functions below) the dataset's uint8 mask as it is - raw or cleaned, 1 byte a pixel."""
     N, K, H, W = logits.shape
-    if K != 3:
-        # out = {loss, ce, dice, w[0..K-1]}: the K-class kernels (3 keeps its own, and its 8 floats)
-        _check_classes(K, "dice_wce_loss_fwd_bwd")
-        if class_weights is not None and class_weights.numel() != K:
-            raise ValueError(f"class_weights holds {class_weights.numel()} values for {K} classes")
-        out = _f32((3 + K,), logits)
-        dl = torch.empty_like(logits) if want_grad else None
-        if ws is None:
-            ws = dice_wce_loss_workspace(logits)
-        check(_target_twin("unet_dice_wce_lossk_fwd_bwd", target)(
-            _ptr(logits), _ptr(target), _ptr(out), _ptr(dl), _ptr(ws), ws.numel(), N, K, H, W,
-            smooth, w_dice, w_ce, ignore_index, 1 if dynamic_weights else 0, _ptr(class_weights),
-            grad_scale, _stream()))
-        return out, dl
-    out = _f32((8,), logits)
+    _check_classes(K, "dice_wce_loss_fwd_bwd")
+    if class_weights is not None and class_weights.numel() != K:
+        raise ValueError(f"class_weights holds {class_weights.numel()} values for {K} classes")
+    # out = {loss, ce, dice, w[0..K-1]}; 8 floats at 3 classes, as ever (the last two unused)
+    out = _f32((8 if K == 3 else 3 + K,), logits)
     dl = torch.empty_like(logits) if want_grad else None
     if ws is None:
-        ws = _ws(lib().unet_dice_wce_loss_workspace_bytes(N, H, W), logits)
-    check(_target_twin("unet_dice_wce_loss_fwd_bwd", target)(
-        _ptr(logits), _ptr(target), _ptr(out), _ptr(dl), _ptr(ws), ws.numel(), N, H, W, smooth,
-        w_dice, w_ce, ignore_index, 1 if dynamic_weights else 0, _ptr(class_weights), grad_scale,
-        _stream()))
+        ws = dice_wce_loss_workspace(logits)
+    check(_target_twin("unet_dice_wce_lossk_fwd_bwd", target)(
+        _ptr(logits), _ptr(target), _ptr(out), _ptr(dl), _ptr(ws), ws.numel(), N, K, H, W,
+        smooth, w_dice, w_ce, ignore_index, 1 if dynamic_weights else 0, _ptr(class_weights),
+        grad_scale, _stream()))
     return out, dl
 
 
 def dice_wce_loss_workspace(logits):
     N, K, H, W = logits.shape
-    if K != 3:
-        _check_classes(K, "dice_wce_loss_workspace")
-        nbytes = lib().unet_dice_wce_lossk_workspace_bytes(N, K, H, W)
-        if nbytes == 0:
-            raise ValueError(f"dice_wce_loss: a batch of {N} images is outside the 1..1024 the "
-                             "loss kernels take per call")
-        return _ws(nbytes, logits)
-    return _ws(lib().unet_dice_wce_loss_workspace_bytes(N, H, W), logits)
+    _check_classes(K, "dice_wce_loss_workspace")
+    nbytes = lib().unet_dice_wce_lossk_workspace_bytes(N, K, H, W)
+    # (at 3 classes a batch outside the limit has always been refused by the call that follows)
+    if nbytes == 0 and K != 3:
+        raise ValueError(f"dice_wce_loss: a batch of {N} images is outside the 1..1024 the "
+                         "loss kernels take per call")
+    return _ws(nbytes, logits)
 
 
 def dice_wce_loss_grad(logits, target, ws, upstream, ignore_index):
@@ -1191,14 +1180,9 @@ def dice_wce_loss_grad(logits, target, ws, upstream, ignore_index):
     dl = torch.empty_like(logits)
     if upstream is not None:
         upstream = upstream.reshape(1).float().contiguous()
-    if K != 3:
-        _check_classes(K, "dice_wce_loss_grad")
-        check(_target_twin("unet_dice_wce_lossk_grad", target)(
-            _ptr(logits), _ptr(target), _ptr(ws), ws.numel(), _ptr(upstream), _ptr(dl), N, K, H, W,
-            ignore_index, _stream()))
-        return dl
-    check(_target_twin("unet_dice_wce_loss_grad", target)(
-        _ptr(logits), _ptr(target), _ptr(ws), ws.numel(), _ptr(upstream), _ptr(dl), N, H, W,
+    _check_classes(K, "dice_wce_loss_grad")
+    check(_target_twin("unet_dice_wce_lossk_grad", target)(
+        _ptr(logits), _ptr(target), _ptr(ws), ws.numel(), _ptr(upstream), _ptr(dl), N, K, H, W,
         ignore_index, _stream()))
     return dl
 
@@ -1237,20 +1221,14 @@ def argmax_dice_counts(logits, target, ignore_index=255, want_preds=True):
     {intersection, predicted, labelled}); everything stays on the device.  target: int64 labels
     or the dataset's uint8 mask."""
     N, K, H, W = logits.shape
-    if K != 3:
-        _check_classes(K, "argmax_dice_counts")
+    _check_classes(K, "argmax_dice_counts")
     logits, target = logits.contiguous(), target.contiguous()
     if logits.dtype != torch.float32 or target.dtype not in (torch.int64, torch.uint8):
         raise TypeError("argmax_dice_counts takes fp32 logits and int64 (or uint8) targets")
     preds = torch.empty((N, H, W), dtype=torch.uint8, device=logits.device) if want_preds else None
     counts = torch.empty((K, 3), dtype=torch.int64, device=logits.device)
-    if K != 3:
-        check(_target_twin("unet_argmax_countsk", target)(
-            _ptr(logits), _ptr(target), _ptr(preds), counts.data_ptr(), N, K, H, W, ignore_index,
-            _stream()))
-        return preds, counts
-    check(_target_twin("unet_argmax_dice_counts", target)(
-        _ptr(logits), _ptr(target), _ptr(preds), counts.data_ptr(), N, H, W, ignore_index,
+    check(_target_twin("unet_argmax_countsk", target)(
+        _ptr(logits), _ptr(target), _ptr(preds), counts.data_ptr(), N, K, H, W, ignore_index,
         _stream()))
     return preds, counts
 
@@ -1260,16 +1238,11 @@ def argmax_classes(logits):
     N, K, H, W = logits.shape
     if logits.dtype != torch.float32:
         raise TypeError("argmax_classes takes fp32 logits")
-    if K != 3:
-        _check_classes(K, "argmax_classes")
+    _check_classes(K, "argmax_classes")
     logits = logits.contiguous()
     preds = torch.empty((N, H, W), dtype=torch.uint8, device=logits.device)
-    if K != 3:
-        check(lib().unet_argmax_countsk(_ptr(logits), None, _ptr(preds), None, N, K, H, W, 255,
-                                        _stream()))
-        return preds
-    check(lib().unet_argmax_dice_counts(_ptr(logits), None, _ptr(preds), None, N, H, W, 255,
-                                        _stream()))
+    check(lib().unet_argmax_countsk(_ptr(logits), None, _ptr(preds), None, N, K, H, W, 255,
+                                    _stream()))
     return preds
 
 
@@ -1312,12 +1285,8 @@ def eval_confusion(logits, target, dims=None, ignore_index=255):
             raise TypeError("dims must be an int64 [B, 2] tensor of (orig_h, orig_w)")
         dims = dims.contiguous()
     cm = torch.empty((B, K, K), dtype=torch.int64, device=logits.device)
-    if K != 3:
-        check(lib().unet_eval_confusionk(_ptr(logits), _ptr(target), _ptr(dims), cm.data_ptr(), B,
-                                         K, H, W, int(ignore_index), _stream()))
-        return cm
-    check(lib().unet_eval_confusion(_ptr(logits), _ptr(target), _ptr(dims), cm.data_ptr(), B, H,
-                                    W, int(ignore_index), _stream()))
+    check(lib().unet_eval_confusionk(_ptr(logits), _ptr(target), _ptr(dims), cm.data_ptr(), B, K,
+                                     H, W, int(ignore_index), _stream()))
     return cm
 
 

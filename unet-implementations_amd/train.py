@@ -194,14 +194,17 @@ def validate(model, val_loader, loss_function, device, ignore_label=255, input_l
     return (val_loss / n).item(), dice_scores(dice_sum, n)
 
 
+def class_names(K):
+    """The reference's names for its 3 classes, class_0 .. class_{K-1} otherwise."""
+    return ("background", "cat", "dog") if K == 3 else tuple(f"class_{c}" for c in range(K))
+
+
 def dice_scores(dice_sum, n):
-    """validate()'s score dictionary from the per-class sums of the batch Dice values: the
-    reference's background / cat / dog for 3 classes, class_0 .. class_{K-1} otherwise;
-    mean_foreground averages the classes 1 .. K-1 either way."""
+    """validate()'s score dictionary from the per-class sums of the batch Dice values, keyed by
+    `class_names`; mean_foreground averages the classes 1 .. K-1 either way."""
     d = [0.0] * 3 if dice_sum is None else (dice_sum / n).tolist()
     K = len(d)
-    names = ("background", "cat", "dog") if K == 3 else tuple(f"class_{c}" for c in range(K))
-    scores = dict(zip(names, d))
+    scores = dict(zip(class_names(K), d))
     scores["mean_foreground"] = sum(d[1:]) / (K - 1)
     return scores
 
