@@ -9,7 +9,9 @@ mode-independent kernel names and the step recorder.  Loaded by path like fp64_l
     network's walk makes it in that operand mode and returns a dict: names (the recorded kernel
     names), metrics (against a float64 evaluation of the same fp32 operands) and, where they
     apply, bad (metrics against an altered reference - the check of the check), term and eq32
-    (the split mode's verdicts);
+    (the split mode's verdicts); the forward runners take an operand generator (`gen`) for
+    tests/test_in_stats_fp64_gpu.py and then also return stats / stats_bad, the statistics
+    against those of the returned y per element (tests/tools/in_stats_refs.py, loaded as S);
   * Mode, the record a table hands to the runners: how one layer's weights are packed and which
     forms and keywords carry the mode into each entry point;
   * the kernel names and name builders more than one table uses;
@@ -33,6 +35,7 @@ def load(name, *where):
 
 
 R = load("fp64_layer_refs", "tools")
+S = load("in_stats_refs", "tools")
 DEV, SLOPE, EPS = R.DEV, R.SLOPE, R.EPS
 grand, coeffs, nchw64, act64, metric = R.grand, R.coeffs, R.nchw64, R.act64, R.metric
 
@@ -109,20 +112,64 @@ def fused_stats(y_ref, st, gamma, beta, mask):
                    scale=scale)]
 
 
+def operand(gen, kind, shape, seed, scale=1.0):
+    """A forward runner's operand: grand(shape, seed, scale) for the rows of the tables; with an
+    operand generator (tests/test_in_stats_fp64_gpu.py) gen(kind, shape, seed), kind = "source"
+    (an NHWC layer tensor) or "bias"."""
+    return grand(shape, seed, scale) if gen is None else gen(kind, shape, seed)
+
+
+def structured(kind, shape, seed, dev=None):
+    """The operand generator of the statistics tests: sources whose channels cycle over the plane
+    families corner, ramp and halves (low noise, levels that differ per image and channel), and a
+    bias with per-channel offsets up to +-30, which puts every plane of y far from 0.  (The
+    runners' y metric is relative to max |y_ref|, ~30 here: y is held ~30 x looser in absolute
+    terms than by the tables' own rows, which still hold it; these cases are about the
+    statistics.)  dev: "cpu" for tests/test_in_stats_refs_cpu.py."""
+    dev = DEV if dev is None else dev
+    if kind == "bias":
+        g = torch.Generator(device=dev).manual_seed(seed)
+        return (torch.rand(shape, generator=g, device=dev) * 60.0 - 30.0).contiguous()
+    c = torch.arange(shape[3], device=dev) % 3
+    planes = [S.FAMILIES[f](*shape, seed, dev) for f in ("corner", "ramp", "halves")]
+    return torch.where(c == 0, planes[0], torch.where(c == 1, planes[1], planes[2])).contiguous()
+
+
+def returned_stats(y, st, gamma, beta, mask, perturb=None):
+    """The statistics st against the fp64 statistics of THE y THE CALL RETURNED (so that the
+    convolution's rounding does not enter), element by element (in_stats_refs.compare).
+    perturb: the check of the check - the reference from perturb(y)."""
+    ref = S.plane_stats(y if perturb is None else perturb(y), gamma, beta, mask)
+    return S.compare(st, ref, S.plane_max(y))
+
+
 # --------------------------------------------------------------------------- one runner per call
 # N, H, W: the layer's input grid.  drop_row = (image, row): the check of the check - the
 # reference is evaluated a second time with that row zeroed (input row for a forward, dy row for
 # gradients) and the metrics against it come back as out["bad"].  x3 (read where mode.term is
 # set): the split kernel runs; else an fp32 kernel behind the same entry.
-def run_fwd(ua, mode, N, H, W, C0, C1, Cout, stride, plain0=False, x3=True, drop_row=None):
+# gen (forward runners): an operand generator (`operand` above) instead of the tables' Gaussian
+# operands; the result then also carries out["stats"], the statistics against those of the
+# returned y per element, and out["stats_bad"], the same against two altered references: the last
+# image's first 8 x 32 tile of y replaced by the tile next to it, and its first 8 rows zeroed.
+def _with_returned_stats(out, gen, y, st, gamma, beta, mask):
+    if gen is not None:
+        out["stats"] = returned_stats(y, st, gamma, beta, mask)
+        out["stats_bad"] = [returned_stats(y, st, gamma, beta, mask, perturb=f)
+                            for f in (S.first_tile_replaced, S.rows_zeroed)]
+    return out
+
+
+def run_fwd(ua, mode, N, H, W, C0, C1, Cout, stride, plain0=False, x3=True, drop_row=None,
+            gen=None):
     """unet_conv_in_fwd[_wino | _bf16x3] as _Walk.run_layer_fused calls it: sources activated on
     load with per-image coefficients, the mode's weight form, dropout mask folded into alpha /
     beta.  plain0: the first source is a plain tensor (the materialised activated up-sampling of
     a decoder stage's first convolution in the split mode), the second the activated skip."""
-    x0, c0 = grand((N, H, W, C0), 1), (() if plain0 else coeffs(N, C0, 10))
-    x1, c1 = (grand((N, H, W, C1), 2), coeffs(N, C1, 20)) if C1 else (None, None)
+    x0, c0 = operand(gen, "source", (N, H, W, C0), 1), (() if plain0 else coeffs(N, C0, 10))
+    x1, c1 = (operand(gen, "source", (N, H, W, C1), 2), coeffs(N, C1, 20)) if C1 else (None, None)
     w = R.he_weight(Cout, C0 + C1, 3, 9 * (C0 + C1))
-    b, gamma, beta = grand((Cout,), 4, 0.3), grand((Cout,), 5) * 0.2 + 1.0, grand((Cout,), 6) * 0.2
+    b, gamma, beta = operand(gen, "bias", (Cout,), 4, 0.3), grand((Cout,), 5) * 0.2 + 1.0, grand((Cout,), 6) * 0.2
     mask = R.keep_mask(N, Cout, 7, 0.7)
     table = mode.pack(ua, w, stride)
     own = mode.forms(ua, "fwd", table, (N, H, W, C0, C1, Cout))
@@ -154,15 +201,15 @@ def run_fwd(ua, mode, N, H, W, C0, C1, Cout, stride, plain0=False, x3=True, drop
         a[drop_row[0], :, drop_row[1], :] = 0
         out["bad"] = [metric("y against the reference without one input row", nchw64(y),
                              R.ref_conv(a, wd_, bd, stride), TOL_Y)]
-    return out
+    return _with_returned_stats(out, gen, y, st, gamma, beta, mask)
 
 
-def run_stem_fwd(ua, mode, N, H, W):
+def run_stem_fwd(ua, mode, N, H, W, gen=None):
     """unet_conv_in_fwd on the plain RGB image (3 -> 32): no mode has a weight form for it (no
     Winograd form, no planes in the PackTable), so the walk makes the fp32 mode's call."""
-    x = grand((N, H, W, 3), 1)
+    x = operand(gen, "source", (N, H, W, 3), 1)
     w = R.he_weight(32, 3, 2, 27)
-    b, gamma, beta = grand((32,), 3, 0.1), grand((32,), 5) * 0.2 + 1.0, grand((32,), 6) * 0.2
+    b, gamma, beta = operand(gen, "bias", (32,), 3, 0.1), grand((32,), 5) * 0.2 + 1.0, grand((32,), 6) * 0.2
     mask = torch.ones(N, 32, device=DEV)
     table = mode.pack(ua, w, 1)
     own = mode.forms(ua, "fwd", table, (N, H, W, 3, 0, 32))
@@ -171,17 +218,18 @@ def run_stem_fwd(ua, mode, N, H, W):
         y, st = ua.ops.conv_in_fwd(ua.ops.Act(x), None, SLOPE, table.wf[0], b, 3, 1, gamma, beta,
                                    EPS, None, **own)
     y_ref = R.ref_conv(nchw64(x), w.double(), b.double(), 1)
-    return dict(names=rec.names, metrics=[metric("y", nchw64(y), y_ref, TOL_Y)] +
-                fused_stats(y_ref, st, gamma, beta, mask))
+    out = dict(names=rec.names, metrics=[metric("y", nchw64(y), y_ref, TOL_Y)] +
+               fused_stats(y_ref, st, gamma, beta, mask))
+    return _with_returned_stats(out, gen, y, st, gamma, beta, mask)
 
 
-def run_up_fwd(ua, mode, N, h, w, C0, C1, Cout):
+def run_up_fwd(ua, mode, N, h, w, C0, C1, Cout, gen=None):
     """unet_conv_up_in_fwd / _wino as _Walk.run_up_layer calls it: bilinear 2x up-sampling of the
     activated low-resolution source [N, h, w, C0] in the loader, activated skip [N, 2h, 2w, C1]."""
-    low, cl = grand((N, h, w, C0), 1), coeffs(N, C0, 10)
-    skip, cs = grand((N, 2 * h, 2 * w, C1), 2), coeffs(N, C1, 20)
+    low, cl = operand(gen, "source", (N, h, w, C0), 1), coeffs(N, C0, 10)
+    skip, cs = operand(gen, "source", (N, 2 * h, 2 * w, C1), 2), coeffs(N, C1, 20)
     wt = R.he_weight(Cout, C0 + C1, 3, 9 * (C0 + C1))
-    b, gamma, beta = grand((Cout,), 4, 0.3), grand((Cout,), 5) * 0.2 + 1.0, grand((Cout,), 6) * 0.2
+    b, gamma, beta = operand(gen, "bias", (Cout,), 4, 0.3), grand((Cout,), 5) * 0.2 + 1.0, grand((Cout,), 6) * 0.2
     mask = R.keep_mask(N, Cout, 7, 0.7)
     table = mode.pack(ua, wt, 1)
     s_low, s_skip = ua.ops.Act(low, *cl), ua.ops.Act(skip, *cs)
@@ -193,8 +241,9 @@ def run_up_fwd(ua, mode, N, h, w, C0, C1, Cout):
                                           mask, **own)
     a = torch.cat([R.upsample64(act64(low, *cl)), act64(skip, *cs)], 1)
     y_ref = R.ref_conv(a, wt.double(), b.double(), 1)
-    return dict(names=rec.names, metrics=[metric("y", nchw64(y), y_ref, TOL_Y)] +
-                fused_stats(y_ref, st, gamma, beta, mask))
+    out = dict(names=rec.names, metrics=[metric("y", nchw64(y), y_ref, TOL_Y)] +
+               fused_stats(y_ref, st, gamma, beta, mask))
+    return _with_returned_stats(out, gen, y, st, gamma, beta, mask)
 
 
 def run_dgrad(ua, mode, N, H, W, Cin, Cout, stride, nxt=False, acc=False, ci_off=0, cin_total=None,

@@ -28,6 +28,14 @@ __host__ __device__ inline int split_for(int N, int HW, int C) {
 
 // ---------------------------------------------------------------- statistics
 // grid (split, N); partial[n][s][c] = (mean, M2), count implied by the pixel range.
+// The merges of chunk and lane means are first order in the rounding of those means, an ulp of
+// |mean|: on a block far from 0 (|mean| / std = R) M2 comes out wrong by ~7e-8 R relative, which
+// many pixels per lane average away and few do not (2 x 2 pixels at R = 5000: rstd to 1.7e-4).
+// So on a block of at most 64 pixels the thread that merges a channel tests R: above 64 (~2e-6
+// in rstd) it forms the block's M2 again in one pass around the merged mean, M2 = sum(d^2) -
+// (sum d)^2 / n with d = y - mean (the second term is a correction of rounding size, nothing
+// cancels): at most 64 loads.  Larger blocks average the error by ~sqrt(8 / n): measured 6e-6 in
+// rstd at R = 1000 on 77 pixels.
 template <typename TS>
 __global__ __launch_bounds__(kThreads) void in_stats_kernel(const TS* __restrict__ y,
                                                             float2* __restrict__ partial, int HW,
@@ -96,6 +104,18 @@ __global__ __launch_bounds__(kThreads) void in_stats_kernel(const TS* __restrict
     float n0 = 0.f, mu = 0.f, q = 0.f;
     for (int g = 0; g < groups; ++g)
       wf_merge(n0, mu, q, sm_cnt[g * lpp + (c >> 2)], sm_mean[g * C + c], sm_m2[g * C + c]);
+    if (n0 <= 64.f && q > 0.f && mu * mu * n0 > 4096.f * q) {
+      const TS* col = y + (size_t)n * HW * C + c;
+      float s1 = 0.f, s2 = 0.f;
+      for (int p = p_begin; p < p_end; ++p) {
+        const float d = (float)col[(size_t)p * C] - mu;
+        s1 += d;
+        s2 = fmaf(d, d, s2);
+      }
+      const float dm = s1 / n0;
+      q = fmaxf(s2 - s1 * dm, 0.f);
+      mu += dm;
+    }
     partial[((size_t)n * split + s) * C + c] = float2{mu, q};
   }
 }
@@ -207,8 +227,17 @@ __global__ __launch_bounds__(32 * FL) void in_stats_finalize_eq_kernel(
 // merge above would run on C/32 x N blocks only.  Two launches instead: G groups of tiles per
 // (image, 32 channels) reduce shifted sums
 //   S1 = sum(mean_t - K),  S2 = sum(M2_t + per (mean_t - K)^2),   K = mean of tile 0
-// (the tile means cluster around the channel mean, so the final subtraction
-// M2 = S2 - tiles per (S1/tiles)^2 cancels nothing of size), then one small kernel combines.
+// then one small kernel combines: M2 = S2 - tiles per (S1/tiles)^2.  Where the tile means cluster
+// around the channel mean that subtraction cancels nothing of size, and every rounding error of
+// the sums is a few ulp of S2.  That is an assumption about the plane (a bright image corner over
+// a flat background breaks it: tile 0 lies far from the mean, S2 >> M2, and rstd lost four
+// digits), so the combine kernel tests it.  S1 and S2 each carry a few eps of relative rounding
+// error (lane sums of <= 8 terms, a 5-level tree, 16 groups) and M2 inherits that of S2
+// magnified by S2 / M2 = 1 + (K - mean)^2 / var: while S2 <= 16 M2 (tile 0 within 3.9 standard
+// deviations of the plane mean) the shifted result stands, good to ~1e-6 in rstd; otherwise the
+// plane's wave merges its summaries again the way in_stats_finalize_eq_kernel does, mean =
+// avg(mean_t), M2 = sum(M2_t) + per sum((mean_t - mean)^2), 64 lanes striding over the tiles and
+// a fixed butterfly (2 x tiles / 64 loads per lane).  Deterministic either way.
 constexpr int kFinGroups = 16;
 __global__ __launch_bounds__(32 * FL) void in_stats_finalize_grp_kernel(
     const float2* __restrict__ partial, float2* __restrict__ grp, int C, int tiles, float per) {
@@ -237,26 +266,51 @@ __global__ __launch_bounds__(32 * FL) void in_stats_finalize_grp_kernel(
   if (l == 0 && c < C) grp[((size_t)n * kFinGroups + g) * C + c] = float2{sa[0][cl], sb[0][cl]};
 }
 
+// block = 4 waves, one (image, channel) plane per wave.  Every lane forms the sums of the 16 groups
+// in group order (the order a single thread would use), so the test below is uniform over the
+// wave; where it fails the wave's 64 lanes stride over the plane's summaries together.
+__device__ __forceinline__ float wave_sum(float v) {   // xor butterfly: the same bits on every lane
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
 __global__ __launch_bounds__(256) void in_stats_finalize_comb_kernel(
     const float2* __restrict__ partial, const float2* __restrict__ grp,
     const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
     const float* __restrict__ mask, float* __restrict__ mean, float* __restrict__ rstd,
     float* __restrict__ alpha, float* __restrict__ beta2, int N, int HW, int C, int tiles,
     float per) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= N * C) return;
   const int n = i / C, c = i - n * C;
+  float2 mine = {0.f, 0.f};
+  if (lane < kFinGroups) mine = grp[((size_t)n * kFinGroups + lane) * C + c];
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int g = 0; g < kFinGroups; ++g) {
-    const float2 v = grp[((size_t)n * kFinGroups + g) * C + c];
-    s1 += v.x;
-    s2 += v.y;
+    s1 += __shfl(mine.x, g);
+    s2 += __shfl(mine.y, g);
   }
-  const float K = partial[(size_t)n * tiles * C + c].x;
+  const float2* src = partial + (size_t)n * tiles * C + c;
+  const float K = src[0].x;
   const float d = s1 / (float)tiles;
-  const float mu = K + d;
-  const float q = s2 - (float)tiles * per * d * d;
+  float mu = K + d;
+  float q = s2 - (float)tiles * per * d * d;
+  if (!(s2 <= 16.f * q)) {   // the shift was a bad origin for this plane (also: q < 0, NaN)
+    float a = 0.f;
+    for (int t = lane; t < tiles; t += 64) a += src[(size_t)t * C].x;
+    mu = wave_sum(a) / (float)tiles;
+    a = 0.f;
+    for (int t = lane; t < tiles; t += 64) {
+      const float2 v = src[(size_t)t * C];
+      const float dd = v.x - mu;
+      a += fmaf(per * dd, dd, v.y);
+    }
+    q = wave_sum(a);
+  }
+  if (lane != 0) return;
   const float var = fmaxf(q, 0.f) / (float)HW;
   const float rs = 1.0f / sqrtf(var + eps);
   mean[i] = mu;
@@ -530,7 +584,7 @@ int unet_in_finalize_tiles(const void* partial, int tiles, int px_per_tile, cons
                        dim3(32 * FL), 0, stream, reinterpret_cast<const float2*>(partial), grp, C,
                        tiles, (float)px_per_tile);
     UNET_CHECK_LAUNCH("in_stats_finalize(groups)");
-    hipLaunchKernelGGL(in_stats_finalize_comb_kernel, dim3(ceil_div(N * C, 256)), dim3(256), 0,
+    hipLaunchKernelGGL(in_stats_finalize_comb_kernel, dim3(ceil_div(N * C, 4)), dim3(256), 0,
                        stream, reinterpret_cast<const float2*>(partial), grp, gamma, beta, eps, mask,
                        mean, rstd, alpha, beta2, N, HW, C, tiles, (float)px_per_tile);
     UNET_CHECK_LAUNCH("in_stats_finalize(combine)");
