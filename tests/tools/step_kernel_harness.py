@@ -12,6 +12,10 @@ mode-independent kernel names and the step recorder.  Loaded by path like fp64_l
     (the split mode's verdicts); the forward runners take an operand generator (`gen`) for
     tests/test_in_stats_fp64_gpu.py and then also return stats / stats_bad, the statistics
     against those of the returned y per element (tests/tools/in_stats_refs.py, loaded as S);
+    the runners whose call ends in the InstanceNorm backward (run_dgrad with nxt, run_up_dgrad,
+    run_head_bwd, run_in_bwd) take one for tests/test_in_bwd_fp64_gpu.py and then also return
+    bwd / bwd_bad, the reductions and dz per plane and per element against the fp64 formulas on
+    the g the call returned (tests/tools/in_bwd_refs.py, loaded as B);
   * Mode, the record a table hands to the runners: how one layer's weights are packed and which
     forms and keywords carry the mode into each entry point;
   * the kernel names and name builders more than one table uses;
@@ -36,6 +40,7 @@ def load(name, *where):
 
 R = load("fp64_layer_refs", "tools")
 S = load("in_stats_refs", "tools")
+B = load("in_bwd_refs", "tools")
 DEV, SLOPE, EPS = R.DEV, R.SLOPE, R.EPS
 grand, coeffs, nchw64, act64, metric = R.grand, R.coeffs, R.nchw64, R.act64, R.metric
 
@@ -143,6 +148,94 @@ def returned_stats(y, st, gamma, beta, mask, perturb=None):
     return S.compare(st, ref, S.plane_max(y))
 
 
+def structured_norm(n, H, W, C, seed, dev=None):
+    """The layer a BSTATS epilogue reduces for, on structured planes: y whose channels cycle over
+    corner / ramp / halves / offset, its fp64 statistics rounded once (st [4, n, C] like
+    R.norm_layer's), gamma, beta and a dropout mask with a 0 entry and a keep scale of 1 / 0.7
+    (B.affine) -> dict(y, st, gamma, beta, mask)."""
+    dev = DEV if dev is None else dev
+    c = torch.arange(C, device=dev) % 4
+    planes = [S.FAMILIES[f](n, H, W, C, seed, dev) for f in ("corner", "ramp", "halves", "offset")]
+    y = torch.where(c == 0, planes[0], torch.where(c == 1, planes[1],
+                                                   torch.where(c == 2, planes[2], planes[3]))).contiguous()
+    gamma, beta, mask = B.affine(n, C, seed + 1, dev)
+    ref = S.plane_stats(y)
+    al = gamma.double()[None] * ref["rstd"]
+    st = torch.stack([ref["mean"], ref["rstd"], al, beta.double()[None] - ref["mean"] * al])
+    return dict(y=y, st=st.float().contiguous(), gamma=gamma, beta=beta, mask=mask)
+
+
+def structured_bwd(kind, shape, seed, dev=None):
+    """The operand generator of the InstanceNorm-backward tests: kind = "norm" -> structured_norm
+    (shape = (n, H, W, C)); kind = "grad" -> an NHWC gradient whose channels cycle over the
+    families level / corner / signed_tiles / gauss of in_bwd_refs.py, so that the data gradient
+    formed from it has a level per plane, a corner and tiles that cancel.  dev: "cpu" for
+    tests/test_in_bwd_refs_cpu.py."""
+    dev = DEV if dev is None else dev
+    if kind == "norm":
+        return structured_norm(*shape, seed, dev)
+    c = torch.arange(shape[3], device=dev) % 4
+    planes = [B.G_FAMILIES[f](*shape, seed, dev) for f in ("level", "corner", "signed_tiles", "gauss")]
+    return torch.where(c == 0, planes[0], torch.where(c == 1, planes[1],
+                                                      torch.where(c == 2, planes[2], planes[3]))).contiguous()
+
+
+def next_norm_of(ua, gen, n, H, W, C, seed):
+    """The NextNorm of a backward runner: R.norm_layer's for the rows of the tables, gen("norm",
+    ...)'s with an operand generator"""
+    if gen is None:
+        return next_norm(ua, n, H, W, C, seed)
+    d = gen("norm", (n, H, W, C), seed)
+    return ua.ops.NextNorm(d["y"], d["st"], d["gamma"], d["beta"], d["mask"], SLOPE)
+
+
+def _in_bwd_call(ua, g, nn, partials):
+    C = nn.y.shape[3]
+    dg, db, dbias = (torch.empty(C, device=g.device) for _ in range(3))
+    dz = ua.ops.instnorm_lrelu_drop_bwd(g.clone(), nn.y, nn.st[0], nn.st[1], nn.gamma, nn.beta,
+                                        nn.mask, SLOPE, dg, db, dbias, partials=partials)
+    return dict(dz=dz, dgamma=dg, dbeta=db, dbias=dbias)
+
+
+def bwd_results(ua, g, nn, routes=("partial", "fed", "reduce")):
+    """What the InstanceNorm backward of the layer nn makes of the gradient g, by route:
+      partial  the per-tile summaries the producer's epilogue left, summed over the tiles in fp64;
+      fed      instnorm_lrelu_drop_bwd(partials=...): dz, dgamma, dbeta, dbias, and the merged
+               (S1, S2) of instnorm_bwd_merge_partials;
+      reduce   the same from the stand-alone reduction pass (no S1, S2: the call keeps them in
+               its workspace)."""
+    N, H, W, C = nn.y.shape
+    out = {}
+    if "partial" in routes or "fed" in routes:
+        assert nn.tiles > 0, "no BSTATS epilogue ran"
+    if "partial" in routes:
+        part = nn.partial.view(torch.float32)[:N * nn.tiles * C * 2].reshape(N, nn.tiles, C, 2)
+        out["partial"] = dict(sums=part.double().sum(dim=1))
+    if "fed" in routes:
+        out["fed"] = _in_bwd_call(ua, g, nn, (nn.partial, nn.tiles))
+        out["fed"]["sums"] = ua.ops.instnorm_bwd_merge_partials(nn.partial, nn.tiles, N, H * W, C)[1]
+    if "reduce" in routes:
+        out["reduce"] = _in_bwd_call(ua, g, nn, None)
+    return out
+
+
+def _with_bwd(out, gen, ua, g, nn, routes=("partial", "fed", "reduce"), results=None):
+    """out["bwd"] = {route: metrics of in_bwd_refs.compare} against the fp64 formulas on THE g THE
+    CALL RETURNED (so that the convolution's rounding does not enter) and nn's y and statistics;
+    out["bwd_bad"] = {altered reference: the metrics of the first route against it}."""
+    if gen is None:
+        return out
+    c = dict(g=g, y=nn.y, mean=nn.st[0], rstd=nn.st[1], gamma=nn.gamma, beta=nn.beta, mask=nn.mask)
+    got = bwd_results(ua, g, nn, routes) if results is None else results
+    ref = B.reference(g, nn.y, nn.st[0], nn.st[1], nn.gamma, nn.beta, nn.mask, SLOPE)
+    out["bwd"] = {route: B.compare(r, ref) for route, r in got.items()}
+    out["ties"] = B.tie_count(ref)
+    del ref
+    first = got["fed" if "fed" in got else next(iter(got))]
+    out["bwd_bad"] = {kind: B.compare(first, B.altered(kind, c, SLOPE)) for kind in B.ALTERED}
+    return out
+
+
 # --------------------------------------------------------------------------- one runner per call
 # N, H, W: the layer's input grid.  drop_row = (image, row): the check of the check - the
 # reference is evaluated a second time with that row zeroed (input row for a forward, dy row for
@@ -158,6 +251,12 @@ def _with_returned_stats(out, gen, y, st, gamma, beta, mask):
         out["stats_bad"] = [returned_stats(y, st, gamma, beta, mask, perturb=f)
                             for f in (S.first_tile_replaced, S.rows_zeroed)]
     return out
+
+
+# gen (the runners that end in the InstanceNorm backward): an operand generator of kinds "norm"
+# and "grad" (structured_bwd).  The NextNorm then comes from gen("norm", ...), dy / D / dlogits
+# from gen("grad", ...), and the result also carries out["bwd"], out["bwd_bad"] and out["ties"]
+# (_with_bwd above).  With gen=None nothing changes.
 
 
 def run_fwd(ua, mode, N, H, W, C0, C1, Cout, stride, plain0=False, x3=True, drop_row=None,
@@ -247,7 +346,7 @@ def run_up_fwd(ua, mode, N, h, w, C0, C1, Cout, gen=None):
 
 
 def run_dgrad(ua, mode, N, H, W, Cin, Cout, stride, nxt=False, acc=False, ci_off=0, cin_total=None,
-              x3=True, drop_row=None):
+              x3=True, drop_row=None, gen=None):
     """unet_conv3x3_bwd_data[_bs][_wino | _bf16x3] as _Walk.layer_bwd calls it: dx[N, H, W, Cin]
     (+)= the data gradient of dy for input channels [ci_off, ci_off + Cin) of a layer with
     cin_total inputs; nxt = with the BSTATS epilogue; acc = accumulate into the gradient the
@@ -256,10 +355,10 @@ def run_dgrad(ua, mode, N, H, W, Cin, Cout, stride, nxt=False, acc=False, ci_off
     (Cout, Cin))."""
     cin_total = cin_total or Cin
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    dy = grand((N, Ho, Wo, Cout), 1)
+    dy = grand((N, Ho, Wo, Cout), 1) if gen is None else gen("grad", (N, Ho, Wo, Cout), 1)
     w = R.he_weight(Cout, cin_total, 2, 9 * Cout)
     base = grand((N, H, W, Cin), 3) if acc else None
-    nn = next_norm(ua, N, H, W, Cin, 10) if nxt else None
+    nn = next_norm_of(ua, gen, N, H, W, Cin, 10) if nxt else None
     table = mode.pack(ua, w, stride)
     own = mode.forms(ua, "dgrad", table, (N, H, W, Cout, 0, Cin), bool(cin_total == Cin or ci_off))
     same32 = mode.term is not None and not x3
@@ -297,7 +396,7 @@ def run_dgrad(ua, mode, N, H, W, Cin, Cout, stride, nxt=False, acc=False, ci_off
         dyd[drop_row[0], :, drop_row[1], :] = 0
         bad = R.ref_dgrad(dyd, wsl, stride, H, W) + (nchw64(base) if acc else 0)
         out["bad"] = [metric("dx against the reference without one dy row", nchw64(dx), bad, TOL_DX)]
-    return out
+    return _with_bwd(out, gen if nxt else None, ua, dx, nn)
 
 
 def run_wgrad(ua, mode, N, H, W, Cx, Cout, stride, ci_off=0, cin_total=None, x3=True, drop_row=None):
@@ -381,21 +480,22 @@ def run_up_wgrad(ua, mode, N, h, w, Cx, Cout, cin_total):
     return dict(names=rec.names, metrics=[metric("dw", dw[:, :Cx], ref, TOL_UP)])
 
 
-def run_up_dgrad(ua, mode, N, h, w, C0, Cout, cin_total):
+def run_up_dgrad(ua, mode, N, h, w, C0, Cout, cin_total, gen=None):
     """unet_conv3x3_up_bwd_data_bs: the low-resolution data gradient of the up-sampled operand as a
     GEMM g = D B (fp32 D: no mode passes a weight form), with the BSTATS epilogue of the layer
     that produced the low-resolution tensor."""
     wt = R.he_weight(Cout, cin_total, 3, 9 * Cout)
     table = mode.pack(ua, wt, 1)
-    D = grand((N, h, w, 9 * Cout), 5)
-    nn = next_norm(ua, N, h, w, C0, 20)
+    D = grand((N, h, w, 9 * Cout), 5) if gen is None else gen("grad", (N, h, w, 9 * Cout), 5)
+    nn = next_norm_of(ua, gen, N, h, w, C0, 20)
     with ua.ops.record_launches() as rec:
         g = ua.ops.conv3x3_up_bwd_data(D, table.wd[0], 0, C0, nxt=nn,
                                        **mode.forms(ua, "up_dgrad", table))
     ref = R.ref_up_dgrad(D.double(), wt.double()[:, :C0])
     plain = ua.ops.conv3x3_up_bwd_data(D, table.wd[0], 0, C0)
     assert torch.equal(plain, g), "the BSTATS epilogue changed the gradient"
-    return dict(names=rec.names, metrics=[metric("g", g, ref, TOL_UP)] + summaries(ua, g, nn))
+    out = dict(names=rec.names, metrics=[metric("g", g, ref, TOL_UP)] + summaries(ua, g, nn))
+    return _with_bwd(out, gen, ua, g, nn)
 
 
 def run_head_fwd(ua, mode, N, H, W):
@@ -408,13 +508,14 @@ def run_head_fwd(ua, mode, N, H, W):
     return dict(names=rec.names, metrics=[metric("logits", logits, ref, TOL_HEAD_X)])
 
 
-def run_head_bwd(ua, mode, N, H, W):
+def run_head_bwd(ua, mode, N, H, W, gen=None):
     """unet_head1x1_in_bwd_bs: da = W^T dlogits, dW, db and the InstanceNorm-backward reductions
     of the last decoder layer (whose raw output the head reads)."""
-    nn = next_norm(ua, N, H, W, 32, 60)
+    nn = next_norm_of(ua, gen, N, H, W, 32, 60)
     al, be = (nn.st[2] * nn.mask).contiguous(), (nn.st[3] * nn.mask).contiguous()
     x = ua.ops.Act(nn.y, al, be)
-    dl = grand((N, 3, H, W), 2)
+    dl = grand((N, 3, H, W), 2) if gen is None else \
+        gen("grad", (N, H, W, 3), 2).permute(0, 3, 1, 2).contiguous()
     w = grand((3, 32), 3, 0.2)
     dw, db = torch.empty(3, 32, device=DEV), torch.empty(3, device=DEV)
     with ua.ops.record_launches() as rec:
@@ -423,30 +524,43 @@ def run_head_bwd(ua, mode, N, H, W):
     metrics = [metric("da", nchw64(da), torch.einsum("nkhw,kc->nchw", dld, w.double()), TOL_HEAD_X),
                metric("dw", dw, torch.einsum("nkhw,nchw->kc", dld, a), TOL_HEAD),
                metric("db", db, dld.sum(dim=(0, 2, 3)), TOL_HEAD)]
-    return dict(names=rec.names, metrics=metrics + summaries(ua, da, nn))
+    return _with_bwd(dict(names=rec.names, metrics=metrics + summaries(ua, da, nn)), gen, ua, da, nn)
 
 
-def run_in_bwd(ua, mode, N, H, W, C, fed):
+def run_in_bwd(ua, mode, N, H, W, C, fed, gen=None):
     """unet_instnorm_lrelu_drop_bwd[_partials]: InstanceNorm + LeakyReLU + dropout backward
     against fp64 autograd.  fed: the reductions come as BSTATS summaries of the producer of g (here
     the stand-alone up data gradient with Cout = 32), as in the step; else the stand-alone
-    reduction pass runs."""
-    y, st, gamma, beta, mask = R.norm_layer(N, H, W, C, 70)
+    reduction pass runs.  With gen the call is held by out["bwd"] alone (route "fed", with the
+    epilogue's own summaries as "partial", or "reduce"): the max-norm comparison with autograd
+    through recomputed statistics is not one structured planes can be held by."""
+    if gen is None:
+        y, st, gamma, beta, mask = R.norm_layer(N, H, W, C, 70)
+        nn = ua.ops.NextNorm(y, st, gamma, beta, mask, SLOPE)
+    else:
+        nn = next_norm_of(ua, gen, N, H, W, C, 70)
+        y, st, gamma, beta, mask = nn.y, nn.st, nn.gamma, nn.beta, nn.mask
     partials = None
     if fed:
-        nn = ua.ops.NextNorm(y, st, gamma, beta, mask, SLOPE)
         wt = R.he_weight(32, C, 3, 9 * 32)
-        g = ua.ops.conv3x3_up_bwd_data(grand((N, H, W, 9 * 32), 5), mode.pack(ua, wt, 1).wd[0], 0, C,
-                                       nxt=nn)
+        D = grand((N, H, W, 9 * 32), 5) if gen is None else gen("grad", (N, H, W, 9 * 32), 5)
+        g = ua.ops.conv3x3_up_bwd_data(D, mode.pack(ua, wt, 1).wd[0], 0, C, nxt=nn)
         assert nn.tiles > 0, "no BSTATS epilogue ran"
         partials = (nn.partial, nn.tiles)
     else:
-        g = grand((N, H, W, C), 71)
-    dz_ref, dg_ref, db_ref = R.ref_in_bwd(g, y, gamma, beta, mask)
+        g = grand((N, H, W, C), 71) if gen is None else gen("grad", (N, H, W, C), 71)
     dg, db, dbias = (torch.empty(C, device=DEV) for _ in range(3))
     with ua.ops.record_launches() as rec:
         dz = ua.ops.instnorm_lrelu_drop_bwd(g.clone(), y, st[0], st[1], gamma, beta, mask, SLOPE,
                                             dg, db, dbias, partials=partials)
+    if gen is not None:
+        route = dict(dz=dz, dgamma=dg, dbeta=db, dbias=dbias)
+        results = {"fed": route} if fed else {"reduce": route}
+        if fed:
+            results["partial"] = bwd_results(ua, g, nn, ("partial",))["partial"]
+            route["sums"] = ua.ops.instnorm_bwd_merge_partials(nn.partial, nn.tiles, N, H * W, C)[1]
+        return _with_bwd(dict(names=rec.names, metrics=[]), gen, ua, g, nn, results=results)
+    dz_ref, dg_ref, db_ref = R.ref_in_bwd(g, y, gamma, beta, mask)
     return dict(names=rec.names,
                 metrics=[metric("dz", dz, dz_ref, TOL_IN), metric("dgamma", dg, dg_ref, TOL_IN),
                          metric("dbeta", db, db_ref, TOL_IN),
