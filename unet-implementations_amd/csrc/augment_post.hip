@@ -318,39 +318,44 @@ __global__ __launch_bounds__(256) void post_apply_kernel(
 
 extern "C" int unet_augment_post_params_per_sample(void) { return POST; }
 
-extern "C" size_t unet_augment_post_workspace_bytes(int N) {
-  return N > 0 ? (size_t)N * (POST_COUNT_BYTES + POST_LUT_BYTES) : 0;
-}
-
 namespace {
+
+// workspace: counts [N][3][256] uint32 (zeroed by every hist call), then LUTs [N][64][256] bytes
+struct PostWs { unsigned* counts; unsigned char* luts; size_t bytes; };
+PostWs post_ws(void* base, int N) {
+  WsLayout l(base);
+  return {l.take<unsigned>((size_t)N * (POST_COUNT_BYTES / sizeof(unsigned)), 1),
+          l.take<unsigned char>((size_t)N * POST_LUT_BYTES, 1), l.bytes()};
+}
 
 // the checks and the launches of the three entry points: `hist` / `apply` name the kernels to run
 int post_launch(const char* name, bool hist, bool apply, const uint8_t* image, uint8_t* image_out,
                 const float* post, const uint32_t* rng, void* workspace, size_t workspace_bytes,
                 int N, int H, int W, hipStream_t stream) {
-  const size_t need = unet_augment_post_workspace_bytes(N);
+  const PostWs ws = post_ws(workspace, N > 0 ? N : 0);
   if (const int rc = aug_stage_check(name, "post", "blur", apply, image, image_out, post, POST, rng, workspace,
-                                     workspace_bytes, need, N, H, W))
+                                     workspace_bytes, ws.bytes, N, H, W))
     return rc;
-  // workspace: counts [N][3][256] uint32 (zeroed here, every call), then LUTs [N][64][256] bytes
-  unsigned* counts = static_cast<unsigned*>(workspace);
-  unsigned char* luts = static_cast<unsigned char*>(workspace) + (size_t)N * POST_COUNT_BYTES;
   if (hist) {
-    UNET_HIP_CALL(hipMemsetAsync(counts, 0, (size_t)N * POST_COUNT_BYTES, stream));
+    UNET_HIP_CALL(hipMemsetAsync(ws.counts, 0, (size_t)N * POST_COUNT_BYTES, stream));
     hipLaunchKernelGGL(post_hist_kernel, dim3(HIST_WG, N), dim3(256), 0, stream, image, post,
-                       counts, luts, H, W);
+                       ws.counts, ws.luts, H, W);
     UNET_CHECK_LAUNCH(name);
   }
   if (apply) {
     const dim3 grid((unsigned)ceil_div64(W, PT), (unsigned)ceil_div64(H, PT), N);
     hipLaunchKernelGGL(post_apply_kernel, grid, dim3(256), 0, stream, image, image_out, post, rng,
-                       counts, luts, H, W);
+                       ws.counts, ws.luts, H, W);
     UNET_CHECK_LAUNCH(name);
   }
   return UNET_OK;
 }
 
 }  // namespace
+
+extern "C" size_t unet_augment_post_workspace_bytes(int N) {
+  return N > 0 ? post_ws(nullptr, N).bytes : 0;
+}
 
 extern "C" int unet_augment_post_u8(const uint8_t* image, uint8_t* image_out, const float* post,
                                     const uint32_t* rng, void* workspace, size_t workspace_bytes,

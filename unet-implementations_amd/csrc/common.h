@@ -6,6 +6,7 @@
 #include <stdio.h>
 
 #include "../../include/unet_hip.h"
+#include "ws_layout.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -21,6 +22,15 @@ void unet_set_error(const char* fmt, ...);
       unet_set_error(__VA_ARGS__);     \
       return UNET_E_INVALID;           \
     }                                  \
+  } while (0)
+
+// ... and a workspace smaller than its layout: UNET_E_WORKSPACE
+#define UNET_REQUIRE_WS(have, need, ...) \
+  do {                                   \
+    if ((have) < (need)) {               \
+      unet_set_error(__VA_ARGS__);       \
+      return UNET_E_WORKSPACE;           \
+    }                                    \
   } while (0)
 
 #define UNET_CHECK_LAUNCH(name)                                              \
@@ -95,6 +105,13 @@ int unet_in_stats_masked(const float* y, const float* gamma, const float* beta, 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline long long ceil_div64(long long a, long long b) { return (a + b - 1) / b; }
+
+// The (coef, sums) pair unet_instnorm_bwd_merge_partials writes, [N][C] float2 each.  (The
+// elements of a braced list are evaluated in order: this and every layout built so rely on it.)
+struct InBwdPair { float2 *coef, *sums; };
+static inline InBwdPair in_bwd_pair(WsLayout& l, int N, int C) {
+  return {l.take<float2>((size_t)N * C, 256), l.take<float2>((size_t)N * C, 256)};
+}
 
 // ---- device helpers --------------------------------------------------------
 #ifdef __HIPCC__

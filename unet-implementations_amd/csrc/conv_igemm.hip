@@ -1575,19 +1575,24 @@ extern "C" int unet_conv1x1_bwd_data(const float* dy, const float* wT, int Cin_t
 // Replaces Conv2d + InstanceNorm2d of ConvBlock (Our_UNet/models/unet.py:101-134).
 // ---------------------------------------------------------------------------
 namespace {
-// statistics tiles hold at least 64 pixels (the smallest gather-GEMM tile)
-size_t stats_partial_bytes(int N, int HoWo, int Cout) {
-  return align_up((size_t)N * (size_t)ceil_div(HoWo, 64) * Cout * sizeof(float2), 256);
+// The per-tile summaries of the statistics epilogue (tiles hold at least 64 pixels), then the
+// group scratch of their finalize; a chunked call runs the stand-alone statistics pass in the
+// same buffer instead, so the size is the larger of this and the InstanceNorm workspace.
+struct ConvInWs { float2* stats; void* grp_scratch; size_t bytes; };
+ConvInWs conv_in_ws(void* base, int N, int HoWo, int Cout) {
+  WsLayout l(base);
+  ConvInWs w{l.take<float2>((size_t)N * ceil_div(HoWo, 64) * Cout, 256),
+             l.take<char>(unet_in_finalize_scratch_bytes(N, Cout), 256), l.bytes()};
+  const size_t in = unet_instnorm_workspace_bytes(N, HoWo, Cout);
+  if (in > w.bytes) w.bytes = in;
+  return w;
 }
 }  // namespace
 
 extern "C" size_t unet_conv_in_fwd_workspace_bytes(int N, int H, int W, int Cout, int stride) {
   if (N <= 0 || H <= 0 || W <= 0 || Cout <= 0 || stride < 1) return 0;
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-  const size_t a = stats_partial_bytes(N, Ho * Wo, Cout) +
-                   align_up(unet_in_finalize_scratch_bytes(N, Cout), 256);
-  const size_t b = unet_instnorm_workspace_bytes(N, Ho * Wo, Cout);
-  return a > b ? a : b;
+  return conv_in_ws(nullptr, N, Ho * Wo, Cout).bytes;
 }
 
 // The layer tensors (sources other than the fp32 RGB image, and y) are of the mode's element
@@ -1605,12 +1610,11 @@ static int conv_in_fwd_impl(const unet_act_src* s0, const unet_act_src* s1, floa
   UNET_REQUIRE(N > 0 && H > 0 && W > 0, "conv_in_fwd: bad shape");
   UNET_REQUIRE(Cout > 0 && Cout % 32 == 0, "conv_in_fwd: Cout %d must be a multiple of 32", Cout);
   const int C0 = s0->C, C1 = s1 ? s1->C : 0;
-  if (workspace_bytes < unet_conv_in_fwd_workspace_bytes(N, H, W, Cout, stride)) {
-    unet_set_error("conv_in_fwd: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
+  const ConvInWs ws =
+      conv_in_ws(workspace, N, ((H - 1) / stride + 1) * ((W - 1) / stride + 1), Cout);
+  UNET_REQUIRE_WS(workspace_bytes, ws.bytes, "conv_in_fwd: workspace too small");
   const bool b16 = m.b16_tensors();
-  float2* const stats = reinterpret_cast<float2*>(workspace);
+  float2* const stats = ws.stats;
   if (C0 == 3) {   // RGB stem: the image is a plain operand
     UNET_REQUIRE(C1 == 0 && stride == 1 && ksize == 3 && !s0->alpha,
                  "conv_in_fwd: the RGB stem is a plain stride-1 3x3 single source");
@@ -1710,12 +1714,12 @@ static int conv_in_stats_finalize_impl(const void* y, void* workspace, size_t wo
   UNET_REQUIRE(y && workspace && mean && rstd, "conv_in_stats_finalize: null pointer");
   UNET_REQUIRE(stats_px >= 0 && (stats_px == 0 || HoWo % stats_px == 0),
                "conv_in_stats_finalize: %d-pixel tiles do not cover %d pixels", stats_px, HoWo);
-  if (stats_px > 0)   // the group scratch sits behind the summaries in the workspace
-    return unet_in_finalize_tiles(workspace, HoWo / stats_px, stats_px, gamma, beta, eps, mask,
+  if (stats_px > 0) {
+    const ConvInWs ws = conv_in_ws(workspace, N, HoWo, Cout);
+    return unet_in_finalize_tiles(ws.stats, HoWo / stats_px, stats_px, gamma, beta, eps, mask,
                                   mean, rstd, alpha_out, beta_out, N, HoWo, Cout,
-                                  (hipStream_t)stream,
-                                  reinterpret_cast<char*>(workspace) +
-                                      stats_partial_bytes(N, HoWo, Cout));
+                                  (hipStream_t)stream, ws.grp_scratch);
+  }
   // (unet_in_stats_masked reads y by its element flag)
   return unet_in_stats_masked(static_cast<const float*>(y), gamma, beta, eps, mask, mean, rstd,
                               alpha_out, beta_out, workspace, workspace_bytes, N, HoWo, Cout,
@@ -1831,14 +1835,12 @@ static int stem_u8_fwd_impl(const uint8_t* image_hwc, const float* mean3, const 
   UNET_REQUIRE(N > 0 && H > 0 && W > 0 && W % STEM_ROW_PIX == 0 && Cout > 0 && Cout % 32 == 0,
                "stem_u8_fwd: needs W %% %d == 0 and Cout %% 32 == 0 (got W=%d Cout=%d)",
                STEM_ROW_PIX, W, Cout);
-  if (workspace_bytes < unet_conv_in_fwd_workspace_bytes(N, H, W, Cout, 1)) {
-    unet_set_error("stem_u8_fwd: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
+  const ConvInWs ws = conv_in_ws(workspace, N, H * W, Cout);
+  UNET_REQUIRE_WS(workspace_bytes, ws.bytes, "stem_u8_fwd: workspace too small");
   StemNorm nm;
   for (int c = 0; c < 3; ++c) { nm.mean[c] = mean3[c]; nm.std[c] = std3[c]; }
-  launch_stem_fwd_rows<unsigned char, TO>(image_hwc, wf, bias, y, N, H, W, Cout,
-                                          reinterpret_cast<float2*>(workspace), nm, stream);
+  launch_stem_fwd_rows<unsigned char, TO>(image_hwc, wf, bias, y, N, H, W, Cout, ws.stats, nm,
+                                          stream);
   UNET_CHECK_LAUNCH("conv_stem_fwd(u8)");
   *stats_px_out = STEM_ROW_PIX;
   return UNET_OK;
@@ -1935,13 +1937,11 @@ static int conv_up_in_fwd_impl(const char* who, const char* twin, const unet_act
                "%s: shape N=%d %dx%d (%d+%d)->%d has no fused-upsample tile (query "
                "unet_conv_up_in_fwd%s_supported and fall back to unet_upsample2x_in_fwd%s)",
                who, N, H, W, C0, C1, Cout, twin, twin);
-  if (workspace_bytes < unet_conv_in_fwd_workspace_bytes(N, H, W, Cout, 1)) {
-    unet_set_error("%s: workspace too small", who);
-    return UNET_E_WORKSPACE;
-  }
+  const ConvInWs ws = conv_in_ws(workspace, N, H * W, Cout);
+  UNET_REQUIRE_WS(workspace_bytes, ws.bytes, "%s: workspace too small", who);
   IgemmParams p = fwd_params(conv_src(low), conv_src(skip), slope, wf, bias, y, Batch{0, N, false},
                              H, W, Cout, 1, 3, true, m);
-  p.stats = reinterpret_cast<float2*>(workspace);
+  p.stats = ws.stats;
   int px = 0;
   const int rc = b16 ? launch_patch_b16_up_auto(p, stream, &px)
                      : launch_patch_up_auto(p, stream, &px);

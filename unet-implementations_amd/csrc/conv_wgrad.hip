@@ -2972,7 +2972,10 @@ static int conv_bwd_weight_impl(const WgradCall& c, hipStream_t stream) {
     if (rc != UNET_OK) return rc;
   }
   if (c.db) {
-    // the slab workspace is free again at this point of the stream; reuse its head as scratch
+    // the slab workspace is free again at this point of the stream; reuse its head as scratch.
+    // The stage of 64 x Cout floats fits `need`: over tests/data/wgrad_workspace_bytes.json x the
+    // entry points that take db x the c32 switch the smallest need is 15 stages
+    // (swept by tests/test_workspace_layout_cpu.py).
     const float* dy = static_cast<const float*>(c.dy);
     const long long M = (long long)c.N * c.Ho() * c.Wo();
     const int chunks = M >= 4096 ? 64 : 1;
@@ -3157,10 +3160,17 @@ extern "C" int unet_stem_u8_bwd_weight_b16(const uint8_t* image_hwc, const float
 // summaries are merged, then the weight gradient's loader reads g and y and evaluates
 // in_bwd_dz4.  dw has the bits of unet_instnorm_lrelu_drop_bwd_partials followed by the plain
 // stem weight gradient.  x: the fp32 image, or NULL with the uint8 image and its mean3 / std3.
+// Workspace of both folds: the layer's (coef, sums) pair, then the plain weight gradient's slabs.
+struct WgradFoldWs { InBwdPair pair; size_t slab_bytes; void* slabs; size_t bytes; };
+static WgradFoldWs wgrad_fold_ws(void* base, int N, int H, int W, int Cx, int Cout) {
+  const size_t slab_bytes = unet_conv3x3_bwd_weight_workspace_bytes(N, H, W, Cx, Cout, 1);
+  WsLayout l(base);
+  return {in_bwd_pair(l, N, Cout), slab_bytes, l.take<char>(slab_bytes, 1), l.bytes()};
+}
+
 extern "C" size_t unet_stem_in_bwd_weight_fold_workspace_bytes(int N, int H, int W, int Cout) {
   if (N <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-  return 2 * align_up((size_t)N * Cout * sizeof(float2), 256) +
-         unet_conv3x3_bwd_weight_workspace_bytes(N, H, W, 3, Cout, 1);
+  return wgrad_fold_ws(nullptr, N, H, W, 3, Cout).bytes;
 }
 
 extern "C" int unet_stem_in_bwd_weight_fold(const float* x, const uint8_t* image_hwc,
@@ -3178,19 +3188,14 @@ extern "C" int unet_stem_in_bwd_weight_fold(const float* x, const uint8_t* image
   UNET_REQUIRE(N > 0 && H > 0 && W > 0 && W % SW_PIX == 0 && Cout > 0 && Cout % 32 == 0,
                "stem_in_bwd_weight_fold: needs W %% %d == 0 and Cout %% 32 == 0 (got W=%d Cout=%d)",
                SW_PIX, W, Cout);
-  const size_t coef_b = align_up((size_t)N * Cout * sizeof(float2), 256);
-  if (workspace_bytes < 2 * coef_b) {
-    unet_set_error("stem_in_bwd_weight_fold: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
-  char* ws = reinterpret_cast<char*>(workspace);
+  const WgradFoldWs ws = wgrad_fold_ws(workspace, N, H, W, 3, Cout);
+  UNET_REQUIRE_WS(workspace_bytes, ws.bytes, "stem_in_bwd_weight_fold: workspace too small");
   StemNormW f{};
   f.y = y; f.mu = mean; f.rstd = rstd; f.gamma = gamma; f.beta = beta; f.mask = mask;
-  f.coef = reinterpret_cast<const float2*>(ws);
-  f.sums = reinterpret_cast<const float2*>(ws + coef_b);
+  f.coef = ws.pair.coef; f.sums = ws.pair.sums;
   f.dgamma = dgamma; f.dbeta = dbeta; f.dbias = dbias; f.slope = slope;
-  const int rc = unet_instnorm_bwd_merge_partials(partial, tiles, ws, ws + coef_b, N, H * W, Cout,
-                                                  stream);
+  const int rc = unet_instnorm_bwd_merge_partials(partial, tiles, ws.pair.coef, ws.pair.sums, N,
+                                                  H * W, Cout, stream);
   if (rc != UNET_OK) return rc;
   const float ms[6] = {image_hwc ? mean3[0] : 0.f, image_hwc ? mean3[1] : 0.f,
                        image_hwc ? mean3[2] : 0.f, image_hwc ? std3[0] : 1.f,
@@ -3198,7 +3203,7 @@ extern "C" int unet_stem_in_bwd_weight_fold(const float* x, const uint8_t* image
   WgradCall c;
   c.x = x; c.x_u8 = image_hwc; c.u8_mean_std = ms; c.dy = g; c.stem_fold = &f;
   c.dw = dw_oihw; c.Cin_total = 3;
-  c.workspace = ws + 2 * coef_b; c.workspace_bytes = workspace_bytes - 2 * coef_b;
+  c.workspace = ws.slabs; c.workspace_bytes = ws.slab_bytes;
   c.N = N; c.H = H; c.W = W; c.Cx = 3; c.Cout = Cout;
   return conv_bwd_weight_impl(c, (hipStream_t)stream);
 }
@@ -3220,8 +3225,7 @@ extern "C" int unet_conv_in_bwd_weight_fold32_supported(int N, int H, int W, int
 
 extern "C" size_t unet_conv_in_bwd_weight_fold32_workspace_bytes(int N, int H, int W) {
   if (N <= 0 || H <= 0 || W <= 0) return 0;
-  return 2 * align_up((size_t)N * 32 * sizeof(float2), 256) +
-         unet_conv3x3_bwd_weight_workspace_bytes(N, H, W, 32, 32, 1);
+  return wgrad_fold_ws(nullptr, N, H, W, 32, 32).bytes;
 }
 
 extern "C" int unet_conv_in_bwd_weight_fold32(const unet_act_src* x, float slope_x, float* g,
@@ -3241,25 +3245,20 @@ extern "C" int unet_conv_in_bwd_weight_fold32(const unet_act_src* x, float slope
                "Winograd weight gradient", N, H, W, x->C);
   UNET_REQUIRE(x->x != g && x->x != y, "conv_in_bwd_weight_fold32: g is rewritten in place and "
                "cannot be the layer's operand");
-  const size_t coef_b = align_up((size_t)N * 32 * sizeof(float2), 256);
-  if (workspace_bytes < 2 * coef_b) {
-    unet_set_error("conv_in_bwd_weight_fold32: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
-  char* ws = reinterpret_cast<char*>(workspace);
+  const WgradFoldWs ws = wgrad_fold_ws(workspace, N, H, W, 32, 32);
+  UNET_REQUIRE_WS(workspace_bytes, ws.bytes, "conv_in_bwd_weight_fold32: workspace too small");
   StemNormW f{};
   f.y = y; f.mu = mean; f.rstd = rstd; f.gamma = gamma; f.beta = beta; f.mask = mask;
-  f.coef = reinterpret_cast<const float2*>(ws);
-  f.sums = reinterpret_cast<const float2*>(ws + coef_b);
+  f.coef = ws.pair.coef; f.sums = ws.pair.sums;
   f.dgamma = dgamma; f.dbeta = dbeta; f.dbias = dbias; f.slope = slope;
-  const int rc = unet_instnorm_bwd_merge_partials(partial, tiles, ws, ws + coef_b, N, H * W, 32,
-                                                  stream);
+  const int rc = unet_instnorm_bwd_merge_partials(partial, tiles, ws.pair.coef, ws.pair.sums, N,
+                                                  H * W, 32, stream);
   if (rc != UNET_OK) return rc;
   WgradCall c;
   set_source(c, x, slope_x);
   c.dy = g; c.fold32 = &f;
   c.dw = dw_oihw; c.ci_offset = ci_offset; c.Cin_total = Cin_total;
-  c.workspace = ws + 2 * coef_b; c.workspace_bytes = workspace_bytes - 2 * coef_b;
+  c.workspace = ws.slabs; c.workspace_bytes = ws.slab_bytes;
   c.N = N; c.H = H; c.W = W; c.Cout = 32;
   return conv_bwd_weight_impl(c, (hipStream_t)stream);
 }
@@ -3289,10 +3288,8 @@ static int up_bwd_weight_impl(const WgradCall& c, hipStream_t stream) {
   const WgradSel sel = wgrad_select(c, 0);
   UNET_REQUIRE(sel.nmax >= 1, "conv3x3_up_bwd_weight: one image exceeds the 2 GiB buffer-descriptor range");
   const size_t need = wgrad_ws_floats(c, sel) * sizeof(float);
-  if (c.workspace_bytes < need) {
-    unet_set_error("conv3x3_up_bwd_weight: workspace %zu < %zu bytes", c.workspace_bytes, need);
-    return UNET_E_WORKSPACE;
-  }
+  UNET_REQUIRE_WS(c.workspace_bytes, need,
+                  "conv3x3_up_bwd_weight: workspace %zu < %zu bytes", c.workspace_bytes, need);
   float* ws = reinterpret_cast<float*>(c.workspace);
   int nslab = 0;
   const int rc = wgrad_launch_chunks(c, sel, ws, &nslab, stream);

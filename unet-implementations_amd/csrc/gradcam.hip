@@ -42,8 +42,13 @@ int gc_map_per(int N, int HW) {
 }
 int gc_map_tiles(int N, int HW) { return ceil_div(HW, gc_map_per(N, HW)); }
 
-size_t gc_minmax_bytes(int N, int HW) {
-  return align_up((size_t)N * gc_map_tiles(N, HW) * sizeof(float2), 256);
+// The (min, max) pairs the map launch leaves per tile and image, then the slabs of the channel
+// means.  C == 0: the prefix the map and heatmap launches use (the heatmap is not told C).
+struct GcWs { float2* minmax; float* partial; size_t bytes; };
+GcWs gc_ws(void* base, int N, int HW, int C) {
+  WsLayout l(base);
+  return {l.take<float2>((size_t)N * gc_map_tiles(N, HW), 256),
+          C ? l.take<float>((size_t)N * gc_weight_slabs(N, HW, C) * C, 256) : nullptr, l.bytes()};
 }
 
 // level 1 of w = mean_p G: grid (slabs, N); lanes across the channels (4 each), the workgroup's
@@ -230,8 +235,7 @@ int launch_map(const unet_act_src* a, float slope, const float* w, float* cam, f
 
 extern "C" size_t unet_gradcam_workspace_bytes(int N, int HW, int C) {
   if (!gc_shape_ok(N, HW, C)) return 0;
-  return gc_minmax_bytes(N, HW) +
-         align_up((size_t)N * gc_weight_slabs(N, HW, C) * C * sizeof(float), 256);
+  return gc_ws(nullptr, N, HW, C).bytes;
 }
 
 extern "C" int unet_gradcam_weights(const void* g, int g_bf16, float* w, void* workspace,
@@ -244,24 +248,20 @@ extern "C" int unet_gradcam_weights(const void* g, int g_bf16, float* w, void* w
                "1024; HW <= 2^30)", N, HW, C);
   UNET_REQUIRE(gc_aligned(g) && gc_aligned(w) && gc_aligned(workspace),
                "gradcam_weights: pointers must be 16-byte aligned");
-  if (workspace_bytes < unet_gradcam_workspace_bytes(N, HW, C)) {
-    unet_set_error("gradcam_weights: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
+  const GcWs ws = gc_ws(workspace, N, HW, C);
+  UNET_REQUIRE_WS(workspace_bytes, ws.bytes, "gradcam_weights: workspace too small");
   const int slabs = gc_weight_slabs(N, HW, C);
-  float* partial = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) +
-                                            gc_minmax_bytes(N, HW));
   const dim3 grid(slabs, N), block(GC_THREADS);
   if (g_bf16)
     hipLaunchKernelGGL(gradcam_weights_kernel<__bf16>, grid, block, 0, stream,
-                       reinterpret_cast<const __bf16*>(g), partial, w, HW, C, slabs);
+                       reinterpret_cast<const __bf16*>(g), ws.partial, w, HW, C, slabs);
   else
     hipLaunchKernelGGL(gradcam_weights_kernel<float>, grid, block, 0, stream,
-                       reinterpret_cast<const float*>(g), partial, w, HW, C, slabs);
+                       reinterpret_cast<const float*>(g), ws.partial, w, HW, C, slabs);
   UNET_CHECK_LAUNCH("gradcam_weights");
   if (slabs > 1) {
     hipLaunchKernelGGL(gradcam_weights_finalize_kernel, dim3(ceil_div(C, 32), N),
-                       dim3(32 * GC_FL), 0, stream, partial, w, HW, C, slabs);
+                       dim3(32 * GC_FL), 0, stream, ws.partial, w, HW, C, slabs);
     UNET_CHECK_LAUNCH("gradcam_weights_finalize");
   }
   return UNET_OK;
@@ -279,13 +279,10 @@ extern "C" int unet_gradcam_map(const unet_act_src* a, int a_bf16, float slope, 
   UNET_REQUIRE(slope >= 0.f && slope <= 1.f, "gradcam_map: slope must lie in [0, 1]");
   UNET_REQUIRE(gc_aligned(a->x) && gc_aligned(a->alpha) && gc_aligned(a->beta) && gc_aligned(w) &&
                gc_aligned(workspace), "gradcam_map: pointers must be 16-byte aligned");
-  if (workspace_bytes < gc_minmax_bytes(N, HW)) {
-    unet_set_error("gradcam_map: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
-  float2* mm = reinterpret_cast<float2*>(workspace);
-  return a_bf16 ? launch_map<__bf16>(a, slope, w, cam, mm, N, HW, stream)
-                : launch_map<float>(a, slope, w, cam, mm, N, HW, stream);
+  const GcWs ws = gc_ws(workspace, N, HW, 0);
+  UNET_REQUIRE_WS(workspace_bytes, ws.bytes, "gradcam_map: workspace too small");
+  return a_bf16 ? launch_map<__bf16>(a, slope, w, cam, ws.minmax, N, HW, stream)
+                : launch_map<float>(a, slope, w, cam, ws.minmax, N, HW, stream);
 }
 
 extern "C" int unet_gradcam_heatmap(const float* cam, const void* workspace,
@@ -296,16 +293,13 @@ extern "C" int unet_gradcam_heatmap(const float* cam, const void* workspace,
   UNET_REQUIRE(N > 0 && N <= 65535 && h > 0 && w > 0 && H > 0 && W > 0 &&
                (long long)h * w <= (1ll << 30) && (long long)H * W <= (1ll << 30),
                "gradcam_heatmap: bad shape (N in 1..65535, h * w and H * W in 1..2^30)");
-  if (workspace_bytes < gc_minmax_bytes(N, h * w)) {
-    unet_set_error("gradcam_heatmap: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
+  const GcWs ws = gc_ws(const_cast<void*>(workspace), N, h * w, 0);
+  UNET_REQUIRE_WS(workspace_bytes, ws.bytes, "gradcam_heatmap: workspace too small");
   int blocks = ceil_div(H * W, GC_THREADS * 4);
   const int most = ceil_div(GC_MAX_BLOCKS, N);
   blocks = blocks > most ? most : blocks;
   hipLaunchKernelGGL(gradcam_heatmap_kernel, dim3(blocks, N), dim3(GC_THREADS), 0, stream, cam,
-                     reinterpret_cast<const float2*>(workspace), heatmap, gc_map_tiles(N, h * w), h,
-                     w, H, W);
+                     ws.minmax, heatmap, gc_map_tiles(N, h * w), h, w, H, W);
   UNET_CHECK_LAUNCH("gradcam_heatmap");
   return UNET_OK;
 }

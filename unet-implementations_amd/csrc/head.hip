@@ -691,68 +691,12 @@ static int head1x1_bwd_impl(const float* a, const float* dlogits, const float* w
                             float* dw, float* db, void* workspace, size_t workspace_bytes, int N,
                             int HW, int C, int K, const float* alpha, const float* beta,
                             float slope, unet_stream_t stream, int b16 = 0,
-                            unet_bwd_stats* bs = nullptr, const HeadFold* fold = nullptr);
-
-extern "C" int unet_head1x1_bwd(const float* a, const float* dlogits, const float* w, float* da,
-                                float* dw, float* db, void* workspace, size_t workspace_bytes,
-                                int N, int HW, int C, int K, unet_stream_t stream) {
-  return head1x1_bwd_impl(a, dlogits, w, da, dw, db, workspace, workspace_bytes, N, HW, C, K,
-                          nullptr, nullptr, 0.f, stream);
-}
-
-extern "C" int unet_head1x1_in_bwd(const unet_act_src* x, float slope, const float* dlogits,
-                                   const float* w, float* da, float* dw, float* db,
-                                   void* workspace, size_t workspace_bytes, int N, int HW, int K,
-                                   unet_stream_t stream) {
-  UNET_REQUIRE(x && x->x && (!x->alpha || x->beta), "head1x1_in_bwd: null source");
-  return head1x1_bwd_impl(x->x, dlogits, w, da, dw, db, workspace, workspace_bytes, N, HW, x->C, K,
-                          x->alpha, x->beta, slope, stream);
-}
-
-// ... with the reductions of the InstanceNorm + LeakyReLU + dropout backward of the layer whose
-// raw output x->x is (bs->y == x->x): da is that layer's final dL/da, so the kernel that writes
-// it also sums gz and gz * xhat per workgroup (bs->tiles_out summaries per image; 0 = the shape
-// does not split evenly: run unet_instnorm_lrelu_drop_bwd as usual)
-extern "C" int unet_head1x1_in_bwd_bs(const unet_act_src* x, float slope, const float* dlogits,
-                                      const float* w, float* da, float* dw, float* db,
-                                      void* workspace, size_t workspace_bytes, int N, int HW,
-                                      int K, unet_bwd_stats* bs, unet_stream_t stream) {
-  UNET_REQUIRE(x && x->x && (!x->alpha || x->beta), "head1x1_in_bwd_bs: null source");
-  return head1x1_bwd_impl(x->x, dlogits, w, da, dw, db, workspace, workspace_bytes, N, HW, x->C, K,
-                          x->alpha, x->beta, slope, stream, 0, bs);
-}
-
-extern "C" int unet_head1x1_in_bwd_bs_b16(const unet_act_src* x, float slope, const float* dlogits,
-                                          const float* w, uint16_t* da, float* dw, float* db,
-                                          void* workspace, size_t workspace_bytes, int N, int HW,
-                                          int K, unet_bwd_stats* bs, unet_stream_t stream) {
-  UNET_REQUIRE(x && x->x && (!x->alpha || x->beta), "head1x1_in_bwd_bs_b16: null source");
-  return head1x1_bwd_impl(x->x, dlogits, w, reinterpret_cast<float*>(da), dw, db, workspace,
-                          workspace_bytes, N, HW, x->C, K, x->alpha, x->beta, slope, stream, 1, bs);
-}
-
-// x and da are bf16 tensors (mixed-precision pipeline); logits gradient and dw / db stay fp32
-extern "C" int unet_head1x1_in_bwd_b16(const unet_act_src* x, float slope, const float* dlogits,
-                                       const float* w, uint16_t* da, float* dw, float* db,
-                                       void* workspace, size_t workspace_bytes, int N, int HW,
-                                       int K, unet_stream_t stream) {
-  UNET_REQUIRE(x && x->x && (!x->alpha || x->beta), "head1x1_in_bwd_b16: null source");
-  return head1x1_bwd_impl(x->x, dlogits, w, reinterpret_cast<float*>(da), dw, db, workspace,
-                          workspace_bytes, N, HW, x->C, K, x->alpha, x->beta, slope, stream, 1);
-}
-
-static int head1x1_bwd_impl(const float* a, const float* dlogits, const float* w, float* da,
-                            float* dw, float* db, void* workspace, size_t workspace_bytes, int N,
-                            int HW, int C, int K, const float* alpha, const float* beta,
-                            float slope, unet_stream_t stream, int b16, unet_bwd_stats* bs,
-                            const HeadFold* fold) {
+                            unet_bwd_stats* bs = nullptr, const HeadFold* fold = nullptr) {
   UNET_REQUIRE(a && dlogits && w && da && workspace, "head1x1_bwd: null pointer");
   UNET_REQUIRE(C == 32 && K >= 1 && K <= UNET_MAX_CLASSES && N > 0 && HW > 0,
                "head1x1_bwd: needs C == 32, K <= 32 (got C=%d K=%d)", C, K);
-  if (workspace_bytes < unet_head1x1_bwd_workspace_bytes(N, HW, C, K)) {
-    unet_set_error("head1x1_bwd: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
+  UNET_REQUIRE_WS(workspace_bytes, unet_head1x1_bwd_workspace_bytes(N, HW, C, K),
+                  "head1x1_bwd: workspace too small");
   const long long M = (long long)N * HW;
   const long long tiles = ceil_div64(M, HB);
   const int blocks = head_bwd_blocks(tiles);
@@ -804,16 +748,70 @@ static int head1x1_bwd_impl(const float* a, const float* dlogits, const float* w
   return UNET_OK;
 }
 
+extern "C" int unet_head1x1_bwd(const float* a, const float* dlogits, const float* w, float* da,
+                                float* dw, float* db, void* workspace, size_t workspace_bytes,
+                                int N, int HW, int C, int K, unet_stream_t stream) {
+  return head1x1_bwd_impl(a, dlogits, w, da, dw, db, workspace, workspace_bytes, N, HW, C, K,
+                          nullptr, nullptr, 0.f, stream);
+}
+
+extern "C" int unet_head1x1_in_bwd(const unet_act_src* x, float slope, const float* dlogits,
+                                   const float* w, float* da, float* dw, float* db,
+                                   void* workspace, size_t workspace_bytes, int N, int HW, int K,
+                                   unet_stream_t stream) {
+  UNET_REQUIRE(x && x->x && (!x->alpha || x->beta), "head1x1_in_bwd: null source");
+  return head1x1_bwd_impl(x->x, dlogits, w, da, dw, db, workspace, workspace_bytes, N, HW, x->C, K,
+                          x->alpha, x->beta, slope, stream);
+}
+
+// ... with the reductions of the InstanceNorm + LeakyReLU + dropout backward of the layer whose
+// raw output x->x is (bs->y == x->x): da is that layer's final dL/da, so the kernel that writes
+// it also sums gz and gz * xhat per workgroup (bs->tiles_out summaries per image; 0 = the shape
+// does not split evenly: run unet_instnorm_lrelu_drop_bwd as usual)
+extern "C" int unet_head1x1_in_bwd_bs(const unet_act_src* x, float slope, const float* dlogits,
+                                      const float* w, float* da, float* dw, float* db,
+                                      void* workspace, size_t workspace_bytes, int N, int HW,
+                                      int K, unet_bwd_stats* bs, unet_stream_t stream) {
+  UNET_REQUIRE(x && x->x && (!x->alpha || x->beta), "head1x1_in_bwd_bs: null source");
+  return head1x1_bwd_impl(x->x, dlogits, w, da, dw, db, workspace, workspace_bytes, N, HW, x->C, K,
+                          x->alpha, x->beta, slope, stream, 0, bs);
+}
+
+extern "C" int unet_head1x1_in_bwd_bs_b16(const unet_act_src* x, float slope, const float* dlogits,
+                                          const float* w, uint16_t* da, float* dw, float* db,
+                                          void* workspace, size_t workspace_bytes, int N, int HW,
+                                          int K, unet_bwd_stats* bs, unet_stream_t stream) {
+  UNET_REQUIRE(x && x->x && (!x->alpha || x->beta), "head1x1_in_bwd_bs_b16: null source");
+  return head1x1_bwd_impl(x->x, dlogits, w, reinterpret_cast<float*>(da), dw, db, workspace,
+                          workspace_bytes, N, HW, x->C, K, x->alpha, x->beta, slope, stream, 1, bs);
+}
+
+// x and da are bf16 tensors (mixed-precision pipeline); logits gradient and dw / db stay fp32
+extern "C" int unet_head1x1_in_bwd_b16(const unet_act_src* x, float slope, const float* dlogits,
+                                       const float* w, uint16_t* da, float* dw, float* db,
+                                       void* workspace, size_t workspace_bytes, int N, int HW,
+                                       int K, unet_stream_t stream) {
+  UNET_REQUIRE(x && x->x && (!x->alpha || x->beta), "head1x1_in_bwd_b16: null source");
+  return head1x1_bwd_impl(x->x, dlogits, w, reinterpret_cast<float*>(da), dw, db, workspace,
+                          workspace_bytes, N, HW, x->C, K, x->alpha, x->beta, slope, stream, 1);
+}
+
 // The head's backward and the InstanceNorm + LeakyReLU + dropout backward of the layer in front
 // as one call (fp32 tensors): where unet_head1x1_in_bwd_bs would leave that layer's reductions
 // (bs->tiles_out > 0 on return), da never reaches memory - `dz` receives the layer's dL/dz and
 // dgamma / dbeta / dbias (each nullable) its parameter gradients.  bs->tiles_out == 0: the call
 // did what unet_head1x1_in_bwd_bs does, `dz` holds da and unet_instnorm_lrelu_drop_bwd is the
-// caller's next step.
+// caller's next step.  Workspace: the slabs of unet_head1x1_bwd, then the (coef, sums) pair.
+struct HeadFoldWs { InBwdPair pair; size_t bytes; };
+static HeadFoldWs head_fold_ws(void* base, int N, int HW, int K) {
+  WsLayout l(base);
+  l.take<char>(unet_head1x1_bwd_workspace_bytes(N, HW, 32, K), 256);   // at the base: the callee's
+  return {in_bwd_pair(l, N, 32), l.bytes()};
+}
+
 extern "C" size_t unet_head1x1_in_bwd_fold_workspace_bytes(int N, int HW, int K) {
   if (N <= 0 || HW <= 0) return 0;
-  return align_up(unet_head1x1_bwd_workspace_bytes(N, HW, 32, K), 256) +
-         2 * align_up((size_t)N * 32 * sizeof(float2), 256);
+  return head_fold_ws(nullptr, N, HW, K).bytes;
 }
 
 extern "C" int unet_head1x1_in_bwd_fold(const unet_act_src* x, float slope, const float* dlogits,
@@ -825,16 +823,9 @@ extern "C" int unet_head1x1_in_bwd_fold(const unet_act_src* x, float slope, cons
                "head1x1_in_bwd_fold: null pointer");
   UNET_REQUIRE(N > 0 && HW > 0 && K >= 1 && K <= UNET_MAX_CLASSES,
                "head1x1_in_bwd_fold: bad shape");
-  if (workspace_bytes < unet_head1x1_in_bwd_fold_workspace_bytes(N, HW, K)) {
-    unet_set_error("head1x1_in_bwd_fold: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
-  char* ws = reinterpret_cast<char*>(workspace);
-  const size_t slabs = align_up(unet_head1x1_bwd_workspace_bytes(N, HW, 32, K), 256);
-  HeadFold fold{};
-  fold.coef = reinterpret_cast<float2*>(ws + slabs);
-  fold.sums = reinterpret_cast<float2*>(ws + slabs + align_up((size_t)N * 32 * sizeof(float2), 256));
-  fold.dgamma = dgamma; fold.dbeta = dbeta; fold.dbias = dbias;
-  return head1x1_bwd_impl(x->x, dlogits, w, dz, dw, db, workspace, slabs, N, HW, x->C, K, x->alpha,
-                          x->beta, slope, stream, 0, bs, &fold);
+  const HeadFoldWs ws = head_fold_ws(workspace, N, HW, K);
+  UNET_REQUIRE_WS(workspace_bytes, ws.bytes, "head1x1_in_bwd_fold: workspace too small");
+  const HeadFold fold{ws.pair.coef, ws.pair.sums, dgamma, dbeta, dbias};
+  return head1x1_bwd_impl(x->x, dlogits, w, dz, dw, db, workspace, workspace_bytes, N, HW, x->C, K,
+                          x->alpha, x->beta, slope, stream, 0, bs, &fold);
 }

@@ -13,7 +13,6 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kColsumChunks = 32;
 
 __host__ __device__ inline int split_for(int N, int HW, int C) {
   // enough blocks to fill the chip (~2048) but at least 64 pixels-iterations per block
@@ -520,17 +519,24 @@ bool shape_ok(int N, int HW, int C) {
   return N > 0 && HW > 0 && C >= 4 && C % 4 == 0 && C <= 1024 && (kThreads % (C / 4) == 0 || C / 4 > kThreads);
 }
 
+// Per-block slabs, then the backward's pair.  RESERVED behind them (once dbias slabs and their
+// stage; no kernel reads them): sizes are pinned, unet_conv_in_fwd_workspace_bytes maxes with it.
+struct InWs { float2* partial; InBwdPair pair; size_t bytes; };
+InWs in_ws(void* base, int N, int HW, int C) {
+  constexpr size_t kColsumChunks = 32;
+  const size_t slabs = (size_t)N * split_for(N, HW, C) * C;
+  WsLayout l(base);
+  InWs w{l.take<float2>(slabs, 256), in_bwd_pair(l, N, C), 0};
+  l.take<float>(slabs, 256), l.take<float>(kColsumChunks * C, 256);   // reserved
+  w.bytes = l.bytes();
+  return w;
+}
+
 }  // namespace
 
 extern "C" size_t unet_instnorm_workspace_bytes(int N, int HW, int C) {
   if (N <= 0 || HW <= 0 || C <= 0) return 0;
-  const int split = split_for(N, HW, C);
-  // slabs (float2) + bwd coef and raw sums (float2 [N][C] each) + dbias slabs (float) +
-  // one row-chunk stage of the dbias column sum
-  return align_up((size_t)N * split * C * sizeof(float2), 256) +
-         2 * align_up((size_t)N * C * sizeof(float2), 256) +
-         align_up((size_t)N * split * C * sizeof(float), 256) +
-         align_up((size_t)kColsumChunks * C * sizeof(float), 256);
+  return in_ws(nullptr, N, HW, C).bytes;
 }
 
 extern "C" int unet_instnorm_stats(const float* y, const float* gamma, const float* beta, float eps,
@@ -549,13 +555,11 @@ int unet_in_stats_masked(const float* y, const float* gamma, const float* beta, 
   UNET_REQUIRE(y && mean && rstd && workspace, "instnorm_stats: null pointer");
   UNET_REQUIRE(shape_ok(N, HW, C) && C <= 1024 && kThreads % (C / 4) == 0,
                "instnorm_stats: unsupported shape N=%d HW=%d C=%d", N, HW, C);
-  if (workspace_bytes < unet_instnorm_workspace_bytes(N, HW, C)) {
-    unet_set_error("instnorm_stats: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
+  const InWs ws = in_ws(workspace, N, HW, C);
+  UNET_REQUIRE_WS(workspace_bytes, ws.bytes, "instnorm_stats: workspace too small");
   const int split = split_for(N, HW, C);
   const int groups = kThreads / (C / 4);
-  float2* partial = reinterpret_cast<float2*>(workspace);
+  float2* const partial = ws.partial;
   const size_t lds = (size_t)groups * (C / 4 + 2 * C) * sizeof(float);
   if (y_is_bf16)
     hipLaunchKernelGGL(in_stats_kernel<__bf16>, dim3(split, N), dim3(kThreads), lds, stream,
@@ -631,7 +635,36 @@ static int instnorm_bwd_impl(const TS* ga, const TS* y, const float* mean, const
                              const float* gamma, const float* beta, const float* mask, float slope,
                              TS* dy, float* dgamma, float* dbeta, float* dbias, void* workspace,
                              size_t workspace_bytes, int N, int HW, int C, hipStream_t stream,
-                             const float2* ext_partial = nullptr, int ext_tiles = 0);
+                             const float2* ext_partial = nullptr, int ext_tiles = 0) {
+  UNET_REQUIRE(ga && y && mean && rstd && gamma && beta && dy && workspace,
+               "instnorm_lrelu_drop_bwd: null pointer");
+  UNET_REQUIRE(shape_ok(N, HW, C) && kThreads % (C / 4) == 0,
+               "instnorm_lrelu_drop_bwd: unsupported shape N=%d HW=%d C=%d", N, HW, C);
+  const InWs ws = in_ws(workspace, N, HW, C);
+  UNET_REQUIRE_WS(workspace_bytes, ws.bytes, "instnorm_lrelu_drop_bwd: workspace too small");
+  const int split = split_for(N, HW, C);
+  const int groups = kThreads / (C / 4);
+  float2 *const partial = ws.partial, *const coef = ws.pair.coef, *const sums = ws.pair.sums;
+  const size_t lds2 = (size_t)groups * 2 * C * sizeof(float);
+  if (ext_partial) {   // the producer of ga already summarised the reductions per tile
+    hipLaunchKernelGGL(in_bwd_finalize1_kernel, dim3(ceil_div(C, 32), N), dim3(32 * FL), 0, stream,
+                       ext_partial, coef, sums, HW, C, ext_tiles);
+  } else {
+    hipLaunchKernelGGL(in_bwd_reduce_kernel<TS>, dim3(split, N), dim3(kThreads), lds2, stream, ga,
+                       y, mean, rstd, gamma, beta, mask, slope, partial, HW, C, split);
+    UNET_CHECK_LAUNCH("in_bwd_reduce");
+    hipLaunchKernelGGL(in_bwd_finalize1_kernel, dim3(ceil_div(C, 32), N), dim3(32 * FL), 0, stream,
+                       partial, coef, sums, HW, C, split);
+  }
+  UNET_CHECK_LAUNCH("in_bwd_finalize1");
+  const size_t lds1 = (size_t)groups * C * sizeof(float);
+  // block (0, 0) of the apply launch also emits dgamma / dbeta / dbias from `sums`
+  hipLaunchKernelGGL(in_bwd_apply_kernel<TS>, dim3(split, N), dim3(kThreads), lds1, stream, ga, y, mean,
+                     rstd, gamma, beta, mask, slope, coef, dy, (float*)nullptr, HW, C, split, sums,
+                     dgamma, dbeta, dbias);
+  UNET_CHECK_LAUNCH("in_bwd_apply");
+  return UNET_OK;
+}
 
 extern "C" int unet_instnorm_lrelu_drop_bwd_partials(const float* ga, const float* y,
                                                      const float* mean, const float* rstd,
@@ -682,52 +715,4 @@ extern "C" int unet_instnorm_lrelu_drop_bwd_partials_b16(
                                    mask, slope, reinterpret_cast<__bf16*>(dy), dgamma, dbeta, dbias,
                                    workspace, workspace_bytes, N, HW, C, (hipStream_t)stream,
                                    reinterpret_cast<const float2*>(partial), tiles);
-}
-
-template <typename TS>
-static int instnorm_bwd_impl(const TS* ga, const TS* y, const float* mean, const float* rstd,
-                             const float* gamma, const float* beta, const float* mask, float slope,
-                             TS* dy, float* dgamma, float* dbeta, float* dbias, void* workspace,
-                             size_t workspace_bytes, int N, int HW, int C, hipStream_t stream,
-                             const float2* ext_partial, int ext_tiles) {
-  UNET_REQUIRE(ga && y && mean && rstd && gamma && beta && dy && workspace,
-               "instnorm_lrelu_drop_bwd: null pointer");
-  UNET_REQUIRE(shape_ok(N, HW, C) && kThreads % (C / 4) == 0,
-               "instnorm_lrelu_drop_bwd: unsupported shape N=%d HW=%d C=%d", N, HW, C);
-  if (workspace_bytes < unet_instnorm_workspace_bytes(N, HW, C)) {
-    unet_set_error("instnorm_lrelu_drop_bwd: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
-  const int split = split_for(N, HW, C);
-  const int groups = kThreads / (C / 4);
-  char* ws = reinterpret_cast<char*>(workspace);
-  float2* partial = reinterpret_cast<float2*>(ws);
-  ws += align_up((size_t)N * split * C * sizeof(float2), 256);
-  float2* coef = reinterpret_cast<float2*>(ws);
-  ws += align_up((size_t)N * C * sizeof(float2), 256);
-  float2* sums = reinterpret_cast<float2*>(ws);
-  ws += align_up((size_t)N * C * sizeof(float2), 256);
-  float* dbp = reinterpret_cast<float*>(ws);
-  ws += align_up((size_t)N * split * C * sizeof(float), 256);
-  float* dbstage = reinterpret_cast<float*>(ws);
-  const size_t lds2 = (size_t)groups * 2 * C * sizeof(float);
-  if (ext_partial) {   // the producer of ga already summarised the reductions per tile
-    hipLaunchKernelGGL(in_bwd_finalize1_kernel, dim3(ceil_div(C, 32), N), dim3(32 * FL), 0, stream,
-                       ext_partial, coef, sums, HW, C, ext_tiles);
-  } else {
-    hipLaunchKernelGGL(in_bwd_reduce_kernel<TS>, dim3(split, N), dim3(kThreads), lds2, stream, ga,
-                       y, mean, rstd, gamma, beta, mask, slope, partial, HW, C, split);
-    UNET_CHECK_LAUNCH("in_bwd_reduce");
-    hipLaunchKernelGGL(in_bwd_finalize1_kernel, dim3(ceil_div(C, 32), N), dim3(32 * FL), 0, stream,
-                       partial, coef, sums, HW, C, split);
-  }
-  UNET_CHECK_LAUNCH("in_bwd_finalize1");
-  const size_t lds1 = (size_t)groups * C * sizeof(float);
-  // block (0, 0) of the apply launch also emits dgamma / dbeta / dbias from `sums`
-  hipLaunchKernelGGL(in_bwd_apply_kernel<TS>, dim3(split, N), dim3(kThreads), lds1, stream, ga, y, mean,
-                     rstd, gamma, beta, mask, slope, coef, dy, (float*)nullptr, HW, C, split, sums,
-                     dgamma, dbeta, dbias);
-  UNET_CHECK_LAUNCH("in_bwd_apply");
-  (void)dbp; (void)dbstage;
-  return UNET_OK;
 }

@@ -528,10 +528,8 @@ static int latent_colsum(const char* name, const float* x, const float* mean, co
                name, N, D);
   UNET_REQUIRE(lt_aligned(x) && lt_aligned(mean) && lt_aligned(out) && lt_aligned(workspace),
                "%s: pointers must be 16-byte aligned", name);
-  if (workspace_bytes < unet_latent_colsum_workspace_bytes(N, D)) {
-    unet_set_error("%s: workspace too small", name);
-    return UNET_E_WORKSPACE;
-  }
+  UNET_REQUIRE_WS(workspace_bytes, unet_latent_colsum_workspace_bytes(N, D),
+                  "%s: workspace too small", name);
   const int per = cs_rows_per_slab(N, D), slabs = cs_slabs(N, D);
   const int colblocks = ceil_div(D / 4, LT_THREADS);
   float* partial = reinterpret_cast<float*>(workspace);
@@ -580,10 +578,8 @@ extern "C" int unet_latent_gram(const float* x, const float* mean, float* g, voi
                "latent_gram: bad shape N=%d D=%d (N in 2..65536, D a multiple of 4)", N, D);
   UNET_REQUIRE(lt_aligned(x) && lt_aligned(mean) && lt_aligned(workspace),
                "latent_gram: pointers must be 16-byte aligned");
-  if (workspace_bytes < unet_latent_gram_workspace_bytes(N, D)) {
-    unet_set_error("latent_gram: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
+  UNET_REQUIRE_WS(workspace_bytes, unet_latent_gram_workspace_bytes(N, D),
+                  "latent_gram: workspace too small");
   const GramPlan p = gram_plan(N, D);
   float* partial = reinterpret_cast<float*>(workspace);
   hipLaunchKernelGGL(gram_kernel, dim3(p.tiles, p.slabs), dim3(LT_THREADS), 0, stream, x, mean,

@@ -746,22 +746,15 @@ __global__ __launch_bounds__(256) void argmax_countsk_kernel(const float* __rest
 static_assert(LQ == 4 * 3 + 1, "the 3-class slab is the K-class slab at K == 3");
 static_assert(sizeof(LossCoef) <= 256 && sizeof(LossCoefK) <= 256, "one 256-byte record");
 struct LossWs {
-  float* partial; void* coef; float* dice_ab; double* sums;
+  float* partial; void* coef; float* dice_ab; double* sums; size_t bytes;
   LossCoef* coef3() const { return static_cast<LossCoef*>(coef); }
   LossCoefK* coefk() const { return static_cast<LossCoefK*>(coef); }
 };
-size_t loss_ws_layout(int N, int K, LossWs* out, char* base) {
+LossWs loss_ws(void* base, int N, int K) {
   const size_t slab = 4 * (size_t)K + 1;
-  const size_t partial_b = align_up((size_t)N * LOSS_BLOCKS * slab * sizeof(float), 256);
-  const size_t coef_b = 256;
-  const size_t ab_b = align_up((size_t)N * K * 2 * sizeof(float), 256);
-  if (out) {
-    out->partial = reinterpret_cast<float*>(base);
-    out->coef = base + partial_b;
-    out->dice_ab = reinterpret_cast<float*>(base + partial_b + coef_b);
-    out->sums = reinterpret_cast<double*>(base + partial_b + coef_b + ab_b);
-  }
-  return partial_b + coef_b + ab_b + align_up((size_t)N * slab * sizeof(double), 256);
+  WsLayout l(base);
+  return {l.take<float>((size_t)N * LOSS_BLOCKS * slab, 256), l.take<char>(256, 256),
+          l.take<float>((size_t)N * K * 2, 256), l.take<double>((size_t)N * slab, 256), l.bytes()};
 }
 
 int loss_blocks_for(int HW) {
@@ -792,11 +785,8 @@ int loss_open(const char* name, const void* workspace, size_t workspace_bytes, i
               int H, int W, int ignore_index, LossWs* ws) {
   const int rc = loss_check<TT>(name, N, K, H, W, ignore_index);
   if (rc != UNET_OK) return rc;
-  if (workspace_bytes < loss_ws_layout(N, K, nullptr, nullptr)) {
-    unet_set_error("%s: workspace too small", name);
-    return UNET_E_WORKSPACE;
-  }
-  loss_ws_layout(N, K, ws, reinterpret_cast<char*>(const_cast<void*>(workspace)));
+  *ws = loss_ws(const_cast<void*>(workspace), N, K);
+  UNET_REQUIRE_WS(workspace_bytes, ws->bytes, "%s: workspace too small", name);
   return UNET_OK;
 }
 
@@ -982,11 +972,11 @@ inline const long long* i64(const int64_t* t) { return reinterpret_cast<const lo
 // K-class forms take any 2 <= K <= 32; the forms without a K are the same call at K == 3.
 extern "C" size_t unet_dice_wce_loss_workspace_bytes(int N, int H, int W) {
   if (N <= 0 || H <= 0 || W <= 0) return 0;
-  return loss_ws_layout(N, 3, nullptr, nullptr);
+  return loss_ws(nullptr, N, 3).bytes;
 }
 extern "C" size_t unet_dice_wce_lossk_workspace_bytes(int N, int K, int H, int W) {
   if (N <= 0 || N > LOSS_MAX_N || K < 2 || K > KMAX || H <= 0 || W <= 0) return 0;
-  return loss_ws_layout(N, K, nullptr, nullptr);
+  return loss_ws(nullptr, N, K).bytes;
 }
 
 // (the argument list after the classes, and how the implementation receives it)

@@ -387,10 +387,8 @@ extern "C" int unet_feature_mse_fwd(const float* y, double* sums, void* workspac
                                     unet_stream_t stream) {
   UNET_REQUIRE(y && sums && workspace, "feature_mse_fwd: null pointer");
   UNET_REQUIRE(shape_ok(2 * (long long)N, H, W, C), "feature_mse_fwd: bad shape (C %% 32 == 0)");
-  if (workspace_bytes < unet_feature_mse_workspace_bytes(N, H, W, C)) {
-    unet_set_error("feature_mse_fwd: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
+  UNET_REQUIRE_WS(workspace_bytes, unet_feature_mse_workspace_bytes(N, H, W, C),
+                  "feature_mse_fwd: workspace too small");
   const long long vec4 = (long long)H * W * (C / 4);
   const int blocks = fm_blocks(vec4);
   double* partial = reinterpret_cast<double*>(workspace);

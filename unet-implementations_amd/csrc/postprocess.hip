@@ -538,16 +538,30 @@ bool shape_ok(int B, int H, int W) {
          (long long)H * W <= PP_MAX_PIXELS;
 }
 
-size_t cleanup_header_bytes(int B) {
-  // status word, best[B] (uint64), votes[B][32] (uint32)
-  return align_up(PP_HEADER + (size_t)B * 8 + (size_t)B * UNET_MAX_CLASSES * 4, 256);
+// The status word (+ padding), then - mask_cleanup only - best[B] and votes[B][32], this header
+// (zeroed before every call) padded to 256; then one (cc_label: the forest) or four planes.
+struct PpWs { unsigned *status, *votes, *plane[4]; unsigned long long* best;
+              size_t header, bytes; };
+PpWs pp_ws(void* base, int B, int H, int W, bool cleanup) {
+  WsLayout l(base);
+  PpWs w{};
+  w.status = l.take<unsigned>(PP_HEADER / sizeof(unsigned), 1);
+  if (cleanup) {
+    w.best = l.take<unsigned long long>(B, 1);
+    w.votes = l.take<unsigned>((size_t)B * UNET_MAX_CLASSES, 1);
+    l.pad(256);
+  }
+  w.header = l.bytes();
+  for (int k = 0; k < (cleanup ? 4 : 1); ++k) w.plane[k] = l.take<unsigned>((size_t)B * H * W, 1);
+  w.bytes = l.bytes();
+  return w;
 }
 
 }  // namespace
 
 extern "C" size_t unet_cc_workspace_bytes(int B, int H, int W) {
   if (!shape_ok(B, H, W)) return 0;
-  return PP_HEADER + (size_t)B * H * W * sizeof(unsigned);
+  return pp_ws(nullptr, B, H, W, false).bytes;
 }
 
 extern "C" int unet_cc_label_u8(const uint8_t* classes, uint32_t* labels, uint32_t* areas,
@@ -564,19 +578,17 @@ extern "C" int unet_cc_label_u8(const uint8_t* classes, uint32_t* labels, uint32
                connectivity);
   UNET_REQUIRE(mode >= UNET_CC_FOREGROUND && mode <= UNET_CC_BACKGROUND,
                "cc_label: unknown mode %d", mode);
-  UNET_REQUIRE(workspace_bytes >= unet_cc_workspace_bytes(B, H, W),
-               "cc_label: workspace of %zu bytes, %zu needed", workspace_bytes,
-               unet_cc_workspace_bytes(B, H, W));
-  unsigned* status = reinterpret_cast<unsigned*>(workspace);
-  unsigned* parent = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + PP_HEADER);
-  if (int rc = pp_zero(workspace, PP_HEADER, stream)) return rc;
-  return cc_dispatch(classes, parent, labels, areas, status, false, B, K, H, W, connectivity, mode,
-                     stream);
+  const PpWs ws = pp_ws(workspace, B, H, W, false);
+  UNET_REQUIRE(workspace_bytes >= ws.bytes, "cc_label: workspace of %zu bytes, %zu needed",
+               workspace_bytes, ws.bytes);
+  if (int rc = pp_zero(workspace, ws.header, stream)) return rc;
+  return cc_dispatch(classes, ws.plane[0], labels, areas, ws.status, false, B, K, H, W,
+                     connectivity, mode, stream);
 }
 
 extern "C" size_t unet_mask_cleanup_workspace_bytes(int B, int K, int H, int W) {
   if (!shape_ok(B, H, W) || K < 2 || K > UNET_MAX_CLASSES) return 0;
-  return cleanup_header_bytes(B) + (size_t)4 * B * H * W * sizeof(unsigned);
+  return pp_ws(nullptr, B, H, W, true).bytes;
 }
 
 extern "C" int unet_mask_cleanup_u8(const uint8_t* classes_in, uint8_t* classes_out,
@@ -595,23 +607,19 @@ extern "C" int unet_mask_cleanup_u8(const uint8_t* classes_in, uint8_t* classes_
                "mask_cleanup: unknown vote %d", vote);
   UNET_REQUIRE(min_area >= 0, "mask_cleanup: min_area %d is negative", min_area);
   UNET_REQUIRE(max_hole_area >= 0, "mask_cleanup: max_hole_area %d is negative", max_hole_area);
-  UNET_REQUIRE(workspace_bytes >= unet_mask_cleanup_workspace_bytes(B, K, H, W),
-               "mask_cleanup: workspace of %zu bytes, %zu needed", workspace_bytes,
-               unet_mask_cleanup_workspace_bytes(B, K, H, W));
+  const PpWs ws = pp_ws(workspace, B, H, W, true);
+  UNET_REQUIRE(workspace_bytes >= ws.bytes, "mask_cleanup: workspace of %zu bytes, %zu needed",
+               workspace_bytes, ws.bytes);
   const int HW = H * W;
-  const size_t plane = (size_t)B * HW, header = cleanup_header_bytes(B);
-  char* ws = static_cast<char*>(workspace);
-  unsigned* status = reinterpret_cast<unsigned*>(ws);
-  unsigned long long* best = reinterpret_cast<unsigned long long*>(ws + PP_HEADER);
-  unsigned* votes = reinterpret_cast<unsigned*>(ws + PP_HEADER + (size_t)B * 8);
+  const size_t plane = (size_t)B * HW;
   // four planes of one word a pixel: the forest, the labels, the areas, and the component vote's
   // winning class.  The vote's counters reuse the forest and the area planes, which it no longer
   // needs; the background pass of step 3 reuses all three.
-  unsigned* p0 = reinterpret_cast<unsigned*>(ws + header);
-  unsigned *p1 = p0 + plane, *p2 = p1 + plane, *p3 = p2 + plane;
+  unsigned *const p0 = ws.plane[0], *const p1 = ws.plane[1], *const p2 = ws.plane[2],
+           *const p3 = ws.plane[3];
   const dim3 grid(pp_blocks(HW), B), block(256);
 
-  if (int rc = pp_zero(workspace, header, stream)) return rc;
+  if (int rc = pp_zero(workspace, ws.header, stream)) return rc;
   hipLaunchKernelGGL(cleanup_copy_kernel, grid, block, 0, stream, classes_in, classes_out, K, HW);
   UNET_CHECK_LAUNCH("cleanup_copy");
   uint8_t* map = classes_out;
@@ -619,30 +627,30 @@ extern "C" int unet_mask_cleanup_u8(const uint8_t* classes_in, uint8_t* classes_
   const bool removal = keep_largest || min_area > 0;
   bool labelled = false;
   if (removal) {
-    if (int rc = cc_dispatch(map, p0, p1, p2, status, false, B, K, H, W, connectivity,
+    if (int rc = cc_dispatch(map, p0, p1, p2, ws.status, false, B, K, H, W, connectivity,
                              MODE_FOREGROUND, stream))
       return rc;
     labelled = true;
     if (keep_largest) {
-      hipLaunchKernelGGL(cleanup_largest_kernel, grid, block, 0, stream, p2, best, HW);
+      hipLaunchKernelGGL(cleanup_largest_kernel, grid, block, 0, stream, p2, ws.best, HW);
       UNET_CHECK_LAUNCH("cleanup_largest");
     }
-    hipLaunchKernelGGL(cleanup_remove_kernel, grid, block, 0, stream, map, p1, p2, best, HW,
+    hipLaunchKernelGGL(cleanup_remove_kernel, grid, block, 0, stream, map, p1, p2, ws.best, HW,
                        (unsigned)min_area, keep_largest ? 1 : 0);
     UNET_CHECK_LAUNCH("cleanup_remove");
   }
   if (vote == UNET_VOTE_IMAGE) {
-    hipLaunchKernelGGL(cleanup_image_votes_kernel, grid, block, 0, stream, map, votes, K, HW);
+    hipLaunchKernelGGL(cleanup_image_votes_kernel, grid, block, 0, stream, map, ws.votes, K, HW);
     UNET_CHECK_LAUNCH("cleanup_image_votes");
-    hipLaunchKernelGGL(cleanup_image_apply_kernel, grid, block, 0, stream, map, votes, K, HW);
+    hipLaunchKernelGGL(cleanup_image_apply_kernel, grid, block, 0, stream, map, ws.votes, K, HW);
     UNET_CHECK_LAUNCH("cleanup_image_apply");
   } else if (vote == UNET_VOTE_COMPONENT) {
     if (!labelled)
-      if (int rc = cc_dispatch(map, p0, p1, p2, status, false, B, K, H, W, connectivity,
+      if (int rc = cc_dispatch(map, p0, p1, p2, ws.status, false, B, K, H, W, connectivity,
                                MODE_FOREGROUND, stream))
         return rc;
     if (int rc = pp_zero(p0, plane * sizeof(unsigned), stream)) return rc;   // count
-    if (int rc = pp_zero(p2, plane * sizeof(unsigned), stream)) return rc;   // best count
+    if (int rc = pp_zero(p2, plane * sizeof(unsigned), stream)) return rc;   // ws.best count
     for (int c = 1; c < K; ++c) {
       hipLaunchKernelGGL(cleanup_comp_count_kernel, grid, block, 0, stream, map, p1, p0, c, HW);
       UNET_CHECK_LAUNCH("cleanup_comp_count");
@@ -654,8 +662,8 @@ extern "C" int unet_mask_cleanup_u8(const uint8_t* classes_in, uint8_t* classes_
     UNET_CHECK_LAUNCH("cleanup_comp_apply");
   }
   if (fill_holes) {
-    if (int rc = cc_dispatch(map, p0, p1, p2, status, true, B, K, H, W, connectivity == 8 ? 4 : 8,
-                             MODE_BACKGROUND, stream))
+    if (int rc = cc_dispatch(map, p0, p1, p2, ws.status, true, B, K, H, W,
+                             connectivity == 8 ? 4 : 8, MODE_BACKGROUND, stream))
       return rc;
     hipLaunchKernelGGL(cleanup_fill_kernel, grid, block, 0, stream, map, p1, p2, HW,
                        (unsigned)max_hole_area);

@@ -497,10 +497,8 @@ extern "C" int unet_recon3x3_bwd(const unet_act_src* x, int x_bf16, float slope,
                    workspace, "recon3x3_bwd: null pointer");
   UNET_REQUIRE(x->C == 32 && K == RK && recon_shape_ok(N, H, W),
                "recon3x3_bwd: needs C == 32, K == 3, 0 < N <= 1024 (got C=%d K=%d N=%d)", x->C, K, N);
-  if (workspace_bytes < unet_recon3x3_bwd_workspace_bytes(N, H, W)) {
-    unet_set_error("recon3x3_bwd: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
+  UNET_REQUIRE_WS(workspace_bytes, unet_recon3x3_bwd_workspace_bytes(N, H, W),
+                  "recon3x3_bwd: workspace too small");
   const int tiles_x = ceil_div(W, RTW), tpi = tiles_x * ceil_div(H, RTH);
   const int tpb = recon_tpb(N, tpi);
   const int blocks = N * tpi / tpb;
@@ -555,10 +553,8 @@ extern "C" int unet_mse_loss_fwd(const float* out, const void* target, int targe
   UNET_REQUIRE(out && target && loss_out && per_image && workspace, "mse_loss_fwd: null pointer");
   UNET_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && (!target_u8 || C == 3),
                "mse_loss_fwd: bad shape (a uint8 target needs C == 3)");
-  if (workspace_bytes < unet_mse_loss_workspace_bytes(N, C, H, W)) {
-    unet_set_error("mse_loss_fwd: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
+  UNET_REQUIRE_WS(workspace_bytes, unet_mse_loss_workspace_bytes(N, C, H, W),
+                  "mse_loss_fwd: workspace too small");
   const long long HW = (long long)H * W;
   const int blocks = mse_blocks(HW);
   double* partial = reinterpret_cast<double*>(workspace);

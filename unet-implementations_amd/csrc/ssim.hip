@@ -346,10 +346,8 @@ extern "C" int unet_ssim_fwd(const float* pred, const void* target, int target_u
                "ssim_fwd: null pointer");
   UNET_REQUIRE(ssim_shape_ok(N, C, H, W) && (!target_u8 || C == 3),
                "ssim_fwd: bad shape (N, C < 65536; a uint8 target needs C == 3)");
-  if (workspace_bytes < unet_ssim_workspace_bytes(N, C, H, W)) {
-    unet_set_error("ssim_fwd: workspace too small");
-    return UNET_E_WORKSPACE;
-  }
+  UNET_REQUIRE_WS(workspace_bytes, unet_ssim_workspace_bytes(N, C, H, W),
+                  "ssim_fwd: workspace too small");
   Gauss11 g;
   for (int t = 0; t < ST; ++t) g.g[t] = gauss11[t];
   int tiles_x;
